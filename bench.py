@@ -174,6 +174,9 @@ def parse_args():
                     help="share of an image's features that are not observations of the scene: a putative match is geometrically "
                          "right with (1 - f)^2; 0.2 = the headline's 0.64 inlier ratio, 0.5 = a 0.25 ratio (RANSAC needs ~13x the trials)")
     ap.add_argument("--dump-graph", default="", help="rank 0 saves the assembled match graph of the last step to this .npz (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB: per-pair "
+                         "counts of every pair, matches and geometries of a fixed sample of pairs), to compare two builds output for output")
     ap.add_argument("--max-pairs", type=int, default=0, help="truncate the (sharded) pair list (bounded runs of the big configs)")
     ap.add_argument("--fixed-trials", type=int, default=0,
                     help="T > 0: min_num_trials = max_num_trials = T, confidence 0.999999, min_inlier_ratio 0.01 -- exactly T "
@@ -205,7 +208,10 @@ def parse_args():
     ap.add_argument("--dump-line", default="", help="rank 0 also writes the long form of the result (with the prose notes) to this file")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="debug: all ranks on device 0 over gloo (exercises the multi-rank path on a 1-GPU box)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port():
@@ -365,6 +371,42 @@ def parity_sample(keep, view, verify, min_num_inliers, stage_filter=True):
     if first_bad is not None:
         out["first_bad_pair"] = first_bad
     return out
+
+
+DUMP_LIMIT = 64 << 20
+TVG_FIELDS = ("num_matches", "F", "E", "H", "qvec", "tvec", "tri_angle", "num_trials", "num_models")
+
+
+def dump_outputs(out_dir, graph, verify, max_feats):
+    """--dump-outputs: what the timed path handed its caller in the last step, as float32 / float64 .npy files, DUMP_LIMIT bytes at
+    most.  Per pair for the whole list: match_counts (+ inlier_counts, config, num_inliers).  For a fixed sample of pairs (all of
+    them when they fit; which ones depends only on the number of pairs and the feature count, so that two builds dump the same
+    pairs): their matches and inlier matches (feature indices, exact in float32) and the rest of their TwoViewGeometry."""
+    import torch
+    from dagsfm_amd import capi, sharding
+    n = int(graph.match_counts.shape[0])
+    per_pair = (4 if verify else 1) * 8
+    sampled = (2 if verify else 1) * 8 * max_feats + 8 * (1 + (35 + 9 if verify else 0))  # rows of both lists + record + pair index
+    room = DUMP_LIMIT - per_pair * n
+    if room < sampled or max_feats >= 1 << 24:
+        raise SystemExit("bench.py: --dump-outputs cannot hold %d pairs at %d features within %d bytes" % (n, max_feats, DUMP_LIMIT))
+    k = min(n, room // sampled)
+    sel = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    arrays = {"match_counts": graph.match_counts.cpu().numpy().astype(np.float64), "sample_pair_index": sel.astype(np.float64)}
+    pos = torch.as_tensor(sel, dtype=torch.int64, device=graph.match_counts.device)
+    arrays["sample_matches"] = sharding.reorder_rows(graph.match_counts, graph.matches, pos)[1].cpu().numpy().astype(np.float32)
+    if verify:
+        arrays["inlier_counts"] = graph.inlier_counts.cpu().numpy().astype(np.float64)
+        arrays["sample_inlier_matches"] = sharding.reorder_rows(graph.inlier_counts, graph.inlier_matches, pos)[1].cpu().numpy().astype(np.float32)
+        tvg = np.frombuffer(graph.tvg.cpu().numpy().tobytes(), dtype=np.dtype(capi.TwoViewGeometry))
+        arrays["config"] = tvg["config"].astype(np.float64)
+        arrays["num_inliers"] = tvg["num_inliers"].astype(np.float64)
+        for f in TVG_FIELDS:
+            arrays["sample_" + f] = tvg[f][sel].astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def parity_failed(ps):
@@ -578,6 +620,8 @@ def main():
         np.savez(args.dump_graph, match_counts=graph.match_counts.cpu().numpy(), matches=graph.matches.cpu().numpy(),
                  **({"tvg": graph.tvg.cpu().numpy(), "inlier_counts": graph.inlier_counts.cpu().numpy(),
                      "inlier_matches": graph.inlier_matches.cpu().numpy()} if verify else {}))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, graph, verify, max(len(im[0]) for im in images))
     if rank == 0:
         ms_per_step = 1e3 * dt / args.steps
         value = n_pairs * args.steps / dt

@@ -157,3 +157,44 @@ def test_parity_sample_counts_what_differs():
     r = bench.parity_sample(keep, view(flip_bit_of_F), True, 15)
     assert r["geometry_mismatches"] == 1 and r["first_bad_pair"] == 2 and bench.parity_failed(r)
     assert bench.parity_sample(keep, view(drop_inlier), True, 15)["geometry_mismatches"] == 2
+
+
+def test_dump_outputs_is_a_fixed_sample_within_the_limit(tmp_path):
+    """bench.dump_outputs on a CPU stand-in for the assembled graph: per-pair arrays for every pair, the rows and geometries of a
+    sample of pairs that depends only on the number of pairs and the feature count, float32 / float64 files within 64 MB."""
+    import ctypes
+
+    import numpy as np
+    import torch
+
+    import bench
+    from dagsfm_amd import capi, sharding
+    rng = np.random.default_rng(1)
+    n, feats = 3000, 4096
+    mc = torch.as_tensor(rng.integers(0, 600, n))
+    ic = torch.minimum(mc, torch.as_tensor(rng.integers(0, 400, n)))
+    m = torch.as_tensor(rng.integers(0, feats, (int(mc.sum()), 2)).astype(np.int32))
+    im = torch.as_tensor(rng.integers(0, feats, (int(ic.sum()), 2)).astype(np.int32))
+    rec = np.zeros(n, np.dtype(capi.TwoViewGeometry))
+    assert rec.itemsize == ctypes.sizeof(capi.TwoViewGeometry)
+    rec["config"] = rng.integers(0, 7, n)
+    rec["F"] = rng.standard_normal((n, 9))
+    rec["num_trials"] = rng.integers(0, 9999, (n, 4))
+    g = sharding.MatchGraph(mc, m, torch.as_tensor(np.frombuffer(rec.tobytes(), np.uint8).reshape(n, -1).copy()), ic, im)
+    sels = []
+    for run in range(2):
+        d = str(tmp_path / str(run))
+        bench.dump_outputs(d, g, True, feats)
+        files = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= bench.DUMP_LIMIT
+        sel = files["sample_pair_index"].astype(np.int64)
+        assert 0 < len(sel) < n and (np.diff(sel) > 0).all()
+        offs = np.r_[0, np.cumsum(mc.numpy())]
+        assert (files["sample_matches"] == np.concatenate([m.numpy()[offs[p]:offs[p + 1]] for p in sel])).all()
+        assert (files["match_counts"] == mc.numpy()).all() and (files["config"] == rec["config"]).all()
+        assert (files["sample_F"] == rec["F"][sel]).all() and (files["sample_num_trials"] == rec["num_trials"][sel]).all()
+        sels.append(sel)
+    assert (sels[0] == sels[1]).all()
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), sharding.MatchGraph(torch.zeros(9 << 20, dtype=torch.int64), m[:0]), False, feats)

@@ -1,19 +1,19 @@
 """The oracle's 5-point steps 3 / 4 (fivept_build_A, fivept_det_poly: expanded from the term table
 dagsfm_amd/csrc/fivept_terms.tbl) against the reference's OWN generated headers
-(/root/reference/src/estimators/essential_matrix_poly.h, essential_matrix_coeffs.h) compiled behind a shim into
-oracle/_ref/libfivept_ref.so -- bit for bit.  The _ref library exists where the oracle was built next to
-/root/reference (this container; it travels with the tree); without it the test is skipped."""
+(essential_matrix_poly.h, essential_matrix_coeffs.h) -- bit for bit.  The reference's answers for the seeded inputs below
+are committed as SHA-256 digests of their bytes (tests/golden/fivept_ref_digests.npz, written by
+tools/make_ref_golden.py from the headers compiled behind a shim into oracle/_ref/libfivept_ref.so)."""
 import ctypes
+import hashlib
 import os
 
 import numpy as np
-import pytest
 
 from tests import oracle_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SO = os.path.join(ROOT, "oracle", "_ref", "libfivept_ref.so")
-needs_ref = pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (no /root/reference at build time)")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "fivept_ref_digests.npz")
+N_TRIALS = 2000
 
 DP = ctypes.POINTER(ctypes.c_double)
 
@@ -44,22 +44,32 @@ def _inputs(rng, n, trial):
     return np.round(rng.standard_normal(n) * 4) / 4   # many exact cancellations
 
 
-@needs_ref
-def test_constraint_matrix_and_determinant_polynomial_bit_exact():
-    ref = ctypes.CDLL(REF_SO)
-    orc = oracle_lib.load().lib
+def trial_inputs():
+    """The (E basis, coefficient input) pair of every trial: what the reference's answers were recorded for."""
     rng = np.random.default_rng(5)
-    for trial in range(2000):
+    for trial in range(N_TRIALS):
         e = _inputs(rng, 36, trial)
-        a_ref = _call(_fn(ref, "ref_fivept_build_A"), e, 200)
+        yield e, _inputs(rng, 39, trial)
+
+
+def digest(x):
+    return hashlib.sha256(np.ascontiguousarray(x, np.float64).tobytes()).digest()
+
+
+def test_constraint_matrix_and_determinant_polynomial_bit_exact():
+    exp = np.load(GOLDEN)
+    trials = list(trial_inputs())
+    seen = hashlib.sha256()
+    for e, b in trials:
+        seen.update(e.tobytes())
+        seen.update(b.tobytes())
+    assert seen.digest() == exp["inputs"].tobytes(), "the inputs are not those the digests were recorded for: tools/make_ref_golden.py"
+    orc = oracle_lib.load().lib
+    for trial, (e, b) in enumerate(trials):
         a_orc = _call(_fn(orc, "oracle_fivept_build_A"), e, 200)
-        assert not np.isnan(a_ref).any()
-        assert a_ref.tobytes() == a_orc.tobytes()
-        b = _inputs(rng, 39, trial)
-        c_ref = _call(_fn(ref, "ref_fivept_coeffs"), b, 11)
+        assert digest(a_orc) == exp["a"][trial].tobytes(), trial
         c_orc = _call(_fn(orc, "oracle_fivept_coeffs"), b, 11)
-        assert not np.isnan(c_ref).any()
-        assert c_ref.tobytes() == c_orc.tobytes()
+        assert digest(c_orc) == exp["c"][trial].tobytes(), trial
 
 
 def test_table_covers_every_entry_once():

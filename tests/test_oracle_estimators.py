@@ -2,6 +2,9 @@
 holds for it, plus numpy cross-checks of the hand-written Eigen restatements.
 Sources of the vectors: /root/reference/src/estimators/{fundamental,essential,homography}_matrix_test.cc,
 estimators/utils_test.cc, optim/ransac_test.cc, base/polynomial_test.cc, base/essential_matrix_test.cc."""
+import hashlib
+import os
+
 import numpy as np
 
 P7_1 = [0.4964, 1.0577, 0.3650, -0.0919, -0.5412, 0.0159, -0.5239, 0.9467, 0.3467, 0.5301, 0.2797, 0.0012, -0.1986, 0.0460]
@@ -308,44 +311,64 @@ def test_estimate_multiple_ends_when_a_pass_removes_nothing(oracle):
     assert ref.num_trials[2] > 0 and ref.num_trials[1] == 0
 
 
-def _misc_ref():
-    import ctypes
-    import os
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libmisc_ref.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref/libmisc_ref.so is built only where /root/reference exists (make -C oracle ref)")
-    return ctypes.CDLL(path)
+MISC_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_misc_answers.npz")
 
 
-def test_support_measurer_equals_the_references_own_file(oracle):
-    """InlierSupportMeasurer::Evaluate / Compare: the oracle's restatement against /root/reference/src/optim/
-    support_measurement.cc itself (plain standard C++, compiled where it lies into oracle/_ref/libmisc_ref.so) -- counts and
-    residual sums bit for bit on random residual vectors (empty, all in, all out, values at the threshold), and every
-    Compare outcome including equal counts with equal / different sums."""
-    import ctypes
-    R = _misc_ref()
-    L = oracle.lib
-    for lib in (R, L):
-        pre = "ref_" if lib is R else "oracle_"
-        getattr(lib, pre + "inlier_support").argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
-        getattr(lib, pre + "inlier_support_compare").restype = ctypes.c_int
-        getattr(lib, pre + "inlier_support_compare").argtypes = [ctypes.c_uint64, ctypes.c_double, ctypes.c_uint64, ctypes.c_double]
+def support_inputs():
+    """Random residual vectors (empty, all in, all out, values at the threshold) and thresholds: what the reference's answers in
+    tests/golden/ref_misc_answers.npz were recorded for (tools/make_ref_golden.py)."""
     rng = np.random.default_rng(0)
-    supports = []
     for trial in range(300):
         n = int(rng.choice([0, 1, 7, 100, 1000]))
         r = np.ascontiguousarray(rng.exponential(4.0, n) ** rng.choice([1, 2]))
         thr = float(rng.choice([0.0, 1.0, 4.0, 16.0, 1e9]))
         if n and trial % 5 == 0:
             r[rng.integers(n)] = thr  # exactly at the threshold: an inlier (<=)
-        out = []
-        for lib, pre in ((R, "ref_"), (L, "oracle_")):
-            cnt, s = ctypes.c_uint64(0), ctypes.c_double(0)
-            getattr(lib, pre + "inlier_support")(r.ctypes.data, n, thr, ctypes.byref(cnt), ctypes.byref(s))
-            out.append((cnt.value, s.value))
-        assert out[0] == out[1], (trial, out)
-        supports.append(out[0])
-    supports += [(5, 1.0), (5, 1.0), (5, 2.0), (6, 9.0), (0, np.finfo(np.float64).max)]
-    for a in supports[::7] + supports[-5:]:
-        for b in supports[::11] + supports[-5:]:
-            assert R.ref_inlier_support_compare(a[0], a[1], b[0], b[1]) == L.oracle_inlier_support_compare(a[0], a[1], b[0], b[1])
+        yield r, thr
+
+
+def support_compare_sides(supports):
+    """The (count, residual sum) pairs Compare is asked about: a sample of the recorded supports and equal counts with equal /
+    different sums."""
+    supports = supports + [(5, 1.0), (5, 1.0), (5, 2.0), (6, 9.0), (0, np.finfo(np.float64).max)]
+    return supports[::7] + supports[-5:], supports[::11] + supports[-5:]
+
+
+def inlier_support(lib, pre, r, thr):
+    import ctypes
+    f = getattr(lib, pre + "inlier_support")
+    f.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
+    cnt, s = ctypes.c_uint64(0), ctypes.c_double(0)
+    f(r.ctypes.data, len(r), thr, ctypes.byref(cnt), ctypes.byref(s))
+    return cnt.value, s.value
+
+
+def inlier_support_compare(lib, pre, a, b):
+    import ctypes
+    f = getattr(lib, pre + "inlier_support_compare")
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_uint64, ctypes.c_double, ctypes.c_uint64, ctypes.c_double]
+    return f(a[0], a[1], b[0], b[1])
+
+
+def test_support_measurer_equals_the_references_own_file(oracle):
+    """InlierSupportMeasurer::Evaluate / Compare: the oracle's restatement against the reference's optim/support_measurement.cc
+    itself (plain standard C++, compiled where it lies into oracle/_ref/libmisc_ref.so; its answers committed in
+    tests/golden/ref_misc_answers.npz) -- counts and residual sums bit for bit on random residual vectors, and every Compare
+    outcome including equal counts with equal / different sums."""
+    exp = np.load(MISC_GOLDEN)
+    trials = list(support_inputs())
+    seen = hashlib.sha256()
+    for r, thr in trials:
+        seen.update(r.tobytes())
+        seen.update(np.float64(thr).tobytes())
+    assert seen.digest() == exp["support_inputs"].tobytes(), "the inputs are not those the answers were recorded for: tools/make_ref_golden.py"
+    supports = []
+    for trial, (r, thr) in enumerate(trials):
+        got = inlier_support(oracle.lib, "oracle_", r, thr)
+        ref = (int(exp["support_count"][trial]), float(exp["support_sum"][trial]))
+        assert got == ref, (trial, got, ref)
+        supports.append(ref)
+    lhs, rhs = support_compare_sides(supports)
+    got = np.array([[inlier_support_compare(oracle.lib, "oracle_", a, b) for b in rhs] for a in lhs])
+    assert (got == exp["support_compare"]).all()
