@@ -70,6 +70,35 @@ class Vocabulary(ctypes.Structure):
 _libs = {}
 
 
+RA_MAX_L1_ITERATIONS = 8  # DSM_RA_MAX_L1_ITERATIONS
+DSM_ERR_NOT_CONVERGED = 6
+
+
+class RotationAveragingOptions(ctypes.Structure):
+    """dsm_rotation_averaging_options: RobustRotationEstimator::Options + L1Solver::Options defaults
+    (/root/reference/src/rotation_estimation/robust_rotation_estimator.h:96-115, src/solver/l1_solver.h)."""
+    _fields_ = [("max_num_l1_iterations", ctypes.c_int32), ("max_num_irls_iterations", ctypes.c_int32),
+                ("l1_step_convergence_threshold", ctypes.c_double), ("irls_step_convergence_threshold", ctypes.c_double),
+                ("irls_loss_parameter_sigma", ctypes.c_double), ("admm_initial_max_iterations", ctypes.c_int32),
+                ("max_num_cg_iterations", ctypes.c_int32), ("cg_batch_iterations", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("admm_rho", ctypes.c_double), ("admm_alpha", ctypes.c_double), ("admm_absolute_tolerance", ctypes.c_double),
+                ("admm_relative_tolerance", ctypes.c_double), ("max_relative_rotation_difference_degrees", ctypes.c_double),
+                ("cg_tolerance", ctypes.c_double), ("cg_max_residual", ctypes.c_double)]
+
+
+class RotationAveragingReport(ctypes.Structure):
+    _fields_ = [("num_components", ctypes.c_uint32), ("num_images", ctypes.c_uint32), ("num_edges", ctypes.c_uint32),
+                ("num_l1_iterations", ctypes.c_uint32), ("admm_iterations", ctypes.c_uint32 * RA_MAX_L1_ITERATIONS),
+                ("num_irls_iterations", ctypes.c_uint32), ("num_filtered_edges", ctypes.c_uint32), ("num_final_images", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("total_cg_iterations", ctypes.c_uint64), ("max_cg_relative_residual", ctypes.c_double),
+                ("last_l1_step", ctypes.c_double), ("last_irls_step", ctypes.c_double), ("device_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("admm_iterations", "reserved")}
+        d["admm_iterations"] = list(self.admm_iterations)[:self.num_l1_iterations]
+        return d
+
+
 def lib(check=False):
     """Loads the shared library (check=True: the check build); raises if it has not been built (no fallback)."""
     if check not in _libs:
@@ -116,6 +145,9 @@ def lib(check=False):
         L.dsm_retrieval_debug_word_ids.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp]
         L.dsm_get_retrieval_time.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
         L.dsm_view_graph_filter_cycles.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_double, vp, vp]
+        L.dsm_view_graph_rotation_averaging.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.POINTER(RotationAveragingOptions)] + [vp] * 7
+        L.dsm_default_rotation_averaging_options.argtypes = [ctypes.POINTER(RotationAveragingOptions)]
+        L.dsm_default_rotation_averaging_options.restype = None
         L.dsm_debug_image_to_world.argtypes = [vp, ctypes.POINTER(Camera), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double)]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
@@ -160,6 +192,14 @@ def default_match_options(**kw):
 def default_two_view_options(**kw):
     o = TwoViewOptions()
     lib().dsm_default_two_view_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_rotation_averaging_options(**kw):
+    o = RotationAveragingOptions()
+    lib().dsm_default_rotation_averaging_options(ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -471,6 +511,33 @@ class Context:
         self._chk(self._L.dsm_view_graph_filter_cycles(self._h, len(p), p.ctypes.data, q.ctypes.data, max_loop_error_degrees,
                                                      keep.ctypes.data, ctypes.addressof(nt)))
         return keep[:len(p)].astype(bool), nt.value
+
+    def rotation_averaging(self, pairs, qvecs, use=None, options=None):
+        """dsm_view_graph_rotation_averaging (GlobalRotationAveraging: largest component, RobustRotationEstimator, orientation
+        filter, largest component).  Returns a dict: image_ids [n], orientations [n, 3] (angle-axis), in_final_cc [n] bool,
+        edge_state [n_pairs] uint8 (0 unused, 1 outside the component, 2 filtered, 3 kept), relative_rotations [n_pairs, 3],
+        report (RotationAveragingReport)."""
+        p = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        q = np.ascontiguousarray(qvecs, np.float64).reshape(-1, 4)
+        assert len(p) == len(q)
+        n = len(p)
+        u = None if use is None else np.ascontiguousarray(use, np.uint8).reshape(-1)
+        assert u is None or len(u) == n
+        cap = max(2 * n, 1)
+        ids = np.zeros(cap, np.uint32)
+        orient = np.zeros((cap, 3), np.float64)
+        fin = np.zeros(cap, np.uint8)
+        nimg = ctypes.c_uint32(0)
+        state = np.zeros(max(n, 1), np.uint8)
+        rel = np.zeros((max(n, 1), 3), np.float64)
+        rep = RotationAveragingReport()
+        opt = ctypes.byref(options) if options is not None else None
+        self._chk(self._L.dsm_view_graph_rotation_averaging(self._h, n, p.ctypes.data, q.ctypes.data, None if u is None else u.ctypes.data,
+                                                            opt, ids.ctypes.data, orient.ctypes.data, fin.ctypes.data,
+                                                            ctypes.addressof(nimg), state.ctypes.data, rel.ctypes.data, ctypes.addressof(rep)))
+        k = nimg.value
+        return {"image_ids": ids[:k].copy(), "orientations": orient[:k].copy(), "in_final_cc": fin[:k].astype(bool),
+                "edge_state": state[:n].copy(), "relative_rotations": rel[:n].copy(), "report": rep}
 
     def device_info(self):
         d = DeviceInfo()

@@ -18,66 +18,9 @@
 #include <vector>
 
 #include "ctx.h"
+#include "rotation_ceres.h"
 
 namespace {
-
-__device__ void vg_quaternion_to_angle_axis(const double* q, double* aa) {
-  const double q1 = q[1], q2 = q[2], q3 = q[3];
-  const double sin_squared_theta = q1 * q1 + q2 * q2 + q3 * q3;
-  double k = 2.0;
-  if (sin_squared_theta > 0.0) {
-    const double sin_theta = sqrt(sin_squared_theta);
-    const double cos_theta = q[0];
-    const double two_theta = 2.0 * ((cos_theta < 0.0) ? atan2(-sin_theta, -cos_theta) : atan2(sin_theta, cos_theta));
-    k = two_theta / sin_theta;
-  }
-  aa[0] = q1 * k;
-  aa[1] = q2 * k;
-  aa[2] = q3 * k;
-}
-__device__ void vg_angle_axis_to_rotation(const double* aa, double* R) {  // row-major
-  const double theta2 = aa[0] * aa[0] + aa[1] * aa[1] + aa[2] * aa[2];
-  if (theta2 > DBL_EPSILON) {
-    const double theta = sqrt(theta2);
-    const double wx = aa[0] / theta, wy = aa[1] / theta, wz = aa[2] / theta;
-    const double costheta = cos(theta), sintheta = sin(theta);
-    R[0] = costheta + wx * wx * (1.0 - costheta);
-    R[3] = wz * sintheta + wx * wy * (1.0 - costheta);
-    R[6] = -wy * sintheta + wx * wz * (1.0 - costheta);
-    R[1] = wx * wy * (1.0 - costheta) - wz * sintheta;
-    R[4] = costheta + wy * wy * (1.0 - costheta);
-    R[7] = wx * sintheta + wy * wz * (1.0 - costheta);
-    R[2] = wy * sintheta + wx * wz * (1.0 - costheta);
-    R[5] = -wx * sintheta + wy * wz * (1.0 - costheta);
-    R[8] = costheta + wz * wz * (1.0 - costheta);
-  } else {
-    R[0] = 1.0; R[3] = aa[2]; R[6] = -aa[1];
-    R[1] = -aa[2]; R[4] = 1.0; R[7] = aa[0];
-    R[2] = aa[1]; R[5] = -aa[0]; R[8] = 1.0;
-  }
-}
-__device__ void vg_rotation_to_quaternion(const double* R, double* q) {
-  const double trace = R[0] + R[4] + R[8];
-  if (trace >= 0.0) {
-    double t = sqrt(trace + 1.0);
-    q[0] = 0.5 * t;
-    t = 0.5 / t;
-    q[1] = (R[7] - R[5]) * t;
-    q[2] = (R[2] - R[6]) * t;
-    q[3] = (R[3] - R[1]) * t;
-  } else {
-    int i = 0;
-    if (R[4] > R[0]) i = 1;
-    if (R[8] > R[i * 3 + i]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    double t = sqrt(R[i * 3 + i] - R[j * 3 + j] - R[k * 3 + k] + 1.0);
-    q[i + 1] = 0.5 * t;
-    t = 0.5 / t;
-    q[0] = (R[k * 3 + j] - R[j * 3 + k]) * t;
-    q[j + 1] = (R[j * 3 + i] + R[i * 3 + j]) * t;
-    q[k + 1] = (R[k * 3 + i] + R[i * 3 + k]) * t;
-  }
-}
 
 // ingest: rotation_2 = QuaternionToAngleAxis(qvec) (distributed_mapper_controller.cpp:617-619), kept as the rotation
 // matrix every triplet of the edge needs
@@ -85,8 +28,8 @@ __global__ void k_vg_edge_rotations(const double* __restrict__ qvec, uint32_t n_
   const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_edges) return;
   double aa[3], Rm[9];
-  vg_quaternion_to_angle_axis(qvec + 4 * (size_t)e, aa);
-  vg_angle_axis_to_rotation(aa, Rm);
+  ceres_quaternion_to_angle_axis(qvec + 4 * (size_t)e, aa);
+  ceres_angle_axis_to_rotation(aa, Rm);
   for (int k = 0; k < 9; ++k) R[(size_t)e * 9 + k] = Rm[k];
 }
 
@@ -117,8 +60,8 @@ __global__ void k_vg_triplets(const uint32_t* __restrict__ edge_a, const uint32_
         for (int j = 0; j < 3; ++j) T[i * 3 + j] = R23[i * 3 + 0] * R12[0 * 3 + j] + R23[i * 3 + 1] * R12[1 * 3 + j] + R23[i * 3 + 2] * R12[2 * 3 + j];
       for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) L[i * 3 + j] = T[i * 3 + 0] * R13[j * 3 + 0] + T[i * 3 + 1] * R13[j * 3 + 1] + T[i * 3 + 2] * R13[j * 3 + 2];
-      vg_rotation_to_quaternion(L, q);
-      vg_quaternion_to_angle_axis(q, aa);
+      ceres_rotation_to_quaternion(L, q);
+      ceres_quaternion_to_angle_axis(q, aa);
       const double err = sqrt(aa[0] * aa[0] + aa[1] * aa[1] + aa[2] * aa[2]) * 57.29577951308232286464772187173366546630859375;
       if (err < max_loop_error_degrees) {
         keep[e] = 1;

@@ -27,7 +27,9 @@ enum {
   DSM_ERR_NO_DEVICE = 2,        /* reference: Setup() returns false, matching.cc:732-742 */
   DSM_ERR_HIP = 3,              /* a HIP runtime call failed; see dsm_last_error */
   DSM_ERR_OUT_OF_RANGE = 4,
-  DSM_ERR_NOT_READY = 5         /* results requested before the producing call */
+  DSM_ERR_NOT_READY = 5,        /* results requested before the producing call */
+  DSM_ERR_NOT_CONVERGED = 6     /* an iterative solve ended above its tolerance; reference: a Cholesky
+                                   factorisation fails, RobustRotationEstimator::EstimateRotations returns false */
 };
 
 /* ------------------------------------------------------------------ options */
@@ -422,6 +424,80 @@ int dsm_get_retrieval_time(dsm_ctx* ctx, double* index_ms, double* query_ms);
  * Host pointers. */
 int dsm_view_graph_filter_cycles(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const double* qvecs,
                                  double max_loop_error_degrees, uint8_t* keep, uint64_t* n_triplets);
+
+/* ------------------------------------------------------------------ global rotation averaging
+ * The step after the rotation-cycle filter: DistributedMapperController::GlobalRotationAveraging
+ * (src/controllers/distributed_mapper_controller.cpp:945-1008) with its defaults (reconstruct_largest_cc, ROBUST_L1L2):
+ *   1. the largest connected component of the used edges (ImageGraph::ExtractLargestCC, src/graph/image_graph.cpp:8-50;
+ *      edges outside it are dropped, :953-967).  Ties between equal-size components: the one holding the smallest image
+ *      id wins (the reference takes unordered_map order -- a free choice here);
+ *   2. RobustRotationEstimator (src/rotation_estimation/robust_rotation_estimator.cpp:84-318): every orientation starts
+ *      at zero, the smallest image id is held constant, L1 regression by ADMM (src/solver/l1_solver.h) then IRLS;
+ *   3. FilterViewPairsFromOrientation (src/sfm/filter_view_pairs_from_orientation.cpp:22-90): an edge whose loop
+ *      rotation -R12 * (R2 * -R1) is above the threshold is removed, a kept edge gets RelativeRotationFromTwoRotations
+ *      (src/math/util.h:97-106);
+ *   4. the largest connected component of the surviving edges.
+ * The reference factorises every system with CHOLMOD; here every system is the grounded weighted graph Laplacian
+ * (A^T W A = L_w (x) I3) solved by a Jacobi-preconditioned conjugate gradient on the device: the results agree with the
+ * reference's mathematics by tolerance, not bit for bit.  A solve that ends above a relative residual of
+ * 1e-9 fails the call with DSM_ERR_NOT_CONVERGED. */
+#define DSM_RA_MAX_L1_ITERATIONS 8
+typedef struct dsm_rotation_averaging_options {
+  int32_t max_num_l1_iterations;         /* 5 (robust_rotation_estimator.h:101); at most DSM_RA_MAX_L1_ITERATIONS */
+  int32_t max_num_irls_iterations;       /* 100 (:107) */
+  double l1_step_convergence_threshold;  /* 0.001 (:104); the L1 loop stops on avg_step <= threshold */
+  double irls_step_convergence_threshold;/* 0.001 (:110); the IRLS loop stops on avg_step < threshold */
+  double irls_loss_parameter_sigma;      /* DegToRad(5.0) (:114) */
+  int32_t admm_initial_max_iterations;   /* 5: L1Solver options.max_num_iterations, doubled per L1 iteration (:201-222) */
+  int32_t max_num_cg_iterations;         /* 0: max(1000, 20 * images of the component) per solve */
+  int32_t cg_batch_iterations;           /* 0: 16.  CG iterations the host enqueues between two reads of the device's
+                                            convergence flags; changes the number of no-op launches, never a result */
+  int32_t reserved;
+  double admm_rho;                       /* 1.0 (l1_solver.h Options) */
+  double admm_alpha;                     /* 1.0 */
+  double admm_absolute_tolerance;        /* 1e-4 */
+  double admm_relative_tolerance;        /* 1e-2 */
+  double max_relative_rotation_difference_degrees; /* 5.0 (DistributedMapperController options) */
+  double cg_tolerance;                   /* 1e-12: relative residual at which a solve stops */
+  double cg_max_residual;                /* 1e-9: a solve that ends above it is DSM_ERR_NOT_CONVERGED */
+} dsm_rotation_averaging_options;
+
+typedef struct dsm_rotation_averaging_report {
+  uint32_t num_components;          /* connected components of the used edges */
+  uint32_t num_images;              /* images of the largest one (the estimated orientations) */
+  uint32_t num_edges;               /* edges of the largest one */
+  uint32_t num_l1_iterations;       /* outer L1 iterations run */
+  uint32_t admm_iterations[DSM_RA_MAX_L1_ITERATIONS]; /* ADMM iterations of each outer L1 iteration */
+  uint32_t num_irls_iterations;
+  uint32_t num_filtered_edges;      /* edges removed by the orientation filter */
+  uint32_t num_final_images;        /* images of the largest component after the filter */
+  uint32_t reserved;
+  uint64_t total_cg_iterations;
+  double max_cg_relative_residual;  /* largest final relative residual over all solves */
+  double last_l1_step;              /* average step of the last L1 iteration */
+  double last_irls_step;            /* average step of the last IRLS iteration */
+  double device_ms;                 /* HIP events: first upload to the last kernel */
+} dsm_rotation_averaging_report;
+
+void dsm_default_rotation_averaging_options(dsm_rotation_averaging_options* o);
+
+/* GlobalRotationAveraging() over an edge list (the arrays of dsm_view_graph_filter_cycles).
+ *   pairs    n_pairs x 2 image ids (image_id1, image_id2); qvecs n_pairs x 4 (w, x, y, z): the rotation from image 1 to
+ *            image 2, QuaternionToAngleAxis(qvec) as LoadTwoviewGeometries reads it (distributed_mapper_controller.cpp:617-619)
+ *   use      n_pairs flags (the `keep` output of dsm_view_graph_filter_cycles) or NULL = every edge.  A repeat of an earlier
+ *            used pair, in either order, is ignored (ViewGraph::AddTwoViewGeometry).  id1 == id2, a non-finite or a zero
+ *            qvec on a used edge: DSM_ERR_INVALID_ARGUMENT
+ *   options  NULL = dsm_default_rotation_averaging_options
+ * Per image of the first component, sorted by id (capacity 2 * n_pairs each):
+ *   image_ids_out, orientations_out (x 3, angle-axis), image_in_final_cc (0 / 1); *n_images_out = their number.
+ * Per input edge: edge_state 0 unused / masked / repeat, 1 outside the first component, 2 removed by the orientation filter,
+ *   3 kept -- relative_rotations_out (n_pairs x 3, angle-axis) then holds RelativeRotationFromTwoRotations(R1, R2) (else 0).
+ * report (may be NULL).  Host pointers.  No used edge: DSM_OK with *n_images_out = 0. */
+int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const double* qvecs,
+                                      const uint8_t* use, const dsm_rotation_averaging_options* options,
+                                      uint32_t* image_ids_out, double* orientations_out, uint8_t* image_in_final_cc,
+                                      uint32_t* n_images_out, uint8_t* edge_state, double* relative_rotations_out,
+                                      dsm_rotation_averaging_report* report);
 
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
