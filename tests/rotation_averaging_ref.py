@@ -3,10 +3,14 @@
 IRLS), FilterViewPairsFromOrientation, the largest component of what survives ("Global rotation averaging").
 
 Every system A^T W A = L_w (x) I3 is solved by a dense Cholesky of the grounded scalar Laplacian L_w with three right-hand
-sides (fine up to ~1 500 images).  ceres' rotation conversions are restated from the published formulas, vectorised over
+sides (fine up to a few thousand images).  For larger graphs whose structure is known, `partition` (independent blocks of
+images plus a small separator set) solves every system directly by block elimination instead: a batched Cholesky of the
+blocks and a dense Schur complement on the separator.  ceres' rotation conversions are restated from the published formulas, vectorised over
 rows.  Every stopping decision is recorded with its value and its margin to the threshold (`decisions`), so that a fixture
 sitting on a knife edge shows up as a fixture problem.  The tie rule between equal-size components (the one holding the
-smallest image id wins) is this project's choice."""
+smallest image id wins) is this project's choice.  The device's cold-restart rule of its warm-started solver (a column
+restarts from x = 0 when ||rhs - L x_prev||^2 > ||rhs||^2) does not change the answer; it is recorded as decision "cold" so
+that a test can show which fixtures take that path."""
 import numpy as np
 
 DEG2RAD = np.pi / 180.0
@@ -55,51 +59,34 @@ def rotation_to_quaternion(R):
     R = np.asarray(R, np.float64).reshape(-1, 3, 3)
     q = np.empty((len(R), 4))
     tr = (R[:, 0, 0] + R[:, 1, 1]) + R[:, 2, 2]
-    for n in range(len(R)):
-        M = R[n]
-        if tr[n] >= 0.0:
-            t = np.sqrt(tr[n] + 1.0)
-            q[n, 0] = 0.5 * t
-            t = 0.5 / t
-            q[n, 1] = (M[2, 1] - M[1, 2]) * t
-            q[n, 2] = (M[0, 2] - M[2, 0]) * t
-            q[n, 3] = (M[1, 0] - M[0, 1]) * t
-        else:
-            i = 0
-            if M[1, 1] > M[0, 0]:
-                i = 1
-            if M[2, 2] > M[i, i]:
-                i = 2
-            j = (i + 1) % 3
-            k = (j + 1) % 3
-            t = np.sqrt(((M[i, i] - M[j, j]) - M[k, k]) + 1.0)
-            q[n, i + 1] = 0.5 * t
-            t = 0.5 / t
-            q[n, 0] = (M[k, j] - M[j, k]) * t
-            q[n, j + 1] = (M[j, i] + M[i, j]) * t
-            q[n, k + 1] = (M[k, i] + M[i, k]) * t
-    return q
-
-
-def _rotation_to_quaternion_fast(R):
-    """rotation_to_quaternion for the rows whose trace is >= 0 vectorised (the common case), the others row by row."""
-    R = np.asarray(R, np.float64).reshape(-1, 3, 3)
-    tr = (R[:, 0, 0] + R[:, 1, 1]) + R[:, 2, 2]
-    q = np.empty((len(R), 4))
     p = tr >= 0.0
     t = np.sqrt(tr[p] + 1.0)
     q[p, 0] = 0.5 * t
-    h = 0.5 / t
-    q[p, 1] = (R[p, 2, 1] - R[p, 1, 2]) * h
-    q[p, 2] = (R[p, 0, 2] - R[p, 2, 0]) * h
-    q[p, 3] = (R[p, 1, 0] - R[p, 0, 1]) * h
-    if (~p).any():
-        q[~p] = rotation_to_quaternion(R[~p])
+    t = 0.5 / t
+    q[p, 1] = (R[p, 2, 1] - R[p, 1, 2]) * t
+    q[p, 2] = (R[p, 0, 2] - R[p, 2, 0]) * t
+    q[p, 3] = (R[p, 1, 0] - R[p, 0, 1]) * t
+    # trace < 0: the branch of the largest diagonal entry (the first one on ties), row by row in one pass per branch
+    d = R[:, [0, 1, 2], [0, 1, 2]]
+    i = np.where(d[:, 1] > d[:, 0], 1, 0)
+    i = np.where(d[:, 2] > d[np.arange(len(R)), i], 2, i)
+    for b in range(3):
+        m = ~p & (i == b)
+        if not m.any():
+            continue
+        j, k = (b + 1) % 3, (b + 2) % 3
+        M = R[m]
+        t = np.sqrt(((M[:, b, b] - M[:, j, j]) - M[:, k, k]) + 1.0)
+        q[m, b + 1] = 0.5 * t
+        t = 0.5 / t
+        q[m, 0] = (M[:, k, j] - M[:, j, k]) * t
+        q[m, j + 1] = (M[:, j, b] + M[:, b, j]) * t
+        q[m, k + 1] = (M[:, k, b] + M[:, b, k]) * t
     return q
 
 
 def rotation_to_angle_axis(R):
-    return quaternion_to_angle_axis(_rotation_to_quaternion_fast(R))
+    return quaternion_to_angle_axis(rotation_to_quaternion(R))
 
 
 def multiply_rotations(a, b):
@@ -145,15 +132,104 @@ def _at(N, ei, ej, v):
     return out[1:]
 
 
+def _at_sum(N, ei, ej, v):
+    """_at by per-image sums (np.bincount): the same value up to the order of the additions, and far faster on large graphs."""
+    out = np.stack([np.bincount(ej, v[:, c], N) - np.bincount(ei, v[:, c], N) for c in range(3)], 1)
+    return out[1:]
+
+
 def _chol_solve(L, rhs):
     C = np.linalg.cholesky(L)
     y = np.linalg.solve(C, rhs)
     return np.linalg.solve(C.T, y)
 
 
+class BlockFactor:
+    """The grounded Laplacian L_w of a graph whose images split into independent blocks (no edge joins two blocks) and a
+    separator, factorised by block elimination: L = [[A, B], [B^T, S]] with A block-diagonal; every block by a batched Cholesky
+    A_k = C_k C_k^T, the separator by a dense Cholesky of S - sum_k B_k^T A_k^-1 B_k.  One block holding every image is
+a dense Cholesky whose repeated solves are cheap.  `groups` is a list of [n_blocks, size]
+    arrays of component indices, `sep` an array of component indices; image 0 (the grounded one) must be in neither."""
+
+    def __init__(self, N, ei, ej, w, groups, sep):
+        self.N, self.groups, self.sep = N, groups, np.asarray(sep, np.int64)
+        ns = len(self.sep)
+        kind = np.full(N, -2, np.int64)  # -2 unassigned, -1 separator, >= 0 group
+        blk = np.zeros(N, np.int64)
+        pos = np.zeros(N, np.int64)
+        kind[self.sep] = -1
+        pos[self.sep] = np.arange(ns)
+        for g, G in enumerate(groups):
+            if np.any(kind[G] != -2):
+                raise ValueError("an image is in two sets of the partition")
+            kind[G] = g
+            blk[G] = np.arange(len(G))[:, None]
+            pos[G] = np.arange(G.shape[1])[None, :]
+        if kind[0] != -2 or np.any(kind[1:] == -2):
+            raise ValueError("the partition must hold every image but the grounded one, once")
+        d = np.zeros(N)
+        np.add.at(d, ei, w)
+        np.add.at(d, ej, w)
+        A = [np.zeros((len(G), G.shape[1], G.shape[1])) for G in groups]
+        Bm = [np.zeros((len(G), G.shape[1], ns)) for G in groups]
+        S = np.zeros((ns, ns))
+        for g, G in enumerate(groups):
+            A[g][np.arange(len(G))[:, None], np.arange(G.shape[1])[None, :], np.arange(G.shape[1])[None, :]] = d[G]
+        S[np.arange(ns), np.arange(ns)] = d[self.sep]
+        inner = (ei != 0) & (ej != 0)
+        a, b, we = ei[inner], ej[inner], w[inner]
+        for u, v in ((a, b), (b, a)):  # both triangles of L
+            ku, kv = kind[u], kind[v]
+            m = (ku == -1) & (kv == -1)
+            np.add.at(S, (pos[u[m]], pos[v[m]]), -we[m])
+            for g in range(len(groups)):
+                m = (ku == g) & (kv == g)
+                if np.any(blk[u[m]] != blk[v[m]]):
+                    raise ValueError("an edge joins two blocks")
+                np.add.at(A[g], (blk[u[m]], pos[u[m]], pos[v[m]]), -we[m])
+                m = (ku == g) & (kv == -1)
+                np.add.at(Bm[g], (blk[u[m]], pos[u[m]], pos[v[m]]), -we[m])
+            if np.any((ku >= 0) & (kv >= 0) & (ku != kv)):
+                raise ValueError("an edge joins two blocks")
+        # the inverses of the triangular factors are formed once: every solve is then two products per level
+        self.Ci = [np.linalg.inv(np.linalg.cholesky(Ag)) for Ag in A]
+        self.Y = [Ci @ Bg for Ci, Bg in zip(self.Ci, Bm)]  # C_k^-1 B_k
+        schur = S - sum(np.tensordot(Y, Y, axes=([0, 1], [0, 1])) for Y in self.Y)
+        self.Csi = np.linalg.inv(np.linalg.cholesky(schur)) if ns else np.zeros((0, 0))
+
+    def solve(self, rhs):
+        """L x = rhs for rhs [N - 1, 3] (rows 1..N-1 of the component), returns [N - 1, 3]."""
+        full = np.vstack([np.zeros((1, 3)), rhs])
+        x = np.zeros((self.N, 3))
+        yr = [Ci @ full[G] for Ci, G in zip(self.Ci, self.groups)]  # C_k^-1 r_k
+        rs = full[self.sep] - sum(np.tensordot(Y, y, axes=([0, 1], [0, 1])) for Y, y in zip(self.Y, yr))
+        xs = self.Csi.T @ (self.Csi @ rs)
+        x[self.sep] = xs
+        for Ci, G, Y, y in zip(self.Ci, self.groups, self.Y, yr):
+            x[G] = np.transpose(Ci, (0, 2, 1)) @ (y - Y @ xs)
+        return x[1:]
+
+
+def _partition_groups(partition, cimg):
+    """(blocks, separator) of image ids -> (groups of component indices by block size, separator indices); the grounded image
+    (component index 0) is dropped from whichever set holds it, images outside the component are dropped."""
+    blocks, sep = partition
+    where = {int(i): k for k, i in enumerate(cimg)}
+    by_size = {}
+    for blk in blocks:
+        c = [where[int(i)] for i in blk if int(i) in where and where[int(i)] != 0]
+        if c:
+            by_size.setdefault(len(c), []).append(c)
+    groups = [np.array(by_size[k], np.int64) for k in sorted(by_size)]
+    sep_c = np.array([where[int(i)] for i in sep if int(i) in where and where[int(i)] != 0], np.int64)
+    return groups, sep_c
+
+
 def rotation_averaging(pairs, qvecs, use=None, max_num_l1_iterations=5, max_num_irls_iterations=100, l1_thr=0.001, irls_thr=0.001,
-                       sigma=5.0 * DEG2RAD, admm_initial=5, rho=1.0, alpha=1.0, abs_tol=1e-4, rel_tol=1e-2, filter_degrees=5.0):
-    """Returns a dict shaped like capi.Context.rotation_averaging plus `decisions`: a list of (name, value, threshold)."""
+                       sigma=5.0 * DEG2RAD, admm_initial=5, rho=1.0, alpha=1.0, abs_tol=1e-4, rel_tol=1e-2, filter_degrees=5.0,
+                       partition=None):
+    """Returns a dict shaped like capi.Context.rotation_averaging plus `decisions`: a list of (name, value, threshold).
+    `partition` = (blocks, separator) of image ids: solve by block elimination (BlockFactor) instead of a dense Cholesky."""
     pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
     qvecs = np.asarray(qvecs, np.float64).reshape(-1, 4)
     n = len(pairs)
@@ -200,12 +276,33 @@ def rotation_averaging(pairs, qvecs, use=None, max_num_l1_iterations=5, max_num_
         R[1:] = multiply_rotations(R[1:], x)
         return float(np.sum(np.sqrt(np.sum(x * x, axis=1)))) / (N - 1)
 
-    b = residuals()
-    L0 = _laplacian(N, ei, ej, np.ones(M))
-    C0 = np.linalg.cholesky(L0)
+    at = _at if partition is None else _at_sum
+    x_prev = np.zeros((N - 1, 3))
 
-    def solve0(rhs):
-        return np.linalg.solve(C0.T, np.linalg.solve(C0, rhs))
+    def record_cold(w, rhs):
+        """the device's warm-start rule per column: cold iff ||rhs - L x_prev||^2 > ||rhs||^2 (an all-zero x_prev is an exact tie)"""
+        xf = np.vstack([np.zeros((1, 3)), x_prev])
+        r = rhs - at(N, ei, ej, w[:, None] * (xf[ej] - xf[ei]))
+        for c in range(3):
+            if np.any(x_prev[:, c] != 0.0):
+                dec.append(("cold", float(np.sum(r[:, c] * r[:, c])), float(np.sum(rhs[:, c] * rhs[:, c]))))
+
+    b = residuals()
+    if partition is None:
+        L0 = _laplacian(N, ei, ej, np.ones(M))
+        C0 = np.linalg.cholesky(L0)
+
+        def solve0(rhs):
+            return np.linalg.solve(C0.T, np.linalg.solve(C0, rhs))
+
+        def solve_w(w, rhs):
+            return _chol_solve(_laplacian(N, ei, ej, w), rhs)
+    else:
+        groups, sep_c = _partition_groups(partition, cimg)
+        solve0 = BlockFactor(N, ei, ej, np.ones(M), groups, sep_c).solve
+
+        def solve_w(w, rhs):
+            return BlockFactor(N, ei, ej, w, groups, sep_c).solve(rhs)
 
     cap = admm_initial
     pabs, dabs = np.sqrt(3.0 * M) * abs_tol, np.sqrt(3.0 * (N - 1)) * abs_tol
@@ -215,7 +312,9 @@ def rotation_averaging(pairs, qvecs, use=None, max_num_l1_iterations=5, max_num_
         bn = np.sqrt(np.sum(b * b))
         n_it = 0
         for t in range(cap):
-            x = solve0(_at(N, ei, ej, (b + z) - u))
+            rhs = at(N, ei, ej, (b + z) - u)
+            record_cold(np.ones(M), rhs)
+            x = x_prev = solve0(rhs)
             xf = np.vstack([np.zeros((1, 3)), x])
             ax = xf[ej] - xf[ei]
             ah = alpha * ax + (1.0 - alpha) * (z + b)
@@ -224,10 +323,10 @@ def rotation_averaging(pairs, qvecs, use=None, max_num_l1_iterations=5, max_num_
             z = np.maximum(0.0, v - 1.0 / rho) - np.maximum(0.0, -v - 1.0 / rho)
             u = u + ((ah - z) - b)
             r_norm = np.sqrt(np.sum(((ax - z) - b) ** 2))
-            s_norm = np.sqrt(np.sum((-rho * _at(N, ei, ej, z - zo)) ** 2))
+            s_norm = np.sqrt(np.sum((-rho * at(N, ei, ej, z - zo)) ** 2))
             max_norm = max(np.sqrt(np.sum(ax * ax)), np.sqrt(np.sum(z * z)), bn)
             pe = pabs + rel_tol * max_norm
-            de = dabs + rel_tol * np.sqrt(np.sum((rho * _at(N, ei, ej, u)) ** 2))
+            de = dabs + rel_tol * np.sqrt(np.sum((rho * at(N, ei, ej, u)) ** 2))
             n_it = t + 1
             dec.append(("admm_r", r_norm, pe))
             dec.append(("admm_s", s_norm, de))
@@ -246,7 +345,9 @@ def rotation_averaging(pairs, qvecs, use=None, max_num_l1_iterations=5, max_num_
         e2 = np.sum(b * b, axis=1)
         tmp = e2 + sigma * sigma
         w = sigma / (tmp * tmp)
-        x = _chol_solve(_laplacian(N, ei, ej, w), _at(N, ei, ej, w[:, None] * b))
+        rhs = at(N, ei, ej, w[:, None] * b)
+        record_cold(w, rhs)
+        x = x_prev = solve_w(w, rhs)
         step = rotate(x)
         b = residuals()
         rep["num_irls_iterations"] = it + 1
@@ -273,8 +374,13 @@ def rotation_averaging(pairs, qvecs, use=None, max_num_l1_iterations=5, max_num_
 
 
 def min_margin(decisions):
-    """Smallest relative margin |value - threshold| / threshold over the recorded decisions."""
-    return min(abs(v - t) / t for _, v, t in decisions) if decisions else np.inf
+    """Smallest margin over the recorded decisions: |value - threshold| / threshold, or |value| where the threshold is 0."""
+    return min(abs(v - t) / t if t != 0 else abs(v) for _, v, t in decisions) if decisions else np.inf
+
+
+def cold_restarts(decisions):
+    """Number of recorded solve columns whose warm start was worse than zero (the device restarts them from x = 0)."""
+    return sum(1 for name, v, t in decisions if name == "cold" and v > t)
 
 
 def angle_between(a, b):
