@@ -99,6 +99,26 @@ class RotationAveragingReport(ctypes.Structure):
         return d
 
 
+class ClusteringOptions(ctypes.Structure):
+    """dsm_clustering_options: ImageClustering::Options defaults (src/clustering/image_clustering.h:126-132)
+    and Spectra's compute() stopping rule."""
+    _fields_ = [("num_images_ub", ctypes.c_uint32), ("image_overlap", ctypes.c_uint32), ("completeness_ratio", ctypes.c_float),
+                ("expand", ctypes.c_int32), ("max_kmeans_iterations", ctypes.c_uint32), ("max_eigen_iterations", ctypes.c_int32),
+                ("eigen_tolerance", ctypes.c_double)]
+
+
+class ClusteringReport(ctypes.Structure):
+    _fields_ = [("num_images", ctypes.c_uint32), ("num_edges", ctypes.c_uint32), ("num_clusters", ctypes.c_uint32),
+                ("num_lost_edges", ctypes.c_uint32), ("num_readded_edges", ctypes.c_uint32), ("eigen_iterations", ctypes.c_uint32),
+                ("kmeans_iterations", ctypes.c_uint32), ("ncv", ctypes.c_uint32), ("clustered_images_num", ctypes.c_uint64),
+                ("clustered_edges_num", ctypes.c_uint64), ("operator_applications", ctypes.c_uint64),
+                ("max_eigen_residual", ctypes.c_double), ("max_eigen_residual_ratio", ctypes.c_double), ("eigen_gap", ctypes.c_double),
+                ("device_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def lib(check=False):
     """Loads the shared library (check=True: the check build); raises if it has not been built (no fallback)."""
     if check not in _libs:
@@ -148,6 +168,10 @@ def lib(check=False):
         L.dsm_view_graph_rotation_averaging.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.POINTER(RotationAveragingOptions)] + [vp] * 7
         L.dsm_default_rotation_averaging_options.argtypes = [ctypes.POINTER(RotationAveragingOptions)]
         L.dsm_default_rotation_averaging_options.restype = None
+        L.dsm_view_graph_cluster.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.POINTER(ClusteringOptions)] + [vp] * 8
+        L.dsm_default_clustering_options.argtypes = [ctypes.POINTER(ClusteringOptions)]
+        L.dsm_default_clustering_options.restype = None
+        L.dsm_get_clustering_spectrum.argtypes = [vp, vp, ctypes.c_uint32, vp, ctypes.c_uint64, vp, vp, vp]
         L.dsm_debug_image_to_world.argtypes = [vp, ctypes.POINTER(Camera), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double)]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
@@ -200,6 +224,14 @@ def default_two_view_options(**kw):
 def default_rotation_averaging_options(**kw):
     o = RotationAveragingOptions()
     lib().dsm_default_rotation_averaging_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_clustering_options(**kw):
+    o = ClusteringOptions()
+    lib().dsm_default_clustering_options(ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -538,6 +570,46 @@ class Context:
         k = nimg.value
         return {"image_ids": ids[:k].copy(), "orientations": orient[:k].copy(), "in_final_cc": fin[:k].astype(bool),
                 "edge_state": state[:n].copy(), "relative_rotations": rel[:n].copy(), "report": rep}
+
+    def cluster_view_graph(self, pairs, weights, use=None, labels_in=None, options=None):
+        """dsm_view_graph_cluster (ClusteringScenes: SPECTRAL on the device, or Cut + Expand over labels_in).  Returns a dict:
+        image_ids [n], labels [n] (intra cluster), edge_cluster [n_pairs] int32 (-1 unused / repeat, -2 lost, else the inter
+        cluster), clusters (list of sorted image-id arrays, one per inter cluster), offsets, eigenvalues (the final Ritz values)
+        and eigenvectors ([n, k]: the vectors the k-means ran on) when the eigen-solver ran, else None; report."""
+        p = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        w = np.ascontiguousarray(weights, np.int32).reshape(-1)
+        assert len(p) == len(w)
+        n = len(p)
+        u = None if use is None else np.ascontiguousarray(use, np.uint8).reshape(-1)
+        assert u is None or len(u) == n
+        li = None if labels_in is None else np.ascontiguousarray(labels_in, np.uint32).reshape(-1)
+        cap = max(2 * n, 1)
+        ids = np.zeros(cap, np.uint32)
+        lab = np.zeros(cap, np.uint32)
+        nimg = ctypes.c_uint32(0)
+        ec = np.zeros(max(n, 1), np.int32)
+        offs = np.zeros(2 * n + 1, np.uint32)
+        imgs = np.zeros(max(3 * n, 1), np.uint32)
+        ncl = ctypes.c_uint32(0)
+        rep = ClusteringReport()
+        opt = ctypes.byref(options) if options is not None else None
+        self._chk(self._L.dsm_view_graph_cluster(self._h, n, p.ctypes.data, w.ctypes.data, None if u is None else u.ctypes.data,
+                                                 None if li is None else li.ctypes.data, opt, ids.ctypes.data, lab.ctypes.data,
+                                                 ctypes.addressof(nimg), ec.ctypes.data, offs.ctypes.data, imgs.ctypes.data,
+                                                 ctypes.addressof(ncl), ctypes.addressof(rep)))
+        k = nimg.value
+        clusters = [imgs[offs[c]:offs[c + 1]].copy() for c in range(ncl.value)]
+        ev = vec = None
+        if labels_in is None and rep.eigen_iterations > 0:
+            nv, nr, nc = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+            ev = np.zeros(max(rep.ncv, 1), np.float64)
+            vec = np.zeros(k * max(rep.ncv, 1), np.float64)  # k <= ncv columns
+            self._chk(self._L.dsm_get_clustering_spectrum(self._h, ev.ctypes.data, len(ev), vec.ctypes.data, vec.size,
+                                                          ctypes.addressof(nv), ctypes.addressof(nr), ctypes.addressof(nc)))
+            ev = ev[:nv.value]
+            vec = vec.reshape(-1)[:nr.value * nc.value].reshape(nr.value, nc.value)
+        return {"image_ids": ids[:k].copy(), "labels": lab[:k].copy(), "edge_cluster": ec[:n].copy(), "clusters": clusters,
+                "offsets": offs[:ncl.value + 1].copy(), "eigenvalues": ev, "eigenvectors": vec, "report": rep}
 
     def device_info(self):
         d = DeviceInfo()

@@ -154,6 +154,11 @@ struct dsm_ctx {
   uint64_t memory_budget = 0;
 
   struct RetrievalState* retrieval = nullptr;  // vocabulary-tree retrieval (retrieval.hip), created on first use
+
+  // the final Ritz values and the k Ritz vectors ([images][k]) of the last dsm_view_graph_cluster that ran the eigen-solver
+  // (view_graph_clustering.hip)
+  std::vector<double> cluster_ritz, cluster_vectors;
+  uint32_t cluster_rows = 0, cluster_cols = 0;
 };
 void dsm_retrieval_destroy(dsm_ctx* ctx);     // retrieval.hip
 void dsm_retrieval_invalidate(dsm_ctx* ctx);  // retrieval.hip: the resident images changed

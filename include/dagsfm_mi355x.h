@@ -499,6 +499,81 @@ int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs, const uint
                                       uint32_t* n_images_out, uint8_t* edge_state, double* relative_rotations_out,
                                       dsm_rotation_averaging_report* report);
 
+/* ------------------------------------------------------------------ view-graph clustering
+ * The step after global rotation averaging: DistributedMapperController::ClusteringScenes
+ * (src/controllers/distributed_mapper_controller.cpp:633-657) = ImageClustering::Cut() + Expand()
+ * (src/clustering/image_clustering.cpp:68-128, 159-199, 451-624), and Cut() alone as the distributed matching path uses it
+ * (:395-407; ExpandAllEdges is not restated).
+ *   Nodes: the images of the used edges sorted by id (Cluster::InitIGraph, src/clustering/cluster.cpp:53-83); the weight of an
+ *   edge is its visibility_score, the inlier count (distributed_mapper_controller.cpp:620).  k = images / num_images_ub
+ *   clusters; k <= 1 (also images < num_images_ub, where the reference aborts on CHECK_GE(num_clusters, 1)): every label 0.
+ *   SPECTRAL (src/clustering/spectral_cluster.cpp:52-176) on the device: the k algebraically smallest eigenvectors of
+ *   L = D - S, D the number of edges of an image (not the sum of weights: the reference's operator, kept as it is), then
+ *   KMeans with k-means++ (src/clustering/kmeans.h:158-235; its random draws run on the host with std::mt19937_64).  The
+ *   reference solves with Spectra (SymEigsSolver<SMALLEST_ALGE>, ncv = min(2k, N)); here a Chebyshev-filtered subspace
+ *   iteration in FP64 with the same block size and stopping rule: parity is by tolerance on the subspace, and the labels are
+ *   identical wherever the k-means decisions are not within rounding of a tie.
+ *   NCUT (the reference's default, Graclus) stays on the host application: it passes its labels in labels_in.
+ *   Expand: the cluster pairs run one after another in ascending (c1, c2) order (the reference races them on a thread pool),
+ *   equal weights keep input order (the reference's order is unordered_map order): free choices, DESIGN.md 10. */
+typedef struct dsm_clustering_options {
+  uint32_t num_images_ub;         /* 100 (image_clustering.h:126); 0 -> DSM_ERR_INVALID_ARGUMENT */
+  uint32_t image_overlap;         /* 50 (:129); <= 2 -> invalid (Options::Check, image_clustering.cpp:49-58) */
+  float completeness_ratio;       /* 0.5 (:132); > 1 -> invalid */
+  int32_t expand;                 /* 1: Cut() + Expand() as ClusteringScenes; 0: Cut() only (inter == intra) */
+  uint32_t max_kmeans_iterations; /* 0: unbounded, as KMeans' default */
+  int32_t max_eigen_iterations;   /* 0: solver default (1000, Spectra's maxit); < 0 invalid */
+  double eigen_tolerance;         /* 1e-10, Spectra's stopping rule (lib/Spectra/SymEigsSolver.h:583):
+                                     ||L v - l v|| <= tol * max(eps^(2/3), |l|) for each of the k vectors */
+} dsm_clustering_options;
+
+typedef struct dsm_clustering_report {
+  uint32_t num_images;              /* images of the used edges */
+  uint32_t num_edges;               /* used edges after repeats */
+  uint32_t num_clusters;            /* intra (= inter) clusters */
+  uint32_t num_lost_edges;          /* edges between two intra clusters */
+  uint32_t num_readded_edges;       /* lost edges Expand added back to one cluster */
+  uint32_t eigen_iterations;        /* filter + Rayleigh-Ritz iterations (0: no device work) */
+  uint32_t kmeans_iterations;       /* Lloyd iterations, the last one without a change included */
+  uint32_t ncv;                     /* block size: min(2k, N) */
+  uint64_t clustered_images_num;    /* AnalyzeStatistic (image_clustering.cpp:626-632): sum of inter cluster sizes */
+  uint64_t clustered_edges_num;     /* sum of inter cluster edges */
+  uint64_t operator_applications;   /* products L x (one per column of the block) */
+  double max_eigen_residual;        /* max over the k vectors of ||L v - l v|| */
+  double max_eigen_residual_ratio;  /* max of ||L v - l v|| / max(eps^(2/3), |l|): <= eigen_tolerance on success */
+  double eigen_gap;                 /* l_(k+1) - l_k of the final Ritz values (0 when ncv == k) */
+  double device_ms;                 /* HIP events: first upload to the last k-means kernel */
+} dsm_clustering_report;
+
+void dsm_default_clustering_options(dsm_clustering_options* o);
+
+/* ClusteringScenes() over an edge list (the arrays of dsm_view_graph_rotation_averaging).
+ *   pairs    n_pairs x 2 image ids; weights n_pairs inlier counts (a negative weight on a used edge: invalid)
+ *   use      n_pairs flags or NULL = every edge; for the chained call: edge_state == 3 with both images in_final_cc.  A repeat
+ *            of an earlier used pair, in either order, is ignored; id1 == id2 on a used edge: DSM_ERR_INVALID_ARGUMENT
+ *   labels_in  NULL: SPECTRAL on the device.  Otherwise one label per image of the used edges in ascending id order (each
+ *            < the number of those images; e.g. Graclus' NCUT labels): Cut()'s bookkeeping and Expand() run on them, no
+ *            device work; the cluster count is max(k, largest label + 1)
+ *   options  NULL = dsm_default_clustering_options.  SPECTRAL with k >= images (Spectra needs nev < ncv <= n): invalid
+ * Per image of the used edges, sorted by id (capacity 2 * n_pairs each): image_ids_out, labels_out (intra cluster);
+ *   *n_images_out = their number.
+ * Per input edge: edge_cluster -1 unused / masked / repeat, -2 lost (between two intra clusters) and not added back,
+ *   otherwise the inter cluster that holds the edge.
+ * Inter clusters: cluster_images[cluster_offsets[c] .. cluster_offsets[c + 1]) their images sorted by id; capacities
+ *   2 * n_pairs + 1 (offsets) and 3 * n_pairs (images); *n_clusters_out = their number.
+ * report (may be NULL).  Host pointers.  No used edge: DSM_OK with no image and no cluster.  The eigen-solver ending above
+ * the tolerance after max_eigen_iterations: DSM_ERR_NOT_CONVERGED (the reference goes on with empty vectors). */
+int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const int32_t* weights, const uint8_t* use,
+                           const uint32_t* labels_in, const dsm_clustering_options* options, uint32_t* image_ids_out,
+                           uint32_t* labels_out, uint32_t* n_images_out, int32_t* edge_cluster, uint32_t* cluster_offsets,
+                           uint32_t* cluster_images, uint32_t* n_clusters_out, dsm_clustering_report* report);
+/* The spectrum behind the labels of the last dsm_view_graph_cluster on this context that ran the eigen-solver: the ncv final
+ * Ritz values ascending (*n_values; the first k are the eigenvalues the labels come from) and the k Ritz vectors the
+ * k-means ran on, [n_rows = images][n_cols = k] row-major.  The first min(count, capacity) of each are copied; either
+ * array may be NULL with capacity 0. */
+int dsm_get_clustering_spectrum(dsm_ctx* ctx, double* values, uint32_t values_capacity, double* vectors, uint64_t vectors_capacity,
+                                uint32_t* n_values, uint32_t* n_rows, uint32_t* n_cols);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
