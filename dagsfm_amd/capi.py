@@ -119,6 +119,33 @@ class ClusteringReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AlignOptions(ctypes.Structure):
+    """dsm_align_options: AlignOptions / RansacSimilarity defaults (src/controllers/sfm_aligner.h,
+    src/estimators/ransac_similarity.h:206-245) and the per-direction seed."""
+    _fields_ = [("threshold", ctypes.c_double), ("max_reprojection_error", ctypes.c_double),
+                ("failure_probability", ctypes.c_double), ("min_iterations", ctypes.c_int32), ("max_iterations", ctypes.c_int32),
+                ("random_seed", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class AlignReport(ctypes.Structure):
+    _fields_ = [("num_clusters", ctypes.c_uint32), ("num_pairs", ctypes.c_uint32), ("num_edges", ctypes.c_uint32),
+                ("num_in_component", ctypes.c_uint32), ("num_prosac_problems", ctypes.c_uint32), ("num_separators", ctypes.c_uint32),
+                ("num_observations", ctypes.c_uint64), ("num_correspondences", ctypes.c_uint64), ("prosac_iterations", ctypes.c_uint64),
+                ("min_residual_margin", ctypes.c_double), ("min_cost_margin", ctypes.c_double), ("min_weight_margin", ctypes.c_double),
+                ("device_ms", ctypes.c_double), ("join_ms", ctypes.c_double), ("prosac_ms", ctypes.c_double), ("refit_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# dsm_align_pair as a numpy record (the C layout: no padding beyond the explicit `reserved`)
+ALIGN_PAIR_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("num_common_images", "<u4"), ("num_correspondences", "<u4"),
+                             ("num_inliers", "<u4", (2,)), ("iterations", "<u4", (2,)), ("edge", "<i4"), ("reserved", "<u4"),
+                             ("msd", "<f8", (2,)), ("weight", "<f8"), ("s", "<f8", (2,)), ("R", "<f8", (2, 9)), ("t", "<f8", (2, 3)),
+                             ("prosac_cost", "<f8", (2,)), ("prosac_s", "<f8", (2,)), ("prosac_R", "<f8", (2, 9)),
+                             ("prosac_t", "<f8", (2, 3))])
+
+
 def lib(check=False):
     """Loads the shared library (check=True: the check build); raises if it has not been built (no fallback)."""
     if check not in _libs:
@@ -172,6 +199,12 @@ def lib(check=False):
         L.dsm_default_clustering_options.argtypes = [ctypes.POINTER(ClusteringOptions)]
         L.dsm_default_clustering_options.restype = None
         L.dsm_get_clustering_spectrum.argtypes = [vp, vp, ctypes.c_uint32, vp, ctypes.c_uint64, vp, vp, vp]
+        L.dsm_default_align_options.argtypes = [ctypes.POINTER(AlignOptions)]
+        L.dsm_default_align_options.restype = None
+        L.dsm_align_seed.argtypes = [ctypes.c_uint32] * 4
+        L.dsm_align_seed.restype = ctypes.c_uint32
+        L.dsm_align_clusters.argtypes = ([vp, ctypes.c_uint32] + [vp] * 7 + [ctypes.POINTER(AlignOptions), vp, vp, ctypes.c_uint32]
+                                         + [vp] * 8)
         L.dsm_debug_image_to_world.argtypes = [vp, ctypes.POINTER(Camera), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double)]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
@@ -235,6 +268,18 @@ def default_clustering_options(**kw):
     for k, v in kw.items():
         setattr(o, k, v)
     return o
+
+
+def default_align_options(**kw):
+    o = AlignOptions()
+    lib().dsm_default_align_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def align_seed(i, j, direction, user_seed=0):
+    return int(lib().dsm_align_seed(i, j, direction, user_seed))
 
 
 # the keys dsm_set_debug_option knows (csrc/ctx.h): scheduling knobs of the product, and the cross-check switches of the check build
@@ -610,6 +655,41 @@ class Context:
             vec = vec.reshape(-1)[:nr.value * nc.value].reshape(nr.value, nc.value)
         return {"image_ids": ids[:k].copy(), "labels": lab[:k].copy(), "edge_cluster": ec[:n].copy(), "clusters": clusters,
                 "offsets": offs[:ncl.value + 1].copy(), "eigenvalues": ev, "eigenvectors": vec, "report": rep}
+
+    def align_clusters(self, clusters, options=None, seeds=None):
+        """dsm_align_clusters (SfMAligner::Align up to the transforms, DESIGN.md 11).  clusters: a list of K dicts with
+        image_ids [r] (registered images), point_ids [p] (uint64), xyz [p, 3] (float64) and obs [m, 3] (image_id, point2D_idx,
+        point index inside the cluster).  seeds: None or a [K, K] uint32 array, seeds[a, b] for the direction a -> b.
+        Returns a dict: pairs (ALIGN_PAIR_DTYPE records in ascending (i, j)), anchor, in_component [K] bool, mst_parent [K],
+        sim3_to_anchor as s [K], R [K, 3, 3], t [K, 3], separators (sorted image ids), report."""
+        K = len(clusters)
+        cat = lambda key, dt, shape: [np.ascontiguousarray(c[key], dt).reshape(shape) for c in clusters]
+        imgs, pids = cat("image_ids", np.uint32, -1), cat("point_ids", np.uint64, -1)
+        xyz, obs = cat("xyz", np.float64, (-1, 3)), cat("obs", np.uint32, (-1, 3))
+        offs = lambda arrs: np.concatenate([[0], np.cumsum([len(a) for a in arrs])]).astype(np.uint32)
+        ioff, poff, ooff = offs(imgs), offs(pids), offs(obs)
+        cimg = np.ascontiguousarray(np.concatenate(imgs) if K else np.zeros(0, np.uint32), np.uint32)
+        cpid = np.ascontiguousarray(np.concatenate(pids) if K else np.zeros(0, np.uint64), np.uint64)
+        cxyz = np.ascontiguousarray(np.concatenate(xyz) if K else np.zeros((0, 3)), np.float64)
+        cobs = np.ascontiguousarray(np.concatenate(obs) if K else np.zeros((0, 3), np.uint32), np.uint32)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint32).reshape(K * K)
+        cap = max(K * (K - 1) // 2, 1)
+        pairs = np.zeros(cap, ALIGN_PAIR_DTYPE)
+        npairs, anchor, nsep = ctypes.c_uint32(0), ctypes.c_int32(0), ctypes.c_uint32(0)
+        inc = np.zeros(max(K, 1), np.uint8)
+        par = np.zeros(max(K, 1), np.int32)
+        sim = np.zeros((max(K, 1), 13), np.float64)
+        seps = np.zeros(max(len(cimg), 1), np.uint32)
+        rep = AlignReport()
+        opt = ctypes.byref(options) if options is not None else None
+        self._chk(self._L.dsm_align_clusters(self._h, K, ioff.ctypes.data, cimg.ctypes.data, poff.ctypes.data, cpid.ctypes.data,
+                                             cxyz.ctypes.data, ooff.ctypes.data, cobs.ctypes.data, opt,
+                                             None if sd is None else sd.ctypes.data, pairs.ctypes.data, cap, ctypes.addressof(npairs),
+                                             ctypes.addressof(anchor), inc.ctypes.data, par.ctypes.data, sim.ctypes.data,
+                                             seps.ctypes.data, ctypes.addressof(nsep), ctypes.addressof(rep)))
+        return {"pairs": pairs[:npairs.value].copy(), "anchor": anchor.value, "in_component": inc[:K].astype(bool),
+                "mst_parent": par[:K].copy(), "s": sim[:K, 0].copy(), "R": sim[:K, 1:10].reshape(K, 3, 3).copy(),
+                "t": sim[:K, 10:13].copy(), "separators": seps[:nsep.value].copy(), "report": rep}
 
     def device_info(self):
         d = DeviceInfo()

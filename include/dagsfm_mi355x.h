@@ -574,6 +574,92 @@ int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs
 int dsm_get_clustering_spectrum(dsm_ctx* ctx, double* values, uint32_t values_capacity, double* vectors, uint64_t vectors_capacity,
                                 uint32_t* n_values, uint32_t* n_rows, uint32_t* n_cols);
 
+/* ------------------------------------------------------------------ cluster alignment
+ * The merge step after every cluster is reconstructed: SfMAligner::Align() (src/controllers/sfm_aligner.cpp:149-228) as
+ * MergeClusters() calls it (distributed_mapper_controller.cpp:742-795), up to the transforms; Reconstruction::Merge stays
+ * with the host application.
+ *   For clusters i < j: the common registered images (all of them go to the separators); the correspondences
+ *   (X(P1) in i, X(P2) in j) of every track element of a point P2 of j on a common image whose point2D carries a point P1 of
+ *   i, ordered by ascending point id of j, then (image_id, point2D_idx).  Pairs with >= 2 common images estimate i -> j and
+ *   j -> i: N > 5 PROSAC (sample 4, MLE cost, Umeyama with scaling) and the refit, 3 <= N <= 5 Umeyama on all N; msd is the
+ *   mean residual over all N; the edge weight max(msd_ij, msd_ji) is kept when <= max_reprojection_error (as float).
+ *   Then the largest component, Kruskal's MST, the anchor (leaves removed layer by layer) and the composed Sim3s.
+ *   Free choices: no edge for N <= 2 (the reference: NaN / a rotation-only LM); the closed form instead of
+ *   Refine_RTS; seeds per (i, j, direction); ties by cluster index. */
+typedef struct dsm_align_options {
+  double threshold;              /* 0.1: PROSAC error_thresh (AlignOptions); <= 0 -> DSM_ERR_INVALID_ARGUMENT */
+  double max_reprojection_error; /* 1.8: larger edge weights are dropped */
+  double failure_probability;    /* 0.01 (RansacParameters); outside (0, 1) -> invalid */
+  int32_t min_iterations;        /* 100 */
+  int32_t max_iterations;        /* 5000; > 5000 or < min_iterations or < 1 -> invalid (PROSAC's index range) */
+  uint32_t random_seed;          /* user part of the per-direction seeds, dsm_align_seed */
+  uint32_t reserved;
+} dsm_align_options;
+
+/* one cluster pair with >= 2 common registered images; direction 0 is i -> j (x_j ~ s R x_i + t), 1 is j -> i */
+typedef struct dsm_align_pair {
+  uint32_t i, j;
+  uint32_t num_common_images;
+  uint32_t num_correspondences;  /* N */
+  uint32_t num_inliers[2];       /* PROSAC's final inliers (N > 5), else 0 */
+  uint32_t iterations[2];        /* PROSAC iterations (N > 5), else 0 */
+  int32_t edge;                  /* 1: an edge of the cluster graph */
+  uint32_t reserved;
+  double msd[2];                 /* mean residual over all N; NaN when N <= 2, DBL_MAX when PROSAC kept < 4 inliers */
+  double weight;                 /* max(msd[0], msd[1]) */
+  double s[2];
+  double R[2][9];                /* row-major */
+  double t[2][3];
+  /* PROSAC's own result before the refit (N > 5; else cost NaN and the identity): the MLE cost of the best model over all
+     N and that model */
+  double prosac_cost[2];
+  double prosac_s[2];
+  double prosac_R[2][9];
+  double prosac_t[2][3];
+} dsm_align_pair;
+
+typedef struct dsm_align_report {
+  uint32_t num_clusters;
+  uint32_t num_pairs;              /* pairs with >= 2 common images (the entries of pairs_out) */
+  uint32_t num_edges;              /* kept edges */
+  uint32_t num_in_component;       /* clusters of the largest component */
+  uint32_t num_prosac_problems;    /* directions with N > 5 */
+  uint32_t num_separators;
+  uint64_t num_observations;
+  uint64_t num_correspondences;    /* summed over every cluster pair that shares an observation */
+  uint64_t prosac_iterations;      /* summed over the PROSAC problems */
+  double min_residual_margin;      /* min |residual - threshold| / threshold over every residual PROSAC scored */
+  double min_cost_margin;          /* min |cost - best| / best over the strict-best tests whose outcome can matter:
+                                      not between two costs without an inlier (both N * threshold); a near-tie between two
+                                      trials of one inlier count counts only when no better model by >= 1e-9 follows it.
+                                      0 means PROSAC's choice may depend on rounding there, not that any output is wrong */
+  double min_weight_margin;        /* min |weight - max_reprojection_error| / max_reprojection_error over the pairs */
+  double device_ms;                /* HIP events: first upload to the last refit kernel */
+  double join_ms, prosac_ms, refit_ms;
+} dsm_align_report;
+
+void dsm_default_align_options(dsm_align_options* o);
+/* the default seed of direction d (0: i -> j, 1: j -> i) of clusters i < j */
+uint32_t dsm_align_seed(uint32_t i, uint32_t j, uint32_t direction, uint32_t user_seed);
+
+/* SfMAligner over K cluster reconstructions, each given as CSR over the clusters (host pointers):
+ *   image_offsets[K + 1], image_ids: the registered images of each cluster (a repeat inside a cluster is ignored)
+ *   point_offsets[K + 1], point_ids, point_xyz (3 doubles per point): the 3D points (ids unique inside a cluster)
+ *   obs_offsets[K + 1], obs (3 x uint32 per track element: image_id, point2D_idx, point index inside the cluster)
+ *   options  NULL = dsm_default_align_options; seeds NULL = dsm_align_seed, else K * K entries, seeds[a * K + b] for a -> b.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT): K == 0 or K > 65536, an observation on an image the cluster has not registered, a point
+ * index out of range, a repeated (image_id, point2D_idx) or point id inside one cluster, options out of range.
+ * Outputs: pairs_out (capacity pairs_capacity; *n_pairs_out = their number, only the first min(number, capacity) written) in
+ *   ascending (i, j); *anchor_out; per cluster in_component, mst_parent (-1: the anchor or outside the component) and
+ *   sim3_to_anchor (13 doubles: s, R row-major, t; the identity outside the component); separators (capacity: the summed
+ *   registered images) sorted ascending, *n_separators_out.  report may be NULL. */
+int dsm_align_clusters(dsm_ctx* ctx, uint32_t num_clusters, const uint32_t* image_offsets, const uint32_t* image_ids,
+                       const uint32_t* point_offsets, const uint64_t* point_ids, const double* point_xyz,
+                       const uint32_t* obs_offsets, const uint32_t* obs, const dsm_align_options* options,
+                       const uint32_t* seeds, dsm_align_pair* pairs_out, uint32_t pairs_capacity, uint32_t* n_pairs_out,
+                       int32_t* anchor_out, uint8_t* in_component, int32_t* mst_parent, double* sim3_to_anchor,
+                       uint32_t* separators, uint32_t* n_separators_out, dsm_align_report* report);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
