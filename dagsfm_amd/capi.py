@@ -138,6 +138,34 @@ class AlignReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BundleAdjustmentOptions(ctypes.Structure):
+    """dsm_bundle_adjustment_options: GlobalBundleAdjustment() / BundleAdjustmentOptions defaults
+    (src/optim/bundle_adjustment.h:70-90, 522-542)."""
+    _fields_ = [("max_num_iterations", ctypes.c_int32), ("max_linear_solver_iterations", ctypes.c_int32),
+                ("gradient_tolerance", ctypes.c_double), ("function_tolerance", ctypes.c_double),
+                ("parameter_tolerance", ctypes.c_double), ("max_num_consecutive_invalid_steps", ctypes.c_int32),
+                ("refine_focal_length", ctypes.c_int32), ("refine_principal_point", ctypes.c_int32),
+                ("refine_extra_params", ctypes.c_int32)]
+
+
+class BundleAdjustmentReport(ctypes.Structure):
+    _fields_ = [("termination", ctypes.c_int32), ("num_iterations", ctypes.c_int32), ("num_successful_steps", ctypes.c_int32),
+                ("num_invalid_steps", ctypes.c_int32), ("num_residuals", ctypes.c_uint64),
+                ("num_effective_parameters", ctypes.c_uint64), ("total_cg_iterations", ctypes.c_uint64),
+                ("initial_cost", ctypes.c_double), ("final_cost", ctypes.c_double),
+                ("initial_mean_reprojection_error", ctypes.c_double), ("final_mean_reprojection_error", ctypes.c_double),
+                ("min_rho_margin", ctypes.c_double), ("min_cg_margin", ctypes.c_double), ("min_gradient_margin", ctypes.c_double),
+                ("setup_ms", ctypes.c_double), ("jacobian_ms", ctypes.c_double), ("cg_ms", ctypes.c_double),
+                ("candidate_ms", ctypes.c_double), ("total_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+BA_CONVERGENCE, BA_NO_CONVERGENCE, BA_FAILURE = 0, 1, 2
+BA_TRACE_COLUMNS = 6  # cost, radius, rho, CG iterations, accepted, gradient max-norm
+
+
 # dsm_align_pair as a numpy record (the C layout: no padding beyond the explicit `reserved`)
 ALIGN_PAIR_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("num_common_images", "<u4"), ("num_correspondences", "<u4"),
                              ("num_inliers", "<u4", (2,)), ("iterations", "<u4", (2,)), ("edge", "<i4"), ("reserved", "<u4"),
@@ -205,6 +233,10 @@ def lib(check=False):
         L.dsm_align_seed.restype = ctypes.c_uint32
         L.dsm_align_clusters.argtypes = ([vp, ctypes.c_uint32] + [vp] * 7 + [ctypes.POINTER(AlignOptions), vp, vp, ctypes.c_uint32]
                                          + [vp] * 8)
+        L.dsm_default_bundle_adjustment_options.argtypes = [ctypes.POINTER(BundleAdjustmentOptions)]
+        L.dsm_default_bundle_adjustment_options.restype = None
+        L.dsm_bundle_adjust.argtypes = ([vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32] + [vp] * 5 + [ctypes.c_uint32] + [vp] * 6
+                                        + [ctypes.POINTER(BundleAdjustmentOptions), vp, vp])
         L.dsm_debug_image_to_world.argtypes = [vp, ctypes.POINTER(Camera), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double)]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
@@ -273,6 +305,14 @@ def default_clustering_options(**kw):
 def default_align_options(**kw):
     o = AlignOptions()
     lib().dsm_default_align_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_bundle_adjustment_options(**kw):
+    o = BundleAdjustmentOptions()
+    lib().dsm_default_bundle_adjustment_options(ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -690,6 +730,37 @@ class Context:
         return {"pairs": pairs[:npairs.value].copy(), "anchor": anchor.value, "in_component": inc[:K].astype(bool),
                 "mst_parent": par[:K].copy(), "s": sim[:K, 0].copy(), "R": sim[:K, 1:10].reshape(K, 3, 3).copy(),
                 "t": sim[:K, 10:13].copy(), "separators": seps[:nsep.value].copy(), "report": rep}
+
+    def bundle_adjust(self, scene, options=None, trace=True):
+        """dsm_bundle_adjust.  scene: a dict with camera_model_ids [C], camera_params (each camera's parameters
+        back to back), image_camera [N], qvec [N, 4], tvec [N, 3], image_constant_pose [N] (optional), image_constant_tvec [N]
+        (optional, bit mask), point_ids [P] (uint64), xyz [P, 3], point_constant [P] (optional), track_offsets [P + 1],
+        obs_image [n], obs_xy [n, 2].  The inputs are not modified.  Returns a dict: camera_params, qvec, tvec, xyz (updated),
+        report, trace ([iterations + 1, 6]: cost, radius, rho, CG iterations, accepted, gradient max-norm)."""
+        arr = lambda key, dt, shape=-1: np.array(scene[key], dtype=dt, copy=True).reshape(shape)
+        opt_u8 = lambda key, n: None if scene.get(key) is None else np.ascontiguousarray(scene[key], np.uint8).reshape(n)
+        models = arr("camera_model_ids", np.int32)
+        params = arr("camera_params", np.float64)
+        icam = arr("image_camera", np.uint32)
+        N = len(icam)
+        qvec, tvec = arr("qvec", np.float64, (N, 4)), arr("tvec", np.float64, (N, 3))
+        pids = arr("point_ids", np.uint64)
+        P = len(pids)
+        xyz = arr("xyz", np.float64, (P, 3))
+        toff = arr("track_offsets", np.uint32)
+        oimg, oxy = arr("obs_image", np.uint32), arr("obs_xy", np.float64, (-1, 2))
+        cpose, cmask, pconst = opt_u8("image_constant_pose", N), opt_u8("image_constant_tvec", N), opt_u8("point_constant", P)
+        o = options if options is not None else default_bundle_adjustment_options()
+        tr = np.full((max(int(o.max_num_iterations), 0) + 1, BA_TRACE_COLUMNS), np.nan) if trace else None
+        rep = BundleAdjustmentReport()
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._chk(self._L.dsm_bundle_adjust(self._h, len(models), ptr(models), ptr(params), N, ptr(icam), ptr(qvec), ptr(tvec),
+                                            ptr(cpose), ptr(cmask), P, ptr(pids), ptr(xyz), ptr(pconst), ptr(toff), ptr(oimg),
+                                            ptr(oxy), ctypes.byref(o), ctypes.addressof(rep), ptr(tr)))
+        out = {"camera_params": params, "qvec": qvec, "tvec": tvec, "xyz": xyz, "report": rep}
+        if trace:
+            out["trace"] = tr[:rep.num_iterations + 1].copy()
+        return out
 
     def device_info(self):
         d = DeviceInfo()

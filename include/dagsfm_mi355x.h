@@ -660,6 +660,74 @@ int dsm_align_clusters(dsm_ctx* ctx, uint32_t num_clusters, const uint32_t* imag
                        int32_t* anchor_out, uint8_t* in_component, int32_t* mst_parent, double* sim3_to_anchor,
                        uint32_t* separators, uint32_t* n_separators_out, dsm_align_report* report);
 
+/* ------------------------------------------------------------------ global bundle adjustment
+ * Step 8 of DistributedMapperController::Run(), AdjustGlobalBundle() (src/controllers/distributed_mapper_controller.cpp:
+ * 836-931): BundleAdjuster::Solve() over the merged reconstruction with the ITERATIVE_SCHUR + SCHUR_JACOBI branch
+ * (src/optim/bundle_adjustment.cc:273-284) at every size.
+ *   Residual: BundleAdjustmentCostFunction (src/base/cost_functions.h:45-85): UnitQuaternionRotatePoint(qvec, X) + tvec,
+ *   divided by z, CameraModel::WorldToImage (src/base/camera_models.h), minus the observation; the trivial loss.
+ *   Blocks (bundle_adjustment.cc:330-456): qvec with QuaternionParameterization (normalised first, :345), tvec with a
+ *   subset parameterisation of the constant-tvec mask, constant pose -> both constant; camera params with a subset
+ *   parameterisation of the indices the refine flags keep (ParameterizeCameras), all three flags off -> constant; a constant
+ *   point keeps its residuals with a fixed block.  Images and cameras without residuals are not in the problem and come back
+ *   bit-identical.
+ *   Minimiser: Levenberg-Marquardt trust region with Jacobi scaling, the Schur complement over the variable points solved
+ *   by Jacobi-block-preconditioned CG (rules in DESIGN.md 12). */
+enum { DSM_BA_CONVERGENCE = 0, DSM_BA_NO_CONVERGENCE = 1, DSM_BA_FAILURE = 2 };  /* ceres::TerminationType names */
+
+typedef struct dsm_bundle_adjustment_options {
+  int32_t max_num_iterations;                /* 50 (GlobalBundleAdjustment(), bundle_adjustment.h:522-542); >= 0 */
+  int32_t max_linear_solver_iterations;      /* 100 (BundleAdjustmentOptions ctor, bundle_adjustment.h:70-90); >= 1 */
+  double gradient_tolerance;                 /* 1.0 */
+  double function_tolerance;                 /* 0 */
+  double parameter_tolerance;                /* 0 */
+  int32_t max_num_consecutive_invalid_steps; /* 10 (Solver::Options); >= 0 */
+  int32_t refine_focal_length;               /* 1 */
+  int32_t refine_principal_point;            /* 0 */
+  int32_t refine_extra_params;               /* 1 */
+} dsm_bundle_adjustment_options;
+
+typedef struct dsm_bundle_adjustment_report {
+  int32_t termination;                /* DSM_BA_CONVERGENCE / DSM_BA_NO_CONVERGENCE / DSM_BA_FAILURE */
+  int32_t num_iterations;             /* LM iterations after iteration 0, accepted or not */
+  int32_t num_successful_steps;
+  int32_t num_invalid_steps;
+  uint64_t num_residuals;             /* 2 x observations */
+  uint64_t num_effective_parameters;  /* tangent dimensions of the variable blocks */
+  uint64_t total_cg_iterations;
+  double initial_cost, final_cost;    /* 1/2 sum |r|^2 over every observation */
+  double initial_mean_reprojection_error, final_mean_reprojection_error;  /* mean |r| */
+  /* the smallest margin of every decision a rounding difference could flip (DBL_MAX when never taken): the acceptance test
+     rho > 1e-3 as |(cost - candidate_cost) - 1e-3 model_cost_change| / cost; the CG stop test and the gradient test as
+     |a - t| / max(|a|, |t|) against eta = 0.1 and gradient_tolerance */
+  double min_rho_margin, min_cg_margin, min_gradient_margin;
+  double setup_ms;                    /* host validation, canonical sort and upload (host clock) */
+  double jacobian_ms, cg_ms, candidate_ms, total_ms;  /* HIP events */
+} dsm_bundle_adjustment_report;
+
+#define DSM_BA_TRACE_COLUMNS 6  /* per iteration: cost, radius, rho, CG iterations, accepted, gradient max-norm */
+
+void dsm_default_bundle_adjustment_options(dsm_bundle_adjustment_options* o);
+
+/* Bundle adjustment in place (host pointers):
+ *   cameras: camera_model_ids[num_cameras] (the eleven models), camera_params: each camera's parameters back to back in
+ *     camera order (CameraModel::kNumParams of its model each)
+ *   images: image_camera[num_images], image_qvec (4 per image, w x y z), image_tvec (3), image_constant_pose (NULL = none),
+ *     image_constant_tvec (NULL = none; bit k: tvec[k] constant)
+ *   points: point_ids (unique), point_xyz (3), point_constant (NULL = none), track_offsets[num_points + 1], obs_image[n],
+ *     obs_xy[2 n] (n = track_offsets[num_points])
+ *   options NULL = dsm_default_bundle_adjustment_options; report may be NULL; trace NULL or (max_num_iterations + 1) x
+ *     DSM_BA_TRACE_COLUMNS doubles (rows past the last iteration untouched).
+ * Invalid (DSM_ERR_INVALID_ARGUMENT): an unknown model, an out-of-range index, a track shorter than 2, one image observing one
+ *   point twice, a repeated point id, non-finite input, a zero qvec, a mask above 7, no residuals, options out of range.
+ * The result is the same bytes for every order of the points and of the elements inside a track. */
+int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32_t* camera_model_ids, double* camera_params,
+                      uint32_t num_images, const uint32_t* image_camera, double* image_qvec, double* image_tvec,
+                      const uint8_t* image_constant_pose, const uint8_t* image_constant_tvec, uint32_t num_points,
+                      const uint64_t* point_ids, double* point_xyz, const uint8_t* point_constant, const uint32_t* track_offsets,
+                      const uint32_t* obs_image, const double* obs_xy, const dsm_bundle_adjustment_options* options,
+                      dsm_bundle_adjustment_report* report, double* trace);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
