@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ba_project.h"
+#include "block_reduce.h"
 #include "ctx.h"
 
 namespace {
@@ -70,46 +71,6 @@ __device__ inline double margin(double a, double thr) {
   if (!isfinite(a)) return DBL_MAX;
   const double den = fmax(fabs(a), fabs(thr));
   return den > 0.0 ? fabs(a - thr) / den : 0.0;
-}
-
-// ---------------------------------------------------------------- fixed-order reductions
-template <int BS>
-__device__ inline void tree(double* sh, int K) {  // sh[v * BS + t]: K columns, summed into sh[v * BS]
-  for (int s = BS / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-      for (int v = 0; v < K; ++v) sh[v * BS + threadIdx.x] += sh[v * BS + threadIdx.x + s];
-    __syncthreads();
-  }
-}
-__device__ inline double block_sum(double v, double* sh) {  // BA_B threads
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  tree<BA_B>(sh, 1);
-  const double out = sh[0];
-  __syncthreads();
-  return out;
-}
-__device__ inline double block_max(double v, double* sh) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = BA_B / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
-    __syncthreads();
-  }
-  const double out = sh[0];
-  __syncthreads();
-  return out;
-}
-// the n partials P[0..n) summed by one BA_B block: thread t takes t, t + BA_B, ... in order, then the tree
-__device__ inline double sum_partials(const double* P, uint32_t n, double* sh) {
-  double s = 0.0;
-  for (uint32_t i = threadIdx.x; i < n; i += BA_B) s += P[i];
-  return block_sum(s, sh);
-}
-__device__ inline double max_partials(const double* P, uint32_t n, double* sh) {
-  double s = 0.0;
-  for (uint32_t i = threadIdx.x; i < n; i += BA_B) s = fmax(s, P[i]);
-  return block_max(s, sh);
 }
 
 // ---------------------------------------------------------------- small dense algebra
@@ -251,7 +212,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_eval(BaDev d, int mode) {
     cost = 0.5 * s2;
     nrm = sqrt(s2);
   }
-  const double a = block_sum(cost, sh), b = block_sum(nrm, sh);
+  const double a = block_sum<BA_B>(cost, sh), b = block_sum<BA_B>(nrm, sh);
   if (threadIdx.x == 0) {
     d.Pc[blockIdx.x] = a;
     d.Pc[gridDim.x + blockIdx.x] = b;
@@ -263,7 +224,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_fin_cost(BaDev d, uint32_t nblk, in
   __shared__ double sh[BA_B];
   BaCtl* c = d.ctl;
   if (which == 1 && c->done) return;
-  const double a = sum_partials(d.Pc, nblk, sh), b = sum_partials(d.Pc + nblk, nblk, sh);
+  const double a = sum_partials<BA_B>(d.Pc, nblk, sh), b = sum_partials<BA_B>(d.Pc + nblk, nblk, sh);
   if (threadIdx.x) return;
   if (which == 0) {
     c->cost = a;
@@ -298,7 +259,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_grad_pts(BaDev d, int gate) {
       gm = fmax(gm, fabs(x - (x + -g[j])));
     }
   }
-  gm = block_max(gm, sh);
+  gm = block_max<BA_B>(gm, sh);
   if (threadIdx.x == 0) d.Pg[blockIdx.x] = gm;
 }
 
@@ -326,7 +287,7 @@ __global__ void __launch_bounds__(BA_W) k_ba_grad_img(BaDev d, int gate, uint32_
     }
   }
   __syncthreads();
-  tree<BA_W>(sh, 36);
+  block_tree<BA_W>(sh, 36);
   if (t) return;
   double gm = 0.0;
   for (int j = 0; j < 6; ++j) {
@@ -363,7 +324,7 @@ __global__ void __launch_bounds__(BA_W) k_ba_grad_cam(BaDev d, int gate, uint32_
     }
   }
   __syncthreads();
-  tree<BA_W>(sh, 24);
+  block_tree<BA_W>(sh, 24);
   if (t) return;
   double gm = 0.0;
   const uint32_t fo = d.cam_foff[c];
@@ -498,7 +459,7 @@ __global__ void __launch_bounds__(BA_W) k_ba_prep_img(BaDev d) {
     }
   }
   __syncthreads();
-  tree<BA_W>(sh, PI_N);
+  block_tree<BA_W>(sh, PI_N);
   if (t) return;
   const double radius = d.ctl->radius;
   for (int blk = 0; blk < 2; ++blk) {
@@ -531,7 +492,7 @@ __global__ void __launch_bounds__(BA_W) k_ba_prep_cam(BaDev d) {
     for (int v = 0; v < nv; ++v) sh[v * BA_W + t] += row[v];
   }
   __syncthreads();
-  tree<BA_W>(sh, nv);
+  block_tree<BA_W>(sh, nv);
   if (t) return;
   const double radius = d.ctl->radius;
   const uint32_t fo = d.cam_foff[c];
@@ -558,14 +519,14 @@ __global__ void __launch_bounds__(BA_B) k_ba_cg_init(BaDev d) {
     d.r[j] = bj;
     s = bj * bj;
   }
-  s = block_sum(s, sh);
+  s = block_sum<BA_B>(s, sh);
   if (threadIdx.x == 0) d.Pq[blockIdx.x] = s;
 }
 __global__ void __launch_bounds__(BA_B) k_ba_cg_init_fin(BaDev d, uint32_t nblk) {
   __shared__ double sh[BA_B];
   BaCtl* c = d.ctl;
   if (c->done) return;
-  const double bb = sum_partials(d.Pq, nblk, sh);
+  const double bb = sum_partials<BA_B>(d.Pq, nblk, sh);
   if (threadIdx.x) return;
   c->cg_fail = 0;
   c->cg_iters = 0;
@@ -601,7 +562,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_cg_z(BaDev d, int k) {
       s += d.r[fo + m] * zm;
     }
   }
-  s = block_sum(s, sh);
+  s = block_sum<BA_B>(s, sh);
   if (threadIdx.x == 0) d.Pq[blockIdx.x] = s;
 }
 __device__ inline bool zero_or_inf(double x) { return x == 0.0 || isinf(x); }
@@ -609,7 +570,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_cg_fin_rz(BaDev d, uint32_t nblk, i
   __shared__ double sh[BA_B];
   BaCtl* c = d.ctl;
   if (cg_gated(c, k)) return;
-  const double rho = sum_partials(d.Pq, nblk, sh);
+  const double rho = sum_partials<BA_B>(d.Pq, nblk, sh);
   if (threadIdx.x) return;
   const double last = c->rho;
   c->rho = rho;
@@ -685,7 +646,7 @@ __global__ void __launch_bounds__(BA_W) k_ba_Sv_img(BaDev d, const double* __res
     for (int j = 0; j < kc; ++j) a[(6 + j) * BA_W] += Jo[J_C + j] * w0 + Jo[J_C + BA_KMAX + j] * w1;
   }
   __syncthreads();
-  tree<BA_W>(sh, 18);
+  block_tree<BA_W>(sh, 18);
   if (t) return;
   double dot = 0.0;
   for (int m = 0; m < 6; ++m) {
@@ -708,7 +669,7 @@ __global__ void __launch_bounds__(BA_W) k_ba_Sv_cam(BaDev d, const double* __res
     for (int j = 0; j < kc; ++j) sh[j * BA_W + t] += row[j];
   }
   __syncthreads();
-  tree<BA_W>(sh, kc);
+  block_tree<BA_W>(sh, kc);
   if (t) return;
   double dot = 0.0;
   const uint32_t fo = d.cam_foff[c];
@@ -723,7 +684,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_cg_fin_pq(BaDev d, int k) {
   __shared__ double sh[BA_B];
   BaCtl* c = d.ctl;
   if (cg_gated(c, k)) return;
-  const double pq = sum_partials(d.Pd, d.n_img + d.n_cam, sh);
+  const double pq = sum_partials<BA_B>(d.Pd, d.n_img + d.n_cam, sh);
   if (threadIdx.x) return;
   if (pq <= 0.0 || isinf(pq) || isnan(pq)) {
     c->cg_fail = 2;
@@ -752,7 +713,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_cg_x(BaDev d, int k, int reset) {
       s = xj * (d.b[j] + rj);
     }
   }
-  s = block_sum(s, sh);
+  s = block_sum<BA_B>(s, sh);
   if (threadIdx.x == 0 && !reset) d.Pq[blockIdx.x] = s;
 }
 // every residual_reset_period = 10 iterations: r = b - S x
@@ -766,7 +727,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_cg_reset(BaDev d, int k) {
     d.r[j] = rj;
     s = d.x[j] * (d.b[j] + rj);
   }
-  s = block_sum(s, sh);
+  s = block_sum<BA_B>(s, sh);
   if (threadIdx.x == 0) d.Pq[blockIdx.x] = s;
 }
 // Q1 = -x.(b + r); stop when k (Q1 - Q0) / Q1 < eta or at the iteration cap
@@ -774,7 +735,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_cg_fin_q(BaDev d, uint32_t nblk, in
   __shared__ double sh[BA_B];
   BaCtl* c = d.ctl;
   if (cg_gated(c, k)) return;
-  const double Q1 = -sum_partials(d.Pq, nblk, sh);
+  const double Q1 = -sum_partials<BA_B>(d.Pq, nblk, sh);
   if (threadIdx.x) return;
   const double zeta = k * (Q1 - c->Q0) / Q1;
   c->m_cg = fmin(c->m_cg, margin(zeta, kEta));
@@ -820,7 +781,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_backsub(BaDev d) {
       }
     }
   }
-  const double a = block_sum(s2, sh), b = block_sum(x2, sh);
+  const double a = block_sum<BA_B>(s2, sh), b = block_sum<BA_B>(x2, sh);
   if (threadIdx.x == 0) {
     d.Pe[blockIdx.x] = a;
     d.Pe[gridDim.x + blockIdx.x] = b;
@@ -876,7 +837,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_cand_f(BaDev d) {
       s2 += dl * dl;
     }
   }
-  const double a = block_sum(s2, sh), b = block_sum(x2, sh);
+  const double a = block_sum<BA_B>(s2, sh), b = block_sum<BA_B>(x2, sh);
   if (threadIdx.x == 0) {
     d.Pd[blockIdx.x] = a;
     d.Pd[gridDim.x + blockIdx.x] = b;
@@ -896,7 +857,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_mcc(BaDev d) {
       s += js * (Jo[J_R + row] + js / 2.0);
     }
   }
-  s = block_sum(s, sh);
+  s = block_sum<BA_B>(s, sh);
   if (threadIdx.x == 0) d.Pm[blockIdx.x] = s;
 }
 
@@ -905,9 +866,9 @@ __global__ void __launch_bounds__(BA_B) k_ba_decide(BaDev d, uint32_t nb_obs, ui
   __shared__ double sh[BA_B];
   BaCtl* c = d.ctl;
   if (c->done) return;
-  const double mcc = -sum_partials(d.Pm, nb_obs, sh);
-  const double s2 = sum_partials(d.Pe, nb_pts, sh) + sum_partials(d.Pd, nb_f, sh);
-  const double x2 = sum_partials(d.Pe + nb_pts, nb_pts, sh) + sum_partials(d.Pd + nb_f, nb_f, sh);
+  const double mcc = -sum_partials<BA_B>(d.Pm, nb_obs, sh);
+  const double s2 = sum_partials<BA_B>(d.Pe, nb_pts, sh) + sum_partials<BA_B>(d.Pd, nb_f, sh);
+  const double x2 = sum_partials<BA_B>(d.Pe + nb_pts, nb_pts, sh) + sum_partials<BA_B>(d.Pd + nb_f, nb_f, sh);
   if (threadIdx.x) return;
   c->iter += 1;
   c->mcc = mcc;
@@ -980,7 +941,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_finalize(BaDev d, uint32_t n_gparts
   if (latched) return;
   const bool fresh = first || (accepted && !done);
   double gm = 0.0;
-  if (fresh) gm = max_partials(d.Pg, n_gparts, sh);
+  if (fresh) gm = max_partials<BA_B>(d.Pg, n_gparts, sh);
   if (threadIdx.x) return;
   if (fresh) c->gnorm = gm;
   if (!done) {
@@ -1044,14 +1005,10 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
                                  const uint32_t* track_offsets, const uint32_t* obs_image, const double* obs_xy,
                                  const dsm_bundle_adjustment_options* options, dsm_bundle_adjustment_report* report, double* trace) {
   const auto t_start = std::chrono::steady_clock::now();
-  auto fail = [&](int code, const char* msg) {
-    if (ctx) ctx->err = msg;
-    return code;
-  };
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
   if (!track_offsets || (num_cameras && (!camera_model_ids || !camera_params)) ||
       (num_images && (!image_camera || !image_qvec || !image_tvec)) || (num_points && (!point_ids || !point_xyz)))
-    return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: NULL argument");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: NULL argument");
   dsm_bundle_adjustment_options o;
   if (options) o = *options;
   else dsm_default_bundle_adjustment_options(&o);
@@ -1059,53 +1016,53 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
   if (o.max_num_iterations < 0 || o.max_num_iterations > 1000000 || o.max_linear_solver_iterations < 1 ||
       o.max_linear_solver_iterations > 1000000 || !fin_nonneg(o.gradient_tolerance) || !fin_nonneg(o.function_tolerance) ||
       !fin_nonneg(o.parameter_tolerance) || o.max_num_consecutive_invalid_steps < 0)
-    return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: option out of range");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: option out of range");
   const uint32_t C = num_cameras, N = num_images, P = num_points;
-  if (track_offsets[0] != 0) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: track_offsets must start at 0");
+  if (track_offsets[0] != 0) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: track_offsets must start at 0");
   const uint64_t n_obs64 = track_offsets[P];
   if (n_obs64 >= (1ull << 31) || (n_obs64 && (!obs_image || !obs_xy)))
-    return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: bad observation count");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: bad observation count");
   const uint32_t n_obs = (uint32_t)n_obs64;
   // ---- validation
   BaProblem pb;
   std::vector<uint32_t> poff(C + 1, 0);
   pb.cam_np.resize(C);
   for (uint32_t c = 0; c < C; ++c) {
-    if (!cam_model_exists(camera_model_ids[c])) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: unknown camera model");
+    if (!cam_model_exists(camera_model_ids[c])) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: unknown camera model");
     pb.cam_np[c] = cam_num_params(camera_model_ids[c]);
     poff[c + 1] = poff[c] + pb.cam_np[c];
   }
   const uint32_t n_prm = poff[C];
   for (uint32_t j = 0; j < n_prm; ++j)
-    if (!std::isfinite(camera_params[j])) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: non-finite camera parameter");
+    if (!std::isfinite(camera_params[j])) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: non-finite camera parameter");
   for (uint32_t i = 0; i < N; ++i) {
-    if (image_camera[i] >= C) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: image camera index out of range");
+    if (image_camera[i] >= C) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: image camera index out of range");
     const double* q = image_qvec + 4 * (size_t)i;
     bool fin = true;
     for (int m = 0; m < 4; ++m) fin = fin && std::isfinite(q[m]);
     for (int m = 0; m < 3; ++m) fin = fin && std::isfinite(image_tvec[3 * (size_t)i + m]);
-    if (!fin) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: non-finite qvec or tvec");
-    if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: zero qvec");
-    if (image_constant_tvec && image_constant_tvec[i] > 7) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: constant-tvec mask above 7");
+    if (!fin) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: non-finite qvec or tvec");
+    if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: zero qvec");
+    if (image_constant_tvec && image_constant_tvec[i] > 7) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: constant-tvec mask above 7");
   }
   for (uint32_t p = 0; p < P; ++p) {
-    if ((uint64_t)track_offsets[p + 1] < (uint64_t)track_offsets[p] + 2) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: track shorter than 2");
+    if ((uint64_t)track_offsets[p + 1] < (uint64_t)track_offsets[p] + 2) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: track shorter than 2");
     for (int m = 0; m < 3; ++m)
-      if (!std::isfinite(point_xyz[3 * (size_t)p + m])) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: non-finite point");
+      if (!std::isfinite(point_xyz[3 * (size_t)p + m])) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: non-finite point");
   }
   for (uint32_t a = 0; a < n_obs; ++a) {
-    if (obs_image[a] >= N) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: observation image index out of range");
+    if (obs_image[a] >= N) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: observation image index out of range");
     if (!std::isfinite(obs_xy[2 * (size_t)a]) || !std::isfinite(obs_xy[2 * (size_t)a + 1]))
-      return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: non-finite observation");
+      return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: non-finite observation");
   }
-  if (n_obs == 0) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: no residuals");
+  if (n_obs == 0) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: no residuals");
   // ---- canonical order: points by id; observations image-major by (image, point rank) (a counting pass over the points in
   // rank order); tracks by (camera, image) (a counting pass over the observations in camera, image order)
   std::vector<uint32_t> order(P);
   std::iota(order.begin(), order.end(), 0u);
   std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return point_ids[a] < point_ids[b]; });
   for (uint32_t r = 1; r < P; ++r)
-    if (point_ids[order[r]] == point_ids[order[r - 1]]) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: repeated point id");
+    if (point_ids[order[r]] == point_ids[order[r - 1]]) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: repeated point id");
   pb.img_off.assign(N + 1, 0);
   for (uint32_t a = 0; a < n_obs; ++a) ++pb.img_off[obs_image[a] + 1];
   for (uint32_t i = 0; i < N; ++i) pb.img_off[i + 1] += pb.img_off[i];
@@ -1127,7 +1084,7 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
   }
   for (uint32_t i = 0; i < N; ++i)
     for (uint32_t o = pb.img_off[i] + 1; o < pb.img_off[i + 1]; ++o)
-      if (pb.o_pt[o] == pb.o_pt[o - 1]) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: an image observes a point twice");
+      if (pb.o_pt[o] == pb.o_pt[o - 1]) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: an image observes a point twice");
   // cameras in the problem, their images, free parameters and f-layout
   pb.cam_img_off.assign(C + 1, 0);
   for (uint32_t i = 0; i < N; ++i)
@@ -1212,7 +1169,7 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
 
   // ---- device
   hipError_t he = hipSetDevice(ctx->device);
-  if (he != hipSuccess) return fail(DSM_ERR_HIP, hipGetErrorString(he));
+  if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   const uint32_t nb_obs = (n_obs + BA_B - 1) / BA_B, nb_pts = std::max<uint32_t>(1, (P + BA_B - 1) / BA_B);
   const uint32_t nf = pb.nf, nb_f = std::max<uint32_t>(1, (nf + BA_B - 1) / BA_B);
@@ -1222,26 +1179,18 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
   const uint32_t n_gparts = nb_pts + N + C;
   const size_t nfa = (size_t)nf + 1;
   const uint32_t nb_fpart = std::max(nb_f, std::max(nb_blk, nb_ent));
+  std::vector<uint32_t> img_cam(image_camera, image_camera + N);  // an upload's source: declared before the buffers, it outlives them
   DevBuf b_oimg, b_opt, b_orun, b_imgoff, b_trkoff, b_trk, b_camimgoff, b_camimgs, b_imgcam, b_campoff, b_camfoff, b_cammoff, b_oxy,
       b_cpose, b_mask, b_ptvar, b_cammodel, b_camnp, b_camk, b_camfree, b_q, b_t, b_X, b_prm, b_cq, b_ct, b_cX, b_cprm, b_J, b_y,
       b_ge, b_cne, b_se, b_De, b_Cinv, b_ve, b_zp, b_dy, b_gf, b_cnf, b_sf, b_Df, b_ddf, b_Minv, b_b, b_x, b_r, b_z, b_p, b_qv,
       b_tmp, b_icam, b_Pc, b_Pm, b_Pg, b_Pe, b_Pd, b_Pq, b_ctl, b_trace;
-  hipEvent_t ev[6] = {};  // jacobian(first): 0-1; per LM iteration: 2 CG 3 candidate 4 Jacobian 5
+  DevEvent ev[6];  // jacobian(first): 0-1; per LM iteration: 2 CG 3 candidate 4 Jacobian 5
   int rc = DSM_OK;
-#define BTRY(call)                                                  \
-  do {                                                              \
-    hipError_t e_ = (call);                                         \
-    if (e_ != hipSuccess && rc == DSM_OK) {                         \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); \
-      rc = DSM_ERR_HIP;                                             \
-    }                                                               \
-  } while (0)
   auto up = [&](DevBuf& b, const void* src, size_t bytes) {
-    BTRY(b.reserve(std::max<size_t>(bytes, 8)));
-    if (rc == DSM_OK && bytes) BTRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
+    HIPTRY(b.reserve(std::max<size_t>(bytes, 8)));
+    if (rc == DSM_OK && bytes) HIPTRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
   };
-  auto alloc = [&](DevBuf& b, size_t bytes) { BTRY(b.reserve(std::max<size_t>(bytes, 8))); };
-  std::vector<uint32_t> img_cam(image_camera, image_camera + N);
+  auto alloc = [&](DevBuf& b, size_t bytes) { HIPTRY(b.reserve(std::max<size_t>(bytes, 8))); };
   up(b_oimg, pb.o_img.data(), 4 * (size_t)n_obs);
   up(b_opt, pb.o_pt.data(), 4 * (size_t)n_obs);
   up(b_orun, pb.o_run.data(), 8 * (size_t)n_obs);
@@ -1286,7 +1235,7 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
   alloc(b_ctl, sizeof(BaCtl));
   const int max_iter = o.max_num_iterations;
   if (trace) alloc(b_trace, 8 * (size_t)DSM_BA_TRACE_COLUMNS * ((size_t)max_iter + 1));
-  for (auto& e : ev) BTRY(hipEventCreate(&e));
+  for (auto& e : ev) HIPTRY(hipEventCreate(&e.e));
   BaCtl init{};
   init.radius = 1e4;
   init.dec = 2.0;
@@ -1338,15 +1287,15 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
   float ms_jac = 0.f, ms_cg = 0.f, ms_cand = 0.f, ms_total = 0.f;
   BaCtl h{};
   if (rc == DSM_OK) {
-    BTRY(hipEventRecord(ev[0], st));
+    HIPTRY(hipEventRecord(ev[0], st));
     jacobian(1);
-    BTRY(hipGetLastError());  // a launch that failed to start
-    BTRY(hipEventRecord(ev[1], st));
-    BTRY(hipMemcpyAsync(&h, d.ctl, sizeof(BaCtl), hipMemcpyDeviceToHost, st));
-    BTRY(hipStreamSynchronize(st));
+    HIPTRY(hipGetLastError());  // a launch that failed to start
+    HIPTRY(hipEventRecord(ev[1], st));
+    HIPTRY(hipMemcpyAsync(&h, d.ctl, sizeof(BaCtl), hipMemcpyDeviceToHost, st));
+    HIPTRY(hipStreamSynchronize(st));
     if (rc == DSM_OK) {
       float ms = 0.f;
-      BTRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+      HIPTRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
       ms_jac += ms;
       ms_total += ms;
       if (!std::isfinite(h.cost)) {  // the initial evaluation failed
@@ -1357,7 +1306,7 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
   }
   const double initial_cost = h.cost, initial_reproj = h.reproj;
   while (rc == DSM_OK && !h.done) {
-    BTRY(hipEventRecord(ev[2], st));
+    HIPTRY(hipEventRecord(ev[2], st));
     hipLaunchKernelGGL(k_ba_prep_pts, dim3(nb_pts), B, 0, st, d);
     hipLaunchKernelGGL(k_ba_prep_img, dim3(N), W, 0, st, d);
     if (C) hipLaunchKernelGGL(k_ba_prep_cam, dim3(C), W, 0, st, d);
@@ -1378,7 +1327,7 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
         }
         hipLaunchKernelGGL(k_ba_cg_fin_q, dim3(1), B, 0, st, d, nb_f, k);
       }
-    BTRY(hipEventRecord(ev[3], st));
+    HIPTRY(hipEventRecord(ev[3], st));
     hipLaunchKernelGGL(k_ba_Fv, dim3(nb_obs), B, 0, st, d, (const double*)d.x, 0);
     hipLaunchKernelGGL(k_ba_backsub, dim3(nb_pts), B, 0, st, d);
     hipLaunchKernelGGL(k_ba_cand_f, dim3(nb_ent), B, 0, st, d);
@@ -1388,17 +1337,17 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
     hipLaunchKernelGGL(k_ba_decide, dim3(1), B, 0, st, d, nb_obs, nb_pts, nb_ent);
     hipLaunchKernelGGL(k_ba_commit, dim3(nb_commit), B, 0, st, d);
     hipLaunchKernelGGL(k_ba_commit_prm, dim3((n_prm + BA_B - 1) / BA_B + 1), B, 0, st, d, n_prm);
-    BTRY(hipEventRecord(ev[4], st));
+    HIPTRY(hipEventRecord(ev[4], st));
     jacobian(0);
-    BTRY(hipGetLastError());
-    BTRY(hipEventRecord(ev[5], st));
-    BTRY(hipMemcpyAsync(&h, d.ctl, sizeof(BaCtl), hipMemcpyDeviceToHost, st));
-    BTRY(hipStreamSynchronize(st));
+    HIPTRY(hipGetLastError());
+    HIPTRY(hipEventRecord(ev[5], st));
+    HIPTRY(hipMemcpyAsync(&h, d.ctl, sizeof(BaCtl), hipMemcpyDeviceToHost, st));
+    HIPTRY(hipStreamSynchronize(st));
     if (rc != DSM_OK) break;
     float a = 0.f, b2 = 0.f, c2 = 0.f;
-    BTRY(hipEventElapsedTime(&a, ev[2], ev[3]));
-    BTRY(hipEventElapsedTime(&b2, ev[3], ev[4]));
-    BTRY(hipEventElapsedTime(&c2, ev[4], ev[5]));
+    HIPTRY(hipEventElapsedTime(&a, ev[2], ev[3]));
+    HIPTRY(hipEventElapsedTime(&b2, ev[3], ev[4]));
+    HIPTRY(hipEventElapsedTime(&c2, ev[4], ev[5]));
     ms_cg += a;
     ms_cand += b2;
     ms_jac += c2;
@@ -1406,16 +1355,16 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
   }
   if (rc == DSM_OK) {
     std::vector<double> Xo(3 * (size_t)P), qo(4 * (size_t)N), to(3 * (size_t)N), po(n_prm);
-    BTRY(hipMemcpyAsync(Xo.data(), d.X, 24 * (size_t)P, hipMemcpyDeviceToHost, st));
-    BTRY(hipMemcpyAsync(qo.data(), d.q, 32 * (size_t)N, hipMemcpyDeviceToHost, st));
-    BTRY(hipMemcpyAsync(to.data(), d.t, 24 * (size_t)N, hipMemcpyDeviceToHost, st));
-    BTRY(hipMemcpyAsync(po.data(), d.prm, 8 * (size_t)n_prm, hipMemcpyDeviceToHost, st));
+    HIPTRY(hipMemcpyAsync(Xo.data(), d.X, 24 * (size_t)P, hipMemcpyDeviceToHost, st));
+    HIPTRY(hipMemcpyAsync(qo.data(), d.q, 32 * (size_t)N, hipMemcpyDeviceToHost, st));
+    HIPTRY(hipMemcpyAsync(to.data(), d.t, 24 * (size_t)N, hipMemcpyDeviceToHost, st));
+    HIPTRY(hipMemcpyAsync(po.data(), d.prm, 8 * (size_t)n_prm, hipMemcpyDeviceToHost, st));
     std::vector<double> tr;
     if (trace) {
       tr.resize((size_t)DSM_BA_TRACE_COLUMNS * (h.iter + 1));
-      BTRY(hipMemcpyAsync(tr.data(), d.trace, 8 * tr.size(), hipMemcpyDeviceToHost, st));
+      HIPTRY(hipMemcpyAsync(tr.data(), d.trace, 8 * tr.size(), hipMemcpyDeviceToHost, st));
     }
-    BTRY(hipStreamSynchronize(st));
+    HIPTRY(hipStreamSynchronize(st));
     if (rc == DSM_OK) {
       for (uint32_t r = 0; r < P; ++r)
         for (int m = 0; m < 3; ++m) point_xyz[3 * (size_t)order[r] + m] = Xo[3 * (size_t)r + m];
@@ -1451,14 +1400,5 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
       }
     }
   }
-  for (auto& e : ev)
-    if (e) (void)hipEventDestroy(e);
-  for (DevBuf* b : {&b_oimg, &b_opt, &b_orun, &b_imgoff, &b_trkoff, &b_trk, &b_camimgoff, &b_camimgs, &b_imgcam, &b_campoff,
-                    &b_camfoff, &b_cammoff, &b_oxy, &b_cpose, &b_mask, &b_ptvar, &b_cammodel, &b_camnp, &b_camk, &b_camfree, &b_q,
-                    &b_t, &b_X, &b_prm, &b_cq, &b_ct, &b_cX, &b_cprm, &b_J, &b_y, &b_ge, &b_cne, &b_se, &b_De, &b_Cinv, &b_ve,
-                    &b_zp, &b_dy, &b_gf, &b_cnf, &b_sf, &b_Df, &b_ddf, &b_Minv, &b_b, &b_x, &b_r, &b_z, &b_p, &b_qv, &b_tmp,
-                    &b_icam, &b_Pc, &b_Pm, &b_Pg, &b_Pe, &b_Pd, &b_Pq, &b_ctl, &b_trace})
-    b->release();
-#undef BTRY
   return rc;
 }

@@ -31,6 +31,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "block_reduce.h"
 #include "ctx.h"
 #include "verify_linalg.h"
 
@@ -450,23 +451,9 @@ struct AlRefitOut {
   uint32_t inliers, pad;
 };
 
-// fixed-order block sum of NV doubles per lane (strided partials, then a tree over the lanes)
-template <int NV>
-__device__ void al_block_sum(double (*red)[AL_BLOCK], double* v) {
-  for (int q = 0; q < NV; ++q) red[q][threadIdx.x] = v[q];
-  __syncthreads();
-  for (int s = AL_BLOCK / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-      for (int q = 0; q < NV; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
-    __syncthreads();
-  }
-  for (int q = 0; q < NV; ++q) v[q] = red[q][0];
-  __syncthreads();
-}
-
 // Umeyama over the selected correspondences (mask: residual of `ref` < thr, or all), FindRTS into m
 __device__ void al_fit(const double* X1, const double* X2, const AlRefitIn& in, bool use_mask, const AlModel& ref, double thr,
-                       double (*red)[AL_BLOCK], AlModel* m) {
+                       double* sh, AlModel* m) {
   double A[9];
   for (int i = 0; i < 9; ++i) A[i] = ref.s * ref.R[i];
   double v[12];
@@ -478,7 +465,7 @@ __device__ void al_fit(const double* X1, const double* X2, const AlRefitIn& in, 
     for (int d = 0; d < 3; ++d) v[d] += a[d], v[3 + d] += b[d];
     v[6] += 1.0;
   }
-  al_block_sum<7>(red, v);
+  block_sum<AL_BLOCK, 7>(v, sh);
   const double one_over_n = 1.0 / v[6];
   double m1[3], m2[3];
   for (int d = 0; d < 3; ++d) m1[d] = v[d] * one_over_n, m2[d] = v[3 + d] * one_over_n;
@@ -494,7 +481,7 @@ __device__ void al_fit(const double* X1, const double* X2, const AlRefitIn& in, 
       for (int c = 0; c < 3; ++c) v[r * 3 + c] += d2[r] * d1[c];
     }
   }
-  al_block_sum<12>(red, v);
+  block_sum<AL_BLOCK, 12>(v, sh);
   double sig[9];
   for (int i = 0; i < 9; ++i) sig[i] = one_over_n * v[i];
   const double var = ((v[9] + v[10]) + v[11]) * one_over_n;
@@ -503,7 +490,7 @@ __device__ void al_fit(const double* X1, const double* X2, const AlRefitIn& in, 
 
 __global__ void __launch_bounds__(AL_BLOCK) k_al_refit(const AlRefitIn* __restrict__ ins, const double* __restrict__ X1g,
                                                        const double* __restrict__ X2g, double thr, AlRefitOut* __restrict__ outs) {
-  __shared__ double red[12][AL_BLOCK];
+  __shared__ double sh[12 * AL_BLOCK];
   const AlRefitIn in = ins[blockIdx.x];
   const double* X1 = X1g + 3 * (size_t)in.off;
   const double* X2 = X2g + 3 * (size_t)in.off;
@@ -520,12 +507,12 @@ __global__ void __launch_bounds__(AL_BLOCK) k_al_refit(const AlRefitIn* __restri
       al_load(X1, X2, in.dir, i, a, b);
       if (al_residual(A, in.model.t, a[0], a[1], a[2], b[0], b[1], b[2]) < thr) v[0] += 1.0;
     }
-    al_block_sum<1>(red, v);
+    block_sum<AL_BLOCK, 1>(v, sh);
     inliers = (uint32_t)v[0];
-    if (inliers >= 3) al_fit(X1, X2, in, true, in.model, thr, red, &m);  // FindRTS returns at once below 3 columns
+    if (inliers >= 3) al_fit(X1, X2, in, true, in.model, thr, sh, &m);  // FindRTS returns at once below 3 columns
     if (inliers < 4) no_edge = true;
   }
-  if (!no_edge && (!in.prosac || inliers <= 5) && in.N >= 3) al_fit(X1, X2, in, false, in.model, thr, red, &m);
+  if (!no_edge && (!in.prosac || inliers <= 5) && in.N >= 3) al_fit(X1, X2, in, false, in.model, thr, sh, &m);
   double msd = DBL_MAX;
   if (!no_edge) {
     double A[9];
@@ -536,7 +523,7 @@ __global__ void __launch_bounds__(AL_BLOCK) k_al_refit(const AlRefitIn* __restri
       al_load(X1, X2, in.dir, i, a, b);
       v[0] += al_residual(A, m.t, a[0], a[1], a[2], b[0], b[1], b[2]);
     }
-    al_block_sum<1>(red, v);
+    block_sum<AL_BLOCK, 1>(v, sh);
     msd = v[0] / (double)in.N;
   }
   if (threadIdx.x == 0) {
@@ -597,12 +584,6 @@ AlSim3 al_sim3_identity() {
 struct AlBufs {
   DevBuf obs_off, obs, pt_off, pcl, reg, head, rid, hpos, key, key2, val, val2, ocl, opt, flags, ids, pkey, pkey2, pval, pval2, rank, cnt, coff;
   DevBuf ckey, ckey2, cval, cval2, csrc, cref, xyz, X1, X2, heads, nheads, tmp, tabs, probs, pout, rin, rout;
-  ~AlBufs() {
-    for (DevBuf* b : {&obs_off, &obs, &pt_off, &pcl, &reg, &head, &rid, &hpos, &key, &key2, &val, &val2, &ocl, &opt, &flags, &ids, &pkey, &pkey2, &pval, &pval2, &rank,
-                      &cnt, &coff, &ckey, &ckey2, &cval, &cval2, &csrc, &cref, &xyz, &X1, &X2, &heads, &nheads, &tmp, &tabs, &probs, &pout,
-                      &rin, &rout})
-      b->release();
-  }
 };
 
 }  // namespace
@@ -684,15 +665,8 @@ extern "C" int dsm_align_clusters(dsm_ctx* ctx, uint32_t K, const uint32_t* imag
   if (he != hipSuccess) return fail(DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   AlBufs d;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  struct EvGuard {
-    hipEvent_t* e;
-    ~EvGuard() {
-      for (int i = 0; i < 4; ++i)
-        if (e[i]) (void)hipEventDestroy(e[i]);
-    }
-  } evg{ev};
-  for (int i = 0; i < 4; ++i) HIPCHK(ctx, hipEventCreate(&ev[i]));
+  DevEvent ev[4];
+  for (int i = 0; i < 4; ++i) HIPCHK(ctx, hipEventCreate(&ev[i].e));
   HIPCHK(ctx, hipEventRecord(ev[0], st));
 
   // ------------------------------------------------------------ the join (device)

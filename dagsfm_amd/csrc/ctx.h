@@ -11,9 +11,28 @@
 
 #include "../../include/dagsfm_mi355x.h"
 
+// a device allocation, freed when its owner goes out of scope (movable, not copyable)
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) {
+    o.p = nullptr;
+    o.cap = 0;
+  }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p;
+      cap = o.cap;
+      o.p = nullptr;
+      o.cap = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     if (p) (void)hipFree(p);
@@ -55,6 +74,18 @@ struct DevBuf {
   }
   template <typename T>
   T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// a hipEvent_t, destroyed when its owner goes out of scope; created by hipEventCreate(&ev.e)
+struct DevEvent {
+  hipEvent_t e = nullptr;
+  DevEvent() = default;
+  DevEvent(const DevEvent&) = delete;
+  DevEvent& operator=(const DevEvent&) = delete;
+  ~DevEvent() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  operator hipEvent_t() const { return e; }
 };
 
 
@@ -182,6 +213,16 @@ static const char* const dsm_check_debug_keys[] = {"DSM_K1_DOT4", "DSM_VERIFY_DE
     }                                                                                  \
   } while (0)
 
+// the sticky form for a driver with a single exit: the first failing call is recorded in ctx->err and in the local int rc,
+// later calls still run (and later failures are not recorded)
+#define HIPTRY(call)                                                   \
+  do {                                                                 \
+    hipError_t e_ = (call);                                            \
+    if (e_ != hipSuccess && rc == DSM_OK) {                            \
+      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);    \
+      rc = DSM_ERR_HIP;                                                \
+    }                                                                  \
+  } while (0)
 
 static inline int dsm_fail(dsm_ctx* ctx, int code, const char* msg) {
   if (ctx) ctx->err = msg;

@@ -25,7 +25,9 @@
 #include <string>
 #include <vector>
 
+#include "block_reduce.h"
 #include "ctx.h"
+#include "graph_edges.h"
 #include "rotation_ceres.h"
 
 namespace {
@@ -70,39 +72,6 @@ __device__ inline void mul_rot(const double* a, const double* b, double* out) {
   R_to_aa(C, out);
 }
 
-// ---------------------------------------------------------------- fixed-order reductions
-// sum of K values over the block: one LDS tree (the same tree for every launch)
-template <int K>
-__device__ inline void block_sum(double (&v)[K], double* sh) {
-  const int t = threadIdx.x;
-  for (int k = 0; k < K; ++k) sh[k * RA_BLOCK + t] = v[k];
-  __syncthreads();
-  for (int s = RA_BLOCK / 2; s > 0; s >>= 1) {
-    if (t < s)
-      for (int k = 0; k < K; ++k) sh[k * RA_BLOCK + t] += sh[k * RA_BLOCK + t + s];
-    __syncthreads();
-  }
-  for (int k = 0; k < K; ++k) v[k] = sh[k * RA_BLOCK];
-  __syncthreads();
-}
-// the K per-block partials of a launch of n_parts blocks (layout P[k * n_parts + block]): thread t sums blocks t, t + 256, ...
-// in order, then the block tree.  Every block that calls it gets the same bytes.
-template <int K>
-__device__ inline void sum_partials(const double* __restrict__ P, int n_parts, double (&out)[K], double* sh) {
-  for (int k = 0; k < K; ++k) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n_parts; i += RA_BLOCK) s += P[(size_t)k * n_parts + i];
-    out[k] = s;
-  }
-  block_sum<K>(out, sh);
-}
-template <int K>
-__device__ inline void write_partials(double (&v)[K], double* sh, double* __restrict__ P) {
-  block_sum<K>(v, sh);
-  if (threadIdx.x == 0)
-    for (int k = 0; k < K; ++k) P[(size_t)k * gridDim.x + blockIdx.x] = v[k];
-}
-
 __device__ inline bool gated(const RaCtl* c, int admm_t) { return admm_t >= 0 && admm_t >= c->admm_stop; }
 
 // ---------------------------------------------------------------- per-edge kernels
@@ -126,7 +95,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_residuals(uint32_t M, const uin
     for (int c = 0; c < 3; ++c) b[3 * (size_t)e + c] = res[c];
     acc[0] = res[0] * res[0] + res[1] * res[1] + res[2] * res[2];
   }
-  write_partials<1>(acc, sh, P);
+  write_partials<RA_BLOCK, 1>(acc, sh, P);
 }
 
 // ADMM after the x update (l1_solver.h Solve): Ax, ax_hat, z (shrinkage), u; partials of ||Ax - z - b||^2, ||Ax||^2, ||z||^2
@@ -159,7 +128,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_admm_edges(uint32_t M, const ui
       acc[2] += zn * zn;
     }
   }
-  write_partials<3>(acc, sh, P);
+  write_partials<RA_BLOCK, 3>(acc, sh, P);
 }
 
 // FilterViewPairsFromOrientation (filter_view_pairs_from_orientation.cpp:22-35, 71-80): keep iff
@@ -257,7 +226,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_cg_init(uint32_t N, const uint3
     d[0] = 1.0;
     for (int c = 0; c < 3; ++c) r[c] = 0.0;
   }
-  write_partials<6>(acc, sh, P);
+  write_partials<RA_BLOCK, 6>(acc, sh, P);
 }
 
 // CG start, part 2 (one block): a column whose warm start is worse than zero (||r|| > ||b||) restarts cold
@@ -265,7 +234,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_cg_init_fin(int nb, const doubl
   if (gated(ctl, t)) return;
   __shared__ double sh[6 * RA_BLOCK];
   double s[6];
-  sum_partials<6>(P, nb, s, sh);
+  sum_partials<RA_BLOCK, 6>(P, nb, s, sh);
   if (threadIdx.x == 0)
     for (int c = 0; c < 3; ++c) {
       ctl->bb[c] = s[3 + c];
@@ -295,7 +264,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_cg_init2(uint32_t N, const doub
       acc[3 + c] = r[k] * r[k];
     }
   }
-  write_partials<6>(acc, sh, P);
+  write_partials<RA_BLOCK, 6>(acc, sh, P);
 }
 
 // the state of the solve after r.z / r.r are known (one writer: thread 0 of the calling block)
@@ -326,7 +295,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_cg_init_fin2(int nb, const doub
   if (gated(ctl, t)) return;
   __shared__ double sh[6 * RA_BLOCK];
   double s[6];
-  sum_partials<6>(P, nb, s, sh);
+  sum_partials<RA_BLOCK, 6>(P, nb, s, sh);
   if (threadIdx.x == 0) cg_decide(ctl, s, 0, 0, cg_max, tol);
 }
 
@@ -347,7 +316,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_cg_lp(uint32_t N, const uint32_
       acc[c] = p[3 * (size_t)v + c] * lq[c];
     }
   }
-  write_partials<3>(acc, sh, P);
+  write_partials<RA_BLOCK, 3>(acc, sh, P);
 }
 
 // CG iteration k, part 2: alpha = rz / pq (every block sums the same partials); x += alpha p, r -= alpha q, z = r / d;
@@ -359,7 +328,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_cg_update(uint32_t N, int nb, c
   if (gated(ctl, t) || k >= ctl->cg_stop) return;
   __shared__ double sh[6 * RA_BLOCK];
   double pq[3];
-  sum_partials<3>(Ppq, nb, pq, sh);
+  sum_partials<RA_BLOCK, 3>(Ppq, nb, pq, sh);
   double alpha[3];
   for (int c = 0; c < 3; ++c) alpha[c] = ctl->active[k & 1][c] ? ctl->rz[k & 1][c] / pq[c] : 0.0;
   const uint32_t v = blockIdx.x * RA_BLOCK + threadIdx.x;
@@ -376,7 +345,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_cg_update(uint32_t N, int nb, c
       acc[3 + c] = rc * rc;
     }
   }
-  write_partials<6>(acc, sh, P);
+  write_partials<RA_BLOCK, 6>(acc, sh, P);
 }
 
 // CG iteration k, part 3: beta = rz_new / rz (every block sums the same partials), p = z + beta p; thread 0 of block 0 writes
@@ -386,7 +355,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_cg_dir(uint32_t N, int nb, cons
   if (gated(ctl, t) || k >= ctl->cg_stop) return;
   __shared__ double sh[6 * RA_BLOCK];
   double s[6];
-  sum_partials<6>(Prz, nb, s, sh);
+  sum_partials<RA_BLOCK, 6>(Prz, nb, s, sh);
   double beta[3];
   for (int c = 0; c < 3; ++c) beta[c] = ctl->active[k & 1][c] ? s[c] / ctl->rz[k & 1][c] : 0.0;
   const uint32_t v = blockIdx.x * RA_BLOCK + threadIdx.x;
@@ -427,7 +396,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_admm_verts(uint32_t N, const ui
       acc[1] += bq * bq;
     }
   }
-  write_partials<2>(acc, sh, P);
+  write_partials<RA_BLOCK, 2>(acc, sh, P);
 }
 
 // ADMM stop (one block): r_norm < primal_eps && s_norm < dual_eps (l1_solver.h)
@@ -437,9 +406,9 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_admm_check(int nbe, const doubl
   if (gated(ctl, t)) return;
   __shared__ double sh[3 * RA_BLOCK];
   double e3[3], b1[1], v2[2];
-  sum_partials<3>(Pe, nbe, e3, sh);
-  sum_partials<1>(Pb, nbe, b1, sh);
-  sum_partials<2>(Pv, nbv, v2, sh);
+  sum_partials<RA_BLOCK, 3>(Pe, nbe, e3, sh);
+  sum_partials<RA_BLOCK, 1>(Pb, nbe, b1, sh);
+  sum_partials<RA_BLOCK, 2>(Pv, nbv, v2, sh);
   if (threadIdx.x == 0) {
     const double r_norm = sqrt(e3[0]), s_norm = sqrt(v2[0]);
     const double max_norm = fmax(fmax(sqrt(e3[1]), sqrt(e3[2])), sqrt(b1[0]));
@@ -467,7 +436,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_rotate(uint32_t N, const double
     for (int c = 0; c < 3; ++c) R[3 * (size_t)v + c] = out[c];
     acc[0] = sqrt(xv[0] * xv[0] + xv[1] * xv[1] + xv[2] * xv[2]);
   }
-  write_partials<1>(acc, sh, P);
+  write_partials<RA_BLOCK, 1>(acc, sh, P);
 }
 
 // average step over N - 1 images; L1 stops on <= threshold, IRLS on < threshold (:207, :258)
@@ -475,7 +444,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_step_check(int nbv, const doubl
                                                             RaCtl* ctl) {
   __shared__ double sh[RA_BLOCK];
   double s[1];
-  sum_partials<1>(P, nbv, s, sh);
+  sum_partials<RA_BLOCK, 1>(P, nbv, s, sh);
   if (threadIdx.x == 0) {
     const double avg = s[0] / (double)n_var;
     ctl->last_step = avg;
@@ -550,14 +519,10 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
                                                  uint32_t* n_images_out, uint8_t* edge_state, double* relative_rotations_out,
                                                  dsm_rotation_averaging_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](int rc, const char* msg) {
-    ctx->err = msg;
-    return rc;
-  };
   if (!n_images_out || (n_pairs && (!pairs || !qvecs || !image_ids_out || !orientations_out || !image_in_final_cc || !edge_state ||
                                     !relative_rotations_out)))
-    return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_rotation_averaging: NULL argument");
-  if (n_pairs > (UINT32_MAX >> 2)) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_rotation_averaging: too many pairs");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_rotation_averaging: NULL argument");
+  if (n_pairs > (UINT32_MAX >> 2)) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_rotation_averaging: too many pairs");
   dsm_rotation_averaging_options o;
   if (options)
     o = *options;
@@ -569,21 +534,21 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
       !(o.max_relative_rotation_difference_degrees >= 0.0) || !(o.cg_tolerance > 0.0) || !(o.cg_max_residual > 0.0) ||
       !std::isfinite(o.admm_alpha) || !std::isfinite(o.admm_absolute_tolerance) || !std::isfinite(o.admm_relative_tolerance) ||
       !std::isfinite(o.l1_step_convergence_threshold) || !std::isfinite(o.irls_step_convergence_threshold))
-    return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_rotation_averaging: option out of range");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_rotation_averaging: option out of range");
   dsm_rotation_averaging_report rep{};
   *n_images_out = 0;
   if (report) *report = rep;
   // argument checks on every used edge before anything is written
   for (uint32_t e = 0; e < n_pairs; ++e) {
     if (use && !use[e]) continue;
-    if (pairs[2 * e] == pairs[2 * e + 1]) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_rotation_averaging: image_id1 == image_id2");
+    if (pairs[2 * e] == pairs[2 * e + 1]) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_rotation_averaging: image_id1 == image_id2");
     const double* q = qvecs + 4 * (size_t)e;
     bool finite = true, zero = true;
     for (int c = 0; c < 4; ++c) {
       finite &= std::isfinite(q[c]);
       zero &= q[c] == 0.0;
     }
-    if (!finite || zero) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_rotation_averaging: non-finite or zero qvec");
+    if (!finite || zero) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_rotation_averaging: non-finite or zero qvec");
   }
   for (uint32_t e = 0; e < n_pairs; ++e) {
     edge_state[e] = 0;
@@ -592,31 +557,11 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
   // host: unique used edges (the first occurrence of an unordered pair wins, ViewGraph::AddTwoViewGeometry), images renumbered
   // by ascending id, the first component (ImageGraph::ExtractLargestCC)
   std::vector<uint32_t> ids;
-  for (uint32_t e = 0; e < n_pairs; ++e)
-    if (!use || use[e]) {
-      ids.push_back(pairs[2 * e]);
-      ids.push_back(pairs[2 * e + 1]);
-    }
-  std::sort(ids.begin(), ids.end());
-  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-  auto vid = [&](uint32_t id) { return (uint32_t)(std::lower_bound(ids.begin(), ids.end(), id) - ids.begin()); };
-  struct E {
-    uint32_t lo, hi, i, j, orig;
-  };
-  std::vector<E> edges;
-  for (uint32_t e = 0; e < n_pairs; ++e)
-    if (!use || use[e]) {
-      const uint32_t a = vid(pairs[2 * e]), b = vid(pairs[2 * e + 1]);
-      edges.push_back(E{std::min(a, b), std::max(a, b), a, b, e});
-    }
-  std::stable_sort(edges.begin(), edges.end(), [](const E& l, const E& r) { return l.lo != r.lo ? l.lo < r.lo : l.hi < r.hi; });
-  std::vector<E> uniq;
-  for (const E& x : edges)
-    if (uniq.empty() || uniq.back().lo != x.lo || uniq.back().hi != x.hi) uniq.push_back(x);
+  const std::vector<GraphEdge> uniq = graph_unique_edges(n_pairs, pairs, use, ids);
   if (uniq.empty()) return DSM_OK;
   const uint32_t V = (uint32_t)ids.size();
   std::vector<std::pair<uint32_t, uint32_t>> ue;
-  for (const E& x : uniq) ue.emplace_back(x.lo, x.hi);
+  for (const GraphEdge& x : uniq) ue.emplace_back(x.lo, x.hi);
   std::vector<uint8_t> in1;
   rep.num_components = largest_component(V, ue, in1);
   std::vector<uint32_t> cid(V, UINT32_MAX), cimg;  // component renumbering: ascending id, cimg[0] is the constant image
@@ -626,26 +571,30 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
       cimg.push_back(ids[v]);
     }
   const uint32_t N = (uint32_t)cimg.size();
-  std::vector<E> ce_edges;  // edges of the component in canonical (lo, hi) order, vertices in component numbering
-  for (const E& x : uniq) {
+  std::vector<GraphEdge> ce_edges;  // edges of the component in canonical (lo, hi) order, vertices in component numbering
+  for (const GraphEdge& x : uniq) {
     if (!in1[x.lo]) {
       edge_state[x.orig] = 1;
       continue;
     }
-    ce_edges.push_back(E{cid[x.lo], cid[x.hi], cid[x.i], cid[x.j], x.orig});
+    ce_edges.push_back(GraphEdge{cid[x.lo], cid[x.hi], cid[x.i], cid[x.j], x.orig});
   }
   const uint32_t M = (uint32_t)ce_edges.size();
   rep.num_images = N;
   rep.num_edges = M;
-  // CSR over images, entries sorted by neighbour
-  std::vector<uint32_t> ei(M), ej(M), off(N + 1, 0), nb(2 * (size_t)M), cev(2 * (size_t)M);
+  // CSR over images, entries sorted by neighbour; cev: 2 k + 1 where the entry's image is edge k's image j, else 2 k
+  std::vector<uint32_t> ei(M), ej(M), off, nb, cev;
+  graph_neighbour_csr(N, ce_edges, off, nb, cev);
+  for (uint32_t v = 0; v < N; ++v)
+    for (uint32_t p = off[v]; p < off[v + 1]; ++p) {
+      const uint32_t k = cev[p];
+      cev[p] = 2 * k + (ce_edges[k].j == v ? 1u : 0u);
+    }
   std::vector<double> r12(3 * (size_t)M);
   for (uint32_t k = 0; k < M; ++k) {
-    const E& x = ce_edges[k];
+    const GraphEdge& x = ce_edges[k];
     ei[k] = x.i;
     ej[k] = x.j;
-    off[x.lo + 1]++;
-    off[x.hi + 1]++;
     // QuaternionToAngleAxis (ceres) on the host, the formula of rotation_ceres.h
     const double* q = qvecs + 4 * (size_t)x.orig;
     const double q1 = q[1], q2 = q[2], q3 = q[3];
@@ -659,65 +608,33 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
     r12[3 * (size_t)k + 1] = q2 * kk;
     r12[3 * (size_t)k + 2] = q3 * kk;
   }
-  for (uint32_t v = 0; v < N; ++v) off[v + 1] += off[v];
-  {
-    std::vector<uint32_t> fill(off.begin(), off.end() - 1);
-    // fill every row, then sort it by neighbour
-    for (uint32_t k = 0; k < M; ++k) {
-      const E& x = ce_edges[k];
-      nb[fill[x.lo]] = x.hi;
-      cev[fill[x.lo]++] = 2 * k + (x.j == x.lo ? 1u : 0u);
-      nb[fill[x.hi]] = x.lo;
-      cev[fill[x.hi]++] = 2 * k + (x.j == x.hi ? 1u : 0u);
-    }
-    std::vector<std::pair<uint32_t, uint32_t>> row;
-    for (uint32_t v = 0; v < N; ++v) {
-      row.clear();
-      for (uint32_t p = off[v]; p < off[v + 1]; ++p) row.emplace_back(nb[p], cev[p]);
-      std::sort(row.begin(), row.end());
-      for (uint32_t p = off[v]; p < off[v + 1]; ++p) {
-        nb[p] = row[p - off[v]].first;
-        cev[p] = row[p - off[v]].second;
-      }
-    }
-  }
 
   hipError_t he = hipSetDevice(ctx->device);
-  if (he != hipSuccess) return fail(DSM_ERR_HIP, hipGetErrorString(he));
+  if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   const int nbv = (int)((N + RA_BLOCK - 1) / RA_BLOCK), nbe = (int)((M + RA_BLOCK - 1) / RA_BLOCK);
   const size_t n3 = 3 * (size_t)N, m3 = 3 * (size_t)M;
   DevBuf d_ei, d_ej, d_off, d_nb, d_ce, d_r12, d_R, d_x, d_rhs, d_r, d_zp, d_p, d_q, d_d, d_b, d_w, d_one, d_z, d_zold, d_u, d_P1, d_P2,
       d_P3, d_P4, d_ctl, d_state, d_rel;
-  DevBuf* all[] = {&d_ei, &d_ej, &d_off, &d_nb, &d_ce, &d_r12, &d_R, &d_x, &d_rhs, &d_r, &d_zp, &d_p, &d_q, &d_d, &d_b,
-                   &d_w, &d_one, &d_z, &d_zold, &d_u, &d_P1, &d_P2, &d_P3, &d_P4, &d_ctl, &d_state, &d_rel};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevEvent ev0, ev1;
   int rc = DSM_OK;
-#define RTRY(call)                                                     \
-  do {                                                                 \
-    hipError_t e_ = (call);                                            \
-    if (e_ != hipSuccess && rc == DSM_OK) {                            \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);    \
-      rc = DSM_ERR_HIP;                                                \
-    }                                                                  \
-  } while (0)
   const size_t np = (size_t)std::max(nbv, nbe);
-  RTRY(d_ei.reserve((size_t)M * 4));
-  RTRY(d_ej.reserve((size_t)M * 4));
-  RTRY(d_off.reserve(((size_t)N + 1) * 4));
-  RTRY(d_nb.reserve((size_t)M * 8));
-  RTRY(d_ce.reserve((size_t)M * 8));
-  RTRY(d_r12.reserve(m3 * 8));
-  for (DevBuf* b : {&d_R, &d_x, &d_rhs, &d_r, &d_zp, &d_p, &d_q}) RTRY(b->reserve(n3 * 8));
-  RTRY(d_d.reserve((size_t)N * 8));
-  for (DevBuf* b : {&d_b, &d_z, &d_zold, &d_u, &d_rel}) RTRY(b->reserve(m3 * 8));
-  RTRY(d_w.reserve((size_t)M * 8));
-  RTRY(d_one.reserve((size_t)M * 8));
-  for (DevBuf* b : {&d_P1, &d_P2, &d_P3, &d_P4}) RTRY(b->reserve(np * 6 * 8));
-  RTRY(d_ctl.reserve(sizeof(RaCtl)));
-  RTRY(d_state.reserve(M));
-  RTRY(hipEventCreate(&ev0));
-  RTRY(hipEventCreate(&ev1));
+  HIPTRY(d_ei.reserve((size_t)M * 4));
+  HIPTRY(d_ej.reserve((size_t)M * 4));
+  HIPTRY(d_off.reserve(((size_t)N + 1) * 4));
+  HIPTRY(d_nb.reserve((size_t)M * 8));
+  HIPTRY(d_ce.reserve((size_t)M * 8));
+  HIPTRY(d_r12.reserve(m3 * 8));
+  for (DevBuf* b : {&d_R, &d_x, &d_rhs, &d_r, &d_zp, &d_p, &d_q}) HIPTRY(b->reserve(n3 * 8));
+  HIPTRY(d_d.reserve((size_t)N * 8));
+  for (DevBuf* b : {&d_b, &d_z, &d_zold, &d_u, &d_rel}) HIPTRY(b->reserve(m3 * 8));
+  HIPTRY(d_w.reserve((size_t)M * 8));
+  HIPTRY(d_one.reserve((size_t)M * 8));
+  for (DevBuf* b : {&d_P1, &d_P2, &d_P3, &d_P4}) HIPTRY(b->reserve(np * 6 * 8));
+  HIPTRY(d_ctl.reserve(sizeof(RaCtl)));
+  HIPTRY(d_state.reserve(M));
+  HIPTRY(hipEventCreate(&ev0.e));
+  HIPTRY(hipEventCreate(&ev1.e));
   RaCtl h{}, init{};
   init.cg_stop = 0;
   init.admm_stop = INT_MAX;
@@ -725,16 +642,16 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
   std::vector<uint8_t> st8(M);
   std::vector<double> Rh(n3), relh(m3);
   if (rc == DSM_OK) {
-    RTRY(hipEventRecord(ev0, st));
-    RTRY(hipMemcpyAsync(d_ei.p, ei.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
-    RTRY(hipMemcpyAsync(d_ej.p, ej.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
-    RTRY(hipMemcpyAsync(d_off.p, off.data(), ((size_t)N + 1) * 4, hipMemcpyHostToDevice, st));
-    RTRY(hipMemcpyAsync(d_nb.p, nb.data(), (size_t)M * 8, hipMemcpyHostToDevice, st));
-    RTRY(hipMemcpyAsync(d_ce.p, cev.data(), (size_t)M * 8, hipMemcpyHostToDevice, st));
-    RTRY(hipMemcpyAsync(d_r12.p, r12.data(), m3 * 8, hipMemcpyHostToDevice, st));
-    RTRY(hipMemcpyAsync(d_ctl.p, &init, sizeof(RaCtl), hipMemcpyHostToDevice, st));
-    for (DevBuf* b : {&d_R, &d_x, &d_rhs, &d_r, &d_zp, &d_p, &d_q}) RTRY(hipMemsetAsync(b->p, 0, n3 * 8, st));
-    RTRY(hipMemsetAsync(d_d.p, 0, (size_t)N * 8, st));
+    HIPTRY(hipEventRecord(ev0, st));
+    HIPTRY(hipMemcpyAsync(d_ei.p, ei.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_ej.p, ej.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_off.p, off.data(), ((size_t)N + 1) * 4, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_nb.p, nb.data(), (size_t)M * 8, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_ce.p, cev.data(), (size_t)M * 8, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_r12.p, r12.data(), m3 * 8, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_ctl.p, &init, sizeof(RaCtl), hipMemcpyHostToDevice, st));
+    for (DevBuf* b : {&d_R, &d_x, &d_rhs, &d_r, &d_zp, &d_p, &d_q}) HIPTRY(hipMemsetAsync(b->p, 0, n3 * 8, st));
+    HIPTRY(hipMemsetAsync(d_d.p, 0, (size_t)N * 8, st));
   }
   RaCtl* ctl = d_ctl.as<RaCtl>();
   const uint32_t* off_ = d_off.as<uint32_t>();
@@ -744,8 +661,8 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
   const int batch = o.cg_batch_iterations > 0 ? o.cg_batch_iterations : 16;
   const double sigma = o.irls_loss_parameter_sigma;
   auto read_ctl = [&]() {
-    RTRY(hipMemcpyAsync(&h, d_ctl.p, sizeof(RaCtl), hipMemcpyDeviceToHost, st));
-    RTRY(hipStreamSynchronize(st));
+    HIPTRY(hipMemcpyAsync(&h, d_ctl.p, sizeof(RaCtl), hipMemcpyDeviceToHost, st));
+    HIPTRY(hipStreamSynchronize(st));
   };
   auto residuals = [&]() {
     hipLaunchKernelGGL(k_ra_residuals, dim3(nbe), dim3(RA_BLOCK), 0, st, M, d_ei.as<uint32_t>(), d_ej.as<uint32_t>(), d_r12.as<double>(),
@@ -770,7 +687,7 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
         hipLaunchKernelGGL(k_ra_cg_dir, dim3(nbv), dim3(RA_BLOCK), 0, st, N, nbv, (const double*)d_P2.as<double>(),
                            (const double*)d_zp.as<double>(), d_p.as<double>(), ctl, t, k, cg_max, o.cg_tolerance);
       }
-      RTRY(hipGetLastError());
+      HIPTRY(hipGetLastError());
       read_ctl();
       if (t >= 0 && t >= h.admm_stop) break;
       if (h.cg_stop <= k0 + batch || k0 + batch >= cg_max) break;
@@ -785,7 +702,7 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
     hipLaunchKernelGGL(k_ra_rotate, dim3(nbv), dim3(RA_BLOCK), 0, st, N, (const double*)d_x.as<double>(), d_R.as<double>(), d_P3.as<double>());
     residuals();
     hipLaunchKernelGGL(k_ra_step_check, dim3(1), dim3(RA_BLOCK), 0, st, nbv, (const double*)d_P3.as<double>(), N - 1, thr, irls, ctl);
-    RTRY(hipGetLastError());
+    HIPTRY(hipGetLastError());
     read_ctl();
   };
   if (rc == DSM_OK) {
@@ -796,9 +713,9 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
   int admm_cap = o.admm_initial_max_iterations;
   const double primal_abs = sqrt((double)m3) * o.admm_absolute_tolerance, dual_abs = sqrt(3.0 * (N - 1)) * o.admm_absolute_tolerance;
   for (int it = 0; rc == DSM_OK && it < o.max_num_l1_iterations; ++it) {
-    RTRY(hipMemsetAsync(d_z.p, 0, m3 * 8, st));
-    RTRY(hipMemsetAsync(d_u.p, 0, m3 * 8, st));
-    RTRY(hipMemcpyAsync(&ctl->admm_stop, kAdmmReset, sizeof(kAdmmReset), hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemsetAsync(d_z.p, 0, m3 * 8, st));
+    HIPTRY(hipMemsetAsync(d_u.p, 0, m3 * 8, st));
+    HIPTRY(hipMemcpyAsync(&ctl->admm_stop, kAdmmReset, sizeof(kAdmmReset), hipMemcpyHostToDevice, st));
     for (int t = 0; rc == DSM_OK && t < admm_cap; ++t) {
       hipLaunchKernelGGL(k_ra_rhs, dim3(nbv), dim3(RA_BLOCK), 0, st, N, off_, ce_, 0, (const double*)d_b.as<double>(),
                          (const double*)d_z.as<double>(), (const double*)d_u.as<double>(), (const double*)d_w.as<double>(),
@@ -814,7 +731,7 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
       hipLaunchKernelGGL(k_ra_admm_check, dim3(1), dim3(RA_BLOCK), 0, st, nbe, (const double*)d_P1.as<double>(),
                          (const double*)d_P4.as<double>(), nbv, (const double*)d_P2.as<double>(), primal_abs, dual_abs,
                          o.admm_relative_tolerance, ctl, t);
-      RTRY(hipGetLastError());
+      HIPTRY(hipGetLastError());
     }
     if (rc != DSM_OK) break;
     read_ctl();
@@ -841,22 +758,18 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
     const double thr = o.max_relative_rotation_difference_degrees * kRaDegToRad;
     hipLaunchKernelGGL(k_ra_filter, dim3(nbe), dim3(RA_BLOCK), 0, st, M, d_ei.as<uint32_t>(), d_ej.as<uint32_t>(), d_r12.as<double>(),
                        (const double*)d_R.as<double>(), thr * thr, d_state.as<uint8_t>(), d_rel.as<double>());
-    RTRY(hipGetLastError());
-    RTRY(hipEventRecord(ev1, st));
-    RTRY(hipMemcpyAsync(Rh.data(), d_R.p, n3 * 8, hipMemcpyDeviceToHost, st));
-    RTRY(hipMemcpyAsync(st8.data(), d_state.p, M, hipMemcpyDeviceToHost, st));
-    RTRY(hipMemcpyAsync(relh.data(), d_rel.p, m3 * 8, hipMemcpyDeviceToHost, st));
-    RTRY(hipMemcpyAsync(&h, d_ctl.p, sizeof(RaCtl), hipMemcpyDeviceToHost, st));
-    RTRY(hipStreamSynchronize(st));
+    HIPTRY(hipGetLastError());
+    HIPTRY(hipEventRecord(ev1, st));
+    HIPTRY(hipMemcpyAsync(Rh.data(), d_R.p, n3 * 8, hipMemcpyDeviceToHost, st));
+    HIPTRY(hipMemcpyAsync(st8.data(), d_state.p, M, hipMemcpyDeviceToHost, st));
+    HIPTRY(hipMemcpyAsync(relh.data(), d_rel.p, m3 * 8, hipMemcpyDeviceToHost, st));
+    HIPTRY(hipMemcpyAsync(&h, d_ctl.p, sizeof(RaCtl), hipMemcpyDeviceToHost, st));
+    HIPTRY(hipStreamSynchronize(st));
     float ms = 0.f;
-    RTRY(hipEventElapsedTime(&ms, ev0, ev1));
+    HIPTRY(hipEventElapsedTime(&ms, ev0, ev1));
     rep.device_ms = ms;
   }
-#undef RTRY
   if (rc != DSM_OK) (void)hipStreamSynchronize(st);
-  for (DevBuf* b : all) b->release();
-  if (ev0) (void)hipEventDestroy(ev0);
-  if (ev1) (void)hipEventDestroy(ev1);
   rep.total_cg_iterations = h.cg_total;
   rep.max_cg_relative_residual = h.cg_worst;
   if (rc == DSM_OK) {

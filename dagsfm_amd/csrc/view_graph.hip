@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "graph_edges.h"
 #include "rotation_ceres.h"
 
 namespace {
@@ -78,103 +79,64 @@ __global__ void k_vg_triplets(const uint32_t* __restrict__ edge_a, const uint32_
 
 }  // namespace
 
-#define VCHK(ctx, call)                                                              \
-  do {                                                                               \
-    hipError_t e_ = (call);                                                          \
-    if (e_ != hipSuccess) {                                                          \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                \
-      return DSM_ERR_HIP;                                                            \
-    }                                                                                \
-  } while (0)
-
 extern "C" int dsm_view_graph_filter_cycles(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const double* qvecs,
                                             double max_loop_error_degrees, uint8_t* keep, uint64_t* n_triplets) {
   if (!ctx || (n_pairs && (!pairs || !qvecs || !keep))) return DSM_ERR_INVALID_ARGUMENT;
   if (n_triplets) *n_triplets = 0;
   if (n_pairs == 0) return DSM_OK;
-  VCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   // host: unique edges (a < b; a repeated pair is ignored like ViewGraph::AddTwoViewGeometry, view_graph.cpp:85-96),
   // vertices renumbered 0..V-1, CSR of upper neighbours sorted by neighbour
   std::vector<uint32_t> verts;
-  verts.reserve(2 * (size_t)n_pairs);
-  for (uint32_t e = 0; e < 2 * n_pairs; ++e) verts.push_back(pairs[e]);
-  std::sort(verts.begin(), verts.end());
-  verts.erase(std::unique(verts.begin(), verts.end()), verts.end());
-  auto vid = [&](uint32_t id) { return (uint32_t)(std::lower_bound(verts.begin(), verts.end(), id) - verts.begin()); };
+  const std::vector<GraphEdge> uniq = graph_unique_edges(n_pairs, pairs, nullptr, verts);
   const uint32_t V = (uint32_t)verts.size();
-  struct E { uint32_t a, b, orig; };
-  std::vector<E> edges;
-  edges.reserve(n_pairs);
-  for (uint32_t e = 0; e < n_pairs; ++e) {
-    const uint32_t x = vid(pairs[2 * e]), y = vid(pairs[2 * e + 1]);
-    if (x == y) continue;
-    edges.push_back(E{std::min(x, y), std::max(x, y), e});
-  }
-  std::stable_sort(edges.begin(), edges.end(), [](const E& l, const E& r) { return l.a != r.a ? l.a < r.a : l.b < r.b; });
-  std::vector<E> uniq;
-  uniq.reserve(edges.size());
-  for (const E& x : edges)  // the first occurrence in list order wins (stable sort)
-    if (uniq.empty() || uniq.back().a != x.a || uniq.back().b != x.b) uniq.push_back(x);
   const uint32_t NE = (uint32_t)uniq.size();
   std::vector<uint32_t> ea(NE), eb(NE), off(V + 1, 0), nbr(NE), eid(NE);
   std::vector<double> q((size_t)NE * 4);
   for (uint32_t k = 0; k < NE; ++k) {
-    ea[k] = uniq[k].a;
-    eb[k] = uniq[k].b;
-    off[uniq[k].a + 1]++;
-    nbr[k] = uniq[k].b;  // sorted by (a, b): already CSR order
+    ea[k] = uniq[k].lo;
+    eb[k] = uniq[k].hi;
+    off[uniq[k].lo + 1]++;
+    nbr[k] = uniq[k].hi;  // sorted by (lo, hi): already CSR order
     eid[k] = k;
     for (int c = 0; c < 4; ++c) q[(size_t)k * 4 + c] = qvecs[(size_t)uniq[k].orig * 4 + c];
   }
   for (uint32_t v = 0; v < V; ++v) off[v + 1] += off[v];
-  DevBuf d_ea, d_eb, d_off, d_nbr, d_eid, d_q, d_R, d_keep, d_cnt;
-  int rc = DSM_OK;
-  auto cleanup = [&]() {
-    for (DevBuf* b : {&d_ea, &d_eb, &d_off, &d_nbr, &d_eid, &d_q, &d_R, &d_keep, &d_cnt}) b->release();
-  };
-#define VTRY(call)                                                       \
-  do {                                                                   \
-    hipError_t e_ = (call);                                              \
-    if (e_ != hipSuccess && rc == DSM_OK) {                              \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);      \
-      rc = DSM_ERR_HIP;                                                  \
-    }                                                                    \
-  } while (0)
-  const size_t ne1 = std::max<uint32_t>(NE, 1);
-  VTRY(d_ea.reserve(ne1 * 4));
-  VTRY(d_eb.reserve(ne1 * 4));
-  VTRY(d_off.reserve(((size_t)V + 1) * 4));
-  VTRY(d_nbr.reserve(ne1 * 4));
-  VTRY(d_eid.reserve(ne1 * 4));
-  VTRY(d_q.reserve(ne1 * 32));
-  VTRY(d_R.reserve(ne1 * 72));
-  VTRY(d_keep.reserve(ne1));
-  VTRY(d_cnt.reserve(8));
   std::vector<uint8_t> k8(NE, 0);
   unsigned long long cnt = 0;
+  DevBuf d_ea, d_eb, d_off, d_nbr, d_eid, d_q, d_R, d_keep, d_cnt;
+  int rc = DSM_OK;
+  const size_t ne1 = std::max<uint32_t>(NE, 1);
+  HIPTRY(d_ea.reserve(ne1 * 4));
+  HIPTRY(d_eb.reserve(ne1 * 4));
+  HIPTRY(d_off.reserve(((size_t)V + 1) * 4));
+  HIPTRY(d_nbr.reserve(ne1 * 4));
+  HIPTRY(d_eid.reserve(ne1 * 4));
+  HIPTRY(d_q.reserve(ne1 * 32));
+  HIPTRY(d_R.reserve(ne1 * 72));
+  HIPTRY(d_keep.reserve(ne1));
+  HIPTRY(d_cnt.reserve(8));
   if (rc == DSM_OK && NE) {
-    VTRY(hipMemcpyAsync(d_ea.p, ea.data(), (size_t)NE * 4, hipMemcpyHostToDevice, st));
-    VTRY(hipMemcpyAsync(d_eb.p, eb.data(), (size_t)NE * 4, hipMemcpyHostToDevice, st));
-    VTRY(hipMemcpyAsync(d_off.p, off.data(), ((size_t)V + 1) * 4, hipMemcpyHostToDevice, st));
-    VTRY(hipMemcpyAsync(d_nbr.p, nbr.data(), (size_t)NE * 4, hipMemcpyHostToDevice, st));
-    VTRY(hipMemcpyAsync(d_eid.p, eid.data(), (size_t)NE * 4, hipMemcpyHostToDevice, st));
-    VTRY(hipMemcpyAsync(d_q.p, q.data(), (size_t)NE * 32, hipMemcpyHostToDevice, st));
-    VTRY(hipMemsetAsync(d_keep.p, 0, NE, st));
-    VTRY(hipMemsetAsync(d_cnt.p, 0, 8, st));
+    HIPTRY(hipMemcpyAsync(d_ea.p, ea.data(), (size_t)NE * 4, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_eb.p, eb.data(), (size_t)NE * 4, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_off.p, off.data(), ((size_t)V + 1) * 4, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_nbr.p, nbr.data(), (size_t)NE * 4, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_eid.p, eid.data(), (size_t)NE * 4, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_q.p, q.data(), (size_t)NE * 32, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemsetAsync(d_keep.p, 0, NE, st));
+    HIPTRY(hipMemsetAsync(d_cnt.p, 0, 8, st));
     if (rc == DSM_OK) {
       hipLaunchKernelGGL(k_vg_edge_rotations, dim3((NE + 255) / 256), dim3(256), 0, st, d_q.as<double>(), NE, d_R.as<double>());
       hipLaunchKernelGGL(k_vg_triplets, dim3((NE + 127) / 128), dim3(128), 0, st, d_ea.as<uint32_t>(), d_eb.as<uint32_t>(), NE,
                          d_off.as<uint32_t>(), d_nbr.as<uint32_t>(), d_eid.as<uint32_t>(), d_R.as<double>(), max_loop_error_degrees,
                          d_keep.as<unsigned char>(), d_cnt.as<unsigned long long>());
-      VTRY(hipGetLastError());
-      VTRY(hipMemcpyAsync(k8.data(), d_keep.p, NE, hipMemcpyDeviceToHost, st));
-      VTRY(hipMemcpyAsync(&cnt, d_cnt.p, 8, hipMemcpyDeviceToHost, st));
-      VTRY(hipStreamSynchronize(st));
+      HIPTRY(hipGetLastError());
+      HIPTRY(hipMemcpyAsync(k8.data(), d_keep.p, NE, hipMemcpyDeviceToHost, st));
+      HIPTRY(hipMemcpyAsync(&cnt, d_cnt.p, 8, hipMemcpyDeviceToHost, st));
+      HIPTRY(hipStreamSynchronize(st));
     }
   }
-#undef VTRY
-  cleanup();
   if (rc != DSM_OK) return rc;
   for (uint32_t e = 0; e < n_pairs; ++e) keep[e] = 0;
   for (uint32_t k = 0; k < NE; ++k) keep[uniq[k].orig] = k8[k];

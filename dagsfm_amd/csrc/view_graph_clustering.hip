@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "graph_edges.h"
 
 namespace {
 
@@ -353,14 +354,10 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
                                       uint32_t* labels_out, uint32_t* n_images_out, int32_t* edge_cluster, uint32_t* cluster_offsets,
                                       uint32_t* cluster_images, uint32_t* n_clusters_out, dsm_clustering_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](int rc, const char* msg) {
-    ctx->err = msg;
-    return rc;
-  };
   if (!n_images_out || !n_clusters_out || !cluster_offsets ||
       (n_pairs && (!pairs || !weights || !image_ids_out || !labels_out || !edge_cluster || !cluster_images)))
-    return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: NULL argument");
-  if (n_pairs > (UINT32_MAX >> 2)) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: too many pairs");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: NULL argument");
+  if (n_pairs > (UINT32_MAX >> 2)) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: too many pairs");
   dsm_clustering_options o;
   if (options)
     o = *options;
@@ -368,7 +365,7 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
     dsm_default_clustering_options(&o);
   if (o.num_images_ub == 0 || o.image_overlap <= 2 || !(o.completeness_ratio <= 1.0f) || o.max_eigen_iterations < 0 ||
       !(o.eigen_tolerance > 0.0))
-    return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: option out of range");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: option out of range");
   dsm_clustering_report rep{};
   *n_images_out = 0;
   *n_clusters_out = 0;
@@ -376,44 +373,24 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
   if (report) *report = rep;
   for (uint32_t e = 0; e < n_pairs; ++e) {
     if (use && !use[e]) continue;
-    if (pairs[2 * e] == pairs[2 * e + 1]) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: image_id1 == image_id2");
-    if (weights[e] < 0) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: negative weight");
+    if (pairs[2 * e] == pairs[2 * e + 1]) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: image_id1 == image_id2");
+    if (weights[e] < 0) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: negative weight");
   }
   // unique used edges (the first occurrence of an unordered pair wins), images renumbered by ascending id
   std::vector<uint32_t> ids;
-  for (uint32_t e = 0; e < n_pairs; ++e)
-    if (!use || use[e]) {
-      ids.push_back(pairs[2 * e]);
-      ids.push_back(pairs[2 * e + 1]);
-    }
-  std::sort(ids.begin(), ids.end());
-  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+  const std::vector<GraphEdge> uniq = graph_unique_edges(n_pairs, pairs, use, ids);  // canonical (lo, hi) order
   const uint32_t N = (uint32_t)ids.size();
-  auto vid = [&](uint32_t id) { return (uint32_t)(std::lower_bound(ids.begin(), ids.end(), id) - ids.begin()); };
-  struct E {
-    uint32_t lo, hi, i, j, orig;
-  };
-  std::vector<E> edges;
-  for (uint32_t e = 0; e < n_pairs; ++e)
-    if (!use || use[e]) {
-      const uint32_t a = vid(pairs[2 * e]), b = vid(pairs[2 * e + 1]);
-      edges.push_back(E{std::min(a, b), std::max(a, b), a, b, e});
-    }
-  std::stable_sort(edges.begin(), edges.end(), [](const E& l, const E& r) { return l.lo != r.lo ? l.lo < r.lo : l.hi < r.hi; });
-  std::vector<E> uniq;  // canonical (lo, hi) order
-  for (const E& x : edges)
-    if (uniq.empty() || uniq.back().lo != x.lo || uniq.back().hi != x.hi) uniq.push_back(x);
   const uint32_t M = (uint32_t)uniq.size();
   const uint32_t k_ref = N / o.num_images_ub;
   const uint32_t k = std::max<uint32_t>(1u, k_ref);
   uint32_t n_clusters = k;
   if (labels_in) {
     for (uint32_t v = 0; v < N; ++v) {
-      if (labels_in[v] >= N) return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: label >= number of images");
+      if (labels_in[v] >= N) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: label >= number of images");
       n_clusters = std::max(n_clusters, labels_in[v] + 1);
     }
   } else if (k > 1 && k >= N) {
-    return fail(DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: k >= images (Spectra needs nev < ncv <= n)");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_cluster: k >= images (Spectra needs nev < ncv <= n)");
   }
   for (uint32_t e = 0; e < n_pairs; ++e) edge_cluster[e] = -1;
   if (M == 0) return DSM_OK;
@@ -433,35 +410,10 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
     const int m = (int)std::min<uint32_t>(2 * k, N);
     rep.ncv = (uint32_t)m;
     // CSR over images, entries sorted by neighbour; Gershgorin's upper bound of L
-    std::vector<uint32_t> off(N + 1, 0), nb(2 * (size_t)M);
+    std::vector<uint32_t> off, nb, eidx;
+    graph_neighbour_csr(N, uniq, off, nb, eidx);
     std::vector<double> wv(2 * (size_t)M);
-    for (const E& x : uniq) {
-      off[x.lo + 1]++;
-      off[x.hi + 1]++;
-    }
-    for (uint32_t v = 0; v < N; ++v) off[v + 1] += off[v];
-    {
-      std::vector<uint32_t> fill(off.begin(), off.end() - 1);
-      for (const E& x : uniq) {  // canonical order: every row fills in ascending neighbour order already
-        const double w = (double)weights[x.orig];
-        nb[fill[x.lo]] = x.hi;
-        wv[fill[x.lo]++] = w;
-      }
-      for (const E& x : uniq) {
-        const double w = (double)weights[x.orig];
-        nb[fill[x.hi]] = x.lo;
-        wv[fill[x.hi]++] = w;
-      }
-      for (uint32_t v = 0; v < N; ++v) {  // rows mix the two passes: sort each by neighbour
-        std::vector<std::pair<uint32_t, double>> row;
-        for (uint32_t p = off[v]; p < off[v + 1]; ++p) row.emplace_back(nb[p], wv[p]);
-        std::sort(row.begin(), row.end());
-        for (uint32_t p = off[v]; p < off[v + 1]; ++p) {
-          nb[p] = row[p - off[v]].first;
-          wv[p] = row[p - off[v]].second;
-        }
-      }
-    }
+    for (size_t p = 0; p < wv.size(); ++p) wv[p] = (double)weights[uniq[eidx[p]].orig];
     double bup = -DBL_MAX;
     for (uint32_t v = 0; v < N; ++v) {
       double s = (double)(off[v + 1] - off[v]);
@@ -469,7 +421,7 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
       bup = std::max(bup, s);
     }
     hipError_t he = hipSetDevice(ctx->device);
-    if (he != hipSuccess) return fail(DSM_ERR_HIP, hipGetErrorString(he));
+    if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
     hipStream_t st = ctx->stream;
     const size_t nm = (size_t)N * m, mm = (size_t)m * m;
     const int n_chunks = (int)std::min<uint32_t>(CL_MAX_CHUNKS, (N + 255) / 256);
@@ -478,36 +430,28 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
     const int grid_chunks = (int)((N + chunk_rows - 1) / chunk_rows);
     const unsigned nb_nm = (unsigned)((nm + CL_BLOCK - 1) / CL_BLOCK), nb_v = (N + CL_BLOCK - 1) / CL_BLOCK;
     DevBuf d_ids, d_off, d_nb, d_w, d_B[5], d_P, d_S, d_M, d_theta, d_C, d_dist, d_assign, d_ctl;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-#define CTRY(call)                                                  \
-  do {                                                              \
-    hipError_t e_ = (call);                                         \
-    if (e_ != hipSuccess && rc == DSM_OK) {                         \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); \
-      rc = DSM_ERR_HIP;                                             \
-    }                                                               \
-  } while (0)
-    CTRY(d_ids.reserve((size_t)N * 4));
-    CTRY(d_off.reserve(((size_t)N + 1) * 4));
-    CTRY(d_nb.reserve((size_t)M * 8));
-    CTRY(d_w.reserve((size_t)M * 16));
-    for (DevBuf& b : d_B) CTRY(b.reserve(nm * 8));
-    CTRY(d_P.reserve((size_t)grid_chunks * mm * 8));
-    CTRY(d_S.reserve(mm * 8));
-    CTRY(d_M.reserve(mm * 8));
-    CTRY(d_theta.reserve((size_t)m * 8));
-    CTRY(d_C.reserve((size_t)k * k * 8));
-    CTRY(d_dist.reserve((size_t)N * 8));
-    CTRY(d_assign.reserve((size_t)N * 4));
-    CTRY(d_ctl.reserve(sizeof(KmCtl)));
-    CTRY(hipEventCreate(&ev0));
-    CTRY(hipEventCreate(&ev1));
+    DevEvent ev0, ev1;
+    HIPTRY(d_ids.reserve((size_t)N * 4));
+    HIPTRY(d_off.reserve(((size_t)N + 1) * 4));
+    HIPTRY(d_nb.reserve((size_t)M * 8));
+    HIPTRY(d_w.reserve((size_t)M * 16));
+    for (DevBuf& b : d_B) HIPTRY(b.reserve(nm * 8));
+    HIPTRY(d_P.reserve((size_t)grid_chunks * mm * 8));
+    HIPTRY(d_S.reserve(mm * 8));
+    HIPTRY(d_M.reserve(mm * 8));
+    HIPTRY(d_theta.reserve((size_t)m * 8));
+    HIPTRY(d_C.reserve((size_t)k * k * 8));
+    HIPTRY(d_dist.reserve((size_t)N * 8));
+    HIPTRY(d_assign.reserve((size_t)N * 4));
+    HIPTRY(d_ctl.reserve(sizeof(KmCtl)));
+    HIPTRY(hipEventCreate(&ev0.e));
+    HIPTRY(hipEventCreate(&ev1.e));
     if (rc == DSM_OK) {
-      CTRY(hipEventRecord(ev0, st));
-      CTRY(hipMemcpyAsync(d_ids.p, ids.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
-      CTRY(hipMemcpyAsync(d_off.p, off.data(), ((size_t)N + 1) * 4, hipMemcpyHostToDevice, st));
-      CTRY(hipMemcpyAsync(d_nb.p, nb.data(), (size_t)M * 8, hipMemcpyHostToDevice, st));
-      CTRY(hipMemcpyAsync(d_w.p, wv.data(), (size_t)M * 16, hipMemcpyHostToDevice, st));
+      HIPTRY(hipEventRecord(ev0, st));
+      HIPTRY(hipMemcpyAsync(d_ids.p, ids.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
+      HIPTRY(hipMemcpyAsync(d_off.p, off.data(), ((size_t)N + 1) * 4, hipMemcpyHostToDevice, st));
+      HIPTRY(hipMemcpyAsync(d_nb.p, nb.data(), (size_t)M * 8, hipMemcpyHostToDevice, st));
+      HIPTRY(hipMemcpyAsync(d_w.p, wv.data(), (size_t)M * 16, hipMemcpyHostToDevice, st));
     }
     const uint32_t* off_ = d_off.as<uint32_t>();
     const uint32_t* nb_ = d_nb.as<uint32_t>();
@@ -521,12 +465,12 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
                          chunk_rows, A, Cm, d_P.as<double>());
       hipLaunchKernelGGL(k_cl_sum_chunks, dim3((unsigned)((mm + CL_BLOCK - 1) / CL_BLOCK)), dim3(CL_BLOCK), 0, st, mm, grid_chunks,
                          (const double*)d_P.as<double>(), d_S.as<double>());
-      CTRY(hipGetLastError());
-      CTRY(hipMemcpyAsync(out.data(), d_S.p, mm * 8, hipMemcpyDeviceToHost, st));
-      CTRY(hipStreamSynchronize(st));
+      HIPTRY(hipGetLastError());
+      HIPTRY(hipMemcpyAsync(out.data(), d_S.p, mm * 8, hipMemcpyDeviceToHost, st));
+      HIPTRY(hipStreamSynchronize(st));
     };
     auto rmul = [&](const double* X, const std::vector<double>& Mh, double* Y) {
-      CTRY(hipMemcpyAsync(d_M.p, Mh.data(), mm * 8, hipMemcpyHostToDevice, st));
+      HIPTRY(hipMemcpyAsync(d_M.p, Mh.data(), mm * 8, hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(k_cl_rmul, dim3(nb_nm), dim3(CL_BLOCK), 0, st, N, m, X, (const double*)d_M.as<double>(), Y);
     };
     auto spmm = [&](const double* X, double alpha, double c, double beta, const double* Xp, double* Y) {
@@ -615,14 +559,14 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
       LX = nlx;
       rep.eigen_iterations = (uint32_t)(it + 1);
       if (rc != DSM_OK) break;
-      CTRY(hipMemcpyAsync(d_theta.p, theta.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+      HIPTRY(hipMemcpyAsync(d_theta.p, theta.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(k_cl_resid, dim3(grid_chunks), dim3(CL_BLOCK), 0, st, N, m, (int)k, chunk_rows, (const double*)B[X],
                          (const double*)B[LX], (const double*)d_theta.as<double>(), d_P.as<double>());
       hipLaunchKernelGGL(k_cl_sum_chunks, dim3((k + CL_BLOCK - 1) / CL_BLOCK), dim3(CL_BLOCK), 0, st, (size_t)k, grid_chunks,
                          (const double*)d_P.as<double>(), d_S.as<double>());
-      CTRY(hipGetLastError());
-      CTRY(hipMemcpyAsync(res2.data(), d_S.p, (size_t)k * 8, hipMemcpyDeviceToHost, st));
-      CTRY(hipStreamSynchronize(st));
+      HIPTRY(hipGetLastError());
+      HIPTRY(hipMemcpyAsync(res2.data(), d_S.p, (size_t)k * 8, hipMemcpyDeviceToHost, st));
+      HIPTRY(hipStreamSynchronize(st));
       double worst = 0.0, worst_ratio = 0.0;
       for (uint32_t j = 0; j < k; ++j) {
         const double r = std::sqrt(res2[j]);
@@ -654,15 +598,15 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
       for (int c = 1; c < kk && rc == DSM_OK; ++c) {
         hipLaunchKernelGGL(k_km_mindist, dim3(nb_v), dim3(CL_BLOCK), 0, st, N, m, kk, Xk, (const double*)d_C.as<double>(), c - 1,
                            d_dist.as<double>());
-        CTRY(hipGetLastError());
-        CTRY(hipMemcpyAsync(dist.data(), d_dist.p, (size_t)N * 8, hipMemcpyDeviceToHost, st));
-        CTRY(hipStreamSynchronize(st));
+        HIPTRY(hipGetLastError());
+        HIPTRY(hipMemcpyAsync(dist.data(), d_dist.p, (size_t)N * 8, hipMemcpyDeviceToHost, st));
+        HIPTRY(hipStreamSynchronize(st));
         std::discrete_distribution<size_t> draw(dist.cbegin(), dist.cend());
         hipLaunchKernelGGL(k_km_take, dim3(1), dim3(CL_BLOCK), 0, st, m, kk, Xk, (uint32_t)draw(rng), c, d_C.as<double>());
       }
-      CTRY(hipMemsetAsync(d_ctl.p, 0, sizeof(KmCtl), st));
+      HIPTRY(hipMemsetAsync(d_ctl.p, 0, sizeof(KmCtl), st));
       std::vector<uint32_t> init(N, k);
-      CTRY(hipMemcpyAsync(d_assign.p, init.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
+      HIPTRY(hipMemcpyAsync(d_assign.p, init.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
       KmCtl h{};
       const int batch = 8;
       for (int t0 = 0; rc == DSM_OK && !h.done; t0 += batch) {
@@ -674,31 +618,26 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
                              d_C.as<double>(), (const KmCtl*)d_ctl.as<KmCtl>());
           hipLaunchKernelGGL(k_km_check, dim3(1), dim3(1), 0, st, d_ctl.as<KmCtl>(), t);
         }
-        CTRY(hipGetLastError());
-        CTRY(hipMemcpyAsync(&h, d_ctl.p, sizeof(KmCtl), hipMemcpyDeviceToHost, st));
-        CTRY(hipStreamSynchronize(st));
+        HIPTRY(hipGetLastError());
+        HIPTRY(hipMemcpyAsync(&h, d_ctl.p, sizeof(KmCtl), hipMemcpyDeviceToHost, st));
+        HIPTRY(hipStreamSynchronize(st));
       }
       rep.kmeans_iterations = (uint32_t)h.iters;
-      CTRY(hipEventRecord(ev1, st));
-      CTRY(hipMemcpyAsync(label.data(), d_assign.p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+      HIPTRY(hipEventRecord(ev1, st));
+      HIPTRY(hipMemcpyAsync(label.data(), d_assign.p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
       std::vector<double> Xh(nm);
-      CTRY(hipMemcpyAsync(Xh.data(), Xk, nm * 8, hipMemcpyDeviceToHost, st));
-      CTRY(hipStreamSynchronize(st));
+      HIPTRY(hipMemcpyAsync(Xh.data(), Xk, nm * 8, hipMemcpyDeviceToHost, st));
+      HIPTRY(hipStreamSynchronize(st));
       ctx->cluster_vectors.resize((size_t)N * k);
       for (uint32_t n = 0; n < N; ++n)
         for (uint32_t j = 0; j < k; ++j) ctx->cluster_vectors[(size_t)n * k + j] = Xh[(size_t)n * m + j];
       ctx->cluster_rows = N;
       ctx->cluster_cols = k;
       float ms = 0.f;
-      CTRY(hipEventElapsedTime(&ms, ev0, ev1));
+      HIPTRY(hipEventElapsedTime(&ms, ev0, ev1));
       rep.device_ms = ms;
     }
-#undef CTRY
     if (rc != DSM_OK) (void)hipStreamSynchronize(st);
-    for (DevBuf* b : {&d_ids, &d_off, &d_nb, &d_w, &d_P, &d_S, &d_M, &d_theta, &d_C, &d_dist, &d_assign, &d_ctl}) b->release();
-    for (DevBuf& b : d_B) b.release();
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
     if (rc != DSM_OK) {
       if (report) *report = rep;
       return rc;
@@ -706,7 +645,7 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
   }
 
   for (uint32_t v = 0; v < N; ++v)
-    if (label[v] >= n_clusters) return fail(DSM_ERR_NOT_CONVERGED, "dsm_view_graph_cluster: a point without a nearest centre");
+    if (label[v] >= n_clusters) return dsm_fail(ctx, DSM_ERR_NOT_CONVERGED, "dsm_view_graph_cluster: a point without a nearest centre");
   // ------------------------------------------------------------ Cut (image_clustering.cpp:68-128): intra clusters, lost edges
   ClusterState cs;
   cs.completeness_ratio = o.completeness_ratio;
@@ -716,10 +655,10 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
   cs.sticky.assign(n_clusters, 0);
   cs.n_edges.assign(n_clusters, 0);
   for (uint32_t v = 0; v < N; ++v) cs.add(label[v], v);
-  std::vector<E> in_order(uniq);  // input order of the surviving occurrences
-  std::sort(in_order.begin(), in_order.end(), [](const E& l, const E& r) { return l.orig < r.orig; });
-  std::map<std::pair<uint32_t, uint32_t>, std::vector<E>> lost;
-  for (const E& x : in_order) {
+  std::vector<GraphEdge> in_order(uniq);  // input order of the surviving occurrences
+  std::sort(in_order.begin(), in_order.end(), [](const GraphEdge& l, const GraphEdge& r) { return l.orig < r.orig; });
+  std::map<std::pair<uint32_t, uint32_t>, std::vector<GraphEdge>> lost;
+  for (const GraphEdge& x : in_order) {
     const uint32_t c1 = label[x.i], c2 = label[x.j];
     if (c1 == c2) {
       edge_cluster[x.orig] = (int32_t)c1;
@@ -734,11 +673,11 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
   if (o.expand && n_clusters > 1) {
     for (auto& it : lost) {
       const uint32_t c1 = it.first.first, c2 = it.first.second;
-      std::vector<E>& le = it.second;
+      std::vector<GraphEdge>& le = it.second;
       if (cs.common(c1, c2) > o.image_overlap) continue;
       if (cs.satisfied(c1) && cs.satisfied(c2)) continue;
-      std::stable_sort(le.begin(), le.end(), [&](const E& l, const E& r) { return weights[l.orig] > weights[r.orig]; });
-      for (const E& x : le) {
+      std::stable_sort(le.begin(), le.end(), [&](const GraphEdge& l, const GraphEdge& r) { return weights[l.orig] > weights[r.orig]; });
+      for (const GraphEdge& x : le) {
         const uint32_t src = x.i, dst = x.j;
         const uint32_t added1 = cs.has(c1, src) ? dst : src;
         const uint32_t added2 = cs.has(c2, src) ? dst : src;
