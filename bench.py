@@ -17,6 +17,13 @@ Other workloads of BASELINE.json (parity-test / profile cases, not the default l
   --images 10000 --pairs knn:200 --shard-of 8                       configs[3], one GPU's shard of the 8
   --images 10000 --feats 8192 --pairs knn:200 --fixed-trials 4096 --shard-of 8 --max-pairs N    configs[4], shard
 
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes --dump-outputs / --dump-graph
+if asked and prints the line.  --full adds everything else after the timed region, as side figures that never touch `value`:
+the CPU baseline of oracle/ (-O3 and -O3 -march=native) with the oracle parity of a sample of the timed graph, the side
+workloads (extra.low_inlier_regime, extra.uncalibrated, extra.config1, extra.config3_match_only, each with its own parity
+sample) and the repeated image handover (host_handover.ms_repeat).  --cpu-seconds and the --no-* switches of the side
+workloads shape a --full run.
+
 Rank 0 prints ONE JSON line (README / DESIGN.md "Measurement").
 """
 import argparse
@@ -184,7 +191,10 @@ def parse_args():
     ap.add_argument("--no-verify", action="store_true", help="matching only (BASELINE configs[2])")
     ap.add_argument("--uncalibrated", action="store_true",
                     help="cameras without focal prior: F + H path (EstimateUncalibrated) instead of E + F + H + pose")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="wall-clock budget of the CPU-baseline samples (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the CPU baseline with its oracle parity sample, the side workloads "
+                         "(extra.*) and the repeated image handover; a plain run measures the headline only")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="with --full: wall-clock budget of the CPU-baseline samples (0 = skip)")
     ap.add_argument("--contexts", type=int, default=1,
                     help="dsm contexts per GPU: the rank's share of the pair list is cut into that many contiguous parts, each "
                          "matched + verified by its own context / stream / host thread (the latency-bound tails of one part's "
@@ -194,13 +204,13 @@ def parse_args():
                          "broadcast calls the N-rank exchange makes (the part of the RCCL path a one-GPU box can run); the "
                          "line then carries the measured exchange time")
     ap.add_argument("--no-second-regime", action="store_true",
-                    help="skip the low-inlier-ratio side measurement (extra.low_inlier_regime) after the timed region")
+                    help="with --full: skip the low-inlier-ratio side measurement (extra.low_inlier_regime) after the timed region")
     ap.add_argument("--no-config3", action="store_true",
-                    help="skip the 2 000-image matching-only side measurement (extra.config3_match_only: BASELINE configs[2], the shape north_star's "
-                         ">= 10x the host CPU on 2 000-image exhaustive matching target is stated on) after the timed region")
+                    help="with --full: skip the 2 000-image matching-only side measurement (extra.config3_match_only: BASELINE configs[2], the shape "
+                         "north_star's >= 10x the host CPU on 2 000-image exhaustive matching target is stated on) after the timed region")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the two further side measurements after the timed region: the same pair list with cameras without a focal prior "
-                         "(extra.uncalibrated: F + H) and BASELINE configs[0] on the GPU (extra.config1: 50 x 1 024, every pair checked)")
+                    help="with --full: skip the two further side measurements after the timed region: the same pair list with cameras without a "
+                         "focal prior (extra.uncalibrated: F + H) and BASELINE configs[0] on the GPU (extra.config1: 50 x 1 024, every pair checked)")
     ap.add_argument("--memory-budget-gib", type=float, default=0.0,
                     help="dsm_ctx_set_memory_budget: GiB of transient chunk scratch the matcher and the verifier may hold (0: the defaults)")
     ap.add_argument("--no-match-lock", action="store_true", help="experiment: with --contexts > 1, let the contexts' matching calls overlap")
@@ -506,9 +516,11 @@ def main():
         c.set_images([im[0] for im in images], [im[1] for im in images], cams)  # (synchronous: the images are in HBM when it returns)
         handover_s.append(time.perf_counter() - th)
     # (the first call of a context also allocates the resident buffers and loads the code object: a second one shows the transfer alone)
-    th = time.perf_counter()
-    ctxs[0].set_images([im[0] for im in images], [im[1] for im in images], cams)
-    handover_repeat_s = time.perf_counter() - th
+    handover_repeat_s = None
+    if args.full:
+        th = time.perf_counter()
+        ctxs[0].set_images([im[0] for im in images], [im[1] for im in images], cams)
+        handover_repeat_s = time.perf_counter() - th
     cbounds = sharding.shard_bounds(len(my_pairs), n_ctx)
     cparts = [my_pairs[cbounds[k]:cbounds[k + 1]] for k in range(n_ctx)]
     opts = capi.default_match_options()
@@ -705,8 +717,10 @@ def main():
         # the boundary hands over HOST buffers (dsm_set_images): outside the timed region, once per job.  Its measured time and
         # the rate a job would see that paid it before EVERY step (never `value`)
         image_bytes = sum(im[0].nbytes + (im[1].nbytes if im[1] is not None else 0) for im in images)
-        out["host_handover"] = {"ms": 1e3 * min(handover_s), "ms_repeat": 1e3 * handover_repeat_s, "bytes": image_bytes,
+        out["host_handover"] = {"ms": 1e3 * min(handover_s), "bytes": image_bytes,
                                 "value_if_paid_every_step": n_pairs / (ms_per_step / 1e3 + min(handover_s)) if world == 1 else None}
+        if handover_repeat_s is not None:
+            out["host_handover"]["ms_repeat"] = 1e3 * handover_repeat_s
         if pass1_s > 0 and res["matches"] >= 0:
             # what the matrix pipe executed: pass 1 = the whole matrix; pass 2 = gathered rows in 128-row wave units
             out["roofline"]["frac_pass1_only"] = ops_per_pair * pairs_per_launch / pass1_s / int8_peak
@@ -727,13 +741,13 @@ def main():
         if args.memory_budget_gib > 0:
             res_b, scr_b = ctx.memory_footprint()
             out["memory"] = {"budget_gib": args.memory_budget_gib, "scratch_gib": scr_b / 2 ** 30, "resident_gib": res_b / 2 ** 30}
-        # ---- side measurements after the timed region (never part of `value`), each held against the oracle on a bounded sample of
-        # its own pairs (`parity_sample`): what is timed is what is checked
-        side_ok = (world == 1 and verify and args.shard_of == 1 and not args.max_pairs and args.pairs == "exhaustive" and not args.fixed_trials
-                   and not args.uncalibrated)
+        # ---- --full: side measurements after the timed region (never part of `value`), each held against the oracle on a bounded sample
+        # of its own pairs (`parity_sample`): what is timed is what is checked
+        side_ok = (args.full and world == 1 and verify and args.shard_of == 1 and not args.max_pairs and args.pairs == "exhaustive"
+                   and not args.fixed_trials and not args.uncalibrated)
         cores = min(host_cores(), 256)
         orc = None
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             from tests import oracle_lib
             orc = oracle_lib.load()
 
@@ -829,8 +843,8 @@ def main():
                 extra["config3_match_only"] = {"error": repr(e)}
         if extra:
             out["extra"] = extra
-        # ---- the CPU baseline on a bounded sample of the headline workload -- and the graph of the LAST TIMED STEP held against the
-        # oracle's results for exactly those pairs
+        # ---- --full: the CPU baseline on a bounded sample of the headline workload -- and the graph of the LAST TIMED STEP held against
+        # the oracle's results for exactly those pairs
         if orc is not None:
             share = args.cpu_seconds * 0.6
             keep = {}

@@ -198,3 +198,18 @@ def test_dump_outputs_is_a_fixed_sample_within_the_limit(tmp_path):
     assert (sels[0] == sels[1]).all()
     with pytest.raises(SystemExit):
         bench.dump_outputs(str(tmp_path / "big"), sharding.MatchGraph(torch.zeros(9 << 20, dtype=torch.int64), m[:0]), False, feats)
+
+
+def test_side_measurements_only_with_full(monkeypatch):
+    """A plain run measures the headline only: --full is off unless asked for, and the oracle, the side workloads and the repeated
+    handover are reached only through it."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1", "--full"])
+    assert bench.parse_args().full is True
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    main = src[src.index("def main():"):]
+    assert "if args.full and args.cpu_seconds > 0" in main and "side_ok = (args.full and" in main
+    assert main.index("if args.full:") < main.index("handover_repeat_s = time.perf_counter() - th")

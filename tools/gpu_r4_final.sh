@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 timeout 900 python -m pytest tests -m gpu -x -q > $out/pytest.log 2>&1; tail -4 $out/pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout 600 python bench.py --steps 5 --warmup 1 > $out/bench_default.json 2> $out/bench_default.err; python -c "
+timeout 600 python bench.py --full --steps 5 --warmup 1 > $out/bench_default.json 2> $out/bench_default.err; python -c "
 import json; d=json.load(open('$out/bench_default.json')); print('default', round(d['value']), round(d['ms_per_step'],1), d['kernel_ms_per_step'], d['roofline']['frac'], d['roofline'].get('executed_frac'), d['roofline_verify']['frac'], d['cpu_baseline']['value'], d['cpu_baseline_native']['value'], d['extra'])"
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/prof -o bench -- python $R/bench.py --steps 2 --warmup 1 --cpu-seconds 0 --no-second-regime > $R/$out/bench_under_rocprof.json 2> $R/$out/rocprof.err)
 find $out/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/bench_kernel_stats.csv

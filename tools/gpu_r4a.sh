@@ -6,7 +6,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 timeout 900 python -m pytest tests -m gpu -x -q > $out/pytest.log 2>&1; tail -5 $out/pytest.log
-timeout 400 python bench.py --steps 3 --warmup 1 --cpu-seconds 0 > $out/bench_default.json 2> $out/bench_default.err; tail -c 300 $out/bench_default.err
+timeout 400 python bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 > $out/bench_default.json 2> $out/bench_default.err; tail -c 300 $out/bench_default.err
 python - <<PY
 import json
 d=json.load(open('$out/bench_default.json'))

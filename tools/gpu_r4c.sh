@@ -12,7 +12,7 @@ timeout 600 python tools/check_schedules.py --images 200 --uncalibrated > $out/c
 timeout 600 python tools/fuzz_verify.py --batches 4 --pairs 1500 --seed 41 > $out/fuzz_verify.txt 2>&1; tail -4 $out/fuzz_verify.txt
 timeout 600 python tools/fuzz_verify.py --batches 2 --pairs 300 --seed 43 --big > $out/fuzz_verify_big.txt 2>&1; tail -3 $out/fuzz_verify_big.txt
 for v in 1 0; do
-  DSM_SCORE_PREFILTER=$v timeout 400 python bench.py --steps 3 --warmup 1 --cpu-seconds 0 > $out/bench_prefilter$v.json 2>/dev/null
+  DSM_SCORE_PREFILTER=$v timeout 400 python bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 > $out/bench_prefilter$v.json 2>/dev/null
   python -c "
 import json; d=json.load(open('$out/bench_prefilter$v.json')); print('prefilter $v', round(d['value']), round(d['ms_per_step'],1), d['kernel_ms_per_step']['k_verify_pairs'], d.get('extra'))"
 done

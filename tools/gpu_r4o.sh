@@ -10,5 +10,5 @@ timeout 1200 python tools/check_schedules.py --legacy > $out/check_schedules.txt
 timeout 600 python tools/check_schedules.py --images 150 --outlier-frac 0.5 > $out/check_schedules_ratio025.txt 2>&1; cat $out/check_schedules_ratio025.txt
 timeout 600 python tools/check_score_bounds.py > $out/score_bounds.txt 2>&1; tail -4 $out/score_bounds.txt
 for rep in 1 2; do for v in 3 1; do
-  echo -n "DSM_SCORE_PREFILTER=$v: "; DSM_SCORE_PREFILTER=$v timeout 400 python bench.py --steps 3 --warmup 1 --cpu-seconds 0 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value']), round(d['ms_per_step'],1), d['kernel_ms_per_step']['k_verify_pairs'], d['extra']['low_inlier_regime']['ms_per_step'])"
+  echo -n "DSM_SCORE_PREFILTER=$v: "; DSM_SCORE_PREFILTER=$v timeout 400 python bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value']), round(d['ms_per_step'],1), d['kernel_ms_per_step']['k_verify_pairs'], d['extra']['low_inlier_regime']['ms_per_step'])"
 done; done | tee $out/ab_e_lane_per_model.txt

@@ -3,7 +3,7 @@
 out=gpurun_out/r5h
 mkdir -p $out
 export TMPDIR=/tmp
-timeout 900 python bench.py --dump-line $out/bench_default_long.json > $out/bench_default.json 2> $out/bench_default.err; wc -c $out/bench_default.json; python - <<'P'
+timeout 900 python bench.py --full --dump-line $out/bench_default_long.json > $out/bench_default.json 2> $out/bench_default.err; wc -c $out/bench_default.json; python - <<'P'
 import json
 d=json.loads(open('gpurun_out/r5h/bench_default.json').read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d['kernel_ms_per_step'], d['roofline']['frac'])

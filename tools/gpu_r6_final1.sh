@@ -12,7 +12,7 @@ DSM_VERIFY_LANES=1 timeout 900 python tools/collect_pmc.py --verify --out $out/v
 rm -rf gpurun_out/pmc
 # the collections go where bench.py looks for them BEFORE the driver's command runs: its line then carries fresh from_profiles figures
 cp $out/k1_pmc.json profiles/r06_k1_pmc.json; cp $out/verify_pmc.json profiles/r06_verify_pmc.json
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --dump-line $out/bench_default_long.json > $out/bench_default.json 2> $out/bench_default.err ) 2> $out/bench_time.txt; echo "bench rc=$?"; tail -3 $out/bench_time.txt; wc -c $out/bench_default.json
+( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --dump-line $out/bench_default_long.json > $out/bench_default.json 2> $out/bench_default.err ) 2> $out/bench_time.txt; echo "bench rc=$?"; tail -3 $out/bench_time.txt; wc -c $out/bench_default.json
 python - <<PY
 import json
 d = json.loads(open("$out/bench_default.json").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 timeout 1200 python -m pytest tests/test_verify_gpu.py tests/test_parity_fullsize_gpu.py -m gpu -x -q > $out/pytest.log 2>&1; tail -3 $out/pytest.log
 for i in 1 2; do
-timeout 600 python bench.py --steps 10 --warmup 3 --cpu-seconds 0 --no-config3 --no-extra-configs > $out/bench_$i.json 2> $out/bench_$i.err
+timeout 600 python bench.py --full --steps 10 --warmup 3 --cpu-seconds 0 --no-config3 --no-extra-configs > $out/bench_$i.json 2> $out/bench_$i.err
 python - <<PY
 import json
 d = json.loads(open("$out/bench_$i.json").read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 out=gpurun_out/r6e
 mkdir -p $out
 export TMPDIR=/tmp
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --dump-line $out/bench_long.json > $out/bench_default.json 2> $out/bench_default.err ) 2> $out/time.txt
+( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --dump-line $out/bench_long.json > $out/bench_default.json 2> $out/bench_default.err ) 2> $out/time.txt
 echo "rc=$?"; tail -3 $out/time.txt; tail -5 $out/bench_default.err
 python - <<'PY'
 import json

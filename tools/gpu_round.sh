@@ -5,7 +5,7 @@ tag=${1:-r02}
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-python bench.py --steps 3 --warmup 1 > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full --steps 3 --warmup 1 > $out/bench_default.json 2> $out/bench_default.err
 tail -c 600 $out/bench_default.err
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$out/prof -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --cpu-seconds 0 > $GRAFT_REPO_ROOT/$out/bench_under_rocprof.json 2> $GRAFT_REPO_ROOT/$out/rocprof.err)
 find $out/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/kernel_stats.csv
