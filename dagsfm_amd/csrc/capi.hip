@@ -34,11 +34,6 @@ namespace {
 thread_local std::string g_create_error;
 }  // namespace
 
-static int fail(dsm_ctx* ctx, int code, const char* msg) {
-  if (ctx) ctx->err = msg;
-  return code;
-}
-
 // ---------------------------------------------------------------------------------- hand-over of host buffers
 // The reference's FeatureDescriptors / FeatureKeypoints are Eigen matrices and std::vectors in PAGEABLE memory
 // (/root/reference/src/feature/types.h:102-104), one allocation per image.  hipMemcpy from pageable memory goes through the
@@ -83,14 +78,17 @@ static int staged_upload(dsm_ctx* ctx, uint64_t total, uint8_t* dev_dst, bool th
     HIPCHK(ctx, hipMemcpyAsync(dev, tmp.data(), total, hipMemcpyHostToDevice, ctx->stream));
     if (through_device_slot) {
       const int rc = arrived(dev, 0, total);
-      if (rc != DSM_OK) return rc;
+      if (rc != DSM_OK) {
+        (void)hipStreamSynchronize(ctx->stream);  // the copy may still read tmp
+        return rc;
+      }
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (tmp is read until here)
     return DSM_OK;
   }
-  if (!ctx->h_stage) HIPCHK(ctx, hipHostMalloc(&ctx->h_stage, 2 * kStageSlot, hipHostMallocDefault));
-  for (hipEvent_t& e : ctx->stage_ev)
-    if (!e) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (!ctx->h_stage.p) HIPCHK(ctx, hipHostMalloc(&ctx->h_stage.p, 2 * kStageSlot, hipHostMallocDefault));
+  for (DevEvent& e : ctx->stage_ev)
+    if (!e) HIPCHK(ctx, hipEventCreateWithFlags(&e.e, hipEventDisableTiming));
   if (through_device_slot) HIPCHK(ctx, ctx->d_stage.reserve(2 * kStageSlot));
   const unsigned hw = std::thread::hardware_concurrency();
   const unsigned n_thr = std::max(1u, std::min(kStageThreads, hw / 4));  // (the shim hands over to every device of gpu_index at once)
@@ -98,7 +96,7 @@ static int staged_upload(dsm_ctx* ctx, uint64_t total, uint8_t* dev_dst, bool th
   for (uint32_t piece = 0; begin < total; ++piece) {
     const uint32_t slot = piece & 1u;
     const uint64_t end = std::min(total, begin + kStageSlot);
-    uint8_t* host = static_cast<uint8_t*>(ctx->h_stage) + slot * kStageSlot;
+    uint8_t* host = ctx->h_stage.as<uint8_t>() + slot * kStageSlot;
     if (piece >= 2) HIPCHK(ctx, hipEventSynchronize(ctx->stage_ev[slot]));  // the copy out of this slot two pieces ago is done
     {
       // equal shares of the piece, cut at 4 KB; the caller's thread takes the first
@@ -189,7 +187,7 @@ int dsm_ctx_create(int device, dsm_ctx** out_ctx) {
   }
   dsm_ctx* c = new dsm_ctx();
   c->device = device;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+  if (hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking) != hipSuccess) {
     delete c;
     g_create_error = "hipStreamCreate failed";
     return DSM_ERR_HIP;
@@ -200,7 +198,7 @@ int dsm_ctx_create(int device, dsm_ctx** out_ctx) {
   // own; created lazily at the first dsm_verify_pairs they got whatever was left (bench.py --force-collectives: 322 ms of
   // verification against 288, profiles/r05_lanes_hw_queues.txt).  Not fatal if it fails here: the lane creates it when it runs.
   c->lanes[0].stream = c->stream;
-  if (hipStreamCreateWithFlags(&c->lanes[1].stream, hipStreamNonBlocking) != hipSuccess) c->lanes[1].stream = nullptr;
+  if (hipStreamCreateWithFlags(&c->lanes[1].own_stream.s, hipStreamNonBlocking) == hipSuccess) c->lanes[1].stream = c->lanes[1].own_stream;
   // acos LUT over the integer dot product, built with the host libm so that the float
   // compares of sift.cc:140-155 are reproduced bit for bit.
   std::vector<float> lut(262145);
@@ -210,7 +208,6 @@ int dsm_ctx_create(int device, dsm_ctx** out_ctx) {
       hipMemcpy(c->d_lut.p, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
       c->d_total.reserve(sizeof(uint64_t)) != hipSuccess) {
     g_create_error = "device allocation failed";
-    (void)hipStreamDestroy(c->stream);
     delete c;
     return DSM_ERR_HIP;
   }
@@ -224,37 +221,6 @@ void dsm_ctx_destroy(dsm_ctx* ctx) {
   if (ctx->leaf) dsm_ctx_destroy(ctx->leaf);
   dsm_retrieval_destroy(ctx);
   (void)hipStreamSynchronize(ctx->stream);
-  for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
-  DevBuf* bufs[] = {&ctx->d_desc, &ctx->d_rterm, &ctx->d_kp, &ctx->d_img_row0, &ctx->d_img_rows, &ctx->d_lut,
-                    &ctx->d_dpairs, &ctx->d_doutoff, &ctx->d_pair_dir, &ctx->d_m, &ctx->d_counts,
-                    &ctx->d_offsets, &ctx->d_matches, &ctx->d_total, &ctx->d_cams, &ctx->d_pairs_dev, &ctx->d_seeds,
-                    &ctx->d_tvg, &ctx->d_inl, &ctx->d_inl_counts, &ctx->d_inl_off, &ctx->d_inl_compact,
-                    &ctx->d_vscratch, &ctx->d_inl_total, &ctx->d_nt_table, &ctx->d_nt_off, &ctx->d_nt_off_t,
-                    &ctx->d_pair_state, &ctx->d_pts_px, &ctx->d_pts_norm, &ctx->d_reports, &ctx->d_masks,
-                    &ctx->d_fam_state,
-                    &ctx->d_sidx, &ctx->d_g_nfeat, &ctx->d_g_dpairs, &ctx->d_g_doff, &ctx->d_g_pdir,
-                    &ctx->d_g_params, &ctx->d_g_m, &ctx->d_g_counts, &ctx->d_g_offsets, &ctx->d_g_total, &ctx->d_g_matches, &ctx->d_g_plan,
-                    &ctx->d_g_inl, &ctx->d_g_inl_off, &ctx->d_mm_matches[0], &ctx->d_mm_matches[1], &ctx->d_mm_off[0],
-                    &ctx->d_mm_off[1], &ctx->d_mm_counts, &ctx->d_mm_state, &ctx->d_mm_first, &ctx->d_mm_acc, &ctx->d_mm_keep,
-                    &ctx->d_mm_total, &ctx->d_order, &ctx->d_dpairs2, &ctx->d_ecnt, &ctx->d_eoff, &ctx->d_etotal, &ctx->d_entries,
-                    &ctx->d_out2, &ctx->d_ms, &ctx->d_out2s, &ctx->d_lo_inl, &ctx->d_lo_inl_pool, &ctx->d_nt_table_t, &ctx->d_wm_redo, &ctx->d_wm_total,
-                    &ctx->d_wm_count, &ctx->d_pose_jobs};
-  for (VerifyLane& L : ctx->lanes) {
-    for (DevBuf* b : {&L.samples, &L.draws_end, &L.nmodels, &L.vcounts, &L.vsums, &L.models, &L.ework, &L.active, &L.vscratch, &L.lo_queue,
-                      &L.lo_work, &L.lo_models, &L.lo_slots, &L.lo_ework, &L.tail_items, &L.tail_n, &L.lo_jobs, &L.job_list, &L.hyp_map})
-      b->release();
-    if (L.done) (void)hipEventDestroy(L.done);
-    if (L.host_ctr) (void)hipHostFree(L.host_ctr);
-    if (L.stream && L.stream != ctx->stream) (void)hipStreamDestroy(L.stream);
-  }
-  if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-  for (hipEvent_t e : ctx->stage_ev)
-    if (e) (void)hipEventDestroy(e);
-  ctx->d_stage.release();
-  if (ctx->vev0) (void)hipEventDestroy(ctx->vev0);
-  if (ctx->vev1) (void)hipEventDestroy(ctx->vev1);
-  for (DevBuf* b : bufs) b->release();
-  (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
 
@@ -292,7 +258,7 @@ int dsm_set_debug_option(dsm_ctx* ctx, const char* key, const char* value) {
   for (const char* k : dsm_check_debug_keys) known = known || strcmp(k, key) == 0;
 #endif
   if (!known)
-    return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_set_debug_option: unknown key (the cross-check switches exist in libdagsfm_mi355x_check.so only)");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_set_debug_option: unknown key (the cross-check switches exist in libdagsfm_mi355x_check.so only)");
   if (value)
     ctx->debug_options[key] = value;
   else
@@ -304,16 +270,6 @@ int dsm_set_debug_option(dsm_ctx* ctx, const char* key, const char* value) {
 // quarter of it (at most their default 8 GiB), the verifier the rest.
 static inline uint64_t match_budget_share(uint64_t budget) { return std::min<uint64_t>(8ull << 30, budget / 4); }
 
-static std::vector<DevBuf*> scratch_buffers(dsm_ctx* ctx) {
-  std::vector<DevBuf*> v = {&ctx->d_m, &ctx->d_ms, &ctx->d_entries, &ctx->d_out2, &ctx->d_out2s, &ctx->d_dpairs, &ctx->d_dpairs2, &ctx->d_doutoff, &ctx->d_pair_dir,
-                            &ctx->d_order, &ctx->d_ecnt, &ctx->d_eoff, &ctx->d_vscratch};
-  for (VerifyLane& L : ctx->lanes)
-    for (DevBuf* b : {&L.samples, &L.draws_end, &L.nmodels, &L.vcounts, &L.vsums, &L.models, &L.ework, &L.active, &L.vscratch, &L.lo_queue, &L.lo_work,
-                      &L.lo_models, &L.lo_slots, &L.lo_ework, &L.tail_items, &L.tail_n, &L.lo_jobs, &L.job_list, &L.hyp_map})
-      v.push_back(b);
-  return v;
-}
-
 int dsm_ctx_set_memory_budget(dsm_ctx* ctx, uint64_t bytes) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -321,9 +277,11 @@ int dsm_ctx_set_memory_budget(dsm_ctx* ctx, uint64_t bytes) {
   ctx->memory_budget = bytes;
   if (bytes) {  // scratch held from an earlier, larger call is given back now: the next call allocates inside the budget
     uint64_t held = 0;
-    for (DevBuf* b : scratch_buffers(ctx)) held += b->cap;
+    ctx->for_each_buffer([&](DevBuf& b, bool scratch) { held += scratch ? b.cap : 0; });
     if (held > bytes)
-      for (DevBuf* b : scratch_buffers(ctx)) b->release();
+      ctx->for_each_buffer([](DevBuf& b, bool scratch) {
+        if (scratch) b.release();
+      });
   }
   return DSM_OK;
 }
@@ -332,13 +290,7 @@ int dsm_ctx_memory_footprint(const dsm_ctx* cctx, uint64_t* resident_bytes, uint
   if (!cctx) return DSM_ERR_INVALID_ARGUMENT;
   dsm_ctx* ctx = const_cast<dsm_ctx*>(cctx);
   uint64_t scratch = 0, resident = 0;
-  for (DevBuf* b : scratch_buffers(ctx)) scratch += b->cap;
-  for (DevBuf* b : {&ctx->d_stage, &ctx->d_desc, &ctx->d_rterm, &ctx->d_kp, &ctx->d_img_row0, &ctx->d_img_rows, &ctx->d_lut, &ctx->d_counts, &ctx->d_offsets, &ctx->d_matches,
-                    &ctx->d_total, &ctx->d_etotal, &ctx->d_cams, &ctx->d_pairs_dev, &ctx->d_seeds, &ctx->d_tvg, &ctx->d_inl, &ctx->d_inl_counts, &ctx->d_inl_off,
-                    &ctx->d_inl_compact, &ctx->d_inl_total, &ctx->d_nt_table, &ctx->d_nt_off, &ctx->d_nt_off_t, &ctx->d_pair_state, &ctx->d_pts_px,
-                    &ctx->d_pts_norm, &ctx->d_reports, &ctx->d_masks, &ctx->d_fam_state, &ctx->d_sidx, &ctx->d_lo_inl, &ctx->d_nt_table_t, &ctx->d_wm_redo,
-                    &ctx->d_wm_total, &ctx->d_wm_count, &ctx->d_lo_inl_pool, &ctx->d_pose_jobs})
-    resident += b->cap;
+  ctx->for_each_buffer([&](DevBuf& b, bool is_scratch) { (is_scratch ? scratch : resident) += b.cap; });
   if (resident_bytes) *resident_bytes = resident;
   if (scratch_bytes) *scratch_bytes = scratch;
   return DSM_OK;
@@ -349,24 +301,24 @@ int dsm_ctx_memory_footprint(const dsm_ctx* cctx, uint64_t* resident_bytes, uint
 static int upload_images(dsm_ctx* ctx, bool append, uint32_t n_new, const uint32_t* n_feats, const uint8_t* const* desc,
                          const float* const* kp_xy, uint32_t kp_stride, const dsm_camera* cameras) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  if (n_new && (!n_feats || !desc)) return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "null image arrays");
-  if (kp_xy && kp_stride < 2) return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "kp_stride must be >= 2");
+  if (n_new && (!n_feats || !desc)) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "null image arrays");
+  if (kp_xy && kp_stride < 2) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "kp_stride must be >= 2");
   if (cameras)  // Camera::SetModelId CHECKs ExistsCameraModelWithId (camera.cc:52); never a silent default
     for (uint32_t i = 0; i < n_new; ++i)
-      if (!cam_model_exists(cameras[i].model_id)) return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "camera model id does not exist (0..10)");
+      if (!cam_model_exists(cameras[i].model_id)) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "camera model id does not exist (0..10)");
   const uint32_t n_old = append ? ctx->n_images : 0u;
   const uint64_t rows_old = append ? ctx->total_rows : 0ull;
   if (append && n_old) {
-    if ((kp_xy != nullptr) != ctx->have_kp) return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "appended images must carry keypoints iff the resident ones do");
-    if ((cameras != nullptr) != !ctx->cameras.empty()) return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "appended images must carry cameras iff the resident ones do");
+    if ((kp_xy != nullptr) != ctx->have_kp) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "appended images must carry keypoints iff the resident ones do");
+    if ((cameras != nullptr) != !ctx->cameras.empty()) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "appended images must carry cameras iff the resident ones do");
   }
   std::vector<uint32_t> row0(n_new), rows(n_new);
   uint64_t total = rows_old;
   for (uint32_t i = 0; i < n_new; ++i) {
-    if (n_feats[i] > 0 && !desc[i]) return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "null descriptor pointer");
-    if (kp_xy && n_feats[i] > 0 && !kp_xy[i]) return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "null keypoint pointer");
+    if (n_feats[i] > 0 && !desc[i]) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "null descriptor pointer");
+    if (kp_xy && n_feats[i] > 0 && !kp_xy[i]) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "null keypoint pointer");
     const uint64_t r = ((uint64_t)n_feats[i] + 255) / 256 * 256;
-    if (total + r > 0xffffff00ull) return fail(ctx, DSM_ERR_OUT_OF_RANGE, "too many feature rows for one context");
+    if (total + r > 0xffffff00ull) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "too many feature rows for one context");
     row0[i] = (uint32_t)total;
     rows[i] = (uint32_t)r;
     total += r;
@@ -507,7 +459,7 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
   if (!ctx || !options || (n_pairs && !pairs)) return DSM_ERR_INVALID_ARGUMENT;
   // SiftMatchingOptions::Check, sift.cc:236-250
   if (!(options->max_ratio > 0.0) || !(options->max_distance > 0.0))
-    return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "max_ratio and max_distance must be > 0");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "max_ratio and max_distance must be > 0");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   ctx->matched = false;
@@ -523,7 +475,7 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
   const bool cross = options->cross_check != 0;
   for (uint32_t i = 0; i < n_pairs; ++i) {
     const uint32_t a = pairs[2 * i], b = pairs[2 * i + 1];
-    if (a >= ctx->n_images || b >= ctx->n_images) return fail(ctx, DSM_ERR_OUT_OF_RANGE, "image index out of range");
+    if (a >= ctx->n_images || b >= ctx->n_images) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "image index out of range");
     // max_num_matches is not consulted: MatchSiftFeaturesCPU (sift.cc:810-822), the path this library reproduces,
     // ignores it (only the SiftGPU matcher clamps, sift.cc:200-209); an image of any size is matched in full
   }
@@ -605,9 +557,9 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
     k1.e_off = nullptr;
     k1.e_cnt = nullptr;
     while (ctx->ev.size() < ev_used + 6) {
-      hipEvent_t e;
-      HIPCHK(ctx, hipEventCreate(&e));
-      ctx->ev.push_back(e);
+      DevEvent e;
+      HIPCHK(ctx, hipEventCreate(&e.e));
+      ctx->ev.push_back(std::move(e));
     }
     // DSM_K1_DOT4=1: the LDS-tiled v_dot4 variant of pass 1 (comparison runs only, profiles/r02_k1_variants.md)
 #ifdef DSM_CHECK_BUILD
@@ -746,16 +698,16 @@ int dsm_set_matches(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
   ctx->matched = false;
   ctx->verified = false;
   const uint64_t total = n_pairs ? offsets[n_pairs] : 0;
-  if (total && !matches) return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "null matches");
+  if (total && !matches) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "null matches");
   std::vector<uint32_t> counts(n_pairs);
   for (uint32_t i = 0; i < n_pairs; ++i) {
     const uint32_t a = pairs[2 * i], b = pairs[2 * i + 1];
-    if (a >= ctx->n_images || b >= ctx->n_images) return fail(ctx, DSM_ERR_OUT_OF_RANGE, "image index out of range");
-    if (offsets[i + 1] < offsets[i]) return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing");
+    if (a >= ctx->n_images || b >= ctx->n_images) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "image index out of range");
+    if (offsets[i + 1] < offsets[i]) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing");
     counts[i] = (uint32_t)(offsets[i + 1] - offsets[i]);
     for (uint64_t k = offsets[i]; k < offsets[i + 1]; ++k)
       if (matches[2 * k] >= ctx->nfeat[a] || matches[2 * k + 1] >= ctx->nfeat[b])
-        return fail(ctx, DSM_ERR_OUT_OF_RANGE, "match index out of range");
+        return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "match index out of range");
   }
   ctx->n_pairs = n_pairs;
   ctx->pairs.assign(pairs, pairs + (size_t)n_pairs * 2);
@@ -777,7 +729,7 @@ int dsm_set_matches(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
 
 int dsm_get_match_counts(dsm_ctx* ctx, uint32_t* counts) {
   if (!ctx || !counts) return DSM_ERR_INVALID_ARGUMENT;
-  if (!ctx->matched) return fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
+  if (!ctx->matched) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->n_pairs) HIPCHK(ctx, hipMemcpy(counts, ctx->d_counts.p, (size_t)ctx->n_pairs * 4, hipMemcpyDefault));
   return DSM_OK;
@@ -785,11 +737,11 @@ int dsm_get_match_counts(dsm_ctx* ctx, uint32_t* counts) {
 
 int dsm_get_matches(dsm_ctx* ctx, uint64_t* offsets, uint32_t* matches, uint64_t matches_capacity) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  if (!ctx->matched) return fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
+  if (!ctx->matched) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (offsets) HIPCHK(ctx, hipMemcpy(offsets, ctx->d_offsets.p, ((size_t)ctx->n_pairs + 1) * 8, hipMemcpyDefault));
   if (matches) {
-    if (matches_capacity < ctx->total_matches) return fail(ctx, DSM_ERR_OUT_OF_RANGE, "matches buffer too small");
+    if (matches_capacity < ctx->total_matches) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "matches buffer too small");
     if (ctx->total_matches)
       HIPCHK(ctx, hipMemcpy(matches, ctx->d_matches.p, ctx->total_matches * 8, hipMemcpyDefault));
   }
@@ -802,23 +754,23 @@ int dsm_match_sift_features(dsm_ctx* ctx, const dsm_match_options* options, cons
   *n_matches = 0;
   if (!ctx->leaf) {
     int rc = dsm_ctx_create(ctx->device, &ctx->leaf);
-    if (rc != DSM_OK) return fail(ctx, rc, dsm_last_error(nullptr));
+    if (rc != DSM_OK) return dsm_fail(ctx, rc, dsm_last_error(nullptr));
   }
   dsm_ctx* lf = ctx->leaf;
   lf->debug_options = ctx->debug_options;
   const uint32_t nf[2] = {n1, n2};
   const uint8_t* dp[2] = {desc1, desc2};
   int rc = dsm_set_images(lf, 2, nf, dp, nullptr, 0, nullptr);
-  if (rc != DSM_OK) return fail(ctx, rc, lf->err.c_str());
+  if (rc != DSM_OK) return dsm_fail(ctx, rc, lf->err.c_str());
   const uint32_t pr[2] = {0, 1};
   rc = dsm_match_pairs(lf, 1, pr, options);
-  if (rc != DSM_OK) return fail(ctx, rc, lf->err.c_str());
+  if (rc != DSM_OK) return dsm_fail(ctx, rc, lf->err.c_str());
   uint64_t offs[2] = {0, 0};
   rc = dsm_get_matches(lf, offs, nullptr, 0);
-  if (rc != DSM_OK) return fail(ctx, rc, lf->err.c_str());
-  if (offs[1] && !matches) return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "null matches buffer");
+  if (rc != DSM_OK) return dsm_fail(ctx, rc, lf->err.c_str());
+  if (offs[1] && !matches) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "null matches buffer");
   rc = dsm_get_matches(lf, nullptr, matches, options->cross_check ? std::min<uint64_t>(n1, n2) : n1);
-  if (rc != DSM_OK) return fail(ctx, rc, lf->err.c_str());
+  if (rc != DSM_OK) return dsm_fail(ctx, rc, lf->err.c_str());
   *n_matches = (uint32_t)offs[1];
   return DSM_OK;
 }
@@ -947,6 +899,7 @@ static void verify_lane_run(dsm_ctx* ctx, uint32_t li, VerifyParams vp, VerifyPl
   VerifyLane& L = ctx->lanes[li];
   LANECHK(L, hipSetDevice(ctx->device));
   hipStream_t st = L.stream;
+  uint32_t* const host_ctr = L.host_ctr.as<uint32_t>();
   // the lane's counter fills and read-backs as one-wave kernels, not as the runtime's blit kernels (verify_kernels.hip k_lane_counters:
   // an eight-wave blit workgroup starves for tens of ms behind the other lane's register-filling kernels)
   auto ctr_zero = [st](void* at, size_t bytes) {
@@ -1012,9 +965,9 @@ static void verify_lane_run(dsm_ctx* ctx, uint32_t li, VerifyParams vp, VerifyPl
           LANECHK(L, ctr_zero(actr + 64, 16));  // k_replay's work counter ([17] - [19] are unused words)
           launch_vp_replay(vp, f, nb_heavy, st);
           LANECHK(L, hipGetLastError());
-          LANECHK(L, ctr_read(L.host_ctr, actr, 4));
+          LANECHK(L, ctr_read(host_ctr, actr, 4));
           LANECHK(L, hipStreamSynchronize(st));
-          active = L.host_ctr[0];
+          active = host_ctr[0];
         } else {
           // replay until every pair of the chunk has either consumed the batch or stopped; a pair that reaches a
           // local optimisation is suspended onto the queue, the optimisation runs for the whole queue, and the
@@ -1036,7 +989,6 @@ static void verify_lane_run(dsm_ctx* ctx, uint32_t li, VerifyParams vp, VerifyPl
           int mode = 0;
           bool pass_items = plan.item_mode && round < plan.item_rounds;
           for (uint32_t cur = 0;; cur ^= 1u) {
-            uint32_t* host_ctr = L.host_ctr;
             if (pass_items) {
               // [22], [23]: problems for the general LO kernels; [24]: jobs; [19]: k_lo_prepare's work counter (used after
               // the two read-backs below); [20], [21]: the queue lengths, already read by the host
@@ -1186,10 +1138,8 @@ static int verify_core(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* d_pairs, 
   vp.sampler_serial = ctx->dbg("DSM_SAMPLER_SERIAL") ? 1 : 0;
   vp.reseed = reseed ? 1 : 0;
   vp.keep_generator = keep_generator ? 1 : 0;
-  if (!ctx->vev0) {
-    HIPCHK(ctx, hipEventCreate(&ctx->vev0));
-    HIPCHK(ctx, hipEventCreate(&ctx->vev1));
-  }
+  if (!ctx->vev0) HIPCHK(ctx, hipEventCreate(&ctx->vev0.e));
+  if (!ctx->vev1) HIPCHK(ctx, hipEventCreate(&ctx->vev1.e));
   vp.pair0 = 0;
   vp.n_chunk = n_pairs;
   vp.batch = 0;
@@ -1450,13 +1400,11 @@ static int verify_core(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* d_pairs, 
           // lanes are slower than one" until the queue pool was raised (profiles/r05_lanes_hw_queues.txt).  One stream fewer
           // keeps three lanes inside the default pool.
           if (!L.stream) {
-            if (li == 0)
-              L.stream = ctx->stream;
-            else
-              LRES(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+            LRES(hipStreamCreateWithFlags(&L.own_stream.s, hipStreamNonBlocking));
+            L.stream = L.own_stream;
           }
-          if (!L.done) LRES(hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
-          if (!L.host_ctr) LRES(hipHostMalloc(reinterpret_cast<void**>(&L.host_ctr), 128, hipHostMallocDefault));
+          if (!L.done) LRES(hipEventCreateWithFlags(&L.done.e, hipEventDisableTiming));
+          if (!L.host_ctr.p) LRES(hipHostMalloc(&L.host_ctr.p, 128, hipHostMallocDefault));
           const LaneBytes z = lane_bytes(chunk);
           LRES(L.active.reserve(z.v[0]));
           LRES(L.vscratch.reserve(z.v[1]));
@@ -1490,10 +1438,7 @@ static int verify_core(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* d_pairs, 
         ctx->err = std::string("verification scratch: ") + hipGetErrorString(e);
         return DSM_ERR_HIP;
       }
-      for (VerifyLane& L : ctx->lanes)
-        for (DevBuf* b : {&L.samples, &L.draws_end, &L.nmodels, &L.vcounts, &L.vsums, &L.models, &L.ework, &L.vscratch, &L.lo_queue, &L.lo_work,
-                          &L.lo_models, &L.lo_slots, &L.lo_ework, &L.tail_items, &L.tail_n, &L.lo_jobs, &L.job_list, &L.hyp_map})
-          b->release();
+      for (VerifyLane& L : ctx->lanes) L.for_each_buffer([](DevBuf& b) { b.release(); });
       for (uint32_t li = 0; li < n_lanes; ++li) plan.chunk[li] = std::max<uint32_t>(1, plan.chunk[li] / 2);
     }
     for (uint32_t li = 0; li < n_lanes; ++li) {
@@ -1724,13 +1669,13 @@ uint32_t dsm_pair_seed(uint32_t image_id1, uint32_t image_id2, uint32_t user_see
 int dsm_verify_pairs(dsm_ctx* ctx, const dsm_two_view_options* options, const uint32_t* seeds, uint32_t user_seed,
                      int32_t stage_filter) {
   if (!ctx || !options) return DSM_ERR_INVALID_ARGUMENT;
-  if (!ctx->matched) return fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
+  if (!ctx->matched) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
   if (!ctx->have_kp || ctx->cameras.size() != ctx->n_images)
-    return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_set_images was called without keypoints/cameras");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_set_images was called without keypoints/cameras");
   // RANSACOptions::Check, ransac.h:63-71; TwoViewGeometry::Options::Check
   if (!(options->max_error > 0) || options->min_inlier_ratio < 0 || options->min_inlier_ratio > 1 ||
       options->confidence < 0 || options->confidence > 1 || options->min_num_trials > options->max_num_trials)
-    return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "invalid RANSAC options");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "invalid RANSAC options");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   ctx->verified = false;
   const uint32_t np = ctx->n_pairs;
@@ -1760,7 +1705,7 @@ int dsm_verify_pairs(dsm_ctx* ctx, const dsm_two_view_options* options, const ui
 // (/root/reference/src/feature/matching.cc:441-470) + MatchGuidedSiftFeaturesCPU (src/feature/sift.cc:824-875).
 int dsm_guided_match_pairs(dsm_ctx* ctx, const dsm_match_options* mo, const dsm_two_view_options* to, int32_t stage_filter) {
   if (!ctx || !mo || !to) return DSM_ERR_INVALID_ARGUMENT;
-  if (!ctx->verified) return fail(ctx, DSM_ERR_NOT_READY, "dsm_verify_pairs has not run");
+  if (!ctx->verified) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_verify_pairs has not run");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const uint32_t np = ctx->n_pairs;
@@ -1929,7 +1874,7 @@ int dsm_guided_match_pairs(dsm_ctx* ctx, const dsm_match_options* mo, const dsm_
 
 int dsm_get_two_view_geometries(dsm_ctx* ctx, dsm_two_view_geometry* out) {
   if (!ctx || !out) return DSM_ERR_INVALID_ARGUMENT;
-  if (!ctx->verified) return fail(ctx, DSM_ERR_NOT_READY, "dsm_verify_pairs has not run");
+  if (!ctx->verified) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_verify_pairs has not run");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->n_pairs)
     HIPCHK(ctx, hipMemcpy(out, ctx->d_tvg.p, (size_t)ctx->n_pairs * sizeof(dsm_two_view_geometry), hipMemcpyDefault));
@@ -1938,11 +1883,11 @@ int dsm_get_two_view_geometries(dsm_ctx* ctx, dsm_two_view_geometry* out) {
 
 int dsm_get_inlier_matches(dsm_ctx* ctx, uint64_t* offsets, uint32_t* inlier_matches, uint64_t capacity) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  if (!ctx->verified) return fail(ctx, DSM_ERR_NOT_READY, "dsm_verify_pairs has not run");
+  if (!ctx->verified) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_verify_pairs has not run");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (offsets) HIPCHK(ctx, hipMemcpy(offsets, ctx->d_inl_off.p, ((size_t)ctx->n_pairs + 1) * 8, hipMemcpyDefault));
   if (inlier_matches) {
-    if (capacity < ctx->total_inliers) return fail(ctx, DSM_ERR_OUT_OF_RANGE, "inlier_matches buffer too small");
+    if (capacity < ctx->total_inliers) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "inlier_matches buffer too small");
     if (ctx->total_inliers)
       HIPCHK(ctx, hipMemcpy(inlier_matches, ctx->d_inl_compact.p, ctx->total_inliers * 8, hipMemcpyDefault));
   }
@@ -1951,7 +1896,7 @@ int dsm_get_inlier_matches(dsm_ctx* ctx, uint64_t* offsets, uint32_t* inlier_mat
 
 int dsm_get_verify_kernel_time(dsm_ctx* ctx, double* total_ms) {
   if (!ctx || !total_ms) return DSM_ERR_INVALID_ARGUMENT;
-  if (!ctx->verified) return fail(ctx, DSM_ERR_NOT_READY, "dsm_verify_pairs has not run");
+  if (!ctx->verified) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_verify_pairs has not run");
   *total_ms = ctx->verify_ms;
   return DSM_OK;
 }
@@ -1963,12 +1908,12 @@ int dsm_estimate_two_view_geometry(dsm_ctx* ctx, const dsm_camera* camera1, cons
   if (!ctx || !camera1 || !camera2 || !options || !out || (n_matches && (!matches || !points1 || !points2)))
     return DSM_ERR_INVALID_ARGUMENT;
   if (!cam_model_exists(camera1->model_id) || !cam_model_exists(camera2->model_id))
-    return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "camera model id does not exist (0..10)");
+    return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "camera model id does not exist (0..10)");
   for (uint32_t i = 0; i < n_matches; ++i)
-    if (matches[2 * i] >= n1 || matches[2 * i + 1] >= n2) return fail(ctx, DSM_ERR_OUT_OF_RANGE, "match index out of range");
+    if (matches[2 * i] >= n1 || matches[2 * i + 1] >= n2) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "match index out of range");
   if (!ctx->leaf) {
     int rc = dsm_ctx_create(ctx->device, &ctx->leaf);
-    if (rc != DSM_OK) return fail(ctx, rc, dsm_last_error(nullptr));
+    if (rc != DSM_OK) return dsm_fail(ctx, rc, dsm_last_error(nullptr));
   }
   dsm_ctx* lf = ctx->leaf;
   lf->debug_options = ctx->debug_options;
@@ -1979,30 +1924,22 @@ int dsm_estimate_two_view_geometry(dsm_ctx* ctx, const dsm_camera* camera1, cons
   const uint32_t prs[2] = {0, 1};
   const uint64_t offs[2] = {0, n_matches};
   int rc = DSM_OK;
-#define LCHK(call)                                                      \
-  do {                                                                  \
-    hipError_t e_ = (call);                                             \
-    if (e_ != hipSuccess && rc == DSM_OK) {                             \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);     \
-      rc = DSM_ERR_HIP;                                                 \
-    }                                                                   \
-  } while (0)
-  LCHK(kp.reserve(std::max<size_t>((size_t)(n1 + n2) * 16, 16)));
-  LCHK(row0.reserve(8));
-  LCHK(cams.reserve(2 * sizeof(dsm_camera)));
-  LCHK(pr.reserve(8));
-  LCHK(off.reserve(16));
-  LCHK(mt.reserve(std::max<size_t>((size_t)n_matches * 8, 8)));
-  LCHK(sd.reserve(4));
+  HIPTRY(kp.reserve(std::max<size_t>((size_t)(n1 + n2) * 16, 16)));
+  HIPTRY(row0.reserve(8));
+  HIPTRY(cams.reserve(2 * sizeof(dsm_camera)));
+  HIPTRY(pr.reserve(8));
+  HIPTRY(off.reserve(16));
+  HIPTRY(mt.reserve(std::max<size_t>((size_t)n_matches * 8, 8)));
+  HIPTRY(sd.reserve(4));
   if (rc == DSM_OK) {
-    if (n1) LCHK(hipMemcpy(kp.p, points1, (size_t)n1 * 16, hipMemcpyHostToDevice));
-    if (n2) LCHK(hipMemcpy(kp.as<double>() + 2 * (size_t)n1, points2, (size_t)n2 * 16, hipMemcpyHostToDevice));
-    LCHK(hipMemcpy(row0.p, rows0, 8, hipMemcpyHostToDevice));
-    LCHK(hipMemcpy(cams.p, cc, sizeof(cc), hipMemcpyHostToDevice));
-    LCHK(hipMemcpy(pr.p, prs, 8, hipMemcpyHostToDevice));
-    LCHK(hipMemcpy(off.p, offs, 16, hipMemcpyHostToDevice));
-    if (n_matches) LCHK(hipMemcpy(mt.p, matches, (size_t)n_matches * 8, hipMemcpyHostToDevice));
-    LCHK(hipMemcpy(sd.p, &seed, 4, hipMemcpyHostToDevice));
+    if (n1) HIPTRY(hipMemcpy(kp.p, points1, (size_t)n1 * 16, hipMemcpyHostToDevice));
+    if (n2) HIPTRY(hipMemcpy(kp.as<double>() + 2 * (size_t)n1, points2, (size_t)n2 * 16, hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(row0.p, rows0, 8, hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(cams.p, cc, sizeof(cc), hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(pr.p, prs, 8, hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(off.p, offs, 16, hipMemcpyHostToDevice));
+    if (n_matches) HIPTRY(hipMemcpy(mt.p, matches, (size_t)n_matches * 8, hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(sd.p, &seed, 4, hipMemcpyHostToDevice));
   }
   if (rc == DSM_OK) {
     std::vector<uint32_t> counts(1, n_matches);
@@ -2013,13 +1950,10 @@ int dsm_estimate_two_view_geometry(dsm_ctx* ctx, const dsm_camera* camera1, cons
     if (rc != DSM_OK) ctx->err = lf->err;
   }
   if (rc == DSM_OK) {
-    LCHK(hipMemcpy(out, lf->d_tvg.p, sizeof(dsm_two_view_geometry), hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(out, lf->d_tvg.p, sizeof(dsm_two_view_geometry), hipMemcpyDeviceToHost));
     if (rc == DSM_OK && inlier_matches && out->num_inliers)
-      LCHK(hipMemcpy(inlier_matches, lf->d_inl_compact.p, (size_t)out->num_inliers * 8, hipMemcpyDeviceToHost));
+      HIPTRY(hipMemcpy(inlier_matches, lf->d_inl_compact.p, (size_t)out->num_inliers * 8, hipMemcpyDeviceToHost));
   }
-#undef LCHK
-  DevBuf* bufs[] = {&kp, &row0, &cams, &pr, &off, &mt, &sd};
-  for (DevBuf* b : bufs) b->release();
   return rc;
 }
 
@@ -2046,15 +1980,12 @@ int dsm_debug_sample_sequence(dsm_ctx* ctx, uint32_t seed, uint32_t k, uint32_t 
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   HIPCHK(ctx, hipMemcpy(out, o.p, (size_t)k * n_draws * 4, hipMemcpyDeviceToHost));
-  o.release();
-  idx.release();
-  tmp7.release();
   return DSM_OK;
 }
 
 int dsm_debug_image_to_world(dsm_ctx* ctx, const dsm_camera* camera, uint32_t n, const double* xy, double* out_uv) {
   if (!ctx || !camera || (n && (!xy || !out_uv))) return DSM_ERR_INVALID_ARGUMENT;
-  if (!cam_model_exists(camera->model_id)) return fail(ctx, DSM_ERR_INVALID_ARGUMENT, "camera model id does not exist (0..10)");
+  if (!cam_model_exists(camera->model_id)) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "camera model id does not exist (0..10)");
   if (!n) return DSM_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   DevBuf in, out;
@@ -2065,8 +1996,6 @@ int dsm_debug_image_to_world(dsm_ctx* ctx, const dsm_camera* camera, uint32_t n,
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   HIPCHK(ctx, hipMemcpy(out_uv, out.p, (size_t)n * 16, hipMemcpyDeviceToHost));
-  in.release();
-  out.release();
   return DSM_OK;
 }
 
@@ -2075,7 +2004,7 @@ uint32_t dsm_ctx_num_pairs(const dsm_ctx* ctx) { return (ctx && ctx->matched) ? 
 
 int dsm_get_match_kernel_time(dsm_ctx* ctx, double* total_ms, uint32_t* n_launches) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  if (!ctx->matched) return fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
+  if (!ctx->matched) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
   if (total_ms) *total_ms = ctx->k1_ms;
   if (n_launches) *n_launches = ctx->k1_launches;
   return DSM_OK;
@@ -2083,21 +2012,21 @@ int dsm_get_match_kernel_time(dsm_ctx* ctx, double* total_ms, uint32_t* n_launch
 
 int dsm_get_match_gather_time(dsm_ctx* ctx, double* total_ms) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  if (!ctx->matched) return fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
+  if (!ctx->matched) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
   if (total_ms) *total_ms = ctx->k1g_ms;
   return DSM_OK;
 }
 
 int dsm_get_match_tail_time(dsm_ctx* ctx, double* total_ms) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  if (!ctx->matched) return fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
+  if (!ctx->matched) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
   if (total_ms) *total_ms = ctx->k1t_ms;
   return DSM_OK;
 }
 
 int dsm_get_match_resolve_time(dsm_ctx* ctx, double* total_ms) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  if (!ctx->matched) return fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
+  if (!ctx->matched) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_match_pairs has not run");
   if (total_ms) *total_ms = ctx->k1b_ms;
   return DSM_OK;
 }

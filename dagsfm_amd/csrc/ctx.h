@@ -1,4 +1,4 @@
-// ctx.h -- the context behind the C-ABI (shared by capi.hip and capi_retrieval.hip; not part of the public header).
+// ctx.h -- the context behind the C-ABI (shared by the library's .hip files; not part of the public header).
 #ifndef DAGSFM_AMD_CSRC_CTX_H_
 #define DAGSFM_AMD_CSRC_CTX_H_
 
@@ -76,40 +76,74 @@ struct DevBuf {
   T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-// a hipEvent_t, destroyed when its owner goes out of scope; created by hipEventCreate(&ev.e)
+// a hipEvent_t, destroyed when its owner goes out of scope (movable, not copyable); created by hipEventCreate(&ev.e)
 struct DevEvent {
   hipEvent_t e = nullptr;
   DevEvent() = default;
   DevEvent(const DevEvent&) = delete;
   DevEvent& operator=(const DevEvent&) = delete;
+  DevEvent(DevEvent&& o) noexcept : e(o.e) { o.e = nullptr; }
   ~DevEvent() {
     if (e) (void)hipEventDestroy(e);
   }
   operator hipEvent_t() const { return e; }
 };
 
+// a hipStream_t, destroyed when its owner goes out of scope; created by hipStreamCreateWithFlags(&st.s, ...)
+struct DevStream {
+  hipStream_t s = nullptr;
+  DevStream() = default;
+  DevStream(const DevStream&) = delete;
+  DevStream& operator=(const DevStream&) = delete;
+  ~DevStream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  operator hipStream_t() const { return s; }
+};
+
+// pinned host memory, freed when its owner goes out of scope; allocated by hipHostMalloc(&h.p, ...)
+struct HostBuf {
+  void* p = nullptr;
+  HostBuf() = default;
+  HostBuf(const HostBuf&) = delete;
+  HostBuf& operator=(const HostBuf&) = delete;
+  ~HostBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  template <typename T>
+  T* as() const { return reinterpret_cast<T*>(p); }
+};
 
 // One lane of dsm_verify_pairs: a share of the pair list runs through the whole E -> F -> H pipeline on the lane's own
 // stream, driven by its own host thread, with its own chunk-local buffers.  The rounds of one lane are a serial chain
 // of small launches and host round trips (its length is set by the slowest pair); lanes fill each other's bubbles.
 struct VerifyLane {
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;
+  hipStream_t stream = nullptr;  // what the lane runs on: lane 0 borrows the context's stream, the others their own_stream
+  DevStream own_stream;
+  DevEvent done;
   DevBuf samples, draws_end, nmodels, vcounts, vsums, models, ework, active, vscratch;
   DevBuf lo_queue, lo_work, lo_models, lo_slots, lo_ework;  // batched local optimisation
   DevBuf tail_items, tail_n, lo_jobs, job_list;             // item passes (TailItem, LoJob)
   DevBuf hyp_map;                                           // the round's hypotheses of all pairs for the compact solver grids (verify_kernels.hip hyp_of_lane)
   uint32_t rounds[3] = {0, 0, 0}, lo_iters[3] = {0, 0, 0};
   uint32_t dbg[32] = {0};
-  uint32_t* host_ctr = nullptr;  // pinned read-back target of the lane's counters
+  HostBuf host_ctr;  // pinned read-back target of the lane's counters
   std::string err;
   int rc = 0;
+
+  // every DevBuf of the lane, exactly once (all of them are chunk scratch: dsm_ctx::for_each_buffer)
+  template <typename F>
+  void for_each_buffer(F f) {
+    for (DevBuf* b : {&samples, &draws_end, &nmodels, &vcounts, &vsums, &models, &ework, &active, &vscratch, &lo_queue, &lo_work, &lo_models,
+                      &lo_slots, &lo_ework, &tail_items, &tail_n, &lo_jobs, &job_list, &hyp_map})
+      f(*b);
+  }
 };
 #define DSM_VERIFY_MAX_LANES 4
 
 struct dsm_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
+  DevStream stream;
   std::string err;
 
   // resident images
@@ -121,9 +155,9 @@ struct dsm_ctx {
   DevBuf d_desc, d_rterm, d_kp, d_img_row0, d_img_rows, d_lut;
   // hand-over of pageable host buffers (capi.hip: staged_upload): two pinned host slots, their device mirror for the descriptor
   // rows on their way through k0_prepare, one event per slot; allocated by the first upload that needs them
-  void* h_stage = nullptr;
+  HostBuf h_stage;
   DevBuf d_stage;
-  hipEvent_t stage_ev[2] = {nullptr, nullptr};
+  DevEvent stage_ev[2];
 
   // last dsm_match_pairs
   bool matched = false;
@@ -137,7 +171,7 @@ struct dsm_ctx {
   double k1g_ms = 0.0;  // k1_best_rows<GATHER> (pass 2 of the cross-check)
   DevBuf d_order, d_dpairs2, d_ecnt, d_eoff, d_etotal, d_entries, d_out2, d_ms, d_out2s;
   uint32_t k1_launches = 0;
-  std::vector<hipEvent_t> ev;
+  std::vector<DevEvent> ev;
 
   // last dsm_verify_pairs
   bool verified = false;
@@ -161,7 +195,7 @@ struct dsm_ctx {
   std::vector<uint32_t> nt_table_t;      // translation tables of the inlier counts that needed one (built on demand)
   std::vector<uint64_t> nt_off_t;        // per N (0 = absent; offsets are stored +1)
   bool nt_dirty = true, nt_dirty_t = true;
-  hipEvent_t vev0 = nullptr, vev1 = nullptr;
+  DevEvent vev0, vev1;
 
   dsm_ctx* leaf = nullptr;  // private context of the one-shot leaf entry points
 
@@ -190,6 +224,26 @@ struct dsm_ctx {
   // (view_graph_clustering.hip)
   std::vector<double> cluster_ritz, cluster_vectors;
   uint32_t cluster_rows = 0, cluster_cols = 0;
+
+  // Every DevBuf of the context and of its lanes, exactly once, with its class: f(buf, scratch).  Scratch is the transient
+  // chunk memory dsm_ctx_set_memory_budget governs; resident is the images and the last calls' inputs / results / per-pair
+  // state (include/dagsfm_mi355x.h, dsm_ctx_memory_footprint).  tests/test_ctx_buffers.py holds this list to the declarations.
+  template <typename F>
+  void for_each_buffer(F f) {
+    for (DevBuf* b : {&d_desc, &d_rterm, &d_kp, &d_img_row0, &d_img_rows, &d_lut, &d_stage, &d_counts, &d_offsets, &d_matches, &d_total, &d_etotal,
+                      &d_cams, &d_pairs_dev, &d_seeds, &d_tvg, &d_inl, &d_inl_counts, &d_inl_off, &d_inl_compact, &d_inl_total, &d_nt_table,
+                      &d_nt_off, &d_nt_off_t, &d_pair_state, &d_pts_px, &d_pts_norm, &d_reports, &d_masks, &d_fam_state, &d_sidx, &d_lo_inl,
+                      &d_nt_table_t, &d_wm_redo, &d_wm_total, &d_wm_count, &d_lo_inl_pool, &d_pose_jobs,
+                      &d_g_nfeat, &d_g_dpairs, &d_g_doff, &d_g_pdir, &d_g_params, &d_g_m, &d_g_counts, &d_g_offsets, &d_g_total, &d_g_matches,
+                      &d_g_plan, &d_g_inl, &d_g_inl_off,
+                      &d_mm_matches[0], &d_mm_matches[1], &d_mm_off[0], &d_mm_off[1], &d_mm_counts, &d_mm_state, &d_mm_first, &d_mm_acc,
+                      &d_mm_keep, &d_mm_total})
+      f(*b, false);
+    for (DevBuf* b : {&d_m, &d_ms, &d_entries, &d_out2, &d_out2s, &d_dpairs, &d_dpairs2, &d_doutoff, &d_pair_dir, &d_order, &d_ecnt, &d_eoff,
+                      &d_vscratch})
+      f(*b, true);
+    for (VerifyLane& L : lanes) L.for_each_buffer([&f](DevBuf& b) { f(b, true); });
+  }
 };
 void dsm_retrieval_destroy(dsm_ctx* ctx);     // retrieval.hip
 void dsm_retrieval_invalidate(dsm_ctx* ctx);  // retrieval.hip: the resident images changed

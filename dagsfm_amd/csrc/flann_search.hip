@@ -629,35 +629,14 @@ struct FlannDevice {
   uint32_t n_lanes = 0;
   double last_ms = 0.0;
   uint32_t last_retried = 0;  // queries of the last search that took the second pass
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevEvent ev0, ev1;
 };
 
-void flann_device_destroy(FlannDevice* f) {
-  if (!f) return;
-  for (DevBuf* b : {&f->kd_nodes, &f->kd_roots, &f->km_nodes, &f->km_childs, &f->km_points, &f->pivots, &f->wnorm, &f->heap, &f->checked, &f->clist,
-                    &f->domain, &f->overflow, &f->overflow_rows, &f->overflow_rows2, &f->checked_g, &f->clist_g, &f->stats, &f->q_s8, &f->q_u8, &f->out_ids,
-                    &f->out_dists})
-    b->release();
-  if (f->ev0) (void)hipEventDestroy(f->ev0);
-  if (f->ev1) (void)hipEventDestroy(f->ev1);
-  delete f;
-}
-
-#define FCHK(ctx, call)                                                              \
-  do {                                                                               \
-    hipError_t e_ = (call);                                                          \
-    if (e_ != hipSuccess) {                                                          \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                \
-      return DSM_ERR_HIP;                                                            \
-    }                                                                                \
-  } while (0)
+void flann_device_destroy(FlannDevice* f) { delete f; }
 
 // Every index the kernel will follow is checked here, once: a damaged or hostile index is an error, never an out-of-bounds read.
-int flann_device_set_index(dsm_ctx* ctx, FlannDevice** slot, const dsm_flann_index* ix, const int8_t* d_words_s8, uint32_t num_words) {
-  if (*slot) {
-    flann_device_destroy(*slot);
-    *slot = nullptr;
-  }
+int flann_device_set_index(dsm_ctx* ctx, FlannDevicePtr& slot, const dsm_flann_index* ix, const int8_t* d_words_s8, uint32_t num_words) {
+  slot.reset();
   if (!ix) return DSM_OK;
   if (ix->num_words != num_words) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_retrieval_set_flann_index: the index is over another number of words");
   if (ix->algorithm < 0 || ix->algorithm > 2) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_retrieval_set_flann_index: algorithm must be linear / kd-trees / k-means");
@@ -717,8 +696,8 @@ int flann_device_set_index(dsm_ctx* ctx, FlannDevice** slot, const dsm_flann_ind
       kmp[i] = (uint32_t)ix->km_points[i];
     }
   }
-  FlannDevice* f = new FlannDevice();
-  *slot = f;
+  slot.reset(new FlannDevice());
+  FlannDevice* f = slot.get();
   f->algorithm = ix->algorithm;
   f->num_checks = ix->num_checks;
   f->branching = ix->branching;
@@ -726,28 +705,28 @@ int flann_device_set_index(dsm_ctx* ctx, FlannDevice** slot, const dsm_flann_ind
   f->cb_index = ix->cb_index;
   f->num_words = num_words;
   f->n_kd_roots = ix->n_kd_roots;
-  FCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ix->algorithm == 1) {
-    FCHK(ctx, f->kd_nodes.reserve((size_t)ix->n_kd_nodes * sizeof(dsm_flann_kd_node)));
-    FCHK(ctx, f->kd_roots.reserve((size_t)ix->n_kd_roots * 4));
-    FCHK(ctx, hipMemcpy(f->kd_nodes.p, ix->kd_nodes, (size_t)ix->n_kd_nodes * sizeof(dsm_flann_kd_node), hipMemcpyHostToDevice));
-    FCHK(ctx, hipMemcpy(f->kd_roots.p, ix->kd_roots, (size_t)ix->n_kd_roots * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx, f->kd_nodes.reserve((size_t)ix->n_kd_nodes * sizeof(dsm_flann_kd_node)));
+    HIPCHK(ctx, f->kd_roots.reserve((size_t)ix->n_kd_roots * 4));
+    HIPCHK(ctx, hipMemcpy(f->kd_nodes.p, ix->kd_nodes, (size_t)ix->n_kd_nodes * sizeof(dsm_flann_kd_node), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(f->kd_roots.p, ix->kd_roots, (size_t)ix->n_kd_roots * 4, hipMemcpyHostToDevice));
   } else if (ix->algorithm == 2) {
-    FCHK(ctx, f->km_nodes.reserve(km.size() * sizeof(FlannKmNodeDev)));
-    FCHK(ctx, f->km_childs.reserve(std::max<uint64_t>(ix->n_km_childs, 1) * 4));
-    FCHK(ctx, f->km_points.reserve(kmp.size() * 4));
-    FCHK(ctx, f->pivots.reserve((size_t)ix->n_pivot_floats * 4));
-    FCHK(ctx, hipMemcpy(f->km_nodes.p, km.data(), km.size() * sizeof(FlannKmNodeDev), hipMemcpyHostToDevice));
-    if (ix->n_km_childs) FCHK(ctx, hipMemcpy(f->km_childs.p, ix->km_childs, (size_t)ix->n_km_childs * 4, hipMemcpyHostToDevice));
-    FCHK(ctx, hipMemcpy(f->km_points.p, kmp.data(), kmp.size() * 4, hipMemcpyHostToDevice));
-    FCHK(ctx, hipMemcpy(f->pivots.p, ix->pivots, (size_t)ix->n_pivot_floats * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx, f->km_nodes.reserve(km.size() * sizeof(FlannKmNodeDev)));
+    HIPCHK(ctx, f->km_childs.reserve(std::max<uint64_t>(ix->n_km_childs, 1) * 4));
+    HIPCHK(ctx, f->km_points.reserve(kmp.size() * 4));
+    HIPCHK(ctx, f->pivots.reserve((size_t)ix->n_pivot_floats * 4));
+    HIPCHK(ctx, hipMemcpy(f->km_nodes.p, km.data(), km.size() * sizeof(FlannKmNodeDev), hipMemcpyHostToDevice));
+    if (ix->n_km_childs) HIPCHK(ctx, hipMemcpy(f->km_childs.p, ix->km_childs, (size_t)ix->n_km_childs * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(f->km_points.p, kmp.data(), kmp.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(f->pivots.p, ix->pivots, (size_t)ix->n_pivot_floats * 4, hipMemcpyHostToDevice));
   }
-  FCHK(ctx, f->wnorm.reserve((size_t)num_words * 4));
+  HIPCHK(ctx, f->wnorm.reserve((size_t)num_words * 4));
   hipLaunchKernelGGL(k_flann_word_norms, dim3((num_words + 255) / 256), dim3(256), 0, ctx->stream, d_words_s8, num_words, f->wnorm.as<int32_t>());
-  FCHK(ctx, hipGetLastError());
-  FCHK(ctx, hipEventCreate(&f->ev0));
-  FCHK(ctx, hipEventCreate(&f->ev1));
-  FCHK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipEventCreate(&f->ev0.e));
+  HIPCHK(ctx, hipEventCreate(&f->ev1.e));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return DSM_OK;
 }
 
@@ -765,17 +744,17 @@ static int flann_launch(dsm_ctx* ctx, FlannDevice* f, const int8_t* d_words_s8, 
   uint64_t blocks = std::min<uint64_t>((n_items + 63) / 64, (uint64_t)cus * 16);
   while (blocks > 1 && blocks * 64 * per_lane > (8ull << 30)) blocks = (blocks + 1) / 2;
   const uint32_t n_lanes = (uint32_t)blocks * 64u;
-  FCHK(ctx, f->heap.reserve((size_t)heap_cap * n_lanes * 8));
+  HIPCHK(ctx, f->heap.reserve((size_t)heap_cap * n_lanes * 8));
   if (checked_words) {
     const size_t bytes = (size_t)checked_words * n_lanes * 4;
     const bool fresh = f->checked.cap < bytes || f->n_lanes != n_lanes;
-    FCHK(ctx, f->checked.reserve(bytes));
-    if (fresh) FCHK(ctx, hipMemsetAsync(f->checked.p, 0, f->checked.cap, st));  // every query leaves its lane's bits cleared again
-    FCHK(ctx, f->clist.reserve((size_t)std::max<uint32_t>(list_cap, 1) * n_lanes * 4));
+    HIPCHK(ctx, f->checked.reserve(bytes));
+    if (fresh) HIPCHK(ctx, hipMemsetAsync(f->checked.p, 0, f->checked.cap, st));  // every query leaves its lane's bits cleared again
+    HIPCHK(ctx, f->clist.reserve((size_t)std::max<uint32_t>(list_cap, 1) * n_lanes * 4));
   }
-  FCHK(ctx, f->domain.reserve((size_t)std::max(f->branching, 1) * n_lanes * 4));
-  FCHK(ctx, f->overflow.reserve(4));
-  FCHK(ctx, hipMemsetAsync(f->overflow.p, 0, 4, st));
+  HIPCHK(ctx, f->domain.reserve((size_t)std::max(f->branching, 1) * n_lanes * 4));
+  HIPCHK(ctx, f->overflow.reserve(4));
+  HIPCHK(ctx, hipMemsetAsync(f->overflow.p, 0, 4, st));
   f->n_lanes = n_lanes;
   FlannSearchParams p;
   p.algorithm = f->algorithm;
@@ -811,16 +790,16 @@ static int flann_launch(dsm_ctx* ctx, FlannDevice* f, const int8_t* d_words_s8, 
   p.overflow = f->overflow.as<uint32_t>();
   p.overflow_rows = overflow_rows;
   p.row_list = row_list;
-  FCHK(ctx, hipEventRecord(f->ev0, st));  // (after the allocations above: the events bracket the kernel, not hipMalloc)
+  HIPCHK(ctx, hipEventRecord(f->ev0, st));  // (after the allocations above: the events bracket the kernel, not hipMalloc)
   if (f->algorithm == 0) hipLaunchKernelGGL(k_flann_search<0>, dim3((uint32_t)blocks), dim3(64), 0, st, p);
   if (f->algorithm == 1) hipLaunchKernelGGL(k_flann_search<1>, dim3((uint32_t)blocks), dim3(64), 0, st, p);
   if (f->algorithm == 2) hipLaunchKernelGGL(k_flann_search<2>, dim3((uint32_t)blocks), dim3(64), 0, st, p);
-  FCHK(ctx, hipGetLastError());
-  FCHK(ctx, hipEventRecord(f->ev1, st));
-  FCHK(ctx, hipMemcpyAsync(overflow_out, f->overflow.p, 4, hipMemcpyDeviceToHost, st));
-  FCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipEventRecord(f->ev1, st));
+  HIPCHK(ctx, hipMemcpyAsync(overflow_out, f->overflow.p, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   float ms = 0.f;
-  FCHK(ctx, hipEventElapsedTime(&ms, f->ev0, f->ev1));
+  HIPCHK(ctx, hipEventElapsedTime(&ms, f->ev0, f->ev1));
   f->last_ms += ms;
   return DSM_OK;
 }
@@ -840,17 +819,17 @@ static int flann_launch_kd_grp(dsm_ctx* ctx, FlannDevice* f, const int8_t* d_wor
   uint64_t blocks = std::min<uint64_t>((n_items + per_wave - 1) / per_wave, (uint64_t)cus * 24);
   while (blocks > 1 && blocks * per_wave * (((uint64_t)checked_words + list_cap) * 4 + (uint64_t)heap_cap * 8) > (4ull << 30)) blocks = (blocks + 1) / 2;
   const uint32_t n_groups = (uint32_t)blocks * per_wave;
-  FCHK(ctx, f->heap.reserve((size_t)heap_cap * n_groups * 8));
+  HIPCHK(ctx, f->heap.reserve((size_t)heap_cap * n_groups * 8));
   {
     const size_t bytes = (size_t)checked_words * n_groups * 4;
     const bool fresh = f->checked_g.cap < bytes || f->n_groups != n_groups;
-    FCHK(ctx, f->checked_g.reserve(bytes));
-    if (fresh) FCHK(ctx, hipMemsetAsync(f->checked_g.p, 0, f->checked_g.cap, st));  // every query leaves its group's bits cleared again
-    FCHK(ctx, f->clist_g.reserve((size_t)std::max<uint32_t>(list_cap, 1) * n_groups * 4));
+    HIPCHK(ctx, f->checked_g.reserve(bytes));
+    if (fresh) HIPCHK(ctx, hipMemsetAsync(f->checked_g.p, 0, f->checked_g.cap, st));  // every query leaves its group's bits cleared again
+    HIPCHK(ctx, f->clist_g.reserve((size_t)std::max<uint32_t>(list_cap, 1) * n_groups * 4));
     f->n_groups = n_groups;
   }
-  FCHK(ctx, f->overflow.reserve(4));
-  FCHK(ctx, hipMemsetAsync(f->overflow.p, 0, 4, st));
+  HIPCHK(ctx, f->overflow.reserve(4));
+  HIPCHK(ctx, hipMemsetAsync(f->overflow.p, 0, 4, st));
   FlannSearchParams p = FlannSearchParams();
   p.algorithm = 1;
   p.num_checks = f->num_checks;
@@ -879,24 +858,24 @@ static int flann_launch_kd_grp(dsm_ctx* ctx, FlannDevice* f, const int8_t* d_wor
   p.stats = nullptr;
 #ifdef DSM_CHECK_BUILD
   if (ctx->dbg("DSM_FLANN_STATS")) {
-    FCHK(ctx, f->stats.reserve(64));
-    FCHK(ctx, hipMemsetAsync(f->stats.p, 0, 64, st));
+    HIPCHK(ctx, f->stats.reserve(64));
+    HIPCHK(ctx, hipMemsetAsync(f->stats.p, 0, 64, st));
     p.stats = f->stats.as<uint32_t>();
   }
 #endif
-  FCHK(ctx, hipEventRecord(f->ev0, st));
+  HIPCHK(ctx, hipEventRecord(f->ev0, st));
   hipLaunchKernelGGL(k_flann_search_kd_grp, dim3((uint32_t)blocks), dim3(64), 0, st, p);
-  FCHK(ctx, hipGetLastError());
-  FCHK(ctx, hipEventRecord(f->ev1, st));
-  FCHK(ctx, hipMemcpyAsync(overflow_out, f->overflow.p, 4, hipMemcpyDeviceToHost, st));
-  FCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipEventRecord(f->ev1, st));
+  HIPCHK(ctx, hipMemcpyAsync(overflow_out, f->overflow.p, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   float ms = 0.f;
-  FCHK(ctx, hipEventElapsedTime(&ms, f->ev0, f->ev1));
+  HIPCHK(ctx, hipEventElapsedTime(&ms, f->ev0, f->ev1));
   f->last_ms += ms;
 #ifdef DSM_CHECK_BUILD
   if (p.stats) {
     uint32_t h[16];
-    FCHK(ctx, hipMemcpy(h, f->stats.p, 64, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(h, f->stats.p, 64, hipMemcpyDeviceToHost));
     fprintf(stderr, "[flann kd grp] queries %u  nodes/query %.1f  leaves/query %.1f  pops/query %.1f  pushes/query %.1f  max heap %u  heap > 32/64/128/256/384/511: %u %u %u %u %u %u  overflow %u  %.1f ms\n",
             h[0], (double)h[1] / std::max(h[0], 1u), (double)h[2] / std::max(h[0], 1u), (double)h[3] / std::max(h[0], 1u), (double)h[4] / std::max(h[0], 1u), h[5], h[6], h[7],
             h[8], h[9], h[10], h[11], *overflow_out, ms);
@@ -917,7 +896,7 @@ int flann_device_search(dsm_ctx* ctx, FlannDevice* f, const int8_t* d_words_s8, 
   if (k == 0 || k > FLANN_K_MAX || out_stride < k || out_stride > FLANN_K_MAX) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "FLANN search: 1 <= k <= 8");
   if (n_rows == 0) return DSM_OK;
   if (n_rows > 0xfffffff0ull) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "FLANN search: too many rows");
-  FCHK(ctx, f->overflow_rows.reserve((size_t)n_rows * 4));
+  HIPCHK(ctx, f->overflow_rows.reserve((size_t)n_rows * 4));
   uint32_t overflow = 0;
   f->last_ms = 0.0;
   int rc;
@@ -931,8 +910,8 @@ int flann_device_search(dsm_ctx* ctx, FlannDevice* f, const int8_t* d_words_s8, 
     if (rc != DSM_OK) return rc;
     f->last_retried = overflow;
     if (!overflow) return DSM_OK;
-    FCHK(ctx, f->overflow_rows2.reserve((size_t)overflow * 4));
-    FCHK(ctx, hipMemcpyAsync(f->overflow_rows2.p, f->overflow_rows.p, (size_t)overflow * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, f->overflow_rows2.reserve((size_t)overflow * 4));
+    HIPCHK(ctx, hipMemcpyAsync(f->overflow_rows2.p, f->overflow_rows.p, (size_t)overflow * 4, hipMemcpyDeviceToDevice, st));
     todo = f->overflow_rows2.as<uint32_t>();
     n_todo = overflow;
     overflow = 0;
@@ -959,20 +938,20 @@ int flann_device_search_host(dsm_ctx* ctx, FlannDevice* f, const int8_t* d_words
   if (!f) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_retrieval_set_flann_index has not run");
   if (n == 0) return DSM_OK;
   if (!queries || !ids) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "null queries / ids");
-  FCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  FCHK(ctx, f->q_u8.reserve((size_t)n * 128));
-  FCHK(ctx, f->q_s8.reserve((size_t)n * 128));
-  FCHK(ctx, f->out_ids.reserve((size_t)n * k * 4));
-  FCHK(ctx, f->out_dists.reserve((size_t)n * k * 4));
-  FCHK(ctx, hipMemcpyAsync(f->q_u8.p, queries, (size_t)n * 128, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, f->q_u8.reserve((size_t)n * 128));
+  HIPCHK(ctx, f->q_s8.reserve((size_t)n * 128));
+  HIPCHK(ctx, f->out_ids.reserve((size_t)n * k * 4));
+  HIPCHK(ctx, f->out_dists.reserve((size_t)n * k * 4));
+  HIPCHK(ctx, hipMemcpyAsync(f->q_u8.p, queries, (size_t)n * 128, hipMemcpyHostToDevice, st));
   const uint64_t words = (uint64_t)n * 32;
   hipLaunchKernelGGL(k_flann_u8_to_s8, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, st, f->q_u8.as<uint32_t>(), f->q_s8.as<uint32_t>(), words);
-  FCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   const int rc = flann_device_search(ctx, f, d_words_s8, f->q_s8.as<int8_t>(), nullptr, n, k, f->out_ids.as<int32_t>(), f->out_dists.as<float>(), k, st);
   if (rc != DSM_OK) return rc;
-  FCHK(ctx, hipMemcpy(ids, f->out_ids.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
-  if (dists) FCHK(ctx, hipMemcpy(dists, f->out_dists.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(ids, f->out_ids.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
+  if (dists) HIPCHK(ctx, hipMemcpy(dists, f->out_dists.p, (size_t)n * k * 4, hipMemcpyDeviceToHost));
   return DSM_OK;
 }
 

@@ -57,7 +57,7 @@ struct RetrievalState {
   bool host_ids = false;
   bool host_ids_stale = false;  // the resident images changed after dsm_retrieval_set_word_ids: the ids describe other features
   int host_loaded = 0;  // which list d_wid / d_sig hold: 1 index, 2 query (caller's ids or the device FLANN search)
-  FlannDevice* flann = nullptr;  // dsm_retrieval_set_flann_index: the reference's word search on the device (flann_search.hip)
+  FlannDevicePtr flann{nullptr, flann_device_destroy};  // dsm_retrieval_set_flann_index: the reference's word search on the device (flann_search.hip)
   DevBuf d_words, d_cw, d_projT, d_thr, d_lut;
   DevBuf d_row_img, d_wid, d_sig;                       // per feature row
   DevBuf d_keys, d_keys2, d_vals, d_vals2, d_tmp;        // sort scratch
@@ -69,7 +69,7 @@ struct RetrievalState {
   DevBuf d_acc, d_first, d_skeys, d_skeys2, d_svals, d_svals2, d_seg, d_out_cnt, d_out_idx, d_out_score;
   std::vector<uint32_t> img_valid_start;  // prefix sums of the feature counts
   double index_ms = 0.0, query_ms = 0.0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevEvent ev0, ev1;
 };
 
 // ------------------------------------------------------------------------------------ word assignment
@@ -471,15 +471,6 @@ __global__ void k_score_output(const uint64_t* __restrict__ keys, const uint32_t
 }
 
 // ------------------------------------------------------------------------------------ C-ABI
-#define RCHK(ctx, call)                                                              \
-  do {                                                                               \
-    hipError_t e_ = (call);                                                          \
-    if (e_ != hipSuccess) {                                                          \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                \
-      return DSM_ERR_HIP;                                                            \
-    }                                                                                \
-  } while (0)
-
 void dsm_retrieval_invalidate(dsm_ctx* ctx) {  // the resident images changed
   if (!ctx->retrieval) return;
   ctx->retrieval->indexed = false;
@@ -492,18 +483,7 @@ void dsm_retrieval_invalidate(dsm_ctx* ctx) {  // the resident images changed
 }
 
 void dsm_retrieval_destroy(dsm_ctx* ctx) {
-  RetrievalState* r = ctx->retrieval;
-  if (!r) return;
-  DevBuf* bufs[] = {&r->d_words, &r->d_cw, &r->d_projT, &r->d_thr, &r->d_lut, &r->d_row_img, &r->d_wid, &r->d_sig, &r->d_keys,
-                    &r->d_keys2, &r->d_vals, &r->d_vals2, &r->d_tmp, &r->d_file_start, &r->d_e_img, &r->d_e_sig, &r->d_e_row, &r->d_m_counts, &r->d_m_off, &r->d_m_tuples, &r->d_m_cnt_in, &r->d_m_idx_in, &r->d_nimg,
-                    &r->d_idf, &r->d_img_start, &r->d_normc, &r->d_qnorm, &r->d_nfeat, &r->d_wcounts, &r->d_acc, &r->d_first, &r->d_skeys, &r->d_skeys2,
-                    &r->d_svals, &r->d_svals2, &r->d_seg, &r->d_out_cnt, &r->d_out_idx, &r->d_out_score};
-  for (DevBuf* b : bufs) b->release();
-  flann_device_destroy(r->flann);
-  r->flann = nullptr;
-  if (r->ev0) (void)hipEventDestroy(r->ev0);
-  if (r->ev1) (void)hipEventDestroy(r->ev1);
-  delete r;
+  delete ctx->retrieval;
   ctx->retrieval = nullptr;
 }
 
@@ -689,15 +669,15 @@ static int retrieval_assign(dsm_ctx* ctx, uint32_t k, int purpose) {
     std::vector<int32_t> row_img(std::max<uint64_t>(rows, 1), -1);  // row -> image (padding rows: -1), as below
     for (uint32_t i = 0; i < ctx->n_images; ++i)
       for (uint32_t f = 0; f < ctx->nfeat[i]; ++f) row_img[(uint64_t)ctx->row0[i] + f] = (int32_t)i;
-    RCHK(ctx, r->d_row_img.reserve(row_img.size() * 4));
-    RCHK(ctx, hipMemcpy(r->d_row_img.p, row_img.data(), row_img.size() * 4, hipMemcpyHostToDevice));
-    RCHK(ctx, r->d_wid.reserve(wid.size() * 4));
-    RCHK(ctx, r->d_sig.reserve(wid.size() * 8));
-    RCHK(ctx, hipMemcpy(r->d_wid.p, wid.data(), wid.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx, r->d_row_img.reserve(row_img.size() * 4));
+    HIPCHK(ctx, hipMemcpy(r->d_row_img.p, row_img.data(), row_img.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx, r->d_wid.reserve(wid.size() * 4));
+    HIPCHK(ctx, r->d_sig.reserve(wid.size() * 8));
+    HIPCHK(ctx, hipMemcpy(r->d_wid.p, wid.data(), wid.size() * 4, hipMemcpyHostToDevice));
     if (rows) {
       hipLaunchKernelGGL(k_vocab_signature, dim3(2048), dim3(256), 0, st, ctx->d_desc.as<int8_t>(), rows, r->d_projT.as<float>(),
                          r->d_thr.as<float>(), r->d_wid.as<int32_t>(), (int)kk, r->d_sig.as<uint64_t>());
-      RCHK(ctx, hipGetLastError());
+      HIPCHK(ctx, hipGetLastError());
     }
     r->k_assigned = kk;
     r->host_loaded = purpose;
@@ -714,17 +694,17 @@ static int retrieval_assign(dsm_ctx* ctx, uint32_t k, int purpose) {
       for (uint32_t f = 0; f < ctx->nfeat[i]; ++f) row_img[(uint64_t)ctx->row0[i] + f] = (int32_t)i;
       r->img_valid_start[i + 1] = r->img_valid_start[i] + ctx->nfeat[i];
     }
-    RCHK(ctx, r->d_row_img.reserve(row_img.size() * 4));
-    RCHK(ctx, hipMemcpy(r->d_row_img.p, row_img.data(), row_img.size() * 4, hipMemcpyHostToDevice));
-    RCHK(ctx, r->d_wid.reserve(std::max<uint64_t>(rows, 1) * RK_MAX * 4));
-    RCHK(ctx, r->d_sig.reserve(std::max<uint64_t>(rows, 1) * RK_MAX * 8));
+    HIPCHK(ctx, r->d_row_img.reserve(row_img.size() * 4));
+    HIPCHK(ctx, hipMemcpy(r->d_row_img.p, row_img.data(), row_img.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx, r->d_wid.reserve(std::max<uint64_t>(rows, 1) * RK_MAX * 4));
+    HIPCHK(ctx, r->d_sig.reserve(std::max<uint64_t>(rows, 1) * RK_MAX * 8));
     if (rows) {
-      const int rc = flann_device_search(ctx, r->flann, r->d_words.as<int8_t>(), ctx->d_desc.as<int8_t>(), r->d_row_img.as<int32_t>(), rows, kk,
+      const int rc = flann_device_search(ctx, r->flann.get(), r->d_words.as<int8_t>(), ctx->d_desc.as<int8_t>(), r->d_row_img.as<int32_t>(), rows, kk,
                                          r->d_wid.as<int32_t>(), nullptr, RK_MAX, st);
       if (rc != DSM_OK) return rc;
       hipLaunchKernelGGL(k_vocab_signature, dim3(2048), dim3(256), 0, st, ctx->d_desc.as<int8_t>(), rows, r->d_projT.as<float>(),
                          r->d_thr.as<float>(), r->d_wid.as<int32_t>(), (int)kk, r->d_sig.as<uint64_t>());
-      RCHK(ctx, hipGetLastError());
+      HIPCHK(ctx, hipGetLastError());
     }
     r->k_assigned = kk;
     r->host_loaded = purpose;
@@ -738,10 +718,10 @@ static int retrieval_assign(dsm_ctx* ctx, uint32_t k, int purpose) {
     for (uint32_t f = 0; f < ctx->nfeat[i]; ++f) row_img[(uint64_t)ctx->row0[i] + f] = (int32_t)i;
     r->img_valid_start[i + 1] = r->img_valid_start[i] + ctx->nfeat[i];
   }
-  RCHK(ctx, r->d_row_img.reserve(row_img.size() * 4));
-  RCHK(ctx, hipMemcpy(r->d_row_img.p, row_img.data(), row_img.size() * 4, hipMemcpyHostToDevice));
-  RCHK(ctx, r->d_wid.reserve(std::max<uint64_t>(rows, 1) * RK_MAX * 4));
-  RCHK(ctx, r->d_sig.reserve(std::max<uint64_t>(rows, 1) * RK_MAX * 8));
+  HIPCHK(ctx, r->d_row_img.reserve(row_img.size() * 4));
+  HIPCHK(ctx, hipMemcpy(r->d_row_img.p, row_img.data(), row_img.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(ctx, r->d_wid.reserve(std::max<uint64_t>(rows, 1) * RK_MAX * 4));
+  HIPCHK(ctx, r->d_sig.reserve(std::max<uint64_t>(rows, 1) * RK_MAX * 8));
   if (rows) {
 #ifdef DSM_CHECK_BUILD
     if (ctx->dbg("DSM_VOCAB_ASSIGN_VALU"))  // the LDS-tiled v_dot4 form (comparison / cross-check)
@@ -753,10 +733,10 @@ static int retrieval_assign(dsm_ctx* ctx, uint32_t k, int purpose) {
       hipLaunchKernelGGL(k_vocab_assign_mfma, dim3((uint32_t)((rows + 511) / 512)), dim3(256), 0, st, ctx->d_desc.as<int8_t>(),
                          r->d_row_img.as<int32_t>(), rows, r->d_words.as<int8_t>(), r->d_cw.as<int32_t>(), r->num_words, r->words_padded, (int)k,
                          r->d_wid.as<int32_t>());
-    RCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_vocab_signature, dim3(2048), dim3(256), 0, st, ctx->d_desc.as<int8_t>(), rows, r->d_projT.as<float>(),
                        r->d_thr.as<float>(), r->d_wid.as<int32_t>(), (int)k, r->d_sig.as<uint64_t>());
-    RCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
   }
   r->k_assigned = k;
   return DSM_OK;
@@ -769,7 +749,7 @@ int dsm_retrieval_set_vocabulary(dsm_ctx* ctx, const dsm_vocabulary* v) {
   if (v->num_words == 0 || !v->words || !v->projection || !v->thresholds)
     return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "vocabulary needs words, projection and thresholds");
   if (v->num_words >= 0x7fffff00u) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "too many visual words");
-  RCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
   if (!ctx->retrieval) ctx->retrieval = new RetrievalState();
   RetrievalState* r = ctx->retrieval;
   const uint32_t W = v->num_words, Wp = (W + 63u) / 64u * 64u;
@@ -796,28 +776,25 @@ int dsm_retrieval_set_vocabulary(dsm_ctx* ctx, const dsm_vocabulary* v) {
     const float hd = (float)n;
     lut[n] = hd <= 24.0f ? expf(-hd * hd / sigma_squared) : 0.0f;
   }
-  RCHK(ctx, r->d_words.reserve(w8.size()));
-  RCHK(ctx, r->d_cw.reserve(cw.size() * 4));
-  RCHK(ctx, r->d_projT.reserve(projT.size() * 4));
-  RCHK(ctx, r->d_thr.reserve((size_t)W * 64 * 4));
-  RCHK(ctx, r->d_lut.reserve(sizeof(lut)));
-  RCHK(ctx, hipMemcpy(r->d_words.p, w8.data(), w8.size(), hipMemcpyHostToDevice));
-  RCHK(ctx, hipMemcpy(r->d_cw.p, cw.data(), cw.size() * 4, hipMemcpyHostToDevice));
-  RCHK(ctx, hipMemcpy(r->d_projT.p, projT.data(), projT.size() * 4, hipMemcpyHostToDevice));
-  RCHK(ctx, hipMemcpy(r->d_thr.p, v->thresholds, (size_t)W * 64 * 4, hipMemcpyHostToDevice));
-  RCHK(ctx, hipMemcpy(r->d_lut.p, lut, sizeof(lut), hipMemcpyHostToDevice));
+  HIPCHK(ctx, r->d_words.reserve(w8.size()));
+  HIPCHK(ctx, r->d_cw.reserve(cw.size() * 4));
+  HIPCHK(ctx, r->d_projT.reserve(projT.size() * 4));
+  HIPCHK(ctx, r->d_thr.reserve((size_t)W * 64 * 4));
+  HIPCHK(ctx, r->d_lut.reserve(sizeof(lut)));
+  HIPCHK(ctx, hipMemcpy(r->d_words.p, w8.data(), w8.size(), hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(r->d_cw.p, cw.data(), cw.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(r->d_projT.p, projT.data(), projT.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(r->d_thr.p, v->thresholds, (size_t)W * 64 * 4, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(r->d_lut.p, lut, sizeof(lut), hipMemcpyHostToDevice));
   r->num_words = W;
   r->words_padded = Wp;
   r->have_vocab = true;
-  flann_device_destroy(r->flann);  // an index belongs to the vocabulary it was built over
-  r->flann = nullptr;
+  r->flann.reset();  // an index belongs to the vocabulary it was built over
   r->host_loaded = 0;
   r->indexed = false;
   r->k_assigned = 0;
-  if (!r->ev0) {
-    RCHK(ctx, hipEventCreate(&r->ev0));
-    RCHK(ctx, hipEventCreate(&r->ev1));
-  }
+  if (!r->ev0) HIPCHK(ctx, hipEventCreate(&r->ev0.e));
+  if (!r->ev1) HIPCHK(ctx, hipEventCreate(&r->ev1.e));
   return DSM_OK;
 }
 
@@ -857,12 +834,9 @@ int dsm_retrieval_set_flann_index(dsm_ctx* ctx, const dsm_flann_index* index) {
   r->indexed = false;
   r->k_assigned = 0;
   r->host_loaded = 0;
-  RCHK(ctx, hipSetDevice(ctx->device));
-  const int rc = flann_device_set_index(ctx, &r->flann, index, r->d_words.as<int8_t>(), r->num_words);
-  if (rc != DSM_OK) {  // a refused or half-uploaded index must not stay behind: the exact search again
-    flann_device_destroy(r->flann);
-    r->flann = nullptr;
-  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int rc = flann_device_set_index(ctx, r->flann, index, r->d_words.as<int8_t>(), r->num_words);
+  if (rc != DSM_OK) r->flann.reset();  // a refused or half-uploaded index must not stay behind: the exact search again
   return rc;
 }
 
@@ -870,8 +844,8 @@ int dsm_retrieval_flann_search(dsm_ctx* ctx, const uint8_t* descriptors, uint32_
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
   RetrievalState* r = ctx->retrieval;
   if (!r || !r->have_vocab || !r->flann) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_retrieval_set_flann_index has not run");
-  const int rc = flann_device_search_host(ctx, r->flann, r->d_words.as<int8_t>(), descriptors, n, k, ids, dists);
-  if (ms) *ms = flann_device_last_ms(r->flann);
+  const int rc = flann_device_search_host(ctx, r->flann.get(), r->d_words.as<int8_t>(), descriptors, n, k, ids, dists);
+  if (ms) *ms = flann_device_last_ms(r->flann.get());
   return rc;
 }
 
@@ -879,95 +853,95 @@ int dsm_retrieval_index(dsm_ctx* ctx) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
   RetrievalState* r = ctx->retrieval;
   if (!r || !r->have_vocab) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_retrieval_set_vocabulary has not run");
-  RCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const uint64_t rows = ctx->total_rows;
   const uint32_t W = r->num_words, NI = ctx->n_images;
-  RCHK(ctx, hipEventRecord(r->ev0, st));
+  HIPCHK(ctx, hipEventRecord(r->ev0, st));
   r->k_assigned = 0;  // the resident images may have changed
   r->host_loaded = 0;
   int rc = retrieval_assign(ctx, RK_MAX, ASSIGN_FOR_INDEX);
   if (rc != DSM_OK) return rc;
   const uint64_t n_entries = r->img_valid_start[NI];  // one entry per feature (IndexOptions::num_neighbors = 1)
   const uint64_t rows1 = std::max<uint64_t>(rows, 1);
-  RCHK(ctx, r->d_keys.reserve(rows1 * 4));
-  RCHK(ctx, r->d_keys2.reserve(rows1 * 4));
-  RCHK(ctx, r->d_vals.reserve(rows1 * 4));
-  RCHK(ctx, r->d_vals2.reserve(rows1 * 4));
-  RCHK(ctx, r->d_file_start.reserve(((size_t)W + 2) * 4));
-  RCHK(ctx, r->d_nimg.reserve(((size_t)W + 1) * 4));
-  RCHK(ctx, r->d_idf.reserve(((size_t)W + 1) * 4));
-  RCHK(ctx, r->d_e_img.reserve(rows1 * 4));
-  RCHK(ctx, r->d_e_sig.reserve(rows1 * 8));
-  RCHK(ctx, r->d_e_row.reserve(rows1 * 4));
-  RCHK(ctx, r->d_img_start.reserve(((size_t)NI + 1) * 4));
-  RCHK(ctx, r->d_normc.reserve(std::max<uint32_t>(NI, 1) * 4));
-  RCHK(ctx, hipMemsetAsync(r->d_nimg.p, 0, ((size_t)W + 1) * 4, st));
+  HIPCHK(ctx, r->d_keys.reserve(rows1 * 4));
+  HIPCHK(ctx, r->d_keys2.reserve(rows1 * 4));
+  HIPCHK(ctx, r->d_vals.reserve(rows1 * 4));
+  HIPCHK(ctx, r->d_vals2.reserve(rows1 * 4));
+  HIPCHK(ctx, r->d_file_start.reserve(((size_t)W + 2) * 4));
+  HIPCHK(ctx, r->d_nimg.reserve(((size_t)W + 1) * 4));
+  HIPCHK(ctx, r->d_idf.reserve(((size_t)W + 1) * 4));
+  HIPCHK(ctx, r->d_e_img.reserve(rows1 * 4));
+  HIPCHK(ctx, r->d_e_sig.reserve(rows1 * 8));
+  HIPCHK(ctx, r->d_e_row.reserve(rows1 * 4));
+  HIPCHK(ctx, r->d_img_start.reserve(((size_t)NI + 1) * 4));
+  HIPCHK(ctx, r->d_normc.reserve(std::max<uint32_t>(NI, 1) * 4));
+  HIPCHK(ctx, hipMemsetAsync(r->d_nimg.p, 0, ((size_t)W + 1) * 4, st));
   // counts per word -> file_start (exclusive scan); entries sorted by word, stable = (image, feature) order inside a
   // file: InvertedFile::SortEntries sorts by image id (inverted_file.h:223-230)
   std::vector<uint32_t> counts((size_t)W + 1, 0), starts((size_t)W + 2, 0);
   DevBuf& d_counts = r->d_wcounts;  // owned by the state: no leak on the early returns below
-  RCHK(ctx, d_counts.reserve(((size_t)W + 1) * 4));
-  RCHK(ctx, hipMemsetAsync(d_counts.p, 0, ((size_t)W + 1) * 4, st));
+  HIPCHK(ctx, d_counts.reserve(((size_t)W + 1) * 4));
+  HIPCHK(ctx, hipMemsetAsync(d_counts.p, 0, ((size_t)W + 1) * 4, st));
   if (rows) {
     hipLaunchKernelGGL(k_index_keys, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, st, r->d_wid.as<int32_t>(), rows, W,
                        r->d_keys.as<uint32_t>(), r->d_vals.as<uint32_t>(), d_counts.as<uint32_t>());
-    RCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
     int bits = 1;
     while ((1u << bits) <= W) ++bits;
     size_t tmp_bytes = 0;
-    RCHK(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, r->d_keys.as<uint32_t>(), r->d_keys2.as<uint32_t>(), r->d_vals.as<uint32_t>(),
+    HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, r->d_keys.as<uint32_t>(), r->d_keys2.as<uint32_t>(), r->d_vals.as<uint32_t>(),
                                         r->d_vals2.as<uint32_t>(), (size_t)rows, 0, (unsigned)bits, st));
-    RCHK(ctx, r->d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
-    RCHK(ctx, rocprim::radix_sort_pairs(r->d_tmp.p, tmp_bytes, r->d_keys.as<uint32_t>(), r->d_keys2.as<uint32_t>(), r->d_vals.as<uint32_t>(),
+    HIPCHK(ctx, r->d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
+    HIPCHK(ctx, rocprim::radix_sort_pairs(r->d_tmp.p, tmp_bytes, r->d_keys.as<uint32_t>(), r->d_keys2.as<uint32_t>(), r->d_vals.as<uint32_t>(),
                                         r->d_vals2.as<uint32_t>(), (size_t)rows, 0, (unsigned)bits, st));
   }
-  RCHK(ctx, hipMemcpyAsync(counts.data(), d_counts.p, ((size_t)W + 1) * 4, hipMemcpyDeviceToHost, st));
-  RCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, hipMemcpyAsync(counts.data(), d_counts.p, ((size_t)W + 1) * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   for (uint32_t w = 0; w <= W; ++w) starts[w + 1] = starts[w] + counts[w];
-  RCHK(ctx, hipMemcpyAsync(r->d_file_start.p, starts.data(), ((size_t)W + 2) * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(r->d_file_start.p, starts.data(), ((size_t)W + 2) * 4, hipMemcpyHostToDevice, st));
   if (n_entries) {
     hipLaunchKernelGGL(k_gather_entries, dim3((uint32_t)((n_entries + 255) / 256)), dim3(256), 0, st, r->d_vals2.as<uint32_t>(), n_entries,
                        r->d_row_img.as<int32_t>(), r->d_sig.as<uint64_t>(), r->d_e_img.as<int32_t>(), r->d_e_sig.as<uint64_t>(), r->d_e_row.as<uint32_t>());
     hipLaunchKernelGGL(k_word_image_counts, dim3((uint32_t)((n_entries + 255) / 256)), dim3(256), 0, st, r->d_keys2.as<uint32_t>(),
                        r->d_e_img.as<int32_t>(), n_entries, r->d_nimg.as<uint32_t>());
-    RCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
   }
   // IDF weights with the host libm (InvertedFile::ComputeIDFWeight, inverted_file.h:260-271)
   std::vector<uint32_t> nimg((size_t)W + 1, 0);
-  RCHK(ctx, hipMemcpyAsync(nimg.data(), r->d_nimg.p, ((size_t)W + 1) * 4, hipMemcpyDeviceToHost, st));
-  RCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, hipMemcpyAsync(nimg.data(), r->d_nimg.p, ((size_t)W + 1) * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   uint32_t num_total_images = 0;
   for (uint32_t i = 0; i < NI; ++i) num_total_images += ctx->nfeat[i] ? 1u : 0u;
   std::vector<float> idf((size_t)W + 1, 0.0f);
   for (uint32_t w = 0; w < W; ++w)
     if (nimg[w]) idf[w] = (float)log((double)num_total_images / (double)nimg[w]);
-  RCHK(ctx, hipMemcpyAsync(r->d_idf.p, idf.data(), ((size_t)W + 1) * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(r->d_idf.p, idf.data(), ((size_t)W + 1) * 4, hipMemcpyHostToDevice, st));
   r->idf_host.assign(idf.begin(), idf.begin() + W);
-  RCHK(ctx, hipMemcpyAsync(r->d_img_start.p, r->img_valid_start.data(), ((size_t)NI + 1) * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(r->d_img_start.p, r->img_valid_start.data(), ((size_t)NI + 1) * 4, hipMemcpyHostToDevice, st));
   // per image: its entries in word order = the word-sorted list stably re-sorted by image
   if (n_entries) {
     int bits = 1;
     while ((1u << bits) < std::max<uint32_t>(NI, 2)) ++bits;
     // keys: image of every sorted entry (as unsigned), values: its word
-    RCHK(ctx, hipMemcpyAsync(r->d_keys.p, r->d_e_img.p, n_entries * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(r->d_keys.p, r->d_e_img.p, n_entries * 4, hipMemcpyDeviceToDevice, st));
     size_t tmp_bytes = 0;
-    RCHK(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, r->d_keys.as<uint32_t>(), r->d_vals.as<uint32_t>(), r->d_keys2.as<uint32_t>(),
+    HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, r->d_keys.as<uint32_t>(), r->d_vals.as<uint32_t>(), r->d_keys2.as<uint32_t>(),
                                         r->d_vals2.as<uint32_t>(), (size_t)n_entries, 0, (unsigned)bits, st));
-    RCHK(ctx, r->d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
+    HIPCHK(ctx, r->d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
     // NOTE: d_vals2 (sorted rows) is overwritten here with the words by image; nothing needs the rows any more
-    RCHK(ctx, rocprim::radix_sort_pairs(r->d_tmp.p, tmp_bytes, r->d_keys.as<uint32_t>(), r->d_vals.as<uint32_t>(), r->d_keys2.as<uint32_t>(),
+    HIPCHK(ctx, rocprim::radix_sort_pairs(r->d_tmp.p, tmp_bytes, r->d_keys.as<uint32_t>(), r->d_vals.as<uint32_t>(), r->d_keys2.as<uint32_t>(),
                                         r->d_vals2.as<uint32_t>(), (size_t)n_entries, 0, (unsigned)bits, st));
   }
   if (NI) {
     hipLaunchKernelGGL(k_image_self, dim3((NI + 63) / 64), dim3(64), 0, st, r->d_vals2.as<uint32_t>(), r->d_img_start.as<uint32_t>(), NI,
                        r->d_idf.as<float>(), r->d_normc.as<float>());
-    RCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
   }
-  RCHK(ctx, hipEventRecord(r->ev1, st));
-  RCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, hipEventRecord(r->ev1, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   float ms = 0.f;
-  RCHK(ctx, hipEventElapsedTime(&ms, r->ev0, r->ev1));
+  HIPCHK(ctx, hipEventElapsedTime(&ms, r->ev0, r->ev1));
   r->index_ms = ms;
   r->indexed = true;
   return DSM_OK;
@@ -980,7 +954,7 @@ int dsm_retrieval_query(dsm_ctx* ctx, uint32_t num_neighbors, uint32_t max_num_i
   if (!r || !r->indexed) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_retrieval_index has not run");
   if (num_neighbors == 0 || num_neighbors > RK_MAX) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "num_neighbors must be 1..8");
   if (max_num_images == 0) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "max_num_images must be > 0");
-  RCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const uint32_t NI = ctx->n_images;
   if (NI == 0) return DSM_OK;
@@ -990,30 +964,30 @@ int dsm_retrieval_query(dsm_ctx* ctx, uint32_t num_neighbors, uint32_t max_num_i
     const int rca = retrieval_assign(ctx, num_neighbors, ASSIGN_FOR_QUERY);
     if (rca != DSM_OK) return rca;
   }
-  RCHK(ctx, hipEventRecord(r->ev0, st));
+  HIPCHK(ctx, hipEventRecord(r->ev0, st));
   DevBuf& d_nfeat = r->d_nfeat;  // owned by the state: released with it on every exit path
-  RCHK(ctx, d_nfeat.reserve((size_t)NI * 4));
-  RCHK(ctx, hipMemcpyAsync(d_nfeat.p, ctx->nfeat.data(), (size_t)NI * 4, hipMemcpyHostToDevice, st));
-  RCHK(ctx, r->d_qnorm.reserve((size_t)NI * 4));
+  HIPCHK(ctx, d_nfeat.reserve((size_t)NI * 4));
+  HIPCHK(ctx, hipMemcpyAsync(d_nfeat.p, ctx->nfeat.data(), (size_t)NI * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, r->d_qnorm.reserve((size_t)NI * 4));
   hipLaunchKernelGGL(k_query_self, dim3((NI + 63) / 64), dim3(64), 0, st, r->d_wid.as<int32_t>(), ctx->d_img_row0.as<uint32_t>(),
                      d_nfeat.as<uint32_t>(), NI, k, r->d_idf.as<float>(), r->d_qnorm.as<float>());
-  RCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   // queries in batches: accumulators [batch][NI]
   const uint64_t budget = 1ull << 30;
   const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(NI, budget / ((uint64_t)NI * 24)));
-  RCHK(ctx, r->d_acc.reserve((size_t)batch * NI * 4));
-  RCHK(ctx, r->d_first.reserve((size_t)batch * NI * 4));
-  RCHK(ctx, r->d_skeys.reserve((size_t)batch * NI * 8));
-  RCHK(ctx, r->d_skeys2.reserve((size_t)batch * NI * 8));
-  RCHK(ctx, r->d_svals.reserve((size_t)batch * NI * 4));
-  RCHK(ctx, r->d_svals2.reserve((size_t)batch * NI * 4));
-  RCHK(ctx, r->d_seg.reserve(((size_t)batch + 1) * 4));
-  RCHK(ctx, r->d_out_cnt.reserve((size_t)NI * 4 + (size_t)batch * 4));
-  RCHK(ctx, r->d_out_idx.reserve((size_t)NI * max_num_images * 4));
-  RCHK(ctx, r->d_out_score.reserve((size_t)NI * max_num_images * 4));
+  HIPCHK(ctx, r->d_acc.reserve((size_t)batch * NI * 4));
+  HIPCHK(ctx, r->d_first.reserve((size_t)batch * NI * 4));
+  HIPCHK(ctx, r->d_skeys.reserve((size_t)batch * NI * 8));
+  HIPCHK(ctx, r->d_skeys2.reserve((size_t)batch * NI * 8));
+  HIPCHK(ctx, r->d_svals.reserve((size_t)batch * NI * 4));
+  HIPCHK(ctx, r->d_svals2.reserve((size_t)batch * NI * 4));
+  HIPCHK(ctx, r->d_seg.reserve(((size_t)batch + 1) * 4));
+  HIPCHK(ctx, r->d_out_cnt.reserve((size_t)NI * 4 + (size_t)batch * 4));
+  HIPCHK(ctx, r->d_out_idx.reserve((size_t)NI * max_num_images * 4));
+  HIPCHK(ctx, r->d_out_score.reserve((size_t)NI * max_num_images * 4));
   std::vector<uint32_t> seg((size_t)batch + 1);
   for (uint32_t b = 0; b <= batch; ++b) seg[b] = b * NI;
-  RCHK(ctx, hipMemcpyAsync(r->d_seg.p, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(r->d_seg.p, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, st));
   uint32_t* d_bcounts = r->d_out_cnt.as<uint32_t>() + NI;
   for (uint32_t q0 = 0; q0 < NI; q0 += batch) {
     const uint32_t nq = std::min<uint32_t>(batch, NI - q0);
@@ -1021,33 +995,33 @@ int dsm_retrieval_query(dsm_ctx* ctx, uint32_t num_neighbors, uint32_t max_num_i
                        ctx->d_img_row0.as<uint32_t>(), d_nfeat.as<uint32_t>(), q0, nq, NI, k, r->d_file_start.as<uint32_t>(),
                        r->d_e_img.as<int32_t>(), r->d_e_sig.as<uint64_t>(), r->d_idf.as<float>(), r->d_lut.as<float>(),
                        r->d_acc.as<float>(), r->d_first.as<uint32_t>());
-    RCHK(ctx, hipGetLastError());
-    RCHK(ctx, hipMemsetAsync(d_bcounts, 0, (size_t)nq * 4, st));
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemsetAsync(d_bcounts, 0, (size_t)nq * 4, st));
     const uint64_t total = (uint64_t)nq * NI;
     hipLaunchKernelGGL(k_score_keys, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, st, r->d_acc.as<float>(), r->d_first.as<uint32_t>(),
                        q0, nq, NI, r->d_qnorm.as<float>(), r->d_normc.as<float>(), r->d_skeys.as<uint64_t>(), r->d_svals.as<uint32_t>(),
                        d_bcounts);
-    RCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
     size_t tmp_bytes = 0;
-    RCHK(ctx, rocprim::segmented_radix_sort_pairs(nullptr, tmp_bytes, r->d_skeys.as<uint64_t>(), r->d_skeys2.as<uint64_t>(),
+    HIPCHK(ctx, rocprim::segmented_radix_sort_pairs(nullptr, tmp_bytes, r->d_skeys.as<uint64_t>(), r->d_skeys2.as<uint64_t>(),
                                                   r->d_svals.as<uint32_t>(), r->d_svals2.as<uint32_t>(), (unsigned)total, nq,
                                                   r->d_seg.as<uint32_t>(), r->d_seg.as<uint32_t>() + 1, 0, 64, st));
-    RCHK(ctx, r->d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
-    RCHK(ctx, rocprim::segmented_radix_sort_pairs(r->d_tmp.p, tmp_bytes, r->d_skeys.as<uint64_t>(), r->d_skeys2.as<uint64_t>(),
+    HIPCHK(ctx, r->d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
+    HIPCHK(ctx, rocprim::segmented_radix_sort_pairs(r->d_tmp.p, tmp_bytes, r->d_skeys.as<uint64_t>(), r->d_skeys2.as<uint64_t>(),
                                                   r->d_svals.as<uint32_t>(), r->d_svals2.as<uint32_t>(), (unsigned)total, nq,
                                                   r->d_seg.as<uint32_t>(), r->d_seg.as<uint32_t>() + 1, 0, 64, st));
     hipLaunchKernelGGL(k_score_output, dim3(nq), dim3(64), 0, st, r->d_skeys2.as<uint64_t>(), r->d_svals2.as<uint32_t>(), d_bcounts, q0, nq,
                        NI, max_num_images, r->d_out_cnt.as<uint32_t>(), r->d_out_idx.as<uint32_t>(), r->d_out_score.as<float>());
-    RCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
   }
-  RCHK(ctx, hipEventRecord(r->ev1, st));
-  RCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, hipEventRecord(r->ev1, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   float ms = 0.f;
-  RCHK(ctx, hipEventElapsedTime(&ms, r->ev0, r->ev1));
+  HIPCHK(ctx, hipEventElapsedTime(&ms, r->ev0, r->ev1));
   r->query_ms = ms;
-  RCHK(ctx, hipMemcpy(counts, r->d_out_cnt.p, (size_t)NI * 4, hipMemcpyDefault));
-  RCHK(ctx, hipMemcpy(image_idx, r->d_out_idx.p, (size_t)NI * max_num_images * 4, hipMemcpyDefault));
-  RCHK(ctx, hipMemcpy(scores, r->d_out_score.p, (size_t)NI * max_num_images * 4, hipMemcpyDefault));
+  HIPCHK(ctx, hipMemcpy(counts, r->d_out_cnt.p, (size_t)NI * 4, hipMemcpyDefault));
+  HIPCHK(ctx, hipMemcpy(image_idx, r->d_out_idx.p, (size_t)NI * max_num_images * 4, hipMemcpyDefault));
+  HIPCHK(ctx, hipMemcpy(scores, r->d_out_score.p, (size_t)NI * max_num_images * 4, hipMemcpyDefault));
   return DSM_OK;
 }
 
@@ -1064,23 +1038,23 @@ int dsm_retrieval_matches(dsm_ctx* ctx, uint32_t num_neighbors, uint32_t max_num
   if (NI == 0) return DSM_OK;
   if (r->host_ids || r->flann) {
     if (r->host_ids && num_neighbors != r->host_k_query) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "num_neighbors differs from the k of dsm_retrieval_set_word_ids");
-    RCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     const int rca = retrieval_assign(ctx, num_neighbors, ASSIGN_FOR_QUERY);
     if (rca != DSM_OK) return rca;
   }
   const size_t smem = ((size_t)NI + 31) / 32 * 4;
   if (smem > 60000) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "dsm_retrieval_matches: more than 480 000 resident images");
   if (r->num_words >= (1u << 24)) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "dsm_retrieval_matches: more than 2^24 visual words");
-  RCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  RCHK(ctx, r->d_nfeat.reserve((size_t)NI * 4));
-  RCHK(ctx, hipMemcpyAsync(r->d_nfeat.p, ctx->nfeat.data(), (size_t)NI * 4, hipMemcpyHostToDevice, st));
-  RCHK(ctx, r->d_m_cnt_in.reserve((size_t)NI * 4));
-  RCHK(ctx, r->d_m_idx_in.reserve((size_t)NI * max_num_images * 4));
-  RCHK(ctx, hipMemcpyAsync(r->d_m_cnt_in.p, counts, (size_t)NI * 4, hipMemcpyDefault, st));
-  RCHK(ctx, hipMemcpyAsync(r->d_m_idx_in.p, image_idx, (size_t)NI * max_num_images * 4, hipMemcpyDefault, st));
-  RCHK(ctx, r->d_m_counts.reserve((size_t)NI * 4));
-  RCHK(ctx, r->d_m_off.reserve(((size_t)NI + 1) * 8));
+  HIPCHK(ctx, r->d_nfeat.reserve((size_t)NI * 4));
+  HIPCHK(ctx, hipMemcpyAsync(r->d_nfeat.p, ctx->nfeat.data(), (size_t)NI * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, r->d_m_cnt_in.reserve((size_t)NI * 4));
+  HIPCHK(ctx, r->d_m_idx_in.reserve((size_t)NI * max_num_images * 4));
+  HIPCHK(ctx, hipMemcpyAsync(r->d_m_cnt_in.p, counts, (size_t)NI * 4, hipMemcpyDefault, st));
+  HIPCHK(ctx, hipMemcpyAsync(r->d_m_idx_in.p, image_idx, (size_t)NI * max_num_images * 4, hipMemcpyDefault, st));
+  HIPCHK(ctx, r->d_m_counts.reserve((size_t)NI * 4));
+  HIPCHK(ctx, r->d_m_off.reserve(((size_t)NI + 1) * 8));
   auto launch = [&](bool write) {
     if (write)
       hipLaunchKernelGGL(k_vocab_matches<true>, dim3(NI), dim3(64), smem, st, r->d_wid.as<int32_t>(), r->d_sig.as<uint64_t>(),
@@ -1096,17 +1070,17 @@ int dsm_retrieval_matches(dsm_ctx* ctx, uint32_t num_neighbors, uint32_t max_num
                          (uint32_t*)nullptr);
   };
   launch(false);
-  RCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   std::vector<uint32_t> mc(NI);
-  RCHK(ctx, hipMemcpyAsync(mc.data(), r->d_m_counts.p, (size_t)NI * 4, hipMemcpyDeviceToHost, st));
-  RCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, hipMemcpyAsync(mc.data(), r->d_m_counts.p, (size_t)NI * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   for (uint32_t q = 0; q < NI; ++q) offsets[q + 1] = offsets[q] + mc[q];
   r->m_total = offsets[NI];
-  RCHK(ctx, hipMemcpyAsync(r->d_m_off.p, offsets, ((size_t)NI + 1) * 8, hipMemcpyHostToDevice, st));
-  RCHK(ctx, r->d_m_tuples.reserve(std::max<uint64_t>(r->m_total, 1) * 20));
+  HIPCHK(ctx, hipMemcpyAsync(r->d_m_off.p, offsets, ((size_t)NI + 1) * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, r->d_m_tuples.reserve(std::max<uint64_t>(r->m_total, 1) * 20));
   launch(true);
-  RCHK(ctx, hipGetLastError());
-  RCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(st));
   return DSM_OK;
 }
 
@@ -1116,8 +1090,8 @@ int dsm_get_retrieval_matches(dsm_ctx* ctx, uint32_t* tuples, uint64_t capacity)
   if (capacity < r->m_total) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "dsm_get_retrieval_matches: capacity below the total of dsm_retrieval_matches");
   if (r->m_total == 0) return DSM_OK;
   if (!tuples) return DSM_ERR_INVALID_ARGUMENT;
-  RCHK(ctx, hipSetDevice(ctx->device));
-  RCHK(ctx, hipMemcpy(tuples, r->d_m_tuples.p, (size_t)r->m_total * 20, hipMemcpyDefault));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipMemcpy(tuples, r->d_m_tuples.p, (size_t)r->m_total * 20, hipMemcpyDefault));
   return DSM_OK;
 }
 
@@ -1135,15 +1109,15 @@ int dsm_retrieval_debug_word_ids(dsm_ctx* ctx, uint32_t image, uint32_t k, int32
   RetrievalState* r = ctx->retrieval;
   if (!r || !r->have_vocab) return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_retrieval_set_vocabulary has not run");
   if (image >= ctx->n_images || k == 0 || k > RK_MAX) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "image / k out of range");
-  RCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
   r->k_assigned = 0;
   r->host_loaded = 0;
   int rc = retrieval_assign(ctx, r->flann ? k : RK_MAX, ASSIGN_FOR_QUERY);  // (an approximate search's first k of 8 are not its k of k)
   if (rc != DSM_OK) return rc;
-  RCHK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   std::vector<int32_t> all((size_t)ctx->nfeat[image] * RK_MAX);
   if (!all.empty())
-    RCHK(ctx, hipMemcpy(all.data(), r->d_wid.as<int32_t>() + (size_t)ctx->row0[image] * RK_MAX, all.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(all.data(), r->d_wid.as<int32_t>() + (size_t)ctx->row0[image] * RK_MAX, all.size() * 4, hipMemcpyDeviceToHost));
   for (uint32_t i = 0; i < ctx->nfeat[image]; ++i)
     for (uint32_t n = 0; n < k; ++n) out[(size_t)i * k + n] = all[(size_t)i * RK_MAX + n];
   return DSM_OK;

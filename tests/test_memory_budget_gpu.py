@@ -54,9 +54,25 @@ def test_a_budget_changes_the_chunks_not_the_records():
 
 
 def test_budget_is_per_context_and_argument_checked():
+    """A budget set on one context leaves the scratch of another alone: b keeps (and re-uses) what it holds, above a's budget."""
+    n_img = 6
+    scene = synthetic.Scene(n_img, 1024, seed=3)
+    ims = [scene.image(i) for i in range(n_img)]
+    cams = [capi.simple_pinhole(scene.focal, scene.width / 2.0, scene.height / 2.0, scene.width, scene.height, True) for _ in range(n_img)]
+    pairs = synthetic.exhaustive_pairs(n_img)
+    opts = capi.default_two_view_options()
     a, b = capi.Context(0), capi.Context(0)
-    a.set_memory_budget(1 << 30)
-    assert a.memory_footprint()[1] <= 1 << 30 and b.memory_footprint() == (b.memory_footprint()[0], b.memory_footprint()[1])
+    b.set_images([im[0] for im in ims], [im[1] for im in ims], cams)
+    ref = _run(b, pairs, opts)
+    scr_b = b.memory_footprint()[1]
+    budget = scr_b // 2
+    assert budget > 0
+    a.set_memory_budget(budget)
+    assert a.memory_footprint()[1] <= budget
+    got = _run(b, pairs, opts)
+    assert b.memory_footprint()[1] == scr_b > budget
+    for x, y in zip(got, ref):
+        assert (x == y).all()
     L = capi.lib()
     L.dsm_ctx_set_memory_budget.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
     assert L.dsm_ctx_set_memory_budget(None, 1) != 0

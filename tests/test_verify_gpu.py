@@ -425,27 +425,32 @@ def test_baseline_config1_size(dsm, oracle):
 
 
 @pytest.mark.parametrize("prior,planar,cross", [(1, False, True), (0, False, True), (1, True, True), (1, False, False)])
-def test_guided_matching_stage(dsm, oracle, prior, planar, cross):
+def test_guided_matching_stage(oracle, prior, planar, cross):
     """SiftMatchingOptions::guided_matching: verify, then MatchGuidedSiftFeaturesCPU (sift.cc:824-875) for every pair
     with enough inliers and an F- or H-type configuration replaces the inlier matches (matching.cc:441-470), then
-    Match()'s post-filter.  Compared with the oracle pair by pair."""
+    Match()'s post-filter.  Compared with the oracle pair by pair.  On a context of its own, so that the footprint before the
+    call holds none of the guided matcher's buffers."""
+    ctx = capi.Context(0)
     n_img = 5
     scene = synthetic.Scene(n_img, 640, seed=51 + prior, n_pool=1500, planar=planar)
     ims = [scene.image(i) for i in range(n_img)]
     cams = [capi.simple_pinhole(800.0, 500.0, 375.0, 1000, 750, prior) for _ in range(n_img)]
-    dsm.set_images([im[0] for im in ims], [im[1] for im in ims], cams)
+    ctx.set_images([im[0] for im in ims], [im[1] for im in ims], cams)
     pairs = synthetic.exhaustive_pairs(n_img)
     mo = capi.default_match_options()
     mo.cross_check = 1 if cross else 0
-    dsm.match_pairs(pairs, mo)
+    ctx.match_pairs(pairs, mo)
     opts = capi.default_two_view_options()
-    dsm.verify_pairs(opts, user_seed=8, stage_filter=False)
-    pre = dsm.two_view_geometries()
+    ctx.verify_pairs(opts, user_seed=8, stage_filter=False)
+    pre = ctx.two_view_geometries()
     pre_cfg = [t.config for t in pre]
-    dsm.guided_match_pairs(mo, opts, stage_filter=True)
-    offs, m = dsm.matches()
-    tvgs = dsm.two_view_geometries()
-    ioffs, im = dsm.inlier_matches()
+    res0 = ctx.memory_footprint()[0]
+    ctx.guided_match_pairs(mo, opts, stage_filter=True)
+    offs, m = ctx.matches()
+    tvgs = ctx.two_view_geometries()
+    ioffs, im = ctx.inlier_matches()
+    # the guided matcher's buffers are resident: the footprint counts (at least) the inlier list the call produced
+    assert ctx.memory_footprint()[0] - res0 >= 8 * len(im)
     n_guided = 0
     for k, (i, j) in enumerate(pairs):
         mk = m[int(offs[k]):int(offs[k + 1])]
