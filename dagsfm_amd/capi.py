@@ -162,6 +162,33 @@ class BundleAdjustmentReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TriangulationOptions(ctypes.Structure):
+    """dsm_triangulation_options: IncrementalTriangulator::Options and Create()'s RANSAC settings
+    (src/sfm/incremental_triangulator.h, incremental_triangulator.cc:497-514)."""
+    _fields_ = [("create_max_angle_error", ctypes.c_double), ("continue_max_angle_error", ctypes.c_double),
+                ("min_angle", ctypes.c_double), ("min_focal_length_ratio", ctypes.c_double),
+                ("max_focal_length_ratio", ctypes.c_double), ("max_extra_param", ctypes.c_double),
+                ("ransac_confidence", ctypes.c_double), ("ransac_min_inlier_ratio", ctypes.c_double),
+                ("ransac_max_num_trials", ctypes.c_int32), ("ignore_two_view_tracks", ctypes.c_int32),
+                ("max_transitivity", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class TriangulationReport(ctypes.Structure):
+    _fields_ = [("num_separators", ctypes.c_uint32), ("num_rounds", ctypes.c_uint32), ("num_problems", ctypes.c_uint64),
+                ("num_deferred", ctypes.c_uint64), ("num_correspondences", ctypes.c_uint64), ("ransac_trials", ctypes.c_uint64),
+                ("num_tris", ctypes.c_uint64), ("num_new_points", ctypes.c_uint64), ("num_new_observations", ctypes.c_uint64),
+                ("num_continued", ctypes.c_uint64), ("min_residual_margin", ctypes.c_double), ("min_support_margin", ctypes.c_double),
+                ("min_angle_margin", ctypes.c_double), ("min_depth_margin", ctypes.c_double), ("min_continue_margin", ctypes.c_double),
+                ("min_bogus_margin", ctypes.c_double), ("setup_ms", ctypes.c_double), ("graph_ms", ctypes.c_double),
+                ("continue_ms", ctypes.c_double), ("ransac_ms", ctypes.c_double), ("schedule_ms", ctypes.c_double),
+                ("apply_ms", ctypes.c_double), ("round_gap_ms", ctypes.c_double), ("download_ms", ctypes.c_double),
+                ("assemble_ms", ctypes.c_double), ("replay_ms", ctypes.c_double),
+                ("device_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 BA_CONVERGENCE, BA_NO_CONVERGENCE, BA_FAILURE = 0, 1, 2
 BA_TRACE_COLUMNS = 6  # cost, radius, rho, CG iterations, accepted, gradient max-norm
 
@@ -237,6 +264,11 @@ def lib(check=False):
         L.dsm_default_bundle_adjustment_options.restype = None
         L.dsm_bundle_adjust.argtypes = ([vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32] + [vp] * 5 + [ctypes.c_uint32] + [vp] * 6
                                         + [ctypes.POINTER(BundleAdjustmentOptions), vp, vp])
+        L.dsm_default_triangulation_options.argtypes = [ctypes.POINTER(TriangulationOptions)]
+        L.dsm_default_triangulation_options.restype = None
+        L.dsm_retriangulate.argtypes = ([vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32] + [vp] * 8 + [ctypes.c_uint32, vp, vp, ctypes.c_uint32]
+                                        + [vp] * 3 + [ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.POINTER(TriangulationOptions)]
+                                        + [vp] * 14)
         L.dsm_debug_image_to_world.argtypes = [vp, ctypes.POINTER(Camera), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double)]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
@@ -313,6 +345,14 @@ def default_align_options(**kw):
 def default_bundle_adjustment_options(**kw):
     o = BundleAdjustmentOptions()
     lib().dsm_default_bundle_adjustment_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_triangulation_options(**kw):
+    o = TriangulationOptions()
+    lib().dsm_default_triangulation_options(ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -761,6 +801,46 @@ class Context:
         if trace:
             out["trace"] = tr[:rep.num_iterations + 1].copy()
         return out
+
+    def retriangulate(self, scene, separators, options=None, next_point3D_id=0):
+        """dsm_retriangulate (IncrementalTriangulator::TriangulateImage over the separators, DESIGN.md 13).  scene: a dict with
+        camera_ids [C], cameras (a list of Camera), image_ids [N], image_camera_ids [N], registered [N], qvec [N, 4], tvec [N, 3],
+        points2D_offsets [N + 1], points2D_xy [T, 2], points2D_point3D [T] (index into the points3D or -1), point3D_ids [P],
+        point3D_xyz [P, 3], pairs [K, 2] (image ids), match_offsets [K + 1], matches [m, 2].  separators: image ids.
+        Returns a dict: new_point_ids, new_xyz [n, 3], new_track_offsets [n + 1], new_track_obs [., 2] (image_id, point2D_idx),
+        continued_obs [c, 2], continued_point_ids [c], touched_obs [t, 2], touched_point_ids [t], num_tris_per_separator,
+        num_tris, report."""
+        a = lambda key, dt, shape=-1: np.ascontiguousarray(scene[key], dt).reshape(shape)
+        cam_ids = a("camera_ids", np.uint32)
+        cams = (Camera * max(len(cam_ids), 1))(*scene["cameras"])
+        img_ids, img_cam, reg = a("image_ids", np.uint32), a("image_camera_ids", np.uint32), a("registered", np.uint8)
+        N = len(img_ids)
+        qvec, tvec = a("qvec", np.float64, (N, 4)), a("tvec", np.float64, (N, 3))
+        poff = a("points2D_offsets", np.uint32)
+        xy, p3 = a("points2D_xy", np.float64, (-1, 2)), a("points2D_point3D", np.int32)
+        pids, pxyz = a("point3D_ids", np.uint64), a("point3D_xyz", np.float64, (-1, 3))
+        pairs, moff, m = a("pairs", np.uint32, (-1, 2)), a("match_offsets", np.uint64), a("matches", np.uint32, (-1, 2))
+        seps = np.ascontiguousarray(separators, np.uint32).reshape(-1)
+        T = max(int(poff[-1]) if len(poff) else 0, 1)
+        nid, nxyz, noff = np.zeros(T, np.uint64), np.zeros((T, 3)), np.zeros(T + 1, np.uint64)
+        nobs, cobs, cid = np.zeros((T, 2), np.uint32), np.zeros((T, 2), np.uint32), np.zeros(T, np.uint64)
+        tobs, tid = np.zeros((T, 2), np.uint32), np.zeros(T, np.uint64)
+        sep_tris = np.zeros(max(len(seps), 1), np.uint32)
+        nn, nc, nt, tris = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rep = TriangulationReport()
+        o = options if options is not None else default_triangulation_options()
+        ptr = lambda x: x.ctypes.data
+        self._chk(self._L.dsm_retriangulate(self._h, len(cam_ids), ptr(cam_ids), ctypes.addressof(cams), N, ptr(img_ids), ptr(img_cam),
+                                            ptr(reg), ptr(qvec), ptr(tvec), ptr(poff), ptr(xy), ptr(p3), len(pids), ptr(pids), ptr(pxyz),
+                                            len(pairs), ptr(pairs), ptr(moff), ptr(m), len(seps), ptr(seps), int(next_point3D_id),
+                                            ctypes.byref(o), ptr(nid), ptr(nxyz), ptr(noff), ptr(nobs), ctypes.addressof(nn), ptr(cobs),
+                                            ptr(cid), ctypes.addressof(nc), ptr(tobs), ptr(tid), ctypes.addressof(nt), ptr(sep_tris),
+                                            ctypes.addressof(tris), ctypes.addressof(rep)))
+        n, c, t = nn.value, nc.value, nt.value
+        return {"new_point_ids": nid[:n].copy(), "new_xyz": nxyz[:n].copy(), "new_track_offsets": noff[:n + 1].copy(),
+                "new_track_obs": nobs[:int(noff[n])].copy(), "continued_obs": cobs[:c].copy(), "continued_point_ids": cid[:c].copy(),
+                "touched_obs": tobs[:t].copy(), "touched_point_ids": tid[:t].copy(),
+                "num_tris_per_separator": sep_tris[:len(seps)].copy(), "num_tris": tris.value, "report": rep}
 
     def device_info(self):
         d = DeviceInfo()

@@ -1,0 +1,1128 @@
+// retriangulation.hip -- re-triangulation of the separator images ("Re-triangulation").
+//   DistributedMapperController::Triangulate                       src/controllers/distributed_mapper_controller.cpp:823-834
+//   IncrementalTriangulator::TriangulateImage / Find / Create / Continue   src/sfm/incremental_triangulator.cc:61-117, 419-586
+//   EstimateTriangulation, TriangulationEstimator                   src/estimators/triangulation.cc
+//   LORANSAC + InlierSupportMeasurer + CombinationSampler           src/optim/loransac.h:91-233, combination_sampler.cc
+//   TriangulatePoint / TriangulateMultiViewPoint / CalculateTriangulationAngle   src/base/triangulation.cc
+//   CorrespondenceGraph::AddCorrespondences / IsTwoViewObservation  src/base/correspondence_graph.cc:77-161, 250-261
+// The graph: one workgroup per verified pair applies the duplicate rule in match order (an LDS bitmap of the pair's two
+// images) and flags the accepted matches; each becomes two directed entries placed in its source feature's CSR segment
+// (integer-atomic counts, a fixed-block scan), and every segment is then sorted by pair index -- a feature has at most one
+// correspondence per pair, so this is the reference's (pair, match) append order whatever order the atomics took.
+// The problems: one per (separator in ascending id, point2D) with a non-empty filtered correspondence list.  A problem reads
+// and writes only its own feature set (the reference feature and its correspondences) and point xyz never changes, so the
+// host schedules the problems into rounds before any solve: in sequential order, a problem commits in the current round when
+// its feature set meets no set of an earlier problem of the round (committed or deferred), otherwise it is deferred to the
+// next round.  That is one pass in problem order (a problem's round is 1 + the largest round of the earlier problems sharing
+// a feature with it), and every round is enqueued at once without a host sync.  Each round then solves its committed
+// problems at once, one lane per problem (Continue, then the Create chain with its recursion: LORANSAC, trials in sampler
+// order), and writes their results into the feature -> point state.
+// New points carry slot ids while the rounds run; the host numbers them in (separator, point2D, depth) order at the end.
+// No floating-point atomics: every result is the same bytes for any schedule, any order of the points3D and of the matches
+// inside a pair (as long as the duplicate rule does not fire).
+#include <hip/hip_runtime.h>
+#include <float.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <cmath>
+#include <limits>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "ctx.h"
+#include "verify_camera.h"
+#include "verify_linalg.h"
+
+namespace {
+
+constexpr int RT_BLOCK = 256;
+constexpr uint32_t kRtMaxPoints2D = 262144;   // per image: the pair's two images fit one 64 KiB LDS bitmap
+constexpr int kRtMargins = 5;                  // residual, support, angle, depth, continue
+constexpr double kRtCosineEdge = 1.0 - 8 * DBL_EPSILON;  // above: acos may be NaN by rounding alone (margin 0)
+constexpr double kRtDegToRad = 0.0174532925199432954743716805978692718032360229492187;  // DegToRad, util/math.h
+
+struct RtParams {
+  double max_residual;        // create_max_angle_error^2 (rad^2)
+  double min_tri_angle;       // rad
+  double continue_max_error;  // rad
+  int32_t ignore_two_view;
+  int32_t max_trials;         // ransac max_num_trials
+  uint32_t tab_n;             // dynamic-trial table covers n <= tab_n
+  uint32_t num_points;        // existing points: internal ids < num_points, new points num_points + slot
+};
+
+__global__ void k_rt_dedup(uint32_t n_pairs, const uint32_t* __restrict__ pair_img, const uint64_t* __restrict__ moff,
+                           const uint32_t* __restrict__ matches, const uint32_t* __restrict__ img_nfeat, uint8_t* __restrict__ acc) {
+  __shared__ uint32_t bits[16384];
+  const uint32_t k = blockIdx.x;
+  if (k >= n_pairs) return;
+  const uint32_t n1 = img_nfeat[pair_img[2 * k]], n2 = img_nfeat[pair_img[2 * k + 1]];
+  const uint32_t words = (n1 + n2 + 31) / 32;
+  for (uint32_t w = threadIdx.x; w < words; w += blockDim.x) bits[w] = 0u;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (uint64_t m = moff[k]; m < moff[k + 1]; ++m) {
+    const uint32_t a = matches[2 * m], b = n1 + matches[2 * m + 1];
+    const bool d1 = (bits[a >> 5] >> (a & 31)) & 1u, d2 = (bits[b >> 5] >> (b & 31)) & 1u;
+    if (d1 || d2) {
+      acc[m] = 0;
+    } else {
+      bits[a >> 5] |= 1u << (a & 31);
+      bits[b >> 5] |= 1u << (b & 31);
+      acc[m] = 1;
+    }
+  }
+}
+
+// the accepted matches of a pair counted per feature (integer atomics: the counts do not depend on their order)
+__global__ void k_rt_count(uint32_t n_pairs, const uint32_t* __restrict__ pair_img, const uint64_t* __restrict__ moff,
+                           const uint32_t* __restrict__ matches, const uint8_t* __restrict__ acc, const uint32_t* __restrict__ img_foff,
+                           uint32_t* __restrict__ cnt) {
+  const uint32_t k = blockIdx.x;
+  if (k >= n_pairs) return;
+  const uint32_t fa = img_foff[pair_img[2 * k]], fb = img_foff[pair_img[2 * k + 1]];
+  for (uint64_t m = moff[k] + threadIdx.x; m < moff[k + 1]; m += blockDim.x)
+    if (acc[m]) {
+      atomicAdd(&cnt[fa + matches[2 * m]], 1u);
+      atomicAdd(&cnt[fb + matches[2 * m + 1]], 1u);
+    }
+}
+
+// exclusive scan of n counts in blocks of RT_BLOCK * 4; block totals to sums (scanned by the next level)
+__global__ void k_rt_scan_block(uint32_t n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t* __restrict__ sums) {
+  __shared__ uint32_t sh[RT_BLOCK];
+  const uint32_t base = blockIdx.x * RT_BLOCK * 4 + threadIdx.x * 4;
+  uint32_t v[4], t = 0;
+  for (int i = 0; i < 4; ++i) {
+    v[i] = base + i < n ? in[base + i] : 0u;
+    t += v[i];
+  }
+  sh[threadIdx.x] = t;
+  __syncthreads();
+  for (int d = 1; d < RT_BLOCK; d *= 2) {
+    const uint32_t x = threadIdx.x >= (uint32_t)d ? sh[threadIdx.x - d] : 0u;
+    __syncthreads();
+    sh[threadIdx.x] += x;
+    __syncthreads();
+  }
+  uint32_t run = sh[threadIdx.x] - t;
+  for (int i = 0; i < 4; ++i) {
+    if (base + i < n) out[base + i] = run;
+    run += v[i];
+  }
+  if (threadIdx.x == RT_BLOCK - 1) sums[blockIdx.x] = sh[threadIdx.x];
+}
+
+__global__ void k_rt_scan_add(uint32_t n, uint32_t* __restrict__ out, const uint32_t* __restrict__ sums) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] += sums[i / (RT_BLOCK * 4)];
+}
+
+// every accepted match as two directed entries, each at a slot of its source feature's segment (arrival order)
+__global__ void k_rt_emit(uint32_t n_pairs, const uint32_t* __restrict__ pair_img, const uint64_t* __restrict__ moff,
+                          const uint32_t* __restrict__ matches, const uint8_t* __restrict__ acc, const uint32_t* __restrict__ img_foff,
+                          const uint32_t* __restrict__ goff, uint32_t* __restrict__ fill, uint32_t* __restrict__ epair,
+                          uint32_t* __restrict__ eval) {
+  const uint32_t k = blockIdx.x;
+  if (k >= n_pairs) return;
+  const uint32_t fa = img_foff[pair_img[2 * k]], fb = img_foff[pair_img[2 * k + 1]];
+  for (uint64_t m = moff[k] + threadIdx.x; m < moff[k + 1]; m += blockDim.x)
+    if (acc[m]) {
+      const uint32_t a = fa + matches[2 * m], b = fb + matches[2 * m + 1];
+      const uint32_t sa = goff[a] + atomicAdd(&fill[a], 1u), sb = goff[b] + atomicAdd(&fill[b], 1u);
+      epair[sa] = k;
+      eval[sa] = b;
+      epair[sb] = k;
+      eval[sb] = a;
+    }
+}
+
+// each feature's segment sorted by pair index (distinct inside a segment): the reference's (pair, match) append order
+__global__ void k_rt_segsort(uint32_t F, const uint32_t* __restrict__ goff, uint32_t* __restrict__ epair, uint32_t* __restrict__ eval) {
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= F) return;
+  const uint32_t lo = goff[f], hi = goff[f + 1];
+  for (uint32_t i = lo + 1; i < hi; ++i) {
+    const uint32_t kp = epair[i], kv = eval[i];
+    uint32_t j = i;
+    while (j > lo && epair[j - 1] > kp) {
+      epair[j] = epair[j - 1];
+      eval[j] = eval[j - 1];
+      --j;
+    }
+    epair[j] = kp;
+    eval[j] = kv;
+  }
+}
+
+// Camera::ImageToWorld of every feature of a usable image (registered, camera without bogus parameters)
+__global__ void k_rt_normalize(uint32_t F, const uint32_t* __restrict__ feat_img, const uint8_t* __restrict__ img_ok,
+                               const uint32_t* __restrict__ img_cam, const dsm_camera* __restrict__ cams, const double* __restrict__ xy,
+                               double* __restrict__ uv) {
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= F) return;
+  const uint32_t im = feat_img[f];
+  double u = NAN, v = NAN;
+  if (img_ok[im]) {
+    const dsm_camera cam = cams[img_cam[im]];
+    image_to_world(cam, xy[2 * f], xy[2 * f + 1], &u, &v);
+  }
+  uv[2 * f] = u;
+  uv[2 * f + 1] = v;
+}
+
+// Find (max_transitivity 1): the correspondences on usable images, counted and then written
+__global__ void k_rt_find(uint32_t Q, const uint32_t* __restrict__ ref, const uint32_t* __restrict__ goff, const uint32_t* __restrict__ gval,
+                          const uint32_t* __restrict__ feat_img, const uint8_t* __restrict__ img_ok, const uint32_t* __restrict__ moff,
+                          uint32_t* __restrict__ cnt, uint32_t* __restrict__ mem) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= Q) return;
+  const uint32_t f = ref[q];
+  uint32_t c = 0;
+  for (uint32_t e = goff[f]; e < goff[f + 1]; ++e) {
+    const uint32_t g = gval[e];
+    if (!img_ok[feat_img[g]]) continue;
+    if (mem) mem[moff[q] + c] = g;
+    ++c;
+  }
+  if (cnt) cnt[q] = c;
+}
+
+// ------------------------------------------------------------------ geometry (one lane)
+struct RtView {
+  double P[12];  // row-major 3 x 4
+  double C[3];
+  double u, v;
+};
+
+__device__ inline void rt_load(uint32_t f, const uint32_t* feat_img, const double* img_P, const double* img_C, const double* uv, RtView* w) {
+  const uint32_t im = feat_img[f];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) w->P[i] = img_P[12 * im + i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) w->C[i] = img_C[3 * im + i];
+  w->u = uv[2 * f];
+  w->v = uv[2 * f + 1];
+}
+
+__device__ inline double rt_row(const double* P, int r, const double* X) {
+  return P[4 * r] * X[0] + P[4 * r + 1] * X[1] + P[4 * r + 2] * X[2] + P[4 * r + 3];
+}
+
+// CalculateNormalizedAngularError (projection.cc:185-191), squared; *cosine = the argument of acos.  A cosine that rounds
+// above 1 gives NaN (an outlier, as in the reference) where the exact value is an inlier.
+__device__ inline double rt_residual(const RtView& w, const double* X, double* cosine = nullptr) {
+  const double r1n = sqrt((w.u * w.u + w.v * w.v) + 1.0);
+  const double a0 = rt_row(w.P, 0, X), a1 = rt_row(w.P, 1, X), a2 = rt_row(w.P, 2, X);
+  const double r2n = sqrt((a0 * a0 + a1 * a1) + a2 * a2);
+  const double d = ((w.u / r1n) * (a0 / r2n) + (w.v / r1n) * (a1 / r2n)) + (1.0 / r1n) * (a2 / r2n);
+  if (cosine) *cosine = d;
+  const double e = acos(d);
+  return e * e;
+}
+
+// HasPointPositiveDepth (projection.cc:199-203)
+__device__ inline bool rt_depth(const RtView& w, const double* X, double* margin) {
+  const double z = rt_row(w.P, 2, X);
+  const double m = fabs(z - DBL_EPSILON) / fmax(fabs(z), DBL_EPSILON);
+  if (m < *margin) *margin = m;
+  return z >= DBL_EPSILON;
+}
+
+// CalculateTriangulationAngle (triangulation.cc:122-142)
+__device__ inline double rt_tri_angle(const double* c1, const double* c2, const double* X) {
+  const double b0 = c1[0] - c2[0], b1 = c1[1] - c2[1], b2 = c1[2] - c2[2];
+  const double baseline2 = (b0 * b0 + b1 * b1) + b2 * b2;
+  const double p0 = X[0] - c1[0], p1 = X[1] - c1[1], p2 = X[2] - c1[2];
+  const double q0 = X[0] - c2[0], q1 = X[1] - c2[1], q2 = X[2] - c2[2];
+  const double ray1 = (p0 * p0 + p1 * p1) + p2 * p2, ray2 = (q0 * q0 + q1 * q1) + q2 * q2;
+  const double den = 2.0 * sqrt(ray1 * ray2);
+  if (den == 0.0) return 0.0;
+  const double angle = fabs(acos((ray1 + ray2 - baseline2) / den));
+  return fmin(angle, M_PI - angle);
+}
+
+__device__ inline bool rt_angle_ok(double angle, double min_angle, double* margin) {
+  const double m = fabs(angle - min_angle) / min_angle;
+  if (m < *margin) *margin = m;
+  return angle >= min_angle;
+}
+
+// TriangulatePoint (triangulation.cc:39-53): the reference-order 4 x 4 JacobiSVD, V's last column dehomogenised
+__device__ void rt_triangulate2(const RtView& a, const RtView& b, double* X) {
+  double A[16];
+  for (int c = 0; c < 4; ++c) {
+    A[c] = a.u * a.P[8 + c] - a.P[c];
+    A[4 + c] = a.v * a.P[8 + c] - a.P[4 + c];
+    A[8 + c] = b.u * b.P[8 + c] - b.P[c];
+    A[12 + c] = b.v * b.P[8 + c] - b.P[4 + c];
+  }
+  double V[16], sv[4];
+  pr_jacobi_svd_square_V<4>(A, V, sv);
+  X[0] = V[12] / V[15];
+  X[1] = V[13] / V[15];
+  X[2] = V[14] / V[15];
+}
+
+// the eigenvector of the smallest eigenvalue of a symmetric 4 x 4 matrix (cyclic Jacobi; SelfAdjointEigenSolver's col(0))
+__device__ void rt_sym4_min_vec(double* A, double* x) {
+  double V[16];
+  for (int i = 0; i < 16; ++i) V[i] = (i % 5 == 0) ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 32; ++sweep) {
+    double off = 0.0, diag = 0.0;
+    for (int p = 0; p < 4; ++p) {
+      diag += A[5 * p] * A[5 * p];
+      for (int q = p + 1; q < 4; ++q) off += A[4 * p + q] * A[4 * p + q];
+    }
+    if (off <= 1e-34 * diag || off == 0.0) break;
+    for (int p = 0; p < 3; ++p)
+      for (int q = p + 1; q < 4; ++q) {
+        const double apq = A[4 * p + q];
+        if (apq == 0.0) continue;
+        const double theta = (A[5 * q] - A[5 * p]) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < 4; ++k) {  // A <- A J (columns p, q)
+          const double akp = A[4 * k + p], akq = A[4 * k + q];
+          A[4 * k + p] = c * akp - s * akq;
+          A[4 * k + q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < 4; ++k) {  // A <- J^T A (rows p, q)
+          const double apk = A[4 * p + k], aqk = A[4 * q + k];
+          A[4 * p + k] = c * apk - s * aqk;
+          A[4 * q + k] = s * apk + c * aqk;
+        }
+        for (int k = 0; k < 4; ++k) {
+          const double vkp = V[4 * k + p], vkq = V[4 * k + q];
+          V[4 * k + p] = c * vkp - s * vkq;
+          V[4 * k + q] = s * vkp + c * vkq;
+        }
+      }
+  }
+  int m = 0;
+  for (int i = 1; i < 4; ++i)
+    if (A[5 * i] < A[5 * m]) m = i;
+  x[0] = V[m] / V[12 + m];
+  x[1] = V[4 + m] / V[12 + m];
+  x[2] = V[8 + m] / V[12 + m];
+}
+
+// TriangulateMultiViewPoint (triangulation.cc:72-89) accumulated one view at a time
+__device__ void rt_accumulate(const RtView& w, double* A) {
+  const double n = sqrt((w.u * w.u + w.v * w.v) + 1.0);
+  const double p[3] = {w.u / n, w.v / n, 1.0 / n};
+  double T[12];
+  for (int c = 0; c < 4; ++c) {
+    const double pP = (p[0] * w.P[c] + p[1] * w.P[4 + c]) + p[2] * w.P[8 + c];
+    for (int r = 0; r < 3; ++r) T[4 * r + c] = w.P[4 * r + c] - p[r] * pP;
+  }
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) A[4 * i + j] += (T[i] * T[j] + T[4 + i] * T[4 + j]) + T[8 + i] * T[8 + j];
+}
+
+struct RtLane {
+  const uint32_t* feat_img;
+  const double* img_P;
+  const double* img_C;
+  const double* uv;
+  const int32_t* clist;  // this problem's create list (features)
+  const int32_t* idx;    // the current level's entries (positions in clist)
+  int n;
+  RtParams prm;
+  double mg[kRtMargins];
+};
+
+__device__ inline void rt_view(const RtLane& L, int i, RtView* w) { rt_load((uint32_t)L.clist[L.idx[i]], L.feat_img, L.img_P, L.img_C, L.uv, w); }
+
+// support of X over the level's n entries: count and residual sum in entry order; residual margins recorded
+__device__ void rt_support(RtLane& L, const double* X, uint32_t* cnt, double* sum) {
+  uint32_t c = 0;
+  double s = 0.0;
+  for (int i = 0; i < L.n; ++i) {
+    RtView w;
+    rt_view(L, i, &w);
+    double d;
+    const double r = rt_residual(w, X, &d);
+    const double m = d <= kRtCosineEdge ? fabs(r - L.prm.max_residual) / L.prm.max_residual : 0.0;  // NaN or rounding to NaN
+    if (m < L.mg[0]) L.mg[0] = m;
+    if (r <= L.prm.max_residual) {
+      ++c;
+      s += r;
+    }
+  }
+  *cnt = c;
+  *sum = s;
+}
+
+__device__ inline bool rt_better(RtLane& L, uint32_t c1, double s1, uint32_t c2, double s2) {
+  if (c1 > c2) return true;
+  if (c1 == c2 && c1 > 0 && s2 != DBL_MAX) {  // a tie of two models without an inlier cannot change the outcome
+    const double m = fabs(s1 - s2) / fmax(fmax(s1, s2), DBL_MIN);
+    if (m < L.mg[1]) L.mg[1] = m;
+  }
+  return c1 == c2 && s1 < s2;
+}
+
+// TriangulationEstimator::Estimate on the multi-view set given by `sel` (positions inside the level; NULL = residual of X0
+// within max_residual), returns false when no model passes
+__device__ bool rt_estimate_multi(RtLane& L, const double* X0, double* X) {
+  double A[16];
+  for (int i = 0; i < 16; ++i) A[i] = 0.0;
+  for (int i = 0; i < L.n; ++i) {
+    RtView w;
+    rt_view(L, i, &w);
+    if (rt_residual(w, X0) <= L.prm.max_residual) rt_accumulate(w, A);
+  }
+  rt_sym4_min_vec(A, X);
+  for (int i = 0; i < L.n; ++i) {
+    RtView w;
+    rt_view(L, i, &w);
+    if (rt_residual(w, X0) <= L.prm.max_residual && !rt_depth(w, X, &L.mg[3])) return false;
+  }
+  for (int i = 0; i < L.n; ++i) {
+    RtView wi;
+    rt_view(L, i, &wi);
+    if (!(rt_residual(wi, X0) <= L.prm.max_residual)) continue;
+    for (int j = 0; j < i; ++j) {
+      RtView wj;
+      rt_view(L, j, &wj);
+      if (!(rt_residual(wj, X0) <= L.prm.max_residual)) continue;
+      if (rt_angle_ok(rt_tri_angle(wi.C, wj.C, X), L.prm.min_tri_angle, &L.mg[2])) return true;
+    }
+  }
+  return false;
+}
+
+// LORANSAC over the level's n entries; returns success and the best model
+__device__ bool rt_loransac(RtLane& L, const uint32_t* tab, const uint32_t* tab_off, double* best_X, uint32_t* trials) {
+  const int n = L.n;
+  const uint64_t all = (uint64_t)n * (n - 1) / 2;
+  const uint64_t max_trials = all < (uint64_t)L.prm.max_trials ? all : (uint64_t)L.prm.max_trials;
+  const uint64_t min_trials = n <= 15 ? all : 0;
+  uint32_t best_c = 0;
+  double best_s = DBL_MAX;
+  uint64_t dyn = max_trials;
+  bool abort = false;
+  int si = 0, sj = 1;  // CombinationSampler: lexicographic pairs (never wraps: max_trials <= C(n, 2))
+  uint64_t t = 0;
+  for (t = 0; t < max_trials; ++t) {
+    if (abort) {
+      t += 1;
+      break;
+    }
+    const int a = si, b = sj;
+    if (++sj == n) {
+      ++si;
+      sj = si + 1;
+    }
+    RtView wa, wb;
+    rt_view(L, a, &wa);
+    rt_view(L, b, &wb);
+    double X[3];
+    rt_triangulate2(wa, wb, X);
+    const bool d0 = rt_depth(wa, X, &L.mg[3]);
+    const bool ok = d0 && rt_depth(wb, X, &L.mg[3]) && rt_angle_ok(rt_tri_angle(wa.C, wb.C, X), L.prm.min_tri_angle, &L.mg[2]);
+    if (!ok) continue;
+    uint32_t c;
+    double s;
+    rt_support(L, X, &c, &s);
+    if (rt_better(L, c, s, best_c, best_s)) {
+      best_c = c;
+      best_s = s;
+      best_X[0] = X[0], best_X[1] = X[1], best_X[2] = X[2];
+      if (c > 2) {
+        double XL[3];
+        if (rt_estimate_multi(L, X, XL)) {
+          uint32_t lc;
+          double ls;
+          rt_support(L, XL, &lc, &ls);
+          if (rt_better(L, lc, ls, best_c, best_s)) {
+            best_c = lc;
+            best_s = ls;
+            best_X[0] = XL[0], best_X[1] = XL[1], best_X[2] = XL[2];
+          }
+        }
+      }
+      dyn = (n <= (int)L.prm.tab_n) ? tab[tab_off[n] + best_c] : max_trials;
+    }
+    if (t >= dyn && t >= min_trials) abort = true;
+  }
+  *trials += (uint32_t)t;
+  return best_c >= 2;
+}
+
+// Continue (incremental_triangulator.cc:545-586) for the committed problems of a round
+__global__ void k_rt_continue(uint32_t R, const uint32_t* __restrict__ run, const uint32_t* __restrict__ ref, const uint32_t* __restrict__ moff,
+                              const uint32_t* __restrict__ mem, const int32_t* __restrict__ pid, const double* __restrict__ pxyz,
+                              const double* __restrict__ nxyz, const uint32_t* __restrict__ feat_img, const double* __restrict__ img_P,
+                              const double* __restrict__ img_C, const double* __restrict__ uv, RtParams prm, int32_t* __restrict__ cont,
+                              double* __restrict__ margins) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const uint32_t q = run[r];
+  int32_t target = -1;
+  double mg = INFINITY;
+  if (pid[ref[q]] < 0) {
+    RtView w;
+    rt_load(ref[q], feat_img, img_P, img_C, uv, &w);
+    double best = DBL_MAX, second = DBL_MAX;
+    for (int pass = 0; pass < 2; ++pass)  // the choice (strict <: the first wins ties), then the best error on another point
+      for (uint32_t e = moff[q]; e < moff[q + 1]; ++e) {
+        const int32_t p = pid[mem[e]];
+        if (p < 0 || (pass == 1 && p == target)) continue;
+        const double* X = (uint32_t)p < prm.num_points ? &pxyz[3 * (size_t)p] : &nxyz[3 * (size_t)((uint32_t)p - prm.num_points)];
+        double cd;
+        const double err = sqrt(rt_residual(w, X, &cd));
+        if (!(cd <= kRtCosineEdge)) mg = 0.0;
+        if (pass == 0 && err < best) {
+          best = err;
+          target = p;
+        } else if (pass == 1 && err < second) {
+          second = err;
+        }
+      }
+    if (target >= 0) {
+      if (second != DBL_MAX && best > 0.0) mg = fmin(mg, (second - best) / best);
+      mg = fmin(mg, fabs(best - prm.continue_max_error) / prm.continue_max_error);
+      if (!(best <= prm.continue_max_error)) target = -1;
+    }
+  }
+  cont[q] = target;
+  margins[(size_t)q * kRtMargins + 4] = mg;
+}
+
+// Create (incremental_triangulator.cc:461-543) with its recursion, for the committed problems of a round.  Per problem slot
+// (moff[q] + q, members + 1 entries): clist the create list, assign the depth of the point that takes each entry (-1 none),
+// lvl scratch, nxyz the new points by depth.
+__global__ void k_rt_create(uint32_t R, const uint32_t* __restrict__ run, const uint32_t* __restrict__ ref, const uint32_t* __restrict__ moff,
+                            const uint32_t* __restrict__ mem, const int32_t* __restrict__ pid, const int32_t* __restrict__ cont,
+                            const uint32_t* __restrict__ goff, const uint32_t* __restrict__ gval, const uint32_t* __restrict__ feat_img,
+                            const double* __restrict__ img_P, const double* __restrict__ img_C, const double* __restrict__ uv,
+                            const uint32_t* __restrict__ tab, const uint32_t* __restrict__ tab_off, RtParams prm, int32_t* __restrict__ clist,
+                            int32_t* __restrict__ assign, int32_t* __restrict__ lvl, double* __restrict__ nxyz, uint32_t* __restrict__ ncreated,
+                            uint32_t* __restrict__ ncl, uint32_t* __restrict__ trials, double* __restrict__ margins) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const uint32_t q = run[r];
+  const size_t slot = (size_t)moff[q] + q;
+  int n = 0;
+  for (uint32_t e = moff[q]; e < moff[q + 1]; ++e)
+    if (pid[mem[e]] < 0) clist[slot + n++] = (int32_t)mem[e];
+  if (pid[ref[q]] < 0 && cont[q] < 0) clist[slot + n++] = (int32_t)ref[q];
+  ncl[q] = n;
+  for (int i = 0; i < n; ++i) assign[slot + i] = -1;
+  RtLane L;
+  L.feat_img = feat_img, L.img_P = img_P, L.img_C = img_C, L.uv = uv, L.clist = clist + slot, L.idx = lvl + slot, L.prm = prm;
+  for (int k = 0; k < 4; ++k) L.mg[k] = INFINITY;
+  uint32_t created = 0, tr = 0;
+  bool go = n >= 2;
+  if (go && prm.ignore_two_view && n == 2) {  // IsTwoViewObservation of the first entry
+    const uint32_t f = (uint32_t)clist[slot];
+    if (goff[f + 1] - goff[f] == 1) {
+      const uint32_t g = gval[goff[f]];
+      if (goff[g + 1] - goff[g] == 1) go = false;
+    }
+  }
+  while (go) {
+    int m = 0;
+    for (int i = 0; i < n; ++i)
+      if (assign[slot + i] < 0) lvl[slot + m++] = i;
+    L.n = m;
+    double X[3];
+    if (m < 2 || !rt_loransac(L, tab, tab_off, X, &tr)) break;
+    int len = 0;
+    for (int i = 0; i < m; ++i) {
+      RtView w;
+      rt_view(L, i, &w);
+      if (rt_residual(w, X) <= prm.max_residual) {
+        assign[slot + L.idx[i]] = (int32_t)created;
+        ++len;
+      }
+    }
+    nxyz[3 * (slot + created)] = X[0];
+    nxyz[3 * (slot + created) + 1] = X[1];
+    nxyz[3 * (slot + created) + 2] = X[2];
+    ++created;
+    go = m - len >= 3;
+  }
+  ncreated[q] = created;
+  trials[q] = tr;
+  for (int k = 0; k < 4; ++k) margins[(size_t)q * kRtMargins + k] = L.mg[k];
+}
+
+// the committed problems' writes into the feature -> point state (their feature sets are disjoint)
+__global__ void k_rt_apply(uint32_t R, const uint32_t* __restrict__ run, const uint32_t* __restrict__ ref, const uint32_t* __restrict__ moff,
+                           const int32_t* __restrict__ cont, const int32_t* __restrict__ clist, const int32_t* __restrict__ assign,
+                           const uint32_t* __restrict__ ncl, RtParams prm, int32_t* __restrict__ pid) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const uint32_t q = run[r];
+  const size_t slot = (size_t)moff[q] + q;
+  if (cont[q] >= 0) pid[ref[q]] = cont[q];
+  for (uint32_t i = 0; i < ncl[q]; ++i)
+    if (assign[slot + i] >= 0) pid[clist[slot + i]] = (int32_t)(prm.num_points + slot + (uint32_t)assign[slot + i]);
+}
+
+// CameraModelHasBogusParams (camera_models.h:473-528) with its smallest margin: the ratio tests relative to their bounds
+bool rt_bogus(const dsm_camera& c, double min_ratio, double max_ratio, double max_extra, double* margin) {
+  const int id = c.model_id;
+  const bool two = cam_two_focal(id);
+  const int pp = two ? 2 : 1, nf = two ? 2 : 1;
+  const double cx = c.params[pp], cy = c.params[pp + 1];
+  if (cx < 0 || cx > (double)c.width || cy < 0 || cy > (double)c.height) return true;
+  const double max_size = (double)std::max(c.width, c.height);
+  for (int i = 0; i < nf; ++i) {
+    const double ratio = c.params[i] / max_size;
+    *margin = std::min({*margin, std::fabs(ratio - min_ratio) / min_ratio, std::fabs(ratio - max_ratio) / max_ratio});
+    if (ratio < min_ratio || ratio > max_ratio) return true;
+  }
+  const int first_extra = (id == 0 || id == 1) ? cam_num_params(id) : (two ? 4 : 3);
+  for (int i = first_extra; i < cam_num_params(id); ++i) {
+    if (max_extra > 0) *margin = std::min(*margin, std::fabs(std::fabs(c.params[i]) - max_extra) / max_extra);
+    if (std::fabs(c.params[i]) > max_extra) return true;
+  }
+  return false;
+}
+
+// ComputeNumTrials (ransac.h:151-167) for every (n, inliers), clamped to 32 bits; ceil(-inf) (no inlier) -> never abort
+uint32_t rt_num_trials(uint32_t k, uint32_t n, double confidence) {
+  const double ratio = k / static_cast<double>(n);
+  const double nom = 1 - confidence;
+  if (nom <= 0) return UINT32_MAX;
+  const double denom = 1 - std::pow(ratio, 2);
+  if (denom <= 0) return 1;
+  const double v = std::ceil(std::log(nom) / std::log(denom));
+  if (!(v >= 0.0) || v >= 4294967295.0) return UINT32_MAX;
+  return static_cast<uint32_t>(v);
+}
+
+struct RtBufs {
+  DevBuf pair_img, moff, matches, nfeat, foff, acc, epair, val2, goff, scan_s[4], scan_x[4];
+  DevBuf cnt, feat_img, img_ok, img_cam, cams, xy, uv, img_P, img_C, pid, pxyz;
+  DevBuf ref, pmoff, mem, pcnt, run, cont, clist, assign, lvl, nxyz, ncreated, ncl, trials, margins, tab, tab_off;
+};
+
+// goff[0 .. n) = exclusive scan of d.cnt[0 .. n) in fixed blocks: level l scans the block totals of level l - 1
+hipError_t rt_scan(RtBufs& d, uint32_t n, hipStream_t st) {
+  const uint32_t B = RT_BLOCK * 4;
+  hipError_t e = d.goff.reserve((size_t)n * 4 + 16);
+  std::vector<uint32_t> lens{n};
+  while (lens.back() > B) lens.push_back((lens.back() + B - 1) / B);
+  if (lens.size() > 4) return hipErrorInvalidValue;
+  for (size_t l = 0; l < lens.size() && e == hipSuccess; ++l) {
+    e = d.scan_s[l].reserve(((size_t)(lens[l] + B - 1) / B) * 4 + 16);
+    if (e == hipSuccess) e = d.scan_x[l].reserve((size_t)lens[l] * 4 + 16);
+  }
+  if (e != hipSuccess) return e;
+  std::vector<uint32_t*> outs;
+  const uint32_t* in = d.cnt.as<uint32_t>();
+  for (size_t l = 0; l < lens.size(); ++l) {
+    uint32_t* out = l == 0 ? d.goff.as<uint32_t>() : d.scan_x[l].as<uint32_t>();
+    hipLaunchKernelGGL(k_rt_scan_block, dim3((lens[l] + B - 1) / B), dim3(RT_BLOCK), 0, st, lens[l], in, out, d.scan_s[l].as<uint32_t>());
+    outs.push_back(out);
+    in = d.scan_s[l].as<uint32_t>();
+  }
+  for (size_t l = outs.size(); l-- > 1;)
+    hipLaunchKernelGGL(k_rt_scan_add, dim3((lens[l - 1] + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, lens[l - 1], outs[l - 1], outs[l]);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" void dsm_default_triangulation_options(dsm_triangulation_options* o) {
+  o->create_max_angle_error = 2.0;    // IncrementalTriangulator::Options (incremental_triangulator.h)
+  o->continue_max_angle_error = 2.0;
+  o->min_angle = 1.5;
+  o->min_focal_length_ratio = 0.1;
+  o->max_focal_length_ratio = 10.0;
+  o->max_extra_param = 1.0;
+  o->ransac_confidence = 0.9999;      // Create(), incremental_triangulator.cc:505-508
+  o->ransac_min_inlier_ratio = 0.02;
+  o->ransac_max_num_trials = 10000;
+  o->ignore_two_view_tracks = 1;
+  o->max_transitivity = 1;
+  o->reserved = 0;
+}
+
+extern "C" int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
+                                 uint32_t num_images, const uint32_t* image_ids, const uint32_t* image_camera_ids,
+                                 const uint8_t* image_registered, const double* image_qvec, const double* image_tvec,
+                                 const uint32_t* points2D_offsets, const double* points2D_xy, const int32_t* points2D_point3D,
+                                 uint32_t num_points3D, const uint64_t* point3D_ids, const double* point3D_xyz, uint32_t num_pairs,
+                                 const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
+                                 uint32_t num_separators, const uint32_t* separator_ids, uint64_t next_point3D_id,
+                                 const dsm_triangulation_options* options, uint64_t* new_point_ids, double* new_point_xyz,
+                                 uint64_t* new_track_offsets, uint32_t* new_track_obs, uint64_t* n_new_points,
+                                 uint32_t* continued_obs, uint64_t* continued_point_ids, uint64_t* n_continued, uint32_t* touched_obs,
+                                 uint64_t* touched_point_ids, uint64_t* n_touched, uint32_t* num_tris_per_separator,
+                                 uint64_t* num_tris_out, dsm_triangulation_report* report) {
+  if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
+  auto fail = [&](const std::string& msg) {
+    ctx->err = "dsm_retriangulate: " + msg;
+    return DSM_ERR_INVALID_ARGUMENT;
+  };
+  const auto t_host0 = std::chrono::steady_clock::now();
+  if ((num_cameras && (!camera_ids || !cameras)) || (num_images && (!image_ids || !image_camera_ids || !image_registered || !image_qvec ||
+                                                                     !image_tvec)) ||
+      !points2D_offsets || (num_points3D && (!point3D_ids || !point3D_xyz)) || (num_pairs && (!pair_image_ids || !matches)) ||
+      !match_offsets || (num_separators && (!separator_ids || !num_tris_per_separator)) || !n_new_points || !n_continued || !n_touched ||
+      !num_tris_out)
+    return fail("NULL argument");
+  dsm_triangulation_options o;
+  if (options)
+    o = *options;
+  else
+    dsm_default_triangulation_options(&o);
+  if (o.max_transitivity != 1) return fail("max_transitivity other than 1 is not supported");
+  if (!(o.create_max_angle_error > 0) || !(o.continue_max_angle_error >= 0) || !(o.min_angle > 0) || !(o.min_focal_length_ratio > 0) ||
+      !(o.max_focal_length_ratio >= o.min_focal_length_ratio) || !(o.max_extra_param >= 0) || !(o.ransac_confidence > 0 && o.ransac_confidence < 1) ||
+      !(o.ransac_min_inlier_ratio >= 0 && o.ransac_min_inlier_ratio <= 1) || o.ransac_max_num_trials < 1 || !std::isfinite(o.max_focal_length_ratio) ||
+      !std::isfinite(o.create_max_angle_error) || !std::isfinite(o.continue_max_angle_error) || !std::isfinite(o.min_angle) ||
+      !std::isfinite(o.max_extra_param))
+    return fail("option out of range");
+  dsm_triangulation_report rep{};
+  rep.min_residual_margin = rep.min_support_margin = rep.min_angle_margin = rep.min_depth_margin = rep.min_continue_margin =
+      rep.min_bogus_margin = INFINITY;
+
+  // ------------------------------------------------------------ validation and the canonical image order (host)
+  std::vector<uint32_t> cam_order(num_cameras);
+  std::iota(cam_order.begin(), cam_order.end(), 0u);
+  std::sort(cam_order.begin(), cam_order.end(), [&](uint32_t a, uint32_t b) { return camera_ids[a] < camera_ids[b]; });
+  for (uint32_t i = 1; i < num_cameras; ++i)
+    if (camera_ids[cam_order[i]] == camera_ids[cam_order[i - 1]]) return fail("a repeated camera id");
+  std::vector<uint8_t> cam_bogus(num_cameras);
+  for (uint32_t c = 0; c < num_cameras; ++c) {
+    const dsm_camera& k = cameras[c];
+    if (!cam_model_exists(k.model_id)) return fail("an unknown camera model");
+    for (int i = 0; i < cam_num_params(k.model_id); ++i)
+      if (!std::isfinite(k.params[i])) return fail("non-finite camera parameters");
+    cam_bogus[c] = rt_bogus(k, o.min_focal_length_ratio, o.max_focal_length_ratio, o.max_extra_param, &rep.min_bogus_margin);
+  }
+  auto find_cam = [&](uint32_t id) -> int64_t {
+    auto it = std::lower_bound(cam_order.begin(), cam_order.end(), id, [&](uint32_t a, uint32_t v) { return camera_ids[a] < v; });
+    return (it != cam_order.end() && camera_ids[*it] == id) ? (int64_t)*it : -1;
+  };
+  if (points2D_offsets[0] != 0) return fail("points2D offsets must start at 0");
+  std::vector<uint32_t> order(num_images);  // canonical index -> input index
+  std::iota(order.begin(), order.end(), 0u);
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return image_ids[a] < image_ids[b]; });
+  for (uint32_t i = 1; i < num_images; ++i)
+    if (image_ids[order[i]] == image_ids[order[i - 1]]) return fail("a repeated image id");
+  std::vector<uint32_t> canon(num_images);  // input index -> canonical index
+  for (uint32_t i = 0; i < num_images; ++i) canon[order[i]] = i;
+  std::vector<uint32_t> nfeat(num_images), foff(num_images + 1, 0), img_cam(num_images);
+  std::vector<uint8_t> img_ok(num_images);
+  std::vector<double> img_P(12 * (size_t)num_images), img_C(3 * (size_t)num_images);
+  for (uint32_t i = 0; i < num_images; ++i) {
+    if (points2D_offsets[i + 1] < points2D_offsets[i]) return fail("points2D offsets must be non-decreasing");
+    if (points2D_offsets[i + 1] - points2D_offsets[i] > kRtMaxPoints2D) return fail("more than 262144 points2D in one image");
+  }
+  const uint64_t F = points2D_offsets[num_images];
+  if (F >= 0x40000000u) return fail("too many points2D");
+  if (F && (!points2D_xy || !points2D_point3D)) return fail("NULL argument");
+  for (uint32_t c = 0; c < num_images; ++c) {
+    const uint32_t i = order[c];
+    nfeat[c] = points2D_offsets[i + 1] - points2D_offsets[i];
+    foff[c + 1] = foff[c] + nfeat[c];
+    const int64_t cam = find_cam(image_camera_ids[i]);
+    if (cam < 0) return fail("an image on an unknown camera id");
+    img_cam[c] = (uint32_t)cam;
+    img_ok[c] = image_registered[i] && !cam_bogus[cam];
+    const double* qv = image_qvec + 4 * (size_t)i;
+    const double* tv = image_tvec + 3 * (size_t)i;
+    for (int k = 0; k < 4; ++k)
+      if (!std::isfinite(qv[k])) return fail("non-finite qvec");
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(tv[k])) return fail("non-finite tvec");
+    // NormalizeQuaternion + Eigen's toRotationMatrix (pose.cc:75-91), ProjectionCenterFromPose as -R^T t
+    const double nq = std::sqrt(((qv[0] * qv[0] + qv[1] * qv[1]) + qv[2] * qv[2]) + qv[3] * qv[3]);
+    if (nq == 0) return fail("a zero qvec");
+    const double w = qv[0] / nq, x = qv[1] / nq, y = qv[2] / nq, z = qv[3] / nq;
+    const double tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x,
+                 tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    const double Rm[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
+    double* P = &img_P[12 * (size_t)c];
+    for (int r = 0; r < 3; ++r) {
+      for (int k = 0; k < 3; ++k) P[4 * r + k] = Rm[3 * r + k];
+      P[4 * r + 3] = tv[r];
+    }
+    for (int k = 0; k < 3; ++k) img_C[3 * (size_t)c + k] = -((Rm[k] * tv[0] + Rm[3 + k] * tv[1]) + Rm[6 + k] * tv[2]);
+  }
+  // points3D: internal index = input index; ids unique
+  std::vector<uint64_t> sorted_ids(point3D_ids, point3D_ids + num_points3D);
+  std::sort(sorted_ids.begin(), sorted_ids.end());
+  for (uint32_t i = 1; i < num_points3D; ++i)
+    if (sorted_ids[i] == sorted_ids[i - 1]) return fail("a repeated point3D id");
+  for (size_t i = 0; i < 3 * (size_t)num_points3D; ++i)
+    if (!std::isfinite(point3D_xyz[i])) return fail("non-finite point3D xyz");
+  const uint64_t max_id = num_points3D ? sorted_ids.back() : 0;
+  uint64_t next_id = next_point3D_id ? next_point3D_id : max_id + 1;
+  if (num_points3D && next_id <= max_id) return fail("next_point3D_id at or below an existing id");
+  if (num_points3D >= 0x40000000u) return fail("too many points3D");
+  std::vector<double> xy(2 * F);
+  std::vector<int32_t> pid0(F);
+  std::vector<uint32_t> feat_img(F);
+  for (uint32_t c = 0; c < num_images; ++c) {
+    const uint32_t i = order[c];
+    for (uint32_t k = 0; k < nfeat[c]; ++k) {
+      const size_t s = (size_t)points2D_offsets[i] + k, d = (size_t)foff[c] + k;
+      xy[2 * d] = points2D_xy[2 * s];
+      xy[2 * d + 1] = points2D_xy[2 * s + 1];
+      if (!std::isfinite(xy[2 * d]) || !std::isfinite(xy[2 * d + 1])) return fail("non-finite points2D xy");
+      const int32_t p = points2D_point3D[s];
+      if (p < -1 || p >= (int64_t)num_points3D) return fail("a point3D index out of range");
+      pid0[d] = p;
+      feat_img[d] = c;
+    }
+  }
+  auto find_img = [&](uint32_t id) -> int64_t {
+    auto it = std::lower_bound(order.begin(), order.end(), id, [&](uint32_t a, uint32_t v) { return image_ids[a] < v; });
+    return (it != order.end() && image_ids[*it] == id) ? (int64_t)(it - order.begin()) : -1;
+  };
+  if (match_offsets[0] != 0) return fail("match offsets must start at 0");
+  std::vector<uint32_t> pair_img(2 * (size_t)num_pairs);
+  std::vector<uint64_t> pair_keys(num_pairs);
+  for (uint32_t k = 0; k < num_pairs; ++k) {
+    if (match_offsets[k + 1] < match_offsets[k]) return fail("match offsets must be non-decreasing");
+    const int64_t a = find_img(pair_image_ids[2 * k]), b = find_img(pair_image_ids[2 * k + 1]);
+    if (a < 0 || b < 0) return fail("a pair on an unknown image id");
+    if (a == b) return fail("a self-pair");
+    pair_img[2 * k] = (uint32_t)a;
+    pair_img[2 * k + 1] = (uint32_t)b;
+    pair_keys[k] = ((uint64_t)std::min(a, b) << 32) | (uint64_t)std::max(a, b);
+    for (uint64_t m = match_offsets[k]; m < match_offsets[k + 1]; ++m)
+      if (matches[2 * m] >= nfeat[a] || matches[2 * m + 1] >= nfeat[b]) return fail("a match index out of range");
+  }
+  std::sort(pair_keys.begin(), pair_keys.end());
+  for (uint32_t k = 1; k < num_pairs; ++k)
+    if (pair_keys[k] == pair_keys[k - 1]) return fail("a repeated pair");
+  const uint64_t NM = match_offsets[num_pairs];
+  if (NM >= 0x20000000u) return fail("too many matches");
+  std::vector<uint32_t> sep(num_separators);
+  for (uint32_t s = 0; s < num_separators; ++s) {
+    const int64_t c = find_img(separator_ids[s]);
+    if (c < 0) return fail("a separator on an unknown image id");
+    sep[s] = (uint32_t)c;
+  }
+  std::vector<uint32_t> sep_order(num_separators);  // ascending image id = ascending canonical index
+  std::iota(sep_order.begin(), sep_order.end(), 0u);
+  std::sort(sep_order.begin(), sep_order.end(), [&](uint32_t a, uint32_t b) { return sep[a] < sep[b]; });
+  for (uint32_t s = 1; s < num_separators; ++s)
+    if (sep[sep_order[s]] == sep[sep_order[s - 1]]) return fail("a repeated separator id");
+
+  // candidates: (separator ascending, point2D) of the usable separators
+  std::vector<uint32_t> cand, cand_sep;
+  for (uint32_t s : sep_order) {
+    const uint32_t c = sep[s];
+    if (!img_ok[c]) continue;
+    ++rep.num_separators;
+    for (uint32_t k = 0; k < nfeat[c]; ++k) {
+      cand.push_back(foff[c] + k);
+      cand_sep.push_back(s);
+    }
+  }
+  const double setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
+
+  hipError_t he = hipSetDevice(ctx->device);
+  if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
+  hipStream_t st = ctx->stream;
+  RtBufs d;
+  DevEvent ev[5];
+  for (int i = 0; i < 5; ++i) HIPCHK(ctx, hipEventCreate(&ev[i].e));
+  HIPCHK(ctx, hipEventRecord(ev[0], st));
+  const size_t F1 = std::max<uint64_t>(F, 1);
+  auto up = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
+    hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
+    if (e == hipSuccess && bytes) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
+    return e;
+  };
+
+  // ------------------------------------------------------------ the correspondence graph (device)
+  HIPCHK(ctx, up(d.nfeat, nfeat.data(), nfeat.size() * 4));
+  HIPCHK(ctx, up(d.foff, foff.data(), foff.size() * 4));
+  HIPCHK(ctx, d.goff.reserve((F1 + 1) * 4));
+  uint32_t E = 0;
+  HIPCHK(ctx, d.cnt.reserve((F1 + 1) * 4));
+  HIPCHK(ctx, hipMemsetAsync(d.cnt.p, 0, (F1 + 1) * 4, st));
+  if (NM) {
+    HIPCHK(ctx, up(d.pair_img, pair_img.data(), pair_img.size() * 4));
+    HIPCHK(ctx, up(d.moff, match_offsets, ((size_t)num_pairs + 1) * 8));
+    HIPCHK(ctx, up(d.matches, matches, NM * 8));
+    HIPCHK(ctx, d.acc.reserve(NM));
+    hipLaunchKernelGGL(k_rt_dedup, dim3(num_pairs), dim3(RT_BLOCK), 0, st, num_pairs, d.pair_img.as<uint32_t>(), d.moff.as<uint64_t>(),
+                       d.matches.as<uint32_t>(), d.nfeat.as<uint32_t>(), d.acc.as<uint8_t>());
+    hipLaunchKernelGGL(k_rt_count, dim3(num_pairs), dim3(RT_BLOCK), 0, st, num_pairs, d.pair_img.as<uint32_t>(), d.moff.as<uint64_t>(),
+                       d.matches.as<uint32_t>(), d.acc.as<uint8_t>(), d.foff.as<uint32_t>(), d.cnt.as<uint32_t>());
+    HIPCHK(ctx, hipGetLastError());
+  }
+  HIPCHK(ctx, rt_scan(d, (uint32_t)F + 1, st));  // goff = exclusive scan of the counts (F + 1 entries: the last is E)
+  HIPCHK(ctx, hipMemcpyAsync(&E, d.goff.as<uint32_t>() + F, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  for (DevBuf* b : {&d.epair, &d.val2}) HIPCHK(ctx, b->reserve(std::max<size_t>((size_t)E * 4, 16)));
+  if (E) {
+    HIPCHK(ctx, hipMemsetAsync(d.cnt.p, 0, F1 * 4, st));  // reused as the fill counters
+    hipLaunchKernelGGL(k_rt_emit, dim3(num_pairs), dim3(RT_BLOCK), 0, st, num_pairs, d.pair_img.as<uint32_t>(), d.moff.as<uint64_t>(),
+                       d.matches.as<uint32_t>(), d.acc.as<uint8_t>(), d.foff.as<uint32_t>(), d.goff.as<uint32_t>(), d.cnt.as<uint32_t>(),
+                       d.epair.as<uint32_t>(), d.val2.as<uint32_t>());
+    hipLaunchKernelGGL(k_rt_segsort, dim3((uint32_t)((F + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, st, (uint32_t)F, d.goff.as<uint32_t>(),
+                       d.epair.as<uint32_t>(), d.val2.as<uint32_t>());
+    HIPCHK(ctx, hipGetLastError());
+  }
+  rep.num_correspondences = E;
+  HIPCHK(ctx, hipEventRecord(ev[1], st));
+
+  // ------------------------------------------------------------ the problems: Find on the device, non-empty ones kept
+  std::vector<dsm_camera> cams(cameras, cameras + num_cameras);
+  HIPCHK(ctx, up(d.feat_img, feat_img.data(), F * 4));
+  HIPCHK(ctx, up(d.img_ok, img_ok.data(), num_images));
+  HIPCHK(ctx, up(d.img_cam, img_cam.data(), num_images * 4));
+  HIPCHK(ctx, up(d.cams, cams.data(), cams.size() * sizeof(dsm_camera)));
+  HIPCHK(ctx, up(d.xy, xy.data(), F * 16));
+  HIPCHK(ctx, d.uv.reserve(F1 * 16));
+  HIPCHK(ctx, up(d.img_P, img_P.data(), img_P.size() * 8));
+  HIPCHK(ctx, up(d.img_C, img_C.data(), img_C.size() * 8));
+  HIPCHK(ctx, up(d.pid, pid0.data(), F * 4));
+  HIPCHK(ctx, up(d.pxyz, point3D_xyz, (size_t)num_points3D * 24));
+  if (F)
+    hipLaunchKernelGGL(k_rt_normalize, dim3((uint32_t)((F + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, st, (uint32_t)F, d.feat_img.as<uint32_t>(),
+                       d.img_ok.as<uint8_t>(), d.img_cam.as<uint32_t>(), d.cams.as<dsm_camera>(), d.xy.as<double>(), d.uv.as<double>());
+  const uint32_t Q0 = (uint32_t)cand.size();
+  std::vector<uint32_t> cnt(Q0);
+  if (Q0) {
+    HIPCHK(ctx, up(d.ref, cand.data(), (size_t)Q0 * 4));
+    HIPCHK(ctx, d.pcnt.reserve((size_t)Q0 * 4));
+    hipLaunchKernelGGL(k_rt_find, dim3((Q0 + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, Q0, d.ref.as<uint32_t>(), d.goff.as<uint32_t>(),
+                       d.val2.as<uint32_t>(), d.feat_img.as<uint32_t>(), d.img_ok.as<uint8_t>(), (const uint32_t*)nullptr, d.pcnt.as<uint32_t>(),
+                       (uint32_t*)nullptr);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(cnt.data(), d.pcnt.p, (size_t)Q0 * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+  }
+  std::vector<uint32_t> pref, psep, pmoff(1, 0);
+  for (uint32_t q = 0; q < Q0; ++q)
+    if (cnt[q]) {
+      pref.push_back(cand[q]);
+      psep.push_back(cand_sep[q]);
+      pmoff.push_back(pmoff.back() + cnt[q]);
+    }
+  const uint32_t Q = (uint32_t)pref.size();
+  const uint64_t M = pmoff.back();
+  const uint64_t S = M + Q;  // problem slots: members + 1 each
+  if (S >= 0x40000000u) return fail("too many correspondences in the separator images");
+  rep.num_problems = Q;
+  std::vector<uint32_t> mem(M);
+  uint32_t maxn = 2;
+  for (uint32_t q = 0; q < Q; ++q) maxn = std::max(maxn, pmoff[q + 1] - pmoff[q] + 1);
+  if (Q) {
+    HIPCHK(ctx, up(d.ref, pref.data(), (size_t)Q * 4));
+    HIPCHK(ctx, up(d.pmoff, pmoff.data(), ((size_t)Q + 1) * 4));
+    HIPCHK(ctx, d.mem.reserve(std::max<size_t>(M * 4, 16)));
+    hipLaunchKernelGGL(k_rt_find, dim3((Q + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, Q, d.ref.as<uint32_t>(), d.goff.as<uint32_t>(),
+                       d.val2.as<uint32_t>(), d.feat_img.as<uint32_t>(), d.img_ok.as<uint8_t>(), d.pmoff.as<uint32_t>(), (uint32_t*)nullptr,
+                       d.mem.as<uint32_t>());
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(mem.data(), d.mem.p, M * 4, hipMemcpyDeviceToHost, st));
+  }
+  // ComputeNumTrials for n <= maxn (the host's libm)
+  std::vector<uint32_t> tab_off(maxn + 1, 0), tab;
+  for (uint32_t n = 2; n <= maxn; ++n) {
+    tab_off[n] = (uint32_t)tab.size();
+    for (uint32_t k = 0; k <= n; ++k) tab.push_back(rt_num_trials(k, n, o.ransac_confidence));
+  }
+  HIPCHK(ctx, up(d.tab, tab.data(), tab.size() * 4));
+  HIPCHK(ctx, up(d.tab_off, tab_off.data(), tab_off.size() * 4));
+  const size_t Q1 = std::max<uint32_t>(Q, 1), S1 = std::max<uint64_t>(S, 1);
+  for (DevBuf* b : {&d.cont, &d.ncreated, &d.ncl, &d.trials, &d.run}) HIPCHK(ctx, b->reserve(Q1 * 4));
+  HIPCHK(ctx, d.margins.reserve(Q1 * kRtMargins * 8));
+  for (DevBuf* b : {&d.clist, &d.assign, &d.lvl}) HIPCHK(ctx, b->reserve(S1 * 4));
+  HIPCHK(ctx, d.nxyz.reserve(S1 * 24));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+
+  // ------------------------------------------------------------ the rounds (schedule on the host, solves on the device)
+  // A problem is pending in round r while an earlier problem that shares a feature with it is pending in round r, so its
+  // round is 1 + the largest round of those problems: one pass in problem order with the largest round seen per feature.
+  const auto t_rep0 = std::chrono::steady_clock::now();
+  std::vector<uint32_t> last(F1, 0), qround(Q);
+  uint32_t nrounds = 0;
+  for (uint32_t q = 0; q < Q; ++q) {
+    uint32_t r = last[pref[q]];
+    for (uint32_t e = pmoff[q]; e < pmoff[q + 1]; ++e) r = std::max(r, last[mem[e]]);
+    ++r;
+    qround[q] = r;
+    last[pref[q]] = r;
+    for (uint32_t e = pmoff[q]; e < pmoff[q + 1]; ++e) last[mem[e]] = r;
+    nrounds = std::max(nrounds, r);
+    rep.num_deferred += r - 1;
+  }
+  std::vector<uint32_t> roff(nrounds + 2, 0), run(Q);  // problems by (round, problem order): a counting sort
+  for (uint32_t q = 0; q < Q; ++q) ++roff[qround[q] + 1];
+  for (uint32_t r = 1; r <= nrounds + 1; ++r) roff[r] += roff[r - 1];
+  {
+    std::vector<uint32_t> fillp(roff.begin(), roff.end() - 1);
+    for (uint32_t q = 0; q < Q; ++q) run[fillp[qround[q]]++] = q;
+  }
+  rep.num_rounds = nrounds;
+  rep.schedule_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_rep0).count();
+  RtParams prm;
+  prm.max_residual = (o.create_max_angle_error * kRtDegToRad) * (o.create_max_angle_error * kRtDegToRad);
+  prm.min_tri_angle = o.min_angle * kRtDegToRad;
+  prm.continue_max_error = o.continue_max_angle_error * kRtDegToRad;
+  prm.ignore_two_view = o.ignore_two_view_tracks ? 1 : 0;
+  prm.max_trials = o.ransac_max_num_trials;
+  prm.tab_n = maxn;
+  prm.num_points = num_points3D;
+  HIPCHK(ctx, hipEventRecord(ev[2], st));
+  if (Q) HIPCHK(ctx, hipMemcpyAsync(d.run.p, run.data(), (size_t)Q * 4, hipMemcpyHostToDevice, st));
+  std::vector<DevEvent> rev(4 * (size_t)nrounds);  // per round: before Continue, Create, apply, after apply
+  for (auto& e : rev) HIPCHK(ctx, hipEventCreate(&e.e));
+  const double* nx = d.nxyz.as<double>();
+  for (uint32_t r = 1; r <= nrounds; ++r) {  // every round enqueued back to back: the schedule needs no result
+    const uint32_t R = roff[r + 1] - roff[r];
+    const uint32_t* rl = d.run.as<uint32_t>() + roff[r];
+    const dim3 g((R + RT_BLOCK - 1) / RT_BLOCK);
+    DevEvent* re = &rev[4 * (size_t)(r - 1)];
+    HIPCHK(ctx, hipEventRecord(re[0], st));
+    hipLaunchKernelGGL(k_rt_continue, g, dim3(RT_BLOCK), 0, st, R, rl, d.ref.as<uint32_t>(), d.pmoff.as<uint32_t>(),
+                       d.mem.as<uint32_t>(), d.pid.as<int32_t>(), d.pxyz.as<double>(), nx, d.feat_img.as<uint32_t>(), d.img_P.as<double>(),
+                       d.img_C.as<double>(), d.uv.as<double>(), prm, d.cont.as<int32_t>(), d.margins.as<double>());
+    HIPCHK(ctx, hipEventRecord(re[1], st));
+    hipLaunchKernelGGL(k_rt_create, g, dim3(RT_BLOCK), 0, st, R, rl, d.ref.as<uint32_t>(), d.pmoff.as<uint32_t>(),
+                       d.mem.as<uint32_t>(), d.pid.as<int32_t>(), d.cont.as<int32_t>(), d.goff.as<uint32_t>(), d.val2.as<uint32_t>(),
+                       d.feat_img.as<uint32_t>(), d.img_P.as<double>(), d.img_C.as<double>(), d.uv.as<double>(), d.tab.as<uint32_t>(),
+                       d.tab_off.as<uint32_t>(), prm, d.clist.as<int32_t>(), d.assign.as<int32_t>(), d.lvl.as<int32_t>(), d.nxyz.as<double>(),
+                       d.ncreated.as<uint32_t>(), d.ncl.as<uint32_t>(), d.trials.as<uint32_t>(), d.margins.as<double>());
+    HIPCHK(ctx, hipEventRecord(re[2], st));
+    hipLaunchKernelGGL(k_rt_apply, g, dim3(RT_BLOCK), 0, st, R, rl, d.ref.as<uint32_t>(), d.pmoff.as<uint32_t>(),
+                       d.cont.as<int32_t>(), d.clist.as<int32_t>(), d.assign.as<int32_t>(), d.ncl.as<uint32_t>(), prm, d.pid.as<int32_t>());
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(re[3], st));
+  }
+  HIPCHK(ctx, hipEventRecord(ev[3], st));
+
+  // ------------------------------------------------------------ results back, new ids in (separator, point2D, depth) order
+  std::vector<int32_t> cont(Q), clist(S), assign(S);
+  std::vector<uint32_t> ncreated(Q), ncl(Q), trials(Q);
+  std::vector<double> nxyz(3 * S), margins((size_t)Q * kRtMargins);
+  if (Q) {
+    HIPCHK(ctx, hipMemcpyAsync(cont.data(), d.cont.p, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ncreated.data(), d.ncreated.p, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ncl.data(), d.ncl.p, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(trials.data(), d.trials.p, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(margins.data(), d.margins.p, margins.size() * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(clist.data(), d.clist.p, S * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(assign.data(), d.assign.p, S * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(nxyz.data(), d.nxyz.p, S * 24, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(ctx, hipEventRecord(ev[4], st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  const auto t_out0 = std::chrono::steady_clock::now();
+  std::vector<uint64_t> slot_id(S, 0);  // slot -> final id of the point created there
+  uint64_t nnew = 0, nobs = 0;
+  for (uint32_t q = 0; q < Q; ++q) {
+    const size_t slot = (size_t)pmoff[q] + q;
+    for (uint32_t k = 0; k < ncreated[q]; ++k) slot_id[slot + k] = next_id + nnew++;
+  }
+  auto final_id = [&](int32_t p) -> uint64_t {
+    return (uint32_t)p < num_points3D ? point3D_ids[p] : slot_id[(uint32_t)p - num_points3D];
+  };
+  std::vector<uint64_t> touched_id(F, UINT64_MAX);
+  std::vector<uint64_t> sep_tris(num_separators, 0);
+  uint64_t ncont = 0, pnew = 0, tris = 0;
+  if (new_track_offsets) new_track_offsets[0] = 0;
+  for (uint32_t q = 0; q < Q; ++q) {
+    const size_t slot = (size_t)pmoff[q] + q;
+    uint64_t t = 0;
+    if (cont[q] >= 0) {
+      const uint64_t id = final_id(cont[q]);
+      const uint32_t f = pref[q], c = feat_img[f];
+      if (continued_obs) {
+        continued_obs[2 * ncont] = image_ids[order[c]];
+        continued_obs[2 * ncont + 1] = f - foff[c];
+      }
+      if (continued_point_ids) continued_point_ids[ncont] = id;
+      ++ncont;
+      touched_id[f] = id;
+      ++t;
+    }
+    for (uint32_t k = 0; k < ncreated[q]; ++k) {
+      const uint64_t id = slot_id[slot + k];
+      if (new_point_ids) new_point_ids[pnew] = id;
+      if (new_point_xyz)
+        for (int j = 0; j < 3; ++j) new_point_xyz[3 * pnew + j] = nxyz[3 * (slot + k) + j];
+      for (uint32_t i = 0; i < ncl[q]; ++i)
+        if (assign[slot + i] == (int32_t)k) {
+          const uint32_t f = (uint32_t)clist[slot + i], c = feat_img[f];
+          if (new_track_obs) {
+            new_track_obs[2 * nobs] = image_ids[order[c]];
+            new_track_obs[2 * nobs + 1] = f - foff[c];
+          }
+          ++nobs;
+          ++t;
+          touched_id[f] = id;
+        }
+      ++pnew;
+      if (new_track_offsets) new_track_offsets[pnew] = nobs;
+    }
+    sep_tris[psep[q]] += t;
+    tris += t;
+    rep.ransac_trials += trials[q];
+    const double* mg = &margins[(size_t)q * kRtMargins];
+    rep.min_residual_margin = std::min(rep.min_residual_margin, mg[0]);
+    rep.min_support_margin = std::min(rep.min_support_margin, mg[1]);
+    rep.min_angle_margin = std::min(rep.min_angle_margin, mg[2]);
+    rep.min_depth_margin = std::min(rep.min_depth_margin, mg[3]);
+    rep.min_continue_margin = std::min(rep.min_continue_margin, mg[4]);
+  }
+  uint64_t nt = 0;
+  for (uint64_t f = 0; f < F; ++f)
+    if (touched_id[f] != UINT64_MAX) {
+      const uint32_t c = feat_img[f];
+      if (touched_obs) {
+        touched_obs[2 * nt] = image_ids[order[c]];
+        touched_obs[2 * nt + 1] = (uint32_t)(f - foff[c]);
+      }
+      if (touched_point_ids) touched_point_ids[nt] = touched_id[f];
+      ++nt;
+    }
+  for (uint32_t s = 0; s < num_separators; ++s) num_tris_per_separator[s] = (uint32_t)sep_tris[s];
+  *n_new_points = pnew;
+  *n_continued = ncont;
+  *n_touched = nt;
+  *num_tris_out = tris;
+  rep.num_tris = tris;
+  rep.num_new_points = pnew;
+  rep.num_new_observations = nobs;
+  rep.num_continued = ncont;
+  float g_ms = 0, solve_ms = 0, dl_ms = 0, tot_ms = 0;
+  HIPCHK(ctx, hipEventElapsedTime(&g_ms, ev[0], ev[1]));
+  HIPCHK(ctx, hipEventElapsedTime(&solve_ms, ev[2], ev[3]));
+  HIPCHK(ctx, hipEventElapsedTime(&dl_ms, ev[3], ev[4]));
+  HIPCHK(ctx, hipEventElapsedTime(&tot_ms, ev[0], ev[4]));
+  double cont_ms = 0, create_ms = 0, apply_ms = 0;
+  for (uint32_t r = 0; r < nrounds; ++r) {
+    float a = 0, b = 0, c = 0;
+    HIPCHK(ctx, hipEventElapsedTime(&a, rev[4 * r], rev[4 * r + 1]));
+    HIPCHK(ctx, hipEventElapsedTime(&b, rev[4 * r + 1], rev[4 * r + 2]));
+    HIPCHK(ctx, hipEventElapsedTime(&c, rev[4 * r + 2], rev[4 * r + 3]));
+    cont_ms += a;
+    create_ms += b;
+    apply_ms += c;
+  }
+  rep.setup_ms = setup_ms;
+  rep.graph_ms = g_ms;
+  rep.continue_ms = cont_ms;
+  rep.ransac_ms = create_ms;
+  rep.apply_ms = apply_ms;
+  rep.round_gap_ms = std::max(0.0, (double)solve_ms - cont_ms - create_ms - apply_ms);
+  rep.download_ms = dl_ms;
+  rep.assemble_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_out0).count();
+  rep.replay_ms = rep.schedule_ms + rep.apply_ms + rep.round_gap_ms + rep.assemble_ms;
+  rep.device_ms = tot_ms;
+  if (report) *report = rep;
+  return DSM_OK;
+}

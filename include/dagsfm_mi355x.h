@@ -728,6 +728,97 @@ int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32_t* camera_
                       const uint32_t* obs_image, const double* obs_xy, const dsm_bundle_adjustment_options* options,
                       dsm_bundle_adjustment_report* report, double* trace);
 
+/* ------------------------------------------------------------------ re-triangulation of the separators
+ * Step 7 of DistributedMapperController::Run(), Triangulate() (src/controllers/distributed_mapper_controller.cpp:823-834):
+ * IncrementalTriangulator::TriangulateImage (src/sfm/incremental_triangulator.cc:61-117) for every separator image of the
+ * merged reconstruction, with Find (max_transitivity 1), Continue and Create (LORANSAC, CombinationSampler, ANGULAR_ERROR
+ * residuals; recursion on the unused correspondences) as the reference runs them.  The correspondence graph is built from
+ * the verified pairs as CorrespondenceGraph::AddCorrespondences does (one call per pair in input order; a match whose feature
+ * already holds a correspondence to the other image is dropped).
+ *   Rulings: separators run in ascending image id (the reference: an unordered_set); new point ids are the ids
+ *   the sequential run hands out from next_point3D_id, in (separator, point2D, recursion depth) order, however the device
+ *   schedules the problems; Continue's angular error uses the projection matrix like Create's residual (the reference
+ *   rotates by the quaternion; the same value up to rounding); self-pairs, repeated pairs (either order), repeated ids and
+ *   out-of-range indices are refused instead of dropped. */
+typedef struct dsm_triangulation_options {
+  double create_max_angle_error;   /* 2.0 degrees */
+  double continue_max_angle_error; /* 2.0 degrees */
+  double min_angle;                /* 1.5 degrees */
+  double min_focal_length_ratio;   /* 0.1  (HasBogusParams) */
+  double max_focal_length_ratio;   /* 10.0 */
+  double max_extra_param;          /* 1.0 */
+  double ransac_confidence;        /* 0.9999 */
+  double ransac_min_inlier_ratio;  /* 0.02 (LORANSAC does not read it; kept for the record) */
+  int32_t ransac_max_num_trials;   /* 10000 */
+  int32_t ignore_two_view_tracks;  /* 1 */
+  int32_t max_transitivity;        /* 1; any other value is DSM_ERR_INVALID_ARGUMENT */
+  int32_t reserved;
+} dsm_triangulation_options;
+
+typedef struct dsm_triangulation_report {
+  uint32_t num_separators;        /* separators processed: registered, camera without bogus parameters */
+  uint32_t num_rounds;            /* commit rounds of the schedule */
+  uint64_t num_problems;          /* (separator, point2D) with a non-empty filtered correspondence list */
+  uint64_t num_deferred;          /* problems deferred, summed over the rounds */
+  uint64_t num_correspondences;   /* directed entries of the correspondence graph */
+  uint64_t ransac_trials;         /* LORANSAC trials, summed over every Create level */
+  uint64_t num_tris;              /* observations added: Continue's plus the new tracks' */
+  uint64_t num_new_points;
+  uint64_t num_new_observations;
+  uint64_t num_continued;
+  /* the smallest relative margin of every decision a rounding difference could flip (INFINITY when never taken):
+     |residual - max_error^2| / max_error^2, equal-count support sums |s1 - s2| / max, |angle - min_angle| / min_angle,
+     cheirality |depth - eps| / max(|depth|, eps), Continue's best against the second best and against the threshold,
+     the bogus-parameter ratios against their bounds; 0 for a residual whose cosine is at or above 1 - 8 eps (acos NaN, or
+     NaN by rounding: the reference counts NaN as an outlier) */
+  double min_residual_margin, min_support_margin, min_angle_margin, min_depth_margin, min_continue_margin, min_bogus_margin;
+  double setup_ms;                /* host validation and canonical order (host clock) */
+  double graph_ms;                /* HIP events: uploads, duplicate rule, sort, offsets */
+  double continue_ms, ransac_ms;  /* HIP events, summed over the rounds */
+  double schedule_ms;             /* the round schedule: one pass over the problems' feature sets (host clock) */
+  double apply_ms;                /* HIP events: the state updates of every round */
+  double round_gap_ms;            /* device time of the rounds outside their kernels (launch gaps) */
+  double download_ms;             /* HIP events: the results back to the host */
+  double assemble_ms;             /* ids, tracks and lists from the results (host clock) */
+  double replay_ms;               /* schedule_ms + apply_ms + round_gap_ms + assemble_ms */
+  double device_ms;               /* HIP events: first upload to the last download */
+} dsm_triangulation_report;
+
+void dsm_default_triangulation_options(dsm_triangulation_options* o);
+
+/* TriangulateImage over the separators (host pointers).  T = points2D_offsets[num_images] below.
+ *   cameras: camera_ids[num_cameras] (unique), cameras (the eleven models; width and height feed the bogus test)
+ *   images: image_ids[num_images] (unique), image_camera_ids, image_registered (0 / 1), image_qvec (4 each, w x y z),
+ *     image_tvec (3 each), points2D_offsets[num_images + 1] (CSR over the images in input order, <= 262144 per image),
+ *     points2D_xy (2 per point2D), points2D_point3D (an index into the points3D or -1)
+ *   points3D: point3D_ids (unique), point3D_xyz (3 each)
+ *   pairs: pair_image_ids (2 per pair), match_offsets[num_pairs + 1] (uint64), matches (idx1, idx2 per match), in load order
+ *   separators: separator_ids (unique image ids, any order; as dsm_align_clusters returns them)
+ *   next_point3D_id: the first new id; 0 = the largest existing id + 1; at or below an existing id: invalid
+ * Outputs, each with room for T entries (pairs of uint32 for an observation, 3 doubles for an xyz):
+ *   new points in id order: new_point_ids, new_point_xyz, new_track_offsets[n + 1], new_track_obs (image_id, point2D_idx; the
+ *     track in the order of Create's correspondence list, the reference observation last); *n_new_points
+ *   continued_obs (image_id, point2D_idx) with continued_point_ids, in the sequential order; *n_continued
+ *   touched_obs (image_id, point2D_idx) ascending with touched_point_ids: every point2D that received a point; *n_touched
+ *   num_tris_per_separator[num_separators] (input order; 0 for an unregistered or bogus separator), *num_tris_out
+ * Output arrays other than the counts may be NULL.  report may be NULL.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT): a self-pair, a repeated pair, a repeated id, an unknown image / camera id, an index out
+ *   of range, non-finite input, a zero qvec, an unknown camera model, options out of range.
+ * The result is the same bytes for any order of the points3D and of the matches inside a pair (when no match of the pair is
+ * dropped as a duplicate). */
+int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
+                      uint32_t num_images, const uint32_t* image_ids, const uint32_t* image_camera_ids,
+                      const uint8_t* image_registered, const double* image_qvec, const double* image_tvec,
+                      const uint32_t* points2D_offsets, const double* points2D_xy, const int32_t* points2D_point3D,
+                      uint32_t num_points3D, const uint64_t* point3D_ids, const double* point3D_xyz, uint32_t num_pairs,
+                      const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
+                      uint32_t num_separators, const uint32_t* separator_ids, uint64_t next_point3D_id,
+                      const dsm_triangulation_options* options, uint64_t* new_point_ids, double* new_point_xyz,
+                      uint64_t* new_track_offsets, uint32_t* new_track_obs, uint64_t* n_new_points, uint32_t* continued_obs,
+                      uint64_t* continued_point_ids, uint64_t* n_continued, uint32_t* touched_obs, uint64_t* touched_point_ids,
+                      uint64_t* n_touched, uint32_t* num_tris_per_separator, uint64_t* num_tris_out,
+                      dsm_triangulation_report* report);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
