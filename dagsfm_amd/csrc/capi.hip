@@ -1169,6 +1169,7 @@ static int verify_core(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* d_pairs, 
   vp.dbg_jacobi_groups = ctx->dbg("DSM_LO_JACOBI_GROUPS") ? 1 : 0;  // the 8-lane-group Jacobi kernel for every problem (round-2 form)
   vp.dbg_roots_lds = ctx->dbg("DSM_ROOTS_LDS") ? 1 : 0;              // k_roots_e_lds instead of the register form
   vp.dbg_final_waves = ctx->dbg("DSM_FINAL_WAVES") ? atoi(ctx->dbg("DSM_FINAL_WAVES")) : 0;
+  vp.dbg_pose_full = ctx->dbg("DSM_POSE_FULL") ? 1 : 0;                // the every-candidate pose check (rounds 3 - 6)
   vp.score_prefilter = ctx->dbg("DSM_SCORE_PREFILTER") ? atoi(ctx->dbg("DSM_SCORE_PREFILTER")) : 1;
   // "check": every slot is scored exactly AND held against its bounds (counters [14] violations, [15] slots the filter
   // would have skipped; dsm_debug_verify_counters); the statistics counters stay alive across the rounds

@@ -104,14 +104,14 @@ struct FamState {
 #define TAIL_KMAX 8  // candidates per pair and tail iteration (a pair with more is simply queued once more)
 // EstimateWithRelativePose (two_view_geometry.cc:232-290) leaves k_verify_final as a job: the candidate poses of the pair
 // (the four (R, t) of DecomposeEssentialMatrix, or the solutions of the homography decomposition); k_final_pose checks
-// them, a wave per (pair, candidate); k_final_finish picks the winner.
+// them, a wave per pair, stopping a candidate once it can no longer win; k_final_finish picks the winner.
 struct PoseJob {
   int32_t ncmb;        // candidates (0: the pair has no pose step)
   int32_t ni;          // inlier points (compacted to the front of the pair's pts_norm rows)
   double Rc[4 * 9];
   double tc[4 * 3];
-  int32_t cnt[4];      // k_final_pose: points in front of both cameras, per candidate
-  double med[4];       // k_final_pose: median triangulation angle of those points, per candidate
+  int32_t cnt[4];      // k_final_pose: points in front of both cameras, per candidate (-1: stopped, cannot win)
+  double med[4];       // k_final_pose: median triangulation angle of those points (the winner's; 0 where not computed)
 };
 struct LoJob {
   uint32_t pl;          // pair (chunk-local)
@@ -178,6 +178,7 @@ struct VerifyParams {
   int lo_reg_prepare;          // k_lo_prepare_reg takes the tall problems, k_lo_prepare only the rest
   int dbg_elu_lds;             // check build, DSM_ELU_LDS: k_solve_e_lu (the 10 x 10 elimination in LDS) instead of k_solve_e_lu_reg
   int dbg_jacobi_groups, dbg_roots_lds, dbg_final_waves;  // dsm_set_debug_option switches the launch helpers read
+  int dbg_pose_full;           // check build, DSM_POSE_FULL: k_final_pose_full (every candidate checks every inlier) instead of k_final_pose
   int score_prefilter;         // F / H scoring as bound + exact (k_prescore, k_score_needed); 0: plain k_score (DSM_SCORE_PREFILTER=0)
   int stats;                   // DSM_VERIFY_DEBUG: count candidates / local optimisations (one-address atomics) in the replay
   uint32_t spec_margin[3];     // k_sample: trials a later round speculates beyond what the dynamic stop asks for (samples without a model)

@@ -1565,18 +1565,180 @@ __global__ __launch_bounds__(64, WAVES) void k_verify_final(const VerifyParams p
 #ifndef K_FINAL_POSE_WAVES
 #define K_FINAL_POSE_WAVES 3
 #endif
-// EstimateWithRelativePose, the part that costs: for every candidate pose CheckCheirality (pose.cc:225-247) --
-// every inlier triangulated, a 4 x 4 SVD per point -- and, of the points in front of both cameras, the median
-// triangulation angle (triangulation.cc:183-218, math.h:211-229).  A wave per (pair, candidate) at three waves per SIMD;
-// inside k_verify_final (one wave per SIMD, 512 VGPRs of decision tree around it) the same loops ran latency-bound.
-// The median is computed for every candidate although only the winner's is used: it is cheap next to the SVDs and
-// saves a second pass over the winner's points.
+// Median(CalculateTriangulationAnglesWithPM), triangulation.cc:183-218, math.h:211-229, of the cnt > 0 points in pts3d
+// of the pose (R, t); ang holds cnt doubles.  Called with an LDS and a global ang (two instantiations after inlining,
+// not a selected pointer: that would compile to flat loads).
+DSM_DEV double median_triangulation_angle(const double* R, const double* t, const double* pts3d, int cnt, double* ang, int lane) {
+  double c2[3];
+  for (int i = 0; i < 3; ++i) c2[i] = -(R[0 * 3 + i] * t[0] + R[1 * 3 + i] * t[1] + R[2 * 3 + i] * t[2]);
+  const double c1[3] = {-(1.0 * 0.0 + 0.0 * 0.0 + 0.0 * 0.0), -(0.0 * 0.0 + 1.0 * 0.0 + 0.0 * 0.0), -(0.0 * 0.0 + 0.0 * 0.0 + 1.0 * 0.0)};
+  double baseline2 = 0;
+  for (int i = 0; i < 3; ++i) baseline2 += (c1[i] - c2[i]) * (c1[i] - c2[i]);
+  for (int j = lane; j < cnt; j += 64) {
+    const double* X = pts3d + 3 * (size_t)j;
+    double r1 = 0, r2 = 0;
+    for (int k = 0; k < 3; ++k) {
+      r1 += (X[k] - c1[k]) * (X[k] - c1[k]);
+      r2 += (X[k] - c2[k]) * (X[k] - c2[k]);
+    }
+    const double ray1 = sqrt(r1), ray2 = sqrt(r2);
+    const double angle = fabs(acos((ray1 * ray1 + ray2 * ray2 - baseline2) / (2 * ray1 * ray2)));
+    ang[j] = isnan(angle) ? 0.0 : (angle < M_PI - angle ? angle : M_PI - angle);
+  }
+  wv_sync();
+  // median by rank counting: element of rank mid (and mid-1 for even sizes)
+  const int mid = cnt / 2;
+  double lo_v = 0.0, hi_v = 0.0;
+  for (int b0 = 0; b0 < cnt; b0 += 64) {
+    const int j = b0 + lane;
+    bool is_mid = false, is_lo = false;
+    double a = 0.0;
+    if (j < cnt) {
+      a = ang[j];
+      int rank = 0;
+      for (int k = 0; k < cnt; ++k) {
+        const double b = ang[k];
+        rank += (b < a) || (b == a && k < j);
+      }
+      is_mid = rank == mid;
+      is_lo = rank == mid - 1;
+    }
+    const unsigned long long bm = __ballot(is_mid), bl = __ballot(is_lo);
+    if (bm) hi_v = __shfl(a, __ffsll((long long)bm) - 1);
+    if (bl) lo_v = __shfl(a, __ffsll((long long)bl) - 1);
+  }
+  return (cnt % 2 == 0) ? (hi_v + lo_v) / 2.0 : hi_v;
+}
+
+// One correspondence of CheckCheirality (pose.cc:232-244) for candidate c of the job: the point triangulated into X,
+// true when it lies in front of both cameras.  The same arithmetic as check_cheirality.
+DSM_DEV bool cheirality_point(const PoseJob* job, int c, const double* p, double* X) {
+  const double kMinDepth = DBL_EPSILON;
+  double R[9], t[3];
+  for (int k = 0; k < 9; ++k) R[k] = job->Rc[c * 9 + k];
+  for (int k = 0; k < 3; ++k) t[k] = job->tc[c * 3 + k];
+  double rt[3];
+  for (int i = 0; i < 3; ++i) rt[i] = R[0 * 3 + i] * t[0] + R[1 * 3 + i] * t[1] + R[2 * 3 + i] * t[2];
+  const double max_depth = 1000.0f * sqrt(rt[0] * rt[0] + rt[1] * rt[1] + rt[2] * rt[2]);
+  const double n1 = sqrt(0.0 * 0.0 + 0.0 * 0.0 + 1.0 * 1.0);
+  const double n2 = sqrt(R[2] * R[2] + R[5] * R[5] + R[8] * R[8]);
+  triangulate_point(R, t, p[0], p[1], p[2], p[3], X);
+  const double d1 = (0.0 * X[0] + 0.0 * X[1] + 1.0 * X[2] + 0.0 * 1.0) * n1;
+  if (d1 > kMinDepth && d1 < max_depth) {
+    const double d2 = (R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2] * 1.0) * n2;
+    if (d2 > kMinDepth && d2 < max_depth) return true;
+  }
+  return false;
+}
+
+// EstimateWithRelativePose, the part that costs: CheckCheirality (pose.cc:225-247) of the candidate poses -- every
+// inlier triangulated, a 4 x 4 SVD per point -- and the median triangulation angle (triangulation.cc:183-218,
+// math.h:211-229) of the winner's points.  A wave per pair at three waves per SIMD.
+// Only the winner reaches the output: PoseFromEssentialMatrix / PoseFromHomographyMatrix (essential_matrix.cc:79-87,
+// homography_matrix.cc:185-194) keep the last candidate whose count is >= the best so far.  While a candidate is being
+// checked, its count so far plus the points still to come bounds its final count from above, and any other candidate's
+// count so far bounds that one's from below.  A candidate whose upper bound is STRICTLY below another's lower bound cannot
+// win (equal bounds settle nothing: a later index wins a tie); it stops there and is marked cnt = -1, which
+// k_final_finish's >= scan (nbest from 0) never picks.  The result is exact whatever the order:
+//   probe   lanes = 4 candidates x the first 16 inliers;
+//   leader  the candidate with the most probe points (ties to the higher index) over its remaining inliers, 64 per slice;
+//   others  in index order, slice by slice while still open -- on a normal pair the twisted and reflected poses have
+//           almost no point in front of both cameras and settle at the probe.
+// Every candidate's points are compacted in point order (ballot + popcount) as check_cheirality does; the median is
+// computed for a candidate that is the winner so far when its check ends (the leader, or one that ties or beats it).
+// The check build keeps the every-candidate form (k_final_pose_full, DSM_POSE_FULL).
 __global__ __launch_bounds__(64, K_FINAL_POSE_WAVES) void k_final_pose(const VerifyParams p) {
   const int lane = threadIdx.x;
   const WgScratch ws = wg_scratch(p);
   double* pts3d = ws.pts3d_a;
-  // the angles of a candidate's points: read cnt times each by the rank counting below -- from LDS when they fit
-  // (a broadcast ds_read instead of a global load per comparison), from the work area otherwise
+  // the winner's angles: read cnt times each by the rank counting -- from LDS when they fit (a broadcast ds_read
+  // instead of a global load per comparison), from the work area otherwise
+  constexpr int kAngLds = 1024;
+  __shared__ double s_ang[kAngLds];
+  constexpr int kProbe = 16;  // inliers per candidate in the probe (4 x 16 = one wave)
+  const int gc = lane / kProbe, gk = lane % kProbe;
+  const uint32_t n_items = p.final_list ? p.n_final : p.n_chunk;
+  for (uint32_t idx = blockIdx.x; idx < n_items; idx += gridDim.x) {
+    const uint32_t pi = p.final_list ? p.final_list[idx] : p.pair0 + idx;
+    PoseJob* job = p.pose_jobs + pi;
+    const int ncmb = job->ncmb;
+    if (ncmb <= 0) continue;
+    wv_sync();
+    const int ni = job->ni;
+    const double* ipts = p.pts_norm + 4 * p.match_off[pi];
+    const int np = ni < kProbe ? ni : kProbe;
+    double PX[3] = {0, 0, 0};
+    const bool pok = (gc < ncmb && gk < np) ? cheirality_point(job, gc, ipts + 4 * (size_t)gk, PX) : false;
+    const unsigned long long pbal = __ballot(pok);
+    int lb[4];  // lower bound of each candidate's final count: its count so far (exact once its check has ended)
+    for (int c = 0; c < 4; ++c) lb[c] = __popcll((pbal >> (kProbe * c)) & 0xffffull);
+    int lead = 0;
+    for (int c = 1; c < ncmb; ++c)
+      if (lb[c] >= lb[lead]) lead = c;
+    int best_c = -1, best_cnt = -1;
+    for (int o = 0; o < ncmb; ++o) {
+      const int c = o == 0 ? lead : (o - 1 < lead ? o - 1 : o);  // the leader, then the others in index order
+      int bound = 0, cnt = 0;
+      for (int k = 0; k < ncmb; ++k) {
+        if (k == c) cnt = lb[k];
+        else bound = lb[k] > bound ? lb[k] : bound;
+      }
+      // the probe's points of c first
+      if (gc == c && pok) {
+        double* dst = pts3d + 3 * (size_t)__popcll((pbal >> (kProbe * c)) & ((1ull << gk) - 1ull));
+        dst[0] = PX[0];
+        dst[1] = PX[1];
+        dst[2] = PX[2];
+      }
+      bool settled = false;
+      for (int base = np; base < ni; base += 64) {
+        if (cnt + (ni - base) < bound) {
+          settled = true;
+          break;
+        }
+        const int i = base + lane;
+        double X[3] = {0, 0, 0};
+        const bool ok = i < ni ? cheirality_point(job, c, ipts + 4 * (size_t)i, X) : false;
+        const unsigned long long bal = __ballot(ok);
+        if (ok) {
+          double* dst = pts3d + (size_t)(cnt + __popcll(bal & ((1ull << lane) - 1ull))) * 3;
+          dst[0] = X[0];
+          dst[1] = X[1];
+          dst[2] = X[2];
+        }
+        cnt += __popcll(bal);
+      }
+      wv_sync();
+      for (int k = 0; k < 4; ++k)
+        if (k == c) lb[k] = cnt;
+      double med = 0.0;
+      if (!settled && (cnt > best_cnt || (cnt == best_cnt && c > best_c))) {
+        best_cnt = cnt;
+        best_c = c;
+        if (cnt > 0) {
+          double R[9], t[3];
+          for (int k = 0; k < 9; ++k) R[k] = job->Rc[c * 9 + k];
+          for (int k = 0; k < 3; ++k) t[k] = job->tc[c * 3 + k];
+          med = cnt <= kAngLds ? median_triangulation_angle(R, t, pts3d, cnt, s_ang, lane)
+                               : median_triangulation_angle(R, t, pts3d, cnt, ws.resid, lane);
+        }
+      }
+      wv_sync();
+      if (lane == 0) {
+        job->cnt[c] = settled ? -1 : cnt;
+        job->med[c] = med;
+      }
+    }
+  }
+}
+
+#ifdef DSM_CHECK_BUILD
+// Cross-check form (check build, DSM_POSE_FULL): every candidate checks every inlier and computes its median, a wave per
+// (pair, candidate) -- the schedule of rounds 3 - 6.  Same records as k_final_pose.
+__global__ __launch_bounds__(64, K_FINAL_POSE_WAVES) void k_final_pose_full(const VerifyParams p) {
+  const int lane = threadIdx.x;
+  const WgScratch ws = wg_scratch(p);
+  double* pts3d = ws.pts3d_a;
   constexpr int kAngLds = 1024;
   __shared__ double s_ang[kAngLds];
   const uint32_t n_items = (p.final_list ? p.n_final : p.n_chunk) * 4u;
@@ -1593,58 +1755,16 @@ __global__ __launch_bounds__(64, K_FINAL_POSE_WAVES) void k_final_pose(const Ver
     for (int k = 0; k < 3; ++k) t[k] = job->tc[c * 3 + k];
     const int cnt = check_cheirality(R, t, ipts, job->ni, pts3d, lane);
     double med = 0.0;
-    if (cnt > 0) {
-      // Median(CalculateTriangulationAnglesWithPM), triangulation.cc:183-218, math.h:211-229
-      double c2[3];
-      for (int i = 0; i < 3; ++i) c2[i] = -(R[0 * 3 + i] * t[0] + R[1 * 3 + i] * t[1] + R[2 * 3 + i] * t[2]);
-      const double c1[3] = {-(1.0 * 0.0 + 0.0 * 0.0 + 0.0 * 0.0), -(0.0 * 0.0 + 1.0 * 0.0 + 0.0 * 0.0), -(0.0 * 0.0 + 0.0 * 0.0 + 1.0 * 0.0)};
-      double baseline2 = 0;
-      for (int i = 0; i < 3; ++i) baseline2 += (c1[i] - c2[i]) * (c1[i] - c2[i]);
-      // (two instantiations, not a selected pointer: that would compile to flat loads)
-      auto median_of_angles = [&](double* ang) {
-        for (int j = lane; j < cnt; j += 64) {
-          const double* X = pts3d + 3 * (size_t)j;
-          double r1 = 0, r2 = 0;
-          for (int k = 0; k < 3; ++k) {
-            r1 += (X[k] - c1[k]) * (X[k] - c1[k]);
-            r2 += (X[k] - c2[k]) * (X[k] - c2[k]);
-          }
-          const double ray1 = sqrt(r1), ray2 = sqrt(r2);
-          const double angle = fabs(acos((ray1 * ray1 + ray2 * ray2 - baseline2) / (2 * ray1 * ray2)));
-          ang[j] = isnan(angle) ? 0.0 : (angle < M_PI - angle ? angle : M_PI - angle);
-        }
-        wv_sync();
-        // median by rank counting: element of rank mid (and mid-1 for even sizes)
-        const int mid = cnt / 2;
-        double lo_v = 0.0, hi_v = 0.0;
-        for (int b0 = 0; b0 < cnt; b0 += 64) {
-          const int j = b0 + lane;
-          bool is_mid = false, is_lo = false;
-          double a = 0.0;
-          if (j < cnt) {
-            a = ang[j];
-            int rank = 0;
-            for (int k = 0; k < cnt; ++k) {
-              const double b = ang[k];
-              rank += (b < a) || (b == a && k < j);
-            }
-            is_mid = rank == mid;
-            is_lo = rank == mid - 1;
-          }
-          const unsigned long long bm = __ballot(is_mid), bl = __ballot(is_lo);
-          if (bm) hi_v = __shfl(a, __ffsll((long long)bm) - 1);
-          if (bl) lo_v = __shfl(a, __ffsll((long long)bl) - 1);
-        }
-        return (cnt % 2 == 0) ? (hi_v + lo_v) / 2.0 : hi_v;
-      };
-      med = cnt <= kAngLds ? median_of_angles(s_ang) : median_of_angles(ws.resid);
-    }
+    if (cnt > 0)
+      med = cnt <= kAngLds ? median_triangulation_angle(R, t, pts3d, cnt, s_ang, lane)
+                           : median_triangulation_angle(R, t, pts3d, cnt, ws.resid, lane);
     if (lane == 0) {
       job->cnt[c] = cnt;
       job->med[c] = med;
     }
   }
 }
+#endif  // DSM_CHECK_BUILD
 
 // The winner among the candidates (pose.cc:80-105: the last one with the most points in front of both cameras),
 // its quaternion, the median angle, PLANAR vs PANORAMIC (two_view_geometry.cc:266-279).  A lane per pair.
@@ -5260,8 +5380,13 @@ void launch_vp_replay(const VerifyParams& p, int fam, uint32_t n_blocks, hipStre
 static void launch_final_pose_finish(const VerifyParams& p, uint32_t n_blocks, hipStream_t st) {
   const uint32_t n = p.final_list ? p.n_final : p.n_chunk;
   if (!n) return;
-  const uint32_t items = n * 4u;
-  hipLaunchKernelGGL(k_final_pose, dim3(items < n_blocks ? items : n_blocks), dim3(64), 0, st, p);
+#ifdef DSM_CHECK_BUILD
+  if (p.dbg_pose_full) {  // DSM_POSE_FULL: a wave per (pair, candidate), every inlier of every candidate
+    const uint32_t items = n * 4u;
+    hipLaunchKernelGGL(k_final_pose_full, dim3(items < n_blocks ? items : n_blocks), dim3(64), 0, st, p);
+  } else
+#endif
+    hipLaunchKernelGGL(k_final_pose, dim3(n < n_blocks ? n : n_blocks), dim3(64), 0, st, p);
   hipLaunchKernelGGL(k_final_finish, dim3((n + 63) / 64), dim3(64), 0, st, p);
 }
 void launch_vp_final(const VerifyParams& p, uint32_t n_blocks, hipStream_t st) {

@@ -23,7 +23,9 @@ one is compared with the product's `batched` records -- so the comparison also s
     product's k_solve_e_lu_reg keeps the matrix in registers), hyp_pair_grid (DSM_HYP_GRID=pair: the lane-per-hypothesis solvers of E / F on the
     (pair, 64 trials) grid in every round; the product's take the hypotheses of later rounds 64 per wave across the pairs), lo_prepare_wave
     (DSM_LO_PREPARE_WAVE: every local optimisation's design matrix + pivoted QR by the general kernel k_lo_prepare, matrix in memory; the
-    product's k_lo_prepare_reg keeps it in registers for E / F up to 384 inliers and H up to 64)
+    product's k_lo_prepare_reg keeps it in registers for E / F up to 384 inliers and H up to 64), pose_full (DSM_POSE_FULL: every
+    candidate pose checks every inlier and computes its median, a wave per (pair, candidate); the product's k_final_pose stops a
+    candidate once it can no longer win)
 This exercises the paths too rare for the oracle-sized tests (a Lemire rejection in the sampler happens for a few
 dozen pairs of config 2; pairs with > 15 local optimisations in one round).
 
@@ -79,6 +81,9 @@ def run(ctx, opts, schedule):
         os.environ["DSM_HYP_GRID"] = "pair"
     if schedule == "replay_legacy":
         os.environ["DSM_REPLAY_LEGACY"] = "1"
+    os.environ.pop("DSM_POSE_FULL", None)
+    if schedule == "pose_full":
+        os.environ["DSM_POSE_FULL"] = "1"
     ctx.verify_pairs(opts, user_seed=0, stage_filter=True)
     recs = np.zeros((ctx.n_pairs, ctypes.sizeof(capi.TwoViewGeometry)), dtype=np.uint8)
     rc = ctx._L.dsm_get_two_view_geometries(ctx._h, recs.ctypes.data)
@@ -113,8 +118,8 @@ def main():
     opts = capi.default_two_view_options()
     r0 = run(ctxs[False], opts, "batched")
     ok = True
-    CHECK_ONLY = ("no_prefilter", "e_fused", "final_1wave", "legacy", "h_mfma", "h_f64", "ef_f64", "replay_legacy", "elu_lds", "hyp_pair_grid", "lo_prepare_wave")
-    for name in ["batched_check_build", "replay_legacy", "elu_lds", "hyp_pair_grid", "lo_prepare_wave", "no_prefilter", "e_fused", "h_mfma", "h_f64", "ef_f64", "one_lane", "no_tail", "tail_inline", "final_1wave", "inline"] + (["legacy"] if a.legacy else []):
+    CHECK_ONLY = ("no_prefilter", "e_fused", "final_1wave", "legacy", "h_mfma", "h_f64", "ef_f64", "replay_legacy", "elu_lds", "hyp_pair_grid", "lo_prepare_wave", "pose_full")
+    for name in ["batched_check_build", "pose_full", "replay_legacy", "elu_lds", "hyp_pair_grid", "lo_prepare_wave", "no_prefilter", "e_fused", "h_mfma", "h_f64", "ef_f64", "one_lane", "no_tail", "tail_inline", "final_1wave", "inline"] + (["legacy"] if a.legacy else []):
         use_check = name in CHECK_ONLY or name == "batched_check_build"
         r1 = run(ctxs[use_check], opts, "batched" if name == "batched_check_build" else name)
         for k in capi.CHECK_OPTION_KEYS:  # the product context must not see a check-only switch
