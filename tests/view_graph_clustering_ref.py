@@ -2,7 +2,7 @@
 src/controllers/distributed_mapper_controller.cpp:633-657; DESIGN.md 10, "View-graph clustering").
 
 SPECTRAL (src/clustering/spectral_cluster.cpp:52-176): the dense L = D_cnt - S (D_cnt counts the edges of an image, S holds
-the weights), numpy.linalg.eigh for its k algebraically smallest eigenvectors, then KMeans (src/clustering/kmeans.h:158-235)
+the weights), numpy.linalg.eigh (scipy's eigsh above SPARSE_ABOVE images) for its k algebraically smallest eigenvectors, then KMeans (src/clustering/kmeans.h:158-235)
 with k-means++ driven by a restatement of libstdc++'s std::mt19937_64, uniform_int_distribution<size_t> and
 discrete_distribution<size_t> (GCC 11).  Cut's bookkeeping and Expand (src/clustering/image_clustering.cpp:68-128, 159-199,
 451-624) with the device's free choices: cluster pairs in ascending (c1, c2) order, equal weights in input order.
@@ -150,6 +150,7 @@ def kmeans(X, k, max_iterations=0):
     C = np.array(centers)
     assign = np.full(N, k, np.int64)
     lloyd_margins = []
+    empty = []
     it = 0
     while True:
         D = _sq_dists(X, C)
@@ -164,14 +165,49 @@ def kmeans(X, k, max_iterations=0):
             mem = assign == c
             if mem.any():
                 C[c] = X[mem].sum(0) / mem.sum()
+            else:
+                empty.append((it, c))  # ComputeCenterOfMass divides 0 / 0: the centre is NaN from here on
         it += 1
         if not changed or (max_iterations and it >= max_iterations):
             break
-    return assign, it, np.array(draw_margins), np.concatenate(lloyd_margins) if lloyd_margins else np.zeros(0)
+    return assign, it, np.array(draw_margins), np.concatenate(lloyd_margins) if lloyd_margins else np.zeros(0), empty
 
 
-def spectral(N, edges, k):
-    """(eigenvalues [N], eigenvectors [N, N]) of L ascending, numpy.linalg.eigh."""
+SPARSE_ABOVE = 2500  # images above which spectral() leaves the dense eigh (about 10 s there) for the sparse path
+
+
+def sparse_laplacian(N, edges):
+    """L = D_cnt - S as scipy.sparse CSR (the same matrix as laplacian())."""
+    import scipy.sparse as sp
+    i, j, w = edges[:, 0], edges[:, 1], edges[:, 2].astype(np.float64)
+    one = np.ones(len(i))
+    rows = np.concatenate([i, j, i, j])
+    cols = np.concatenate([j, i, i, j])
+    return sp.coo_matrix((np.concatenate([-w, -w, one, one]), (rows, cols)), shape=(N, N)).tocsr()
+
+
+def spectral_sparse(N, edges, k, extra=1):
+    """The k + extra algebraically smallest eigenpairs of L, ascending: Lanczos on L itself (scipy eigsh, ARPACK, which =
+    "SA", run to machine precision from a fixed start vector), then one Rayleigh-Ritz step on the orthonormalised vectors.
+    No shift-invert: L is indefinite, the wanted end of its spectrum is an extreme one, and the factorisation of a shifted
+    L fills in badly on graphs that expand."""
+    import scipy.sparse.linalg as spla
+    L = sparse_laplacian(N, edges)
+    nev = min(k + extra, N - 1)
+    _, V = spla.eigsh(L, k=nev, which="SA", tol=0, ncv=min(N, max(3 * nev, 40)), v0=np.ones(N) / math.sqrt(N))
+    Q, _ = np.linalg.qr(V)
+    H = Q.T @ (L @ Q)
+    t, Z = np.linalg.eigh(0.5 * (H + H.T))
+    return t, Q @ Z
+
+
+def spectral(N, edges, k, sparse=None):
+    """(eigenvalues, eigenvectors) of L ascending: all N of them by numpy.linalg.eigh, or (sparse; the default above
+    SPARSE_ABOVE images) the first k + 1 by spectral_sparse."""
+    if sparse is None:
+        sparse = N > SPARSE_ABOVE
+    if sparse:
+        return spectral_sparse(N, edges, k)
     return np.linalg.eigh(laplacian(N, edges))
 
 
@@ -231,7 +267,7 @@ def cut_expand(N, edges, labels, n_clusters, n_pairs, image_overlap=50, complete
 
 
 def cluster(pairs, weights, use=None, labels_in=None, num_images_ub=100, image_overlap=50, completeness_ratio=0.5, expand=True,
-            max_kmeans_iterations=0):
+            max_kmeans_iterations=0, sparse=None):
     """dsm_view_graph_cluster restated.  Returns a dict with image_ids, labels, edge_cluster, clusters (sorted image ids per
     inter cluster), report-like counts, and for SPECTRAL the eigenvalues / eigenvectors and the decision margins."""
     n_pairs = len(np.asarray(pairs).reshape(-1, 2))
@@ -239,14 +275,15 @@ def cluster(pairs, weights, use=None, labels_in=None, num_images_ub=100, image_o
     N = len(ids)
     k = max(1, N // num_images_ub)
     out = {"image_ids": ids, "k": k, "eigenvalues": None, "subspace": None, "draw_margins": np.zeros(0),
-           "lloyd_margins": np.zeros(0), "kmeans_iterations": 0}
+           "lloyd_margins": np.zeros(0), "kmeans_iterations": 0, "empty_centres": []}
     if labels_in is not None:
         labels = np.asarray(labels_in, np.int64)
         n_clusters = max(k, int(labels.max()) + 1 if N else 0)
     elif k > 1:
-        evals, evecs = spectral(N, edges, k)
-        labels, it, dm, lm = kmeans(evecs[:, :k], k, max_kmeans_iterations)
-        out.update(eigenvalues=evals, subspace=evecs[:, :k], draw_margins=dm, lloyd_margins=lm, kmeans_iterations=it)
+        evals, evecs = spectral(N, edges, k, sparse)
+        labels, it, dm, lm, empty = kmeans(evecs[:, :k], k, max_kmeans_iterations)
+        out.update(eigenvalues=evals, subspace=evecs[:, :k], draw_margins=dm, lloyd_margins=lm, kmeans_iterations=it,
+                   empty_centres=empty)
         n_clusters = k
     else:
         labels = np.zeros(N, np.int64)
