@@ -201,6 +201,33 @@ ALIGN_PAIR_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("num_common_images", "
                              ("prosac_t", "<f8", (2, 3))])
 
 
+class AbsolutePoseOptions(ctypes.Structure):
+    """dsm_absolute_pose_options: AbsolutePoseEstimationOptions with its RANSACOptions as IncrementalMapper::RegisterNextImage
+    fills them (src/estimators/pose.h:51-77, src/sfm/incremental_mapper.cc:438-449)."""
+    _fields_ = [("num_focal_length_samples", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("min_focal_length_ratio", ctypes.c_double), ("max_focal_length_ratio", ctypes.c_double),
+                ("max_error", ctypes.c_double), ("min_inlier_ratio", ctypes.c_double), ("confidence", ctypes.c_double),
+                ("min_num_trials", ctypes.c_uint64), ("max_num_trials", ctypes.c_uint64), ("random_seed", ctypes.c_uint32),
+                ("reserved2", ctypes.c_uint32)]
+
+
+class AbsolutePoseResult(ctypes.Structure):
+    _fields_ = [("success", ctypes.c_int32), ("factor_index", ctypes.c_int32), ("num_inliers", ctypes.c_uint32),
+                ("num_trials", ctypes.c_uint32), ("model_is_local", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("focal_length_factor", ctypes.c_double), ("proj_matrix", ctypes.c_double * 12), ("qvec", ctypes.c_double * 4),
+                ("tvec", ctypes.c_double * 3), ("focal_params", ctypes.c_double * 2)]
+
+
+ABSOLUTE_POSE_MARGINS = ("residual", "depth", "support_tie", "root_imag", "root_sign", "rank", "beta_sign", "error_choice", "determinant")
+
+
+class AbsolutePoseReport(ctypes.Structure):
+    _fields_ = [("num_problems", ctypes.c_uint32), ("num_factors", ctypes.c_uint32), ("num_runs", ctypes.c_uint64),
+                ("num_trials", ctypes.c_uint64), ("num_models", ctypes.c_uint64), ("num_local_optimizations", ctypes.c_uint64),
+                ("min_margin", ctypes.c_double * 9), ("setup_ms", ctypes.c_double), ("prepare_ms", ctypes.c_double),
+                ("ransac_ms", ctypes.c_double), ("choice_ms", ctypes.c_double), ("device_ms", ctypes.c_double)]
+
+
 def lib(check=False):
     """Loads the shared library (check=True: the check build); raises if it has not been built (no fallback)."""
     if check not in _libs:
@@ -269,6 +296,15 @@ def lib(check=False):
         L.dsm_retriangulate.argtypes = ([vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32] + [vp] * 8 + [ctypes.c_uint32, vp, vp, ctypes.c_uint32]
                                         + [vp] * 3 + [ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.POINTER(TriangulationOptions)]
                                         + [vp] * 14)
+        L.dsm_default_absolute_pose_options.argtypes = [ctypes.POINTER(AbsolutePoseOptions)]
+        L.dsm_default_absolute_pose_options.restype = None
+        L.dsm_absolute_pose_seed.argtypes = [ctypes.c_uint32] * 3
+        L.dsm_absolute_pose_seed.restype = ctypes.c_uint32
+        L.dsm_absolute_pose_factors.argtypes = [ctypes.POINTER(AbsolutePoseOptions), vp, ctypes.c_uint32]
+        L.dsm_absolute_pose_factors.restype = ctypes.c_uint32
+        L.dsm_absolute_pose_max_trials.argtypes = [ctypes.POINTER(AbsolutePoseOptions)]
+        L.dsm_absolute_pose_max_trials.restype = ctypes.c_uint64
+        L.dsm_estimate_absolute_poses.argtypes = [vp, ctypes.c_uint32] + [vp] * 5 + [ctypes.POINTER(AbsolutePoseOptions)] + [vp] * 5
         L.dsm_debug_image_to_world.argtypes = [vp, ctypes.POINTER(Camera), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double)]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
@@ -356,6 +392,32 @@ def default_triangulation_options(**kw):
     for k, v in kw.items():
         setattr(o, k, v)
     return o
+
+
+def default_absolute_pose_options(**kw):
+    o = AbsolutePoseOptions()
+    lib().dsm_default_absolute_pose_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def absolute_pose_seed(problem, factor_index, user_seed=0):
+    return int(lib().dsm_absolute_pose_seed(problem, factor_index, user_seed))
+
+
+def absolute_pose_factors(options=None):
+    """The focal-length factors of pose.cc:87-102 for these options (what a problem with estimate_focal_length runs over)."""
+    o = options if options is not None else default_absolute_pose_options()
+    n = int(lib().dsm_absolute_pose_factors(ctypes.byref(o), None, 0))
+    out = np.zeros(max(n, 1))
+    lib().dsm_absolute_pose_factors(ctypes.byref(o), out.ctypes.data, n)
+    return out[:n].copy()
+
+
+def absolute_pose_max_trials(options=None):
+    o = options if options is not None else default_absolute_pose_options()
+    return int(lib().dsm_absolute_pose_max_trials(ctypes.byref(o)))
 
 
 def align_seed(i, j, direction, user_seed=0):
@@ -842,6 +904,34 @@ class Context:
                 "new_track_obs": nobs[:int(noff[n])].copy(), "continued_obs": cobs[:c].copy(), "continued_point_ids": cid[:c].copy(),
                 "touched_obs": tobs[:t].copy(), "touched_point_ids": tid[:t].copy(),
                 "num_tris_per_separator": sep_tris[:len(seps)].copy(), "num_tris": tris.value, "report": rep}
+
+    def estimate_absolute_poses(self, cameras, estimate_focal_length, offsets, points2D, points3D, options=None, seeds=None):
+        """dsm_estimate_absolute_poses (EstimateAbsolutePose for a batch of problems).  cameras: a list of Camera
+        [B]; estimate_focal_length [B]; offsets [B + 1] (CSR over the problems); points2D [T, 2] pixels; points3D [T, 3]; seeds:
+        None or [B, S] with S = len(absolute_pose_factors(options)).  Returns a dict: results (a list of AbsolutePoseResult),
+        inlier_mask [T] uint8, margins [B, 9] (ABSOLUTE_POSE_MARGINS), report."""
+        B = len(cameras)
+        cams = (Camera * max(B, 1))(*cameras)
+        flags = np.ascontiguousarray(estimate_focal_length, np.uint8).reshape(-1)
+        offs = np.ascontiguousarray(offsets, np.uint64).reshape(-1)
+        p2 = np.ascontiguousarray(points2D, np.float64).reshape(-1, 2)
+        p3 = np.ascontiguousarray(points3D, np.float64).reshape(-1, 3)
+        if len(flags) != B or len(offs) != B + 1 or len(p2) != len(p3) or (B and int(offs[-1]) > len(p2)):
+            raise DsmError("estimate_absolute_poses: array sizes do not match")
+        o = options if options is not None else default_absolute_pose_options()
+        sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        if sd is not None and len(sd) != B * len(absolute_pose_factors(o)):
+            raise DsmError("estimate_absolute_poses: seeds must hold B * S entries")
+        res = (AbsolutePoseResult * max(B, 1))()
+        mask = np.zeros(max(len(p2), 1), np.uint8)
+        margins = np.zeros((max(B, 1), len(ABSOLUTE_POSE_MARGINS)))
+        rep = AbsolutePoseReport()
+        ptr = lambda x: x.ctypes.data
+        self._chk(self._L.dsm_estimate_absolute_poses(self._h, B, ctypes.addressof(cams), ptr(flags), ptr(offs), ptr(p2), ptr(p3),
+                                                      ctypes.byref(o), None if sd is None else ptr(sd), ctypes.addressof(res),
+                                                      ptr(mask), ptr(margins), ctypes.addressof(rep)))
+        return {"results": [res[b] for b in range(B)], "inlier_mask": mask[:len(p2)].copy(), "margins": margins[:B].copy(),
+                "report": rep}
 
     def device_info(self):
         d = DeviceInfo()

@@ -819,6 +819,89 @@ int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera
                       uint64_t* n_touched, uint32_t* num_tris_per_separator, uint64_t* num_tris_out,
                       dsm_triangulation_report* report);
 
+/* ------------------------------------------------------------------ absolute pose estimation (image registration)
+ * EstimateAbsolutePose (src/estimators/pose.cc:48-158) as IncrementalMapper::RegisterNextImage calls it
+ * (src/sfm/incremental_mapper.cc:438-496), for a batch of independent problems: per problem a camera, N
+ * 2D-3D correspondences and the flag estimate_focal_length.  One LO-RANSAC (P3P minimal solver, EPnP local optimisation,
+ * src/optim/loransac.h:91-233) per focal-length factor; the unit of work is the RUN = (problem, factor).
+ * Every run draws from its own MT19937 stream: the results depend on the problem, the options and the seeds alone, not on
+ * the batch, the order of the problems or the schedule. */
+#define DSM_ABSOLUTE_POSE_MAX_POINTS 1048576u  /* correspondences of one problem; more is DSM_ERR_INVALID_ARGUMENT */
+#define DSM_ABSOLUTE_POSE_MAX_FACTORS 1024u    /* focal-length factors (num_focal_length_samples + 1 at most) */
+#define DSM_ABSOLUTE_POSE_MAX_TRIALS 1000000u  /* trials of one run after RANSAC's constructor cap; more is DSM_ERR_INVALID_ARGUMENT */
+typedef struct dsm_absolute_pose_options {
+  int32_t num_focal_length_samples; /* 30    AbsolutePoseEstimationOptions, src/estimators/pose.h:55; incremental_mapper.cc:440 */
+  int32_t reserved;
+  double min_focal_length_ratio;    /* 0.1   incremental_mapper.h:106 (pose.h:59 has 0.2) */
+  double max_focal_length_ratio;    /* 10    incremental_mapper.h:107 (pose.h:63 has 5) */
+  double max_error;                 /* 12.0  pixels, abs_pose_max_error, incremental_mapper.h:84 */
+  double min_inlier_ratio;          /* 0.25  abs_pose_min_inlier_ratio, incremental_mapper.h:90 */
+  double confidence;                /* 0.9999 incremental_mapper.cc:449 */
+  uint64_t min_num_trials;          /* 30    incremental_mapper.cc:448 */
+  uint64_t max_num_trials;          /* UINT64_MAX: RANSACOptions' default (ransac.h:62), which the mapper leaves; RANSAC's constructor caps it
+                                       (ransac.h:141-147): 585 with the values above */
+  uint32_t random_seed;             /* user part of the per-run seeds, dsm_absolute_pose_seed */
+  uint32_t reserved2;
+} dsm_absolute_pose_options;
+
+typedef struct dsm_absolute_pose_result {
+  int32_t success;            /* EstimateAbsolutePose's return value */
+  int32_t factor_index;       /* index of the winning focal-length factor (-1: none) */
+  uint32_t num_inliers;
+  uint32_t num_trials;        /* report.num_trials of the winning run */
+  int32_t model_is_local;     /* the winning model came from the local optimisation (EPnP) */
+  int32_t reserved;
+  double focal_length_factor; /* the winning factor (0 when none) */
+  double proj_matrix[12];     /* 3 x 4, row-major */
+  double qvec[4];             /* w x y z */
+  double tvec[3];
+  double focal_params[2];     /* the camera's focal parameters after the call (scaled only with estimate_focal_length);
+                                 a model with one focal length repeats it */
+} dsm_absolute_pose_result;
+
+#define DSM_ABSOLUTE_POSE_MARGINS 9
+typedef struct dsm_absolute_pose_report {
+  uint32_t num_problems, num_factors; /* num_factors: runs of a problem with the flag set */
+  uint64_t num_runs, num_trials, num_models, num_local_optimizations; /* summed over the runs */
+  /* per problem is the call's margins_out; here the minima over the batch (INFINITY where never taken).  In order:
+     0 residual against the threshold (relative)   1 depth against epsilon   2 equal-count residual sums (relative)
+     3 P3P root |imag| against 1e-10 (relative)    4 P3P real root against 0 (absolute; the roots are O(1))
+     5 EPnP rank pivot against its threshold       6 EPnP sign tests on b3 / b4 / b5 (relative to the largest)
+     7 EPnP three-way error comparison (relative)  8 EPnP Procrustes determinant against 0 */
+  double min_margin[DSM_ABSOLUTE_POSE_MARGINS];
+  double setup_ms;            /* host: validation, factors, tables */
+  double prepare_ms, ransac_ms, choice_ms; /* HIP events: uploads + normalisation, the runs, results back + the choice */
+  double device_ms;           /* HIP events: first upload to the last download */
+} dsm_absolute_pose_report;
+
+void dsm_default_absolute_pose_options(dsm_absolute_pose_options* o);
+/* seed of run (problem b, factor index s) */
+uint32_t dsm_absolute_pose_seed(uint32_t problem, uint32_t factor_index, uint32_t user_seed);
+/* The focal-length factors of pose.cc:87-102, the loop restated as written (its length is decided by the accumulated
+ * rounding of f += 1 / n).  Writes at most `capacity` factors, returns their number (0 for options out of range). */
+uint32_t dsm_absolute_pose_factors(const dsm_absolute_pose_options* options, double* factors_out, uint32_t capacity);
+/* RANSAC's constructor cap on max_num_trials (ransac.h:141-147) for these options. */
+uint64_t dsm_absolute_pose_max_trials(const dsm_absolute_pose_options* options);
+
+/* Host pointers, CSR over the problems: problem b owns points offsets[b] .. offsets[b + 1].
+ *   cameras[B], estimate_focal_length[B] (0 / 1), offsets[B + 1] (ascending from 0), points2D (2 per point, pixels),
+ *   points3D (3 per point), options (NULL = defaults), seeds (NULL = dsm_absolute_pose_seed(b, s, options->random_seed),
+ *   else B * S entries, seeds[b * S + s], S = dsm_absolute_pose_factors; a problem without the flag reads seeds[b * S])
+ *   results_out[B], inlier_mask_out[offsets[B]] (0 / 1; all 0 for a failed problem), margins_out (NULL or
+ *   B * DSM_ABSOLUTE_POSE_MARGINS doubles), report (NULL or the sums).
+ * N < 3 is not an error: success = 0, zero trials.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT): NULL where data is needed, non-finite points or camera parameters, an unknown camera
+ *   model, offsets that do not ascend from 0, a problem above DSM_ABSOLUTE_POSE_MAX_POINTS, more factors than
+ *   DSM_ABSOLUTE_POSE_MAX_FACTORS, options outside what AbsolutePoseEstimationOptions::Check / RANSACOptions::Check accept,
+ *   and options that Check accepts but that leave a run's trial count unbounded: dsm_absolute_pose_max_trials above
+ *   DSM_ABSOLUTE_POSE_MAX_TRIALS (confidence = 1 or min_inlier_ratio = 0 with the default max_num_trials).  The reference
+ *   loops that long on a host thread; one kernel launch must not.  Set max_num_trials to bound such a call. */
+int dsm_estimate_absolute_poses(dsm_ctx* ctx, uint32_t num_problems, const dsm_camera* cameras,
+                                const uint8_t* estimate_focal_length, const uint64_t* offsets, const double* points2D,
+                                const double* points3D, const dsm_absolute_pose_options* options, const uint32_t* seeds,
+                                dsm_absolute_pose_result* results_out, uint8_t* inlier_mask_out, double* margins_out,
+                                dsm_absolute_pose_report* report);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
