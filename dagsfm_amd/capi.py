@@ -228,6 +228,33 @@ class AbsolutePoseReport(ctypes.Structure):
                 ("ransac_ms", ctypes.c_double), ("choice_ms", ctypes.c_double), ("device_ms", ctypes.c_double)]
 
 
+class PoseRefinementOptions(ctypes.Structure):
+    """dsm_pose_refinement_options: AbsolutePoseRefinementOptions (src/estimators/pose.h:80-104); the two refine flags are per
+    problem (refine_flags)."""
+    _fields_ = [("gradient_tolerance", ctypes.c_double), ("loss_function_scale", ctypes.c_double),
+                ("max_num_iterations", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class PoseRefinementResult(ctypes.Structure):
+    _fields_ = [("success", ctypes.c_int32), ("termination", ctypes.c_int32), ("num_iterations", ctypes.c_uint32),
+                ("num_successful_steps", ctypes.c_uint32), ("num_invalid_steps", ctypes.c_uint32),
+                ("num_residual_blocks", ctypes.c_uint32), ("initial_cost", ctypes.c_double), ("final_cost", ctypes.c_double),
+                ("qvec", ctypes.c_double * 4), ("tvec", ctypes.c_double * 3), ("camera_params", ctypes.c_double * 12)]
+
+
+POSE_REFINEMENT_MARGINS = ("acceptance", "gradient", "function_tolerance", "parameter_tolerance", "pivot")
+POSE_REFINEMENT_MAX_ITERATIONS = 1000
+POSE_REFINE_FOCAL_LENGTH, POSE_REFINE_EXTRA_PARAMS = 1, 2
+POSE_STEP_ACCEPTED, POSE_STEP_REJECTED, POSE_STEP_INVALID, POSE_STEP_TOLERANCE = 1, 2, 3, 4
+
+
+class PoseRefinementReport(ctypes.Structure):
+    _fields_ = [("num_problems", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("num_points", ctypes.c_uint64),
+                ("num_iterations", ctypes.c_uint64), ("min_margin", ctypes.c_double * 5), ("setup_ms", ctypes.c_double),
+                ("upload_ms", ctypes.c_double), ("solve_ms", ctypes.c_double), ("download_ms", ctypes.c_double),
+                ("device_ms", ctypes.c_double)]
+
+
 def lib(check=False):
     """Loads the shared library (check=True: the check build); raises if it has not been built (no fallback)."""
     if check not in _libs:
@@ -305,6 +332,9 @@ def lib(check=False):
         L.dsm_absolute_pose_max_trials.argtypes = [ctypes.POINTER(AbsolutePoseOptions)]
         L.dsm_absolute_pose_max_trials.restype = ctypes.c_uint64
         L.dsm_estimate_absolute_poses.argtypes = [vp, ctypes.c_uint32] + [vp] * 5 + [ctypes.POINTER(AbsolutePoseOptions)] + [vp] * 5
+        L.dsm_default_pose_refinement_options.argtypes = [ctypes.POINTER(PoseRefinementOptions)]
+        L.dsm_default_pose_refinement_options.restype = None
+        L.dsm_refine_absolute_poses.argtypes = [vp, ctypes.c_uint32] + [vp] * 8 + [ctypes.POINTER(PoseRefinementOptions)] + [vp] * 4
         L.dsm_debug_image_to_world.argtypes = [vp, ctypes.POINTER(Camera), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double)]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
@@ -397,6 +427,14 @@ def default_triangulation_options(**kw):
 def default_absolute_pose_options(**kw):
     o = AbsolutePoseOptions()
     lib().dsm_default_absolute_pose_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_pose_refinement_options(**kw):
+    o = PoseRefinementOptions()
+    lib().dsm_default_pose_refinement_options(ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -932,6 +970,83 @@ class Context:
                                                       ptr(mask), ptr(margins), ctypes.addressof(rep)))
         return {"results": [res[b] for b in range(B)], "inlier_mask": mask[:len(p2)].copy(), "margins": margins[:B].copy(),
                 "report": rep}
+
+    def refine_absolute_poses(self, cameras, offsets, points2D, points3D, inlier_mask, qvecs, tvecs, refine_flags, options=None):
+        """dsm_refine_absolute_poses (RefineAbsolutePose for a batch of problems), on the layout of
+        estimate_absolute_poses.  inlier_mask [T]; qvecs [B, 4]; tvecs [B, 3]; refine_flags [B] (POSE_REFINE_* bits).  Returns a
+        dict: results (a list of PoseRefinementResult), margins [B, 5] (POSE_REFINEMENT_MARGINS), steps (a list of uint8 arrays,
+        POSE_STEP_* per iteration of a problem), report."""
+        B = len(cameras)
+        cams = (Camera * max(B, 1))(*cameras)
+        offs = np.ascontiguousarray(offsets, np.uint64).reshape(-1)
+        p2 = np.ascontiguousarray(points2D, np.float64).reshape(-1, 2)
+        p3 = np.ascontiguousarray(points3D, np.float64).reshape(-1, 3)
+        mask = np.ascontiguousarray(inlier_mask, np.uint8).reshape(-1)
+        q = np.ascontiguousarray(qvecs, np.float64).reshape(-1, 4)
+        t = np.ascontiguousarray(tvecs, np.float64).reshape(-1, 3)
+        flags = np.ascontiguousarray(refine_flags, np.uint8).reshape(-1)
+        if (len(offs) != B + 1 or len(p2) != len(p3) or len(mask) != len(p2) or (B and int(offs[-1]) > len(p2)) or len(q) != B
+                or len(t) != B or len(flags) != B):
+            raise DsmError("refine_absolute_poses: array sizes do not match")
+        o = options if options is not None else default_pose_refinement_options()
+        cap = max(int(o.max_num_iterations), 0)
+        res = (PoseRefinementResult * max(B, 1))()
+        margins = np.zeros((max(B, 1), len(POSE_REFINEMENT_MARGINS)))
+        steps = np.zeros((max(B, 1), max(cap, 1)), np.uint8)
+        rep = PoseRefinementReport()
+        ptr = lambda x: x.ctypes.data
+        self._chk(self._L.dsm_refine_absolute_poses(self._h, B, ctypes.addressof(cams), ptr(offs), ptr(p2), ptr(p3), ptr(mask), ptr(q),
+                                                    ptr(t), ptr(flags), ctypes.byref(o), ctypes.addressof(res), ptr(margins),
+                                                    ptr(steps), ctypes.addressof(rep)))
+        return {"results": [res[b] for b in range(B)], "margins": margins[:B].copy(),
+                "steps": [steps[b, :min(res[b].num_iterations, cap)].copy() for b in range(B)], "report": rep}
+
+    def register_images(self, cameras, offsets, points2D, points3D, estimate_focal_length=None, refine_flags=None,
+                        abs_pose_min_num_inliers=30, pose_options=None, refinement_options=None, seeds=None):
+        """The numerical core of IncrementalMapper::RegisterNextImage (src/sfm/incremental_mapper.cc:438-535) for a batch of images:
+        EstimateAbsolutePose, the abs_pose_min_num_inliers test (incremental_mapper.h:87: 30), RefineAbsolutePose on the estimate's
+        pose and mask.  estimate_focal_length [B] (default: not camera.has_prior_focal_length, as :451-483 chooses without the
+        bogus-parameter history the host keeps); refine_flags [B] (default: focal length and extra parameters).  An image whose
+        estimate failed or found too few inliers is not refined.  Returns a dict: registered [B] bool, qvec [B, 4], tvec [B, 3],
+        camera_params [B, 12], num_inliers [B], inlier_mask [T], estimate (estimate_absolute_poses' dict), refinement
+        (refine_absolute_poses' dict over the images that reached it, or None), refined_index [B] (row in refinement or -1)."""
+        B = len(cameras)
+        offs = np.ascontiguousarray(offsets, np.uint64).reshape(-1)
+        p2 = np.ascontiguousarray(points2D, np.float64).reshape(-1, 2)
+        p3 = np.ascontiguousarray(points3D, np.float64).reshape(-1, 3)
+        est_focal = ([0 if c.has_prior_focal_length else 1 for c in cameras] if estimate_focal_length is None
+                     else [int(f) for f in estimate_focal_length])
+        flags = [POSE_REFINE_FOCAL_LENGTH | POSE_REFINE_EXTRA_PARAMS] * B if refine_flags is None else [int(f) for f in refine_flags]
+        est = self.estimate_absolute_poses(cameras, est_focal, offs, p2, p3, pose_options, seeds)
+        qvec, tvec, prm = np.zeros((B, 4)), np.zeros((B, 3)), np.zeros((B, 12))
+        registered, refined_index = np.zeros(B, bool), -np.ones(B, np.int64)
+        keep, cams2 = [], []
+        for b, r in enumerate(est["results"]):
+            prm[b] = list(cameras[b].params)
+            if not r.success or r.num_inliers < abs_pose_min_num_inliers:
+                continue
+            cam = Camera.from_buffer_copy(bytes(cameras[b]))
+            two = cameras[b].model_id in (1, 4, 5, 6, 7, 10)
+            cam.params[0] = r.focal_params[0]  # the winning factor's focal length (pose.cc:146-151)
+            if two:
+                cam.params[1] = r.focal_params[1]
+            refined_index[b] = len(keep)
+            keep.append(b)
+            cams2.append(cam)
+        ref = None
+        if keep:
+            sub = np.concatenate([[0], np.cumsum([int(offs[b + 1] - offs[b]) for b in keep])]).astype(np.uint64)
+            rows = np.concatenate([np.arange(int(offs[b]), int(offs[b + 1])) for b in keep]).astype(np.int64)
+            ref = self.refine_absolute_poses(cams2, sub, p2[rows], p3[rows], est["inlier_mask"][rows],
+                                             [list(est["results"][b].qvec) for b in keep], [list(est["results"][b].tvec) for b in keep],
+                                             [flags[b] for b in keep], refinement_options)
+            for k, b in enumerate(keep):
+                r = ref["results"][k]
+                registered[b] = bool(r.success)
+                qvec[b], tvec[b], prm[b] = list(r.qvec), list(r.tvec), list(r.camera_params)
+        return {"registered": registered, "qvec": qvec, "tvec": tvec, "camera_params": prm,
+                "num_inliers": np.array([r.num_inliers for r in est["results"]], np.int64), "inlier_mask": est["inlier_mask"],
+                "estimate": est, "refinement": ref, "refined_index": refined_index}
 
     def device_info(self):
         d = DeviceInfo()

@@ -902,6 +902,73 @@ int dsm_estimate_absolute_poses(dsm_ctx* ctx, uint32_t num_problems, const dsm_c
                                 dsm_absolute_pose_result* results_out, uint8_t* inlier_mask_out, double* margins_out,
                                 dsm_absolute_pose_report* report);
 
+/* ------------------------------------------------------------------ absolute pose refinement (image registration, second half)
+ * RefineAbsolutePose (src/estimators/pose.cc:198-311) as IncrementalMapper::RegisterNextImage calls it
+ * (src/sfm/incremental_mapper.cc:498-535) on the pose and the inlier mask of EstimateAbsolutePose, for a batch of independent
+ * problems: BundleAdjustmentCostFunction with the 3D point constant under ceres::CauchyLoss(loss_function_scale),
+ * qvec normalised and moved through QuaternionParameterization, tvec free, the principal point constant, the focal and the
+ * extra parameters free by the problem's flags.  The trust-region rules are DESIGN.md 12's with Ceres' default function (1e-6)
+ * and parameter (1e-8) tolerances and 5 consecutive invalid steps; the damped normal equations are solved by an unpivoted
+ * Cholesky (the reference asks for DENSE_QR).  A result depends on the problem and the options alone. */
+#define DSM_POSE_REFINEMENT_MAX_ITERATIONS 1000u /* max_num_iterations above it is DSM_ERR_INVALID_ARGUMENT: one launch holds the loop */
+#define DSM_POSE_REFINE_FOCAL_LENGTH 1u          /* refine_flags bit 0: AbsolutePoseRefinementOptions::refine_focal_length */
+#define DSM_POSE_REFINE_EXTRA_PARAMS 2u          /* refine_flags bit 1: refine_extra_params */
+typedef struct dsm_pose_refinement_options {
+  double gradient_tolerance;  /* 1.0  AbsolutePoseRefinementOptions, src/estimators/pose.h:82 */
+  double loss_function_scale; /* 1.0  pose.h:88; 0 passes Check() (pose.h:102) but divides by zero: DSM_ERR_INVALID_ARGUMENT */
+  int32_t max_num_iterations; /* 100  pose.h:85 */
+  int32_t reserved;
+} dsm_pose_refinement_options;
+
+typedef struct dsm_pose_refinement_result {
+  int32_t success;               /* RefineAbsolutePose's return value, Solver::Summary::IsSolutionUsable() */
+  int32_t termination;           /* DSM_BA_CONVERGENCE / DSM_BA_NO_CONVERGENCE / DSM_BA_FAILURE */
+  uint32_t num_iterations;       /* every trust-region iteration counts, as in dsm_bundle_adjustment_report */
+  uint32_t num_successful_steps; /* accepted steps */
+  uint32_t num_invalid_steps;
+  uint32_t num_residual_blocks;  /* points with inlier_mask != 0 */
+  double initial_cost, final_cost; /* 1/2 sum rho(|r|^2) */
+  double qvec[4];                /* w x y z, normalised (an empty problem returns the input bits) */
+  double tvec[3];
+  double camera_params[12];      /* the camera's parameters after the call (dsm_camera::params) */
+} dsm_pose_refinement_result;
+
+#define DSM_POSE_REFINEMENT_MARGINS 5
+/* per step in steps_out: 0 not run, then */
+enum { DSM_POSE_STEP_ACCEPTED = 1, DSM_POSE_STEP_REJECTED = 2, DSM_POSE_STEP_INVALID = 3, DSM_POSE_STEP_TOLERANCE = 4 };
+typedef struct dsm_pose_refinement_report {
+  uint32_t num_problems, reserved;
+  uint64_t num_points;     /* offsets[B] */
+  uint64_t num_iterations; /* summed over the problems */
+  /* per problem is the call's margins_out; here the minima over the batch (INFINITY where never taken).  In order:
+     0 acceptance test, in cost: |(cost - candidate) - 1e-3 model_cost_change| / cost   1 gradient test (relative)
+     2 function tolerance (relative)   3 parameter tolerance (relative)   4 Cholesky pivot against 0, relative to the diagonal */
+  double min_margin[DSM_POSE_REFINEMENT_MARGINS];
+  double setup_ms;                          /* host: validation */
+  double upload_ms, solve_ms, download_ms;  /* HIP events: uploads, the kernel, results back */
+  double device_ms;                         /* HIP events: first upload to the last download */
+} dsm_pose_refinement_report;
+
+void dsm_default_pose_refinement_options(dsm_pose_refinement_options* o);
+
+/* Host pointers, the CSR layout of dsm_estimate_absolute_poses (its outputs feed this call without repacking):
+ *   cameras[B], offsets[B + 1], points2D (2 per point, pixels), points3D (3 per point), inlier_mask[offsets[B]] (0 skips the
+ *   point, pose.cc:219-223), qvecs_in[B * 4], tvecs_in[B * 3], refine_flags[B] (DSM_POSE_REFINE_* bits, as
+ *   incremental_mapper.cc:451-483 sets them per image), options (NULL = defaults),
+ *   results_out[B], margins_out (NULL or B * DSM_POSE_REFINEMENT_MARGINS doubles), steps_out (NULL or
+ *   B * max_num_iterations bytes, DSM_POSE_STEP_* per iteration), report (NULL or the sums).
+ * A problem without inliers is not an error: success = 1, zero iterations, qvec / tvec / camera parameters the input bits
+ * (qvec not normalised): Ceres solves the empty problem and calls it usable.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT): NULL where data is needed, non-finite points, poses or camera parameters, an unknown
+ *   camera model, offsets that do not ascend from 0, a problem above DSM_ABSOLUTE_POSE_MAX_POINTS, refine_flags above 3,
+ *   options outside AbsolutePoseRefinementOptions::Check, loss_function_scale = 0, max_num_iterations above
+ *   DSM_POSE_REFINEMENT_MAX_ITERATIONS. */
+int dsm_refine_absolute_poses(dsm_ctx* ctx, uint32_t num_problems, const dsm_camera* cameras, const uint64_t* offsets,
+                              const double* points2D, const double* points3D, const uint8_t* inlier_mask,
+                              const double* qvecs_in, const double* tvecs_in, const uint8_t* refine_flags,
+                              const dsm_pose_refinement_options* options, dsm_pose_refinement_result* results_out,
+                              double* margins_out, uint8_t* steps_out, dsm_pose_refinement_report* report);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
