@@ -255,6 +255,34 @@ class PoseRefinementReport(ctypes.Structure):
                 ("device_ms", ctypes.c_double)]
 
 
+FILTER_NEGATIVE_DEPTH, FILTER_REPROJECTION_ERROR, FILTER_TRIANGULATION_ANGLE, FILTER_MEAN_ERROR = 1, 2, 4, 8
+
+
+class PointFilterOptions(ctypes.Structure):
+    """dsm_point_filter_options: IncrementalMapper::Options' filter_max_reproj_error, filter_min_tri_angle and the three
+    HasBogusParams bounds (src/sfm/incremental_mapper.h:96-108), shared by DistributedMapperController::Options."""
+    _fields_ = [("max_reproj_error", ctypes.c_double), ("min_tri_angle", ctypes.c_double),
+                ("min_focal_length_ratio", ctypes.c_double), ("max_focal_length_ratio", ctypes.c_double),
+                ("max_extra_param", ctypes.c_double), ("passes", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class PointFilterReport(ctypes.Structure):
+    _fields_ = [("num_points", ctypes.c_uint64), ("num_observations", ctypes.c_uint64), ("num_selected", ctypes.c_uint64),
+                ("num_filtered", ctypes.c_uint64 * 4), ("points_deleted", ctypes.c_uint64 * 4),
+                ("observations_deleted", ctypes.c_uint64 * 4), ("num_points_kept", ctypes.c_uint64),
+                ("num_observations_kept", ctypes.c_uint64), ("num_images_filtered", ctypes.c_uint64),
+                ("lane_path_tracks", ctypes.c_uint64), ("wave_path_tracks", ctypes.c_uint64), ("pairs_evaluated", ctypes.c_uint64),
+                ("mean_error_observations", ctypes.c_uint64), ("mean_reprojection_error", ctypes.c_double),
+                ("mean_point_error", ctypes.c_double), ("min_depth_margin", ctypes.c_double), ("min_error_margin", ctypes.c_double),
+                ("min_angle_margin", ctypes.c_double), ("min_bogus_margin", ctypes.c_double), ("setup_ms", ctypes.c_double),
+                ("upload_ms", ctypes.c_double), ("residuals_ms", ctypes.c_double), ("tracks_ms", ctypes.c_double),
+                ("angles_ms", ctypes.c_double), ("compaction_ms", ctypes.c_double), ("download_ms", ctypes.c_double),
+                ("device_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if hasattr(getattr(self, k), "__len__") else getattr(self, k)) for k, _ in self._fields_}
+
+
 def lib(check=False):
     """Loads the shared library (check=True: the check build); raises if it has not been built (no fallback)."""
     if check not in _libs:
@@ -335,6 +363,10 @@ def lib(check=False):
         L.dsm_default_pose_refinement_options.argtypes = [ctypes.POINTER(PoseRefinementOptions)]
         L.dsm_default_pose_refinement_options.restype = None
         L.dsm_refine_absolute_poses.argtypes = [vp, ctypes.c_uint32] + [vp] * 8 + [ctypes.POINTER(PoseRefinementOptions)] + [vp] * 4
+        L.dsm_default_point_filter_options.argtypes = [ctypes.POINTER(PointFilterOptions)]
+        L.dsm_default_point_filter_options.restype = None
+        L.dsm_filter_points3D.argtypes = ([vp, ctypes.c_uint32, vp, ctypes.c_uint32] + [vp] * 4 + [ctypes.c_uint32] + [vp] * 6
+                                          + [ctypes.POINTER(PointFilterOptions)] + [vp] * 7)
         L.dsm_debug_image_to_world.argtypes = [vp, ctypes.POINTER(Camera), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double)]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
@@ -435,6 +467,14 @@ def default_absolute_pose_options(**kw):
 def default_pose_refinement_options(**kw):
     o = PoseRefinementOptions()
     lib().dsm_default_pose_refinement_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_point_filter_options(**kw):
+    o = PointFilterOptions()
+    lib().dsm_default_point_filter_options(ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -901,6 +941,76 @@ class Context:
         out = {"camera_params": params, "qvec": qvec, "tvec": tvec, "xyz": xyz, "report": rep}
         if trace:
             out["trace"] = tr[:rep.num_iterations + 1].copy()
+        return out
+
+    def filter_points3D(self, scene, passes=None, point_selected=None, image_selected=None, **options):
+        """dsm_filter_points3D.  scene: the dict of bundle_adjust (camera_model_ids, camera_params, image_camera,
+        qvec, tvec, xyz, track_offsets, obs_image, obs_xy), optionally with camera_width / camera_height [C] (they feed the bogus
+        test of the image verdict; without them the principal point is taken as the image centre: width = 2 cx, height = 2 cy)
+        and image_registered [N].  passes: FILTER_* bits (None = the default 2 | 4); options: fields of PointFilterOptions.
+        point_selected [P] / image_selected [N]: the selection (both None = every point; image_selected alone selects the points
+        seen in those images).  Returns a dict: point_keep [P] (bool), obs_keep [n] (bool), point_error [P] (-1 = none),
+        kept_track_offsets [P + 1], kept_obs [kept], image_filtered [N] (bool), camera_sizes_given (False: the sizes behind
+        image_filtered and min_bogus_margin were made up as above -- pass camera_width / camera_height where that verdict is to
+        be trusted), report."""
+        a = lambda key, dt, shape=-1: np.ascontiguousarray(scene[key], dt).reshape(shape)
+        models, params = a("camera_model_ids", np.int32), a("camera_params", np.float64)
+        C = len(models)
+        cams = (Camera * max(C, 1))()
+        at = 0
+        sizes_given = scene.get("camera_width") is not None and scene.get("camera_height") is not None
+        for c in range(C):
+            m = int(models[c])
+            k = CAMERA_MODEL_NUM_PARAMS[m] if 0 <= m < len(CAMERA_MODEL_NUM_PARAMS) else 0
+            pr = params[at:at + k]
+            at += k
+            pp = 2 if m in (1, 4, 5, 6, 7, 10) else 1
+            if sizes_given:
+                w, h = int(scene["camera_width"][c]), int(scene["camera_height"][c])
+            else:
+                w, h = (max(int(np.ceil(2 * pr[pp])), 0), max(int(np.ceil(2 * pr[pp + 1])), 0)) if k and np.isfinite(pr[pp:pp + 2]).all() else (0, 0)
+            cams[c] = camera(m, pr, w, h)
+        icam = a("image_camera", np.uint32)
+        N = len(icam)
+        qvec, tvec = a("qvec", np.float64, (N, 4)), a("tvec", np.float64, (N, 3))
+        xyz = a("xyz", np.float64, (-1, 3))
+        P = len(xyz)
+        toff = a("track_offsets", np.uint32)
+        oimg, oxy = a("obs_image", np.uint32), a("obs_xy", np.float64, (-1, 2))
+        n = len(oimg)
+        u8 = lambda v, k: None if v is None else np.ascontiguousarray(np.asarray(v) != 0, np.uint8).reshape(k)
+        reg, psel, isel = u8(scene.get("image_registered"), N), u8(point_selected, P), u8(image_selected, N)
+        if isel is not None and psel is None:
+            psel = np.zeros(P, np.uint8)
+        o = default_point_filter_options(**options)
+        if passes is not None:
+            o.passes = int(passes)
+        pkeep, okeep, perr = np.zeros(max(P, 1), np.uint8), np.zeros(max(n, 1), np.uint8), np.full(max(P, 1), -1.0)
+        koff, kobs, ifilt = np.zeros(P + 1, np.uint32), np.zeros(max(n, 1), np.uint32), np.zeros(max(N, 1), np.uint8)
+        rep = PointFilterReport()
+        ptr = lambda x: None if x is None else x.ctypes.data
+        self._chk(self._L.dsm_filter_points3D(self._h, C, ctypes.addressof(cams), N, ptr(icam), ptr(qvec), ptr(tvec), ptr(reg), P, ptr(xyz),
+                                              ptr(toff), ptr(oimg), ptr(oxy), ptr(psel), ptr(isel), ctypes.byref(o), ptr(pkeep), ptr(okeep),
+                                              ptr(perr), ptr(koff), ptr(kobs), ptr(ifilt), ctypes.addressof(rep)))
+        return {"point_keep": pkeep[:P].astype(bool), "obs_keep": okeep[:n].astype(bool), "point_error": perr[:P].copy(),
+                "kept_track_offsets": koff, "kept_obs": kobs[:int(koff[P])].copy(), "image_filtered": ifilt[:N].astype(bool),
+                "camera_sizes_given": sizes_given, "report": rep}
+
+    @staticmethod
+    def apply_point_filter(scene, result):
+        """The scene dict reduced to the survivors of a filter_points3D result, ready for bundle_adjust: the points that are
+        kept, their compacted tracks, the per-point arrays gathered; cameras and images as they are."""
+        keep = np.asarray(result["point_keep"], bool)
+        koff = np.asarray(result["kept_track_offsets"], np.int64)
+        kobs = np.asarray(result["kept_obs"], np.int64)
+        out = dict(scene)
+        out["track_offsets"] = np.concatenate([[0], np.cumsum((koff[1:] - koff[:-1])[keep])]).astype(np.uint32)
+        out["obs_image"] = np.ascontiguousarray(scene["obs_image"], np.uint32).reshape(-1)[kobs]
+        out["obs_xy"] = np.ascontiguousarray(scene["obs_xy"], np.float64).reshape(-1, 2)[kobs]
+        out["xyz"] = np.ascontiguousarray(scene["xyz"], np.float64).reshape(-1, 3)[keep]
+        for key in ("point_ids", "point_constant"):
+            if scene.get(key) is not None:
+                out[key] = np.asarray(scene[key])[keep]
         return out
 
     def retriangulate(self, scene, separators, options=None, next_point3D_id=0):

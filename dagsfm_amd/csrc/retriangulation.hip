@@ -34,6 +34,7 @@
 #include <string>
 #include <vector>
 
+#include "camera_bogus.h"
 #include "ctx.h"
 #include "verify_camera.h"
 #include "verify_linalg.h"
@@ -568,27 +569,6 @@ __global__ void k_rt_apply(uint32_t R, const uint32_t* __restrict__ run, const u
     if (assign[slot + i] >= 0) pid[clist[slot + i]] = (int32_t)(prm.num_points + slot + (uint32_t)assign[slot + i]);
 }
 
-// CameraModelHasBogusParams (camera_models.h:473-528) with its smallest margin: the ratio tests relative to their bounds
-bool rt_bogus(const dsm_camera& c, double min_ratio, double max_ratio, double max_extra, double* margin) {
-  const int id = c.model_id;
-  const bool two = cam_two_focal(id);
-  const int pp = two ? 2 : 1, nf = two ? 2 : 1;
-  const double cx = c.params[pp], cy = c.params[pp + 1];
-  if (cx < 0 || cx > (double)c.width || cy < 0 || cy > (double)c.height) return true;
-  const double max_size = (double)std::max(c.width, c.height);
-  for (int i = 0; i < nf; ++i) {
-    const double ratio = c.params[i] / max_size;
-    *margin = std::min({*margin, std::fabs(ratio - min_ratio) / min_ratio, std::fabs(ratio - max_ratio) / max_ratio});
-    if (ratio < min_ratio || ratio > max_ratio) return true;
-  }
-  const int first_extra = (id == 0 || id == 1) ? cam_num_params(id) : (two ? 4 : 3);
-  for (int i = first_extra; i < cam_num_params(id); ++i) {
-    if (max_extra > 0) *margin = std::min(*margin, std::fabs(std::fabs(c.params[i]) - max_extra) / max_extra);
-    if (std::fabs(c.params[i]) > max_extra) return true;
-  }
-  return false;
-}
-
 // ComputeNumTrials (ransac.h:151-167) for every (n, inliers), clamped to 32 bits; ceil(-inf) (no inlier) -> never abort
 uint32_t rt_num_trials(uint32_t k, uint32_t n, double confidence) {
   const double ratio = k / static_cast<double>(n);
@@ -701,7 +681,7 @@ extern "C" int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint3
     if (!cam_model_exists(k.model_id)) return fail("an unknown camera model");
     for (int i = 0; i < cam_num_params(k.model_id); ++i)
       if (!std::isfinite(k.params[i])) return fail("non-finite camera parameters");
-    cam_bogus[c] = rt_bogus(k, o.min_focal_length_ratio, o.max_focal_length_ratio, o.max_extra_param, &rep.min_bogus_margin);
+    cam_bogus[c] = cam_has_bogus_params(k, o.min_focal_length_ratio, o.max_focal_length_ratio, o.max_extra_param, &rep.min_bogus_margin);
   }
   auto find_cam = [&](uint32_t id) -> int64_t {
     auto it = std::lower_bound(cam_order.begin(), cam_order.end(), id, [&](uint32_t a, uint32_t v) { return camera_ids[a] < v; });

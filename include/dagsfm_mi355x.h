@@ -969,6 +969,88 @@ int dsm_refine_absolute_poses(dsm_ctx* ctx, uint32_t num_problems, const dsm_cam
                               const dsm_pose_refinement_options* options, dsm_pose_refinement_result* results_out,
                               double* margins_out, uint8_t* steps_out, dsm_pose_refinement_report* report);
 
+/* ------------------------------------------------------------------ point and observation filters
+ * Reconstruction::FilterObservationsWithNegativeDepth, FilterPoints3DWithLargeReprojectionError,
+ * FilterPoints3DWithSmallTriangulationAngle, ComputeMeanReprojectionError(track_ids) and the verdict of FilterImages
+ * (src/base/reconstruction.cc:728-770, 814-858, 1352-1465) in one call, on the arrays of dsm_bundle_adjust.
+ * The passes named by `passes` run in the order of their bits; each works on the survivors of the one before it:
+ *   DSM_FILTER_NEGATIVE_DEPTH      an observation with row 2 of the projection matrix . (X, 1) < DBL_EPSILON goes; a point that
+ *                                  would be left with fewer than two observations goes as a whole (DeleteObservation)
+ *   DSM_FILTER_REPROJECTION_ERROR  observations above max_reproj_error^2 go; a point shorter than 2, or left with one
+ *                                  observation or none, goes; a surviving point's error = mean |r| over the kept observations
+ *   DSM_FILTER_TRIANGULATION_ANGLE a point none of whose pairs of views reaches min_tri_angle goes
+ *   DSM_FILTER_MEAN_ERROR          deletes nothing: every selected surviving point's error = sum |r| over the observations in
+ *                                  front of the camera / track length, and the mean over all of them
+ * FilterAllPoints3D / FilterPoints3D / FilterPoints3DInImages = passes 2 | 4 with a selection; the prelude of
+ * AdjustGlobalBundle = pass 1; the RMSE lines = pass 8. */
+enum {
+  DSM_FILTER_NEGATIVE_DEPTH = 1,
+  DSM_FILTER_REPROJECTION_ERROR = 2,
+  DSM_FILTER_TRIANGULATION_ANGLE = 4,
+  DSM_FILTER_MEAN_ERROR = 8
+};
+
+typedef struct dsm_point_filter_options {
+  double max_reproj_error;       /* 4.0 pixels (IncrementalMapper::Options::filter_max_reproj_error); >= 0 */
+  double min_tri_angle;          /* 1.5 degrees (filter_min_tri_angle); >= 0 */
+  double min_focal_length_ratio; /* 0.1  (HasBogusParams, incremental_mapper.h:106-108); >= 0 */
+  double max_focal_length_ratio; /* 10.0 */
+  double max_extra_param;        /* 1.0 */
+  uint32_t passes;               /* DSM_FILTER_* bits, 1 .. 15; the default is 2 | 4 */
+  uint32_t reserved;
+} dsm_point_filter_options;
+
+typedef struct dsm_point_filter_report {
+  uint64_t num_points, num_observations;  /* the input's */
+  uint64_t num_selected;                  /* points the selection names */
+  /* per pass, in bit order (the fourth deletes nothing): the reference function's return value, points deleted,
+     observations deleted (those of the deleted points included) */
+  uint64_t num_filtered[4], points_deleted[4], observations_deleted[4];
+  uint64_t num_points_kept, num_observations_kept;
+  uint64_t num_images_filtered;
+  uint64_t lane_path_tracks, wave_path_tracks; /* points served by a lane / by a one-wave workgroup (by input track length) */
+  uint64_t pairs_evaluated;                    /* triangulation angles computed */
+  uint64_t mean_error_observations;            /* the divisor of mean_reprojection_error */
+  double mean_reprojection_error; /* pass 8: ComputeMeanReprojectionError(track_ids); NaN when nothing is selected or pass 8 did not run */
+  double mean_point_error;        /* ComputeMeanReprojectionError(): the mean of the surviving points' errors that are set; 0 for none */
+  /* the smallest relative margin |a - t| / max(|a|, |t|) of every decision rounding can flip (INFINITY when never taken):
+     depth against DBL_EPSILON, e^2 against max_reproj_error^2, the deciding triangulation angles against min_tri_angle (a kept
+     point: its first passing pair in the reference's order; a deleted point: every pair), the bogus ratios against their bounds */
+  double min_depth_margin, min_error_margin, min_angle_margin, min_bogus_margin;
+  double setup_ms;  /* host validation and the path bins (host clock) */
+  double upload_ms, residuals_ms, tracks_ms, angles_ms, compaction_ms, download_ms; /* HIP events */
+  double device_ms; /* HIP events: first upload to the last download */
+} dsm_point_filter_report;
+
+void dsm_default_point_filter_options(dsm_point_filter_options* o);
+
+/* The filters over a reconstruction (host pointers; indices as in dsm_bundle_adjust).  n = track_offsets[num_points] below.
+ *   cameras[num_cameras] (the eleven models; width and height feed the bogus test)
+ *   images: image_camera[num_images], image_qvec (4 each, w x y z), image_tvec (3 each), image_registered (NULL = all)
+ *   points: point_xyz (3 each), track_offsets[num_points + 1], obs_image[n], obs_xy[2 n]
+ *   selection, fixed from the input before the first pass: point_selected[num_points] (NULL = all), image_selected[num_images]
+ *     (NULL = none); a point is selected when its flag is set or one of its observations lies in a selected image.
+ *     DSM_FILTER_REPROJECTION_ERROR, DSM_FILTER_TRIANGULATION_ANGLE and DSM_FILTER_MEAN_ERROR leave an unselected point
+ *     untouched; DSM_FILTER_NEGATIVE_DEPTH ignores the selection (the reference's pass has none)
+ *   options NULL = dsm_default_point_filter_options
+ * Outputs, each may be NULL: point_keep[num_points], obs_keep[n] (0 / 1; 0 for every observation of a deleted point),
+ *   point_error[num_points] (-1.0 = no error, Point3D::HasError; a deleted point carries -1.0), kept_track_offsets[num_points + 1]
+ *   and kept_obs[n]: the surviving tracks compacted (a deleted point has an empty segment; kept_obs holds indices into the input
+ *   observations, in track order, kept_track_offsets[num_points] of them), image_filtered[num_images] (1 for a registered image
+ *   that observes no surviving point or whose camera has bogus parameters), report.
+ * Tracks of length 0 and 1 are not refused (the passes delete them as the reference does).
+ * Invalid (DSM_ERR_INVALID_ARGUMENT): NULL where data is needed, offsets that do not ascend from 0, an index out of range, an
+ *   unknown camera model, non-finite input, a zero qvec, an observation in an image flagged unregistered, passes 0 or above 15,
+ *   a negative or non-finite threshold.
+ * A point's results depend on that point, its images and the options alone, not on the batch or the order of the points. */
+int dsm_filter_points3D(dsm_ctx* ctx, uint32_t num_cameras, const dsm_camera* cameras, uint32_t num_images,
+                        const uint32_t* image_camera, const double* image_qvec, const double* image_tvec,
+                        const uint8_t* image_registered, uint32_t num_points, const double* point_xyz,
+                        const uint32_t* track_offsets, const uint32_t* obs_image, const double* obs_xy,
+                        const uint8_t* point_selected, const uint8_t* image_selected, const dsm_point_filter_options* options,
+                        uint8_t* point_keep, uint8_t* obs_keep, double* point_error, uint32_t* kept_track_offsets,
+                        uint32_t* kept_obs, uint8_t* image_filtered, dsm_point_filter_report* report);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
