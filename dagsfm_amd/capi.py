@@ -283,6 +283,44 @@ class PointFilterReport(ctypes.Structure):
         return {k: (list(getattr(self, k)) if hasattr(getattr(self, k), "__len__") else getattr(self, k)) for k, _ in self._fields_}
 
 
+LOSS_TRIVIAL, LOSS_SOFT_L1, LOSS_CAUCHY = 0, 1, 2
+LOCAL_BUNDLE_MARGINS = ("acceptance", "gradient", "pivot", "point_pivot")
+LOCAL_BUNDLE_MAX_REDUCED_DIM = 128
+LOCAL_BUNDLE_MAX_ITERATIONS = 1000
+LOCAL_BUNDLE_TRACE_COLUMNS = 5  # cost, radius, rho, accepted, gradient max-norm
+
+
+class LocalBundleOptions(ctypes.Structure):
+    """dsm_local_bundle_options: IncrementalMapperOptions::LocalBundleAdjustment()
+    (src/controllers/incremental_mapper_controller.cc:234-255)."""
+    _fields_ = [("max_num_iterations", ctypes.c_int32), ("max_num_consecutive_invalid_steps", ctypes.c_int32),
+                ("gradient_tolerance", ctypes.c_double), ("function_tolerance", ctypes.c_double),
+                ("parameter_tolerance", ctypes.c_double), ("refine_focal_length", ctypes.c_int32),
+                ("refine_principal_point", ctypes.c_int32), ("refine_extra_params", ctypes.c_int32),
+                ("loss_function_type", ctypes.c_int32), ("loss_function_scale", ctypes.c_double)]
+
+
+class LocalBundleResult(ctypes.Structure):
+    _fields_ = [("solved", ctypes.c_int32), ("termination", ctypes.c_int32), ("num_iterations", ctypes.c_uint32),
+                ("num_successful_steps", ctypes.c_uint32), ("num_invalid_steps", ctypes.c_uint32), ("reduced_dim", ctypes.c_uint32),
+                ("num_residuals", ctypes.c_uint64), ("num_effective_parameters", ctypes.c_uint64),
+                ("initial_cost", ctypes.c_double), ("final_cost", ctypes.c_double),
+                ("initial_mean_reprojection_error", ctypes.c_double), ("final_mean_reprojection_error", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class LocalBundleReport(ctypes.Structure):
+    _fields_ = [("num_problems", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("num_points", ctypes.c_uint64),
+                ("num_observations", ctypes.c_uint64), ("num_iterations", ctypes.c_uint64), ("min_margin", ctypes.c_double * 4),
+                ("setup_ms", ctypes.c_double), ("upload_ms", ctypes.c_double), ("solve_ms", ctypes.c_double),
+                ("download_ms", ctypes.c_double), ("device_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if hasattr(getattr(self, k), "__len__") else getattr(self, k)) for k, _ in self._fields_}
+
+
 def lib(check=False):
     """Loads the shared library (check=True: the check build); raises if it has not been built (no fallback)."""
     if check not in _libs:
@@ -367,6 +405,9 @@ def lib(check=False):
         L.dsm_default_point_filter_options.restype = None
         L.dsm_filter_points3D.argtypes = ([vp, ctypes.c_uint32, vp, ctypes.c_uint32] + [vp] * 4 + [ctypes.c_uint32] + [vp] * 6
                                           + [ctypes.POINTER(PointFilterOptions)] + [vp] * 7)
+        L.dsm_default_local_bundle_options.argtypes = [ctypes.POINTER(LocalBundleOptions)]
+        L.dsm_default_local_bundle_options.restype = None
+        L.dsm_adjust_local_bundles.argtypes = [vp, ctypes.c_uint32] + [vp] * 18 + [ctypes.POINTER(LocalBundleOptions)] + [vp] * 4
         L.dsm_debug_image_to_world.argtypes = [vp, ctypes.POINTER(Camera), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double)]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
@@ -478,6 +519,117 @@ def default_point_filter_options(**kw):
     for k, v in kw.items():
         setattr(o, k, v)
     return o
+
+
+def default_local_bundle_options(**kw):
+    o = LocalBundleOptions()
+    lib().dsm_default_local_bundle_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def local_bundle_problem(scene, image_id, local_bundle, variable_point_ids, fixed_image_ids=()):
+    """Cuts the problem of IncrementalMapper::AdjustLocalBundle (src/sfm/incremental_mapper.cc:562-656) out of a reconstruction
+    scene, exactly as BundleAdjuster::SetUp (src/optim/bundle_adjustment.cc:316-526) builds it.  Pure host code.
+
+    scene: the dict of Context.bundle_adjust (image and point *indices* stand for the reference's ids; point_ids optional).
+    image_id: the new image; local_bundle: its neighbours in FindLocalBundle's order (best connected first);
+    variable_point_ids: indices of the points AddVariablePoint names -- the caller applies the selection of :611-619
+    (`!HasError() || Track().Length() <= 15`), because it needs Point3D::error, which a scene does not carry;
+    fixed_image_ids: the mapper's fix_existing_images path (:584-590): a neighbour listed there becomes constant-pose.
+
+    - config images: image_id + local_bundle.  Gauge (:592-604): one neighbour -> its pose constant and tvec[0] of image_id
+      constant; more -> the last neighbour's pose constant and tvec[0] of the one before it constant unless it is fixed.
+    - every point seen from a config image enters with its observations in config images (AddImageToProblem);
+    - a variable point additionally brings its observations from outside images as constant-pose images, whose cameras are
+      camera_constant unless a config image with observations shares them (AddPointToProblem, :423-470);
+    - a point that is not variable and whose track is not fully inside the problem is point_constant (ParameterizePoints);
+      one whose track is fully inside stays variable.
+
+    Returns a problem dict for Context.adjust_local_bundles (the scene layout plus camera_constant) with the maps back:
+    image_index [n], camera_index [c], point_index [p] into the scene.  An empty local_bundle returns None (the mapper skips
+    the adjustment)."""
+    local_bundle = [int(i) for i in local_bundle]
+    if not local_bundle:
+        return None
+    image_id = int(image_id)
+    config = [image_id] + local_bundle
+    if len(set(config)) != len(config):
+        raise DsmError("local_bundle_problem: image_id and local_bundle must be distinct images")
+    fixed = set(int(i) for i in fixed_image_ids)
+    variable = set(int(p) for p in variable_point_ids)
+    const_pose = set(i for i in local_bundle if i in fixed)
+    const_tvec0 = set()
+    if len(local_bundle) == 1:
+        const_pose.add(local_bundle[0])
+        const_tvec0.add(image_id)
+    else:
+        const_pose.add(local_bundle[-1])
+        if local_bundle[-2] not in fixed:
+            const_tvec0.add(local_bundle[-2])
+    icam = np.asarray(scene["image_camera"], np.int64).reshape(-1)
+    toff = np.asarray(scene["track_offsets"], np.int64).reshape(-1)
+    oimg = np.asarray(scene["obs_image"], np.int64).reshape(-1)
+    oxy = np.asarray(scene["obs_xy"], np.float64).reshape(-1, 2)
+    P = len(toff) - 1
+    in_config = np.zeros(len(icam), bool)
+    in_config[config] = True
+    images, img_new = [], {}
+
+    def image_slot(i):
+        if i not in img_new:
+            img_new[i] = len(images)
+            images.append(i)
+        return img_new[i]
+
+    for i in config:
+        image_slot(i)
+    points, tracks, pconst = [], [], []
+    cams_with_config_obs = set()
+    for p in range(P):
+        el = range(int(toff[p]), int(toff[p + 1]))
+        inside = [k for k in el if in_config[oimg[k]]]
+        if not inside and p not in variable:
+            continue  # (a variable point no config image sees enters through AddPointToProblem with constant poses only)
+        for k in inside:
+            cams_with_config_obs.add(int(icam[oimg[k]]))
+        take = list(el) if p in variable else inside
+        points.append(p)
+        tracks.append(take)
+        pconst.append(0 if len(take) == len(el) else 1)  # ParameterizePoints: Track().Length() > observations in the problem
+    outside = []
+    for take in tracks:
+        for k in take:
+            if not in_config[oimg[k]] and int(oimg[k]) not in img_new:
+                outside.append(int(oimg[k]))
+                image_slot(int(oimg[k]))
+    cams, cam_new = [], {}
+    for i in images:
+        c = int(icam[i])
+        if c not in cam_new:
+            cam_new[c] = len(cams)
+            cams.append(c)
+    models = np.asarray(scene["camera_model_ids"], np.int32).reshape(-1)
+    poff = np.concatenate([[0], np.cumsum([CAMERA_MODEL_NUM_PARAMS[m] for m in models])]).astype(np.int64)
+    params = np.asarray(scene["camera_params"], np.float64).reshape(-1)
+    qvec = np.asarray(scene["qvec"], np.float64).reshape(-1, 4)
+    tvec = np.asarray(scene["tvec"], np.float64).reshape(-1, 3)
+    xyz = np.asarray(scene["xyz"], np.float64).reshape(-1, 3)
+    ids = np.asarray(scene["point_ids"], np.uint64).reshape(-1) if scene.get("point_ids") is not None else np.arange(P, dtype=np.uint64)
+    cpose = np.array([1 if (i in const_pose or not in_config[i]) else 0 for i in images], np.uint8)
+    cmask = np.array([1 if i in const_tvec0 else 0 for i in images], np.uint8)
+    return {"camera_model_ids": models[cams].copy(),
+            "camera_params": np.concatenate([params[poff[c]:poff[c + 1]] for c in cams]) if cams else np.zeros(0),
+            "camera_constant": np.array([0 if c in cams_with_config_obs else 1 for c in cams], np.uint8),
+            "image_camera": np.array([cam_new[int(icam[i])] for i in images], np.uint32),
+            "qvec": qvec[images].copy(), "tvec": tvec[images].copy(), "image_constant_pose": cpose, "image_constant_tvec": cmask,
+            "point_ids": ids[points].copy(), "xyz": xyz[points].copy(), "point_constant": np.array(pconst, np.uint8),
+            "track_offsets": np.concatenate([[0], np.cumsum([len(t) for t in tracks])]).astype(np.uint32),
+            "obs_image": np.array([img_new[int(oimg[k])] for t in tracks for k in t], np.uint32),
+            "obs_xy": (np.concatenate([oxy[t] for t in tracks]) if tracks else np.zeros((0, 2))).reshape(-1, 2),
+            "image_index": np.array(images, np.int64), "camera_index": np.array(cams, np.int64),
+            "point_index": np.array(points, np.int64)}
 
 
 def absolute_pose_seed(problem, factor_index, user_seed=0):
@@ -1110,6 +1262,71 @@ class Context:
                                                     ptr(steps), ctypes.addressof(rep)))
         return {"results": [res[b] for b in range(B)], "margins": margins[:B].copy(),
                 "steps": [steps[b, :min(res[b].num_iterations, cap)].copy() for b in range(B)], "report": rep}
+
+    def adjust_local_bundles(self, problems, options=None, trace=True):
+        """dsm_adjust_local_bundles: a batch of independent local bundle adjustments in one launch.  problems: a
+        list of dicts in bundle_adjust's scene layout plus camera_constant [C] (optional), e.g. from capi.local_bundle_problem;
+        a track of length 1 is accepted.  The inputs are not modified.  Returns a dict: problems (a list of dicts with
+        camera_params, qvec, tvec, xyz updated, result (LocalBundleResult), margins (a dict by LOCAL_BUNDLE_MARGINS), trace
+        [iterations + 1, 5]: cost, radius, rho, accepted, gradient max-norm) and report (LocalBundleReport)."""
+        B = len(problems)
+        o = options if options is not None else default_local_bundle_options()
+        cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0), dt).reshape(-1)
+        arr = lambda pr, key, dt: np.asarray(pr[key], dt).reshape(-1)
+        flag = lambda pr, key, n: np.zeros(n, np.uint8) if pr.get(key) is None else np.asarray(pr[key], np.uint8).reshape(n)
+        nC = [len(arr(pr, "camera_model_ids", np.int32)) for pr in problems]
+        nI = [len(arr(pr, "image_camera", np.uint32)) for pr in problems]
+        nP = [len(arr(pr, "track_offsets", np.uint32)) - 1 for pr in problems]
+        nO = [len(arr(pr, "obs_image", np.uint32)) for pr in problems]
+        for b, pr in enumerate(problems):
+            ids = pr.get("point_ids")
+            mids = arr(pr, "camera_model_ids", np.int32)
+            if all(0 <= m < len(CAMERA_MODEL_NUM_PARAMS) for m in mids):  # (an unknown model is refused by the library before it reads a parameter)
+                if len(arr(pr, "camera_params", np.float64)) != sum(CAMERA_MODEL_NUM_PARAMS[m] for m in mids):
+                    raise DsmError("adjust_local_bundles: camera_params of problem %d does not hold its models' parameter counts" % b)
+            if (len(arr(pr, "qvec", np.float64)) != 4 * nI[b] or len(arr(pr, "tvec", np.float64)) != 3 * nI[b]
+                    or len(arr(pr, "xyz", np.float64)) != 3 * nP[b] or len(arr(pr, "obs_xy", np.float64)) != 2 * nO[b]
+                    or (ids is not None and len(np.asarray(ids).reshape(-1)) != nP[b])):
+                raise DsmError("adjust_local_bundles: array sizes of problem %d do not match" % b)
+        off = lambda n, dt: np.concatenate([[0], np.cumsum(n)]).astype(dt)
+        coff, ioff, poff, ooff = off(nC, np.uint32), off(nI, np.uint32), off(nP, np.uint32), off(nO, np.uint64)
+        models = cat([arr(pr, "camera_model_ids", np.int32) for pr in problems], np.int32)
+        params = cat([arr(pr, "camera_params", np.float64) for pr in problems], np.float64).copy()
+        cconst = cat([flag(pr, "camera_constant", nC[b]) for b, pr in enumerate(problems)], np.uint8)
+        icam = cat([arr(pr, "image_camera", np.uint32) for pr in problems], np.uint32)
+        qvec = cat([arr(pr, "qvec", np.float64) for pr in problems], np.float64).copy()
+        tvec = cat([arr(pr, "tvec", np.float64) for pr in problems], np.float64).copy()
+        cpose = cat([flag(pr, "image_constant_pose", nI[b]) for b, pr in enumerate(problems)], np.uint8)
+        cmask = cat([flag(pr, "image_constant_tvec", nI[b]) for b, pr in enumerate(problems)], np.uint8)
+        pids = cat([np.arange(nP[b], dtype=np.uint64) if pr.get("point_ids") is None else arr(pr, "point_ids", np.uint64)
+                    for b, pr in enumerate(problems)], np.uint64)
+        xyz = cat([arr(pr, "xyz", np.float64) for pr in problems], np.float64).copy()
+        pconst = cat([flag(pr, "point_constant", nP[b]) for b, pr in enumerate(problems)], np.uint8)
+        toff = cat([arr(pr, "track_offsets", np.uint32) for pr in problems], np.uint32)
+        oimg = cat([arr(pr, "obs_image", np.uint32) for pr in problems], np.uint32)
+        oxy = cat([arr(pr, "obs_xy", np.float64) for pr in problems], np.float64)
+        rows = max(int(o.max_num_iterations), 0) + 1
+        res = (LocalBundleResult * max(B, 1))()
+        margins = np.zeros((max(B, 1), len(LOCAL_BUNDLE_MARGINS)))
+        tr = np.full((max(B, 1), rows, LOCAL_BUNDLE_TRACE_COLUMNS), np.nan) if trace else None
+        rep = LocalBundleReport()
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._chk(self._L.dsm_adjust_local_bundles(self._h, B, ptr(coff), ptr(models), ptr(params), ptr(cconst), ptr(ioff), ptr(icam),
+                                                   ptr(qvec), ptr(tvec), ptr(cpose), ptr(cmask), ptr(poff), ptr(pids), ptr(xyz),
+                                                   ptr(pconst), ptr(toff), ptr(ooff), ptr(oimg), ptr(oxy), ctypes.byref(o),
+                                                   ctypes.addressof(res), ptr(margins), ptr(tr), ctypes.addressof(rep)))
+        out, pa = [], 0
+        for b, pr in enumerate(problems):
+            npar = sum(CAMERA_MODEL_NUM_PARAMS[m] for m in models[coff[b]:coff[b + 1]])
+            r = LocalBundleResult.from_buffer_copy(bytes(res[b]))
+            d = {"camera_params": params[pa:pa + npar].copy(), "qvec": qvec.reshape(-1, 4)[ioff[b]:ioff[b + 1]].copy(),
+                 "tvec": tvec.reshape(-1, 3)[ioff[b]:ioff[b + 1]].copy(), "xyz": xyz.reshape(-1, 3)[poff[b]:poff[b + 1]].copy(),
+                 "result": r, "margins": dict(zip(LOCAL_BUNDLE_MARGINS, margins[b].tolist()))}
+            if trace:
+                d["trace"] = tr[b, :min(int(r.num_iterations) + 1, rows)].copy() if r.solved else tr[b, :0].copy()
+            pa += npar
+            out.append(d)
+        return {"problems": out, "report": rep}
 
     def register_images(self, cameras, offsets, points2D, points3D, estimate_focal_length=None, refine_flags=None,
                         abs_pose_min_num_inliers=30, pose_options=None, refinement_options=None, seeds=None):

@@ -1051,6 +1051,92 @@ int dsm_filter_points3D(dsm_ctx* ctx, uint32_t num_cameras, const dsm_camera* ca
                         uint8_t* point_keep, uint8_t* obs_keep, double* point_error, uint32_t* kept_track_offsets,
                         uint32_t* kept_obs, uint8_t* image_filtered, dsm_point_filter_report* report);
 
+/* ------------------------------------------------------------------ local bundle adjustment (inside every cluster's mapper)
+ * IncrementalMapper::AdjustLocalBundle (src/sfm/incremental_mapper.cc:562-656): BundleAdjuster::Solve() over the new image and
+ * its best-connected neighbours with IncrementalMapperOptions::LocalBundleAdjustment()
+ * (src/controllers/incremental_mapper_controller.cc:234-255), for a batch of independent problems.  Residual,
+ * parameterisations, trust region and termination order are dsm_bundle_adjust's; additionally a robust loss
+ * (Ceres' Corrector, first branch: rho'' < 0 for both losses), cameras held constant per camera, and the DENSE_SCHUR branch the
+ * reference takes up to 50 images (bundle_adjustment.cc:274-278): the points are eliminated, the reduced camera system is formed
+ * explicitly and factored by an unpivoted Cholesky.  One workgroup per problem runs the whole loop in one launch. */
+#define DSM_LOCAL_BUNDLE_MAX_REDUCED_DIM 128u   /* columns of the reduced camera system of one problem; more is DSM_ERR_INVALID_ARGUMENT */
+#define DSM_LOCAL_BUNDLE_MAX_ITERATIONS 1000u   /* max_num_iterations above it is DSM_ERR_INVALID_ARGUMENT: one launch holds the loop */
+enum { DSM_LOSS_TRIVIAL = 0, DSM_LOSS_SOFT_L1 = 1, DSM_LOSS_CAUCHY = 2 };  /* BundleAdjustmentOptions::LossFunctionType */
+
+typedef struct dsm_local_bundle_options {
+  int32_t max_num_iterations;                /* 25   ba_local_max_num_iterations, incremental_mapper_controller.h; :240 */
+  int32_t max_num_consecutive_invalid_steps; /* 10   (dsm_bundle_adjustment_options' value) */
+  double gradient_tolerance;                 /* 10.0 incremental_mapper_controller.cc:238 */
+  double function_tolerance;                 /* 0    :237 */
+  double parameter_tolerance;                /* 0    :239 */
+  int32_t refine_focal_length;               /* 1    :248 (ba_refine_focal_length) */
+  int32_t refine_principal_point;            /* 0    :249 */
+  int32_t refine_extra_params;               /* 1    :250 */
+  int32_t loss_function_type;                /* DSM_LOSS_SOFT_L1  :252-253 */
+  double loss_function_scale;                /* 1.0  :251; > 0 for a non-trivial loss */
+} dsm_local_bundle_options;
+
+typedef struct dsm_local_bundle_result {
+  int32_t solved;                 /* BundleAdjuster::Solve's return value: 0 when the problem has no residuals */
+  int32_t termination;            /* DSM_BA_CONVERGENCE / DSM_BA_NO_CONVERGENCE / DSM_BA_FAILURE */
+  uint32_t num_iterations;        /* every trust-region iteration counts */
+  uint32_t num_successful_steps;
+  uint32_t num_invalid_steps;
+  uint32_t reduced_dim;           /* columns of the reduced camera system */
+  uint64_t num_residuals;         /* 2 x observations; the mapper's num_adjusted_observations is half of it */
+  uint64_t num_effective_parameters; /* tangent dimensions of the variable blocks */
+  double initial_cost, final_cost;   /* 1/2 sum rho(|r|^2) */
+  double initial_mean_reprojection_error, final_mean_reprojection_error; /* mean |r| (before the loss) */
+} dsm_local_bundle_result;
+
+#define DSM_LOCAL_BUNDLE_MARGINS 4
+#define DSM_LOCAL_BUNDLE_TRACE_COLUMNS 5 /* DSM_BA_TRACE_COLUMNS without the CG count: cost, radius, rho, accepted, gradient max-norm */
+typedef struct dsm_local_bundle_report {
+  uint32_t num_problems, reserved;
+  uint64_t num_points, num_observations; /* summed over the problems */
+  uint64_t num_iterations;
+  /* per problem is the call's margins_out; here the minima over the batch (INFINITY where never taken).  In order:
+     0 acceptance test, in cost: |(cost - candidate) - 1e-3 model_cost_change| / cost   1 gradient test (relative)
+     2 Cholesky pivot of the reduced system, relative to its diagonal   3 pivot of a point's 3 x 3 block, relative to its diagonal */
+  double min_margin[DSM_LOCAL_BUNDLE_MARGINS];
+  double setup_ms;                          /* host: validation and the canonical order */
+  double upload_ms, solve_ms, download_ms;  /* HIP events */
+  double device_ms;                         /* HIP events: first upload to the last download */
+} dsm_local_bundle_report;
+
+void dsm_default_local_bundle_options(dsm_local_bundle_options* o);
+
+/* B independent problems, CSR over the problems, host pointers, adjusted in place; indices inside a problem are local to it.
+ *   cameras: camera_offsets[B + 1]; camera_model_ids; camera_params (every camera's parameters back to back, in camera order
+ *     over the whole batch); camera_constant (NULL = none; 1 holds the camera constant whatever the refine flags say)
+ *   images: image_offsets[B + 1]; image_camera (index into the problem's cameras); image_qvec (4 each); image_tvec (3 each);
+ *     image_constant_pose, image_constant_tvec (NULL = none; bit k: tvec[k] constant) as in dsm_bundle_adjust
+ *   points: point_offsets[B + 1]; point_ids (unique inside a problem: the canonical order); point_xyz; point_constant (NULL = none)
+ *   tracks: track_offsets holds, for problem b, num_points_b + 1 entries starting at point_offsets[b] + b, counted from 0
+ *     inside the problem; obs_offsets[B + 1] says where a problem's observations start in obs_image / obs_xy.  A track of
+ *     length 1 (or 0) is accepted.
+ *   options NULL = defaults; results_out[B]; margins_out NULL or B x DSM_LOCAL_BUNDLE_MARGINS; trace_out NULL or
+ *     B x (max_num_iterations + 1) x DSM_LOCAL_BUNDLE_TRACE_COLUMNS (rows past a problem's last iteration are NaN); report NULL or
+ *     the sums.
+ * A problem without residuals: solved = 0, nothing touched.  A problem with residuals and no variable block: CONVERGENCE after
+ * zero iterations, nothing touched.  Blocks without residuals come back bit-identical.
+ * A problem's result depends on that problem and the options alone: not on the batch, its place in it, or the order of its
+ * points, track elements, images or cameras.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT): NULL where data is needed, offsets that do not ascend from 0, an unknown model, an
+ *   out-of-range index, non-finite input, a zero qvec, a mask above 7, one image observing one point twice, a repeated point
+ *   id, an unknown loss type, loss_function_scale <= 0 for a non-trivial loss, options out of range, max_num_iterations above
+ *   DSM_LOCAL_BUNDLE_MAX_ITERATIONS, a reduced camera system above DSM_LOCAL_BUNDLE_MAX_REDUCED_DIM columns (such a problem
+ *   belongs to dsm_bundle_adjust). */
+int dsm_adjust_local_bundles(dsm_ctx* ctx, uint32_t num_problems, const uint32_t* camera_offsets, const int32_t* camera_model_ids,
+                             double* camera_params, const uint8_t* camera_constant, const uint32_t* image_offsets,
+                             const uint32_t* image_camera, double* image_qvec, double* image_tvec,
+                             const uint8_t* image_constant_pose, const uint8_t* image_constant_tvec,
+                             const uint32_t* point_offsets, const uint64_t* point_ids, double* point_xyz,
+                             const uint8_t* point_constant, const uint32_t* track_offsets, const uint64_t* obs_offsets,
+                             const uint32_t* obs_image, const double* obs_xy, const dsm_local_bundle_options* options,
+                             dsm_local_bundle_result* results_out, double* margins_out, double* trace_out,
+                             dsm_local_bundle_report* report);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
