@@ -321,6 +321,17 @@ class LocalBundleReport(ctypes.Structure):
         return {k: (list(getattr(self, k)) if hasattr(getattr(self, k), "__len__") else getattr(self, k)) for k, _ in self._fields_}
 
 
+SIFT_L1_ROOT, SIFT_L2 = 0, 1
+
+
+class SiftOptions(ctypes.Structure):
+    """dsm_sift_options: SiftExtractionOptions (src/feature/sift.h) without the covariant / SiftGPU fields."""
+    _fields_ = [("num_octaves", ctypes.c_int32), ("octave_resolution", ctypes.c_int32), ("first_octave", ctypes.c_int32),
+                ("max_num_orientations", ctypes.c_int32), ("max_num_features", ctypes.c_int32), ("upright", ctypes.c_int32),
+                ("normalization", ctypes.c_int32), ("reserved", ctypes.c_int32), ("peak_threshold", ctypes.c_double),
+                ("edge_threshold", ctypes.c_double)]
+
+
 def lib(check=False):
     """Loads the shared library (check=True: the check build); raises if it has not been built (no fallback)."""
     if check not in _libs:
@@ -410,6 +421,9 @@ def lib(check=False):
         L.dsm_adjust_local_bundles.argtypes = [vp, ctypes.c_uint32] + [vp] * 18 + [ctypes.POINTER(LocalBundleOptions)] + [vp] * 4
         L.dsm_debug_image_to_world.argtypes = [vp, ctypes.POINTER(Camera), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double)]
+        L.dsm_sift_default_options.argtypes = [ctypes.POINTER(SiftOptions)]
+        L.dsm_sift_default_options.restype = None
+        L.dsm_extract_sift.argtypes = [vp, ctypes.POINTER(SiftOptions), vp] + [ctypes.c_uint32] * 4 + [vp, vp, u32p]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
         L.dsm_default_match_options.restype = None
         L.dsm_default_two_view_options.argtypes = [ctypes.POINTER(TwoViewOptions)]
@@ -516,6 +530,14 @@ def default_pose_refinement_options(**kw):
 def default_point_filter_options(**kw):
     o = PointFilterOptions()
     lib().dsm_default_point_filter_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_sift_options(**kw):
+    o = SiftOptions()
+    lib().dsm_sift_default_options(ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -1147,6 +1169,44 @@ class Context:
         return {"point_keep": pkeep[:P].astype(bool), "obs_keep": okeep[:n].astype(bool), "point_error": perr[:P].copy(),
                 "kept_track_offsets": koff, "kept_obs": kobs[:int(koff[P])].copy(), "image_filtered": ifilt[:N].astype(bool),
                 "camera_sizes_given": sizes_given, "report": rep}
+
+    def extract_sift(self, image_u8, options=None, descriptors=True, capacity=None, width=None):
+        """dsm_extract_sift: image_u8 [height, row_stride] grey bytes, of which the first `width` of a row are the
+        image (None: all of them).  Returns (keypoints float32 [n, 4] = (x, y, sigma, angle), descriptors uint8 [n, 128] in UBC
+        order, or None with descriptors=False).  capacity None: room for 32768 features, and a second call with the count the
+        first one reports where that is too little; a given capacity below the count raises DsmError with the count in
+        .num_features."""
+        im = np.ascontiguousarray(image_u8, np.uint8)
+        height, row_stride = im.shape
+        width = row_stride if width is None else int(width)
+        o = options if options is not None else default_sift_options()
+        n = ctypes.c_uint32(0)
+
+        def call(cap):
+            kp = np.zeros((max(cap, 1), 4), np.float32)
+            ds = np.zeros((max(cap, 1), 128), np.uint8) if descriptors else None
+            rc = self._L.dsm_extract_sift(self._h, ctypes.byref(o), im.ctypes.data, width, height, row_stride, cap, kp.ctypes.data,
+                                          None if ds is None else ds.ctypes.data, ctypes.byref(n))
+            return rc, kp, ds
+
+        rc, kp, ds = call(32768 if capacity is None else int(capacity))
+        if rc == 4 and capacity is None and n.value > 0:
+            rc, kp, ds = call(int(n.value))
+        if rc != 0:
+            err = DsmError("dsm_extract_sift failed (%d): %s" % (rc, self._L.dsm_last_error(self._handle).decode()))
+            err.num_features = int(n.value)
+            err.status = rc
+            raise err
+        return kp[:n.value].copy(), (None if ds is None else ds[:n.value].copy())
+
+    SIFT_STAGES = ("base", "smoothing", "detect", "refine", "gradient", "orientations", "descriptors")
+
+    def sift_time(self):
+        """dsm_get_sift_time: {stage: ms} of the last extract_sift (HIP events, summed over the octaves)."""
+        ms = (ctypes.c_double * len(self.SIFT_STAGES))()
+        self._L.dsm_get_sift_time.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._chk(self._L.dsm_get_sift_time(self._h, ctypes.addressof(ms)))
+        return dict(zip(self.SIFT_STAGES, list(ms)))
 
     @staticmethod
     def apply_point_filter(scene, result):

@@ -221,6 +221,7 @@ void dsm_ctx_destroy(dsm_ctx* ctx) {
   if (ctx->leaf) dsm_ctx_destroy(ctx->leaf);
   dsm_retrieval_destroy(ctx);
   (void)hipStreamSynchronize(ctx->stream);
+  dsm_sift_destroy(ctx);
   delete ctx;
 }
 

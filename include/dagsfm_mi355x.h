@@ -1137,6 +1137,49 @@ int dsm_adjust_local_bundles(dsm_ctx* ctx, uint32_t num_problems, const uint32_t
                              dsm_local_bundle_result* results_out, double* margins_out, double* trace_out,
                              dsm_local_bundle_report* report);
 
+/* ---- SIFT feature extraction ----
+ * ExtractSiftFeaturesCPU (src/feature/sift.cc:252-426): VLFeat's vl_sift_process_first_octave / _next_octave, vl_sift_detect,
+ * vl_sift_calc_keypoint_orientations and vl_sift_calc_keypoint_descriptor (lib/VLFeat/sift.c:975-1431, 1559-1692, 1923-2093)
+ * restated in the reference's evaluation order, and COLMAP's loop around them: the groups per DoG level, the first
+ * max_num_orientations orientations of a keypoint, L1_ROOT / L2 (src/feature/utils.cc:47-77), the bytes, the VLFeat -> UBC bin
+ * order (sift.cc:58-74) and the max_num_features cut (sift.cc:387-398; the level that crosses the limit is kept whole).
+ * DESIGN.md 18.  ExtractCovariantSiftFeaturesCPU (estimate_affine_shape, domain_size_pooling) and SiftGPU are not covered. */
+enum { DSM_SIFT_L1_ROOT = 0, DSM_SIFT_L2 = 1 };  /* SiftExtractionOptions::Normalization, src/feature/sift.h */
+
+typedef struct dsm_sift_options {  /* SiftExtractionOptions, src/feature/sift.h:36-112 */
+  int32_t num_octaves;          /* 4; negative: as many as the image allows (vl_sift_new, sift.c:885-887) */
+  int32_t octave_resolution;    /* 3 */
+  int32_t first_octave;         /* -1 */
+  int32_t max_num_orientations; /* 2 */
+  int32_t max_num_features;     /* 8192 */
+  int32_t upright;              /* 0 */
+  int32_t normalization;        /* DSM_SIFT_L1_ROOT */
+  int32_t reserved;
+  double peak_threshold;        /* 0.02 / octave_resolution */
+  double edge_threshold;        /* 10.0 */
+} dsm_sift_options;
+
+void dsm_sift_default_options(dsm_sift_options* o);
+
+/* One grey image, host pointers: gray_u8 holds height rows of row_stride >= width bytes.  keypoints_out [capacity x 4] receives
+ * (x + 0.5, y + 0.5, sigma, angle) as sift.cc:355-357 hands them to FeatureKeypoint(x, y, scale, orientation); descriptors_out
+ * [capacity x 128] the bytes in UBC order, NULL where only keypoints are wanted (sift.cc:358).  options NULL = the defaults.
+ * *num_features_out: the number of features found; above capacity the call fails with DSM_ERR_OUT_OF_RANGE, nothing is written
+ * to the outputs and the count is still valid.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT): NULL where data is needed, an empty image, row_stride < width, options that
+ *   SiftExtractionOptions::Check (sift.cc:218-234) rejects, an unknown normalization.
+ * DSM_ERR_OUT_OF_RANGE: first_octave outside -4 .. 16, octave_resolution or num_octaves above 64, a first octave of 2^31
+ *   samples or more over its levels, or one whose scratch exceeds dsm_ctx_set_memory_budget (the stage does not tile). */
+int dsm_extract_sift(dsm_ctx* ctx, const dsm_sift_options* options, const uint8_t* gray_u8, uint32_t width, uint32_t height,
+                     uint32_t row_stride, uint32_t capacity, float* keypoints_out, uint8_t* descriptors_out,
+                     uint32_t* num_features_out);
+
+/* HIP-event times of the last dsm_extract_sift on this context, in ms, summed over the octaves: 0 the octave's base (load, up- /
+ * downsampling, its smoothing), 1 the smoothing of the levels, 2 DoG + extremum test + candidate count, 3 candidate emission +
+ * refinement, 4 gradient, 5 orientations, 6 descriptors.  DSM_ERR_NOT_READY before the first call. */
+#define DSM_SIFT_STAGES 7
+int dsm_get_sift_time(dsm_ctx* ctx, double* stage_ms);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
