@@ -2,7 +2,7 @@
 float32 kept float32: the groups per DoG level, the first max_num_orientations orientations of a keypoint, L1_ROOT / L2
 (src/feature/utils.cc:47-77, plain left-to-right float sums), round(512 v) truncated to 0 .. 255, the VLFeat -> UBC bin order
 (sift.cc:58-74) and the max_num_features cut (sift.cc:387-398).  Its input is VLFeat's own output as tests/golden/
-sift_vlfeat_v1.npz stores it (tools/make_sift_golden.py), so the expected features of a case are the reference library's
+sift_vlfeat_v1.npz and sift_vlfeat_v2.npz store it (tools/make_sift_golden.py), so the expected features of a case are the reference library's
 bytes carried through this host half -- the same structure as the host half of dagsfm_amd/csrc/sift_extraction.hip.
 
 The second half of this file restates the VLFeat stage itself (scale space, detection, refinement, gradient, orientations,
@@ -14,16 +14,16 @@ import os
 import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sift_vlfeat_v1.npz")
+GOLDEN_V2 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sift_vlfeat_v2.npz")  # sift_scenes.cases_v2()
 L1_ROOT, L2 = 0, 1
 OPTION_KEYS = ("num_octaves", "octave_resolution", "first_octave", "upright", "peak_threshold", "edge_threshold")
-_golden = None
+_golden = {}
 
 
-def golden():
+def golden(path=GOLDEN):
     """{case: {image, options (dict), ints, floats, num_angles, angles, descriptors}} -- loaded once, shared, read-only."""
-    global _golden
-    if _golden is None:
-        z = np.load(GOLDEN)
+    if path not in _golden:
+        z = np.load(path)
         out = {}
         for key in z.files:
             case, field = key.split("/")
@@ -35,8 +35,13 @@ def golden():
             for k in OPTION_KEYS[:4]:
                 o[k] = int(o[k])
             case["options"] = o
-        _golden = out
-    return _golden
+        _golden[path] = out
+    return _golden[path]
+
+
+def golden_v2():
+    """The cases of sift_scenes.cases_v2(), as golden() gives those of cases()."""
+    return golden(GOLDEN_V2)
 
 
 def ubc_permutation():
@@ -383,8 +388,11 @@ def _descriptor(mod, ang, kx, ky, ksigma, xper, angle0):
     return _normalize_histogram(descr)
 
 
-def vlfeat(image, num_octaves=4, octave_resolution=3, first_octave=-1, upright=0, peak_threshold=0.02 / 3, edge_threshold=10.0):
-    """The VLFeat stage in COLMAP's call sequence (sift.cc:266-385) on a uint8 image: the fields of a golden case."""
+def vlfeat(image, num_octaves=4, octave_resolution=3, first_octave=-1, upright=0, peak_threshold=0.02 / 3, edge_threshold=10.0,
+           trace=None):
+    """The VLFeat stage in COLMAP's call sequence (sift.cc:266-385) on a uint8 image: the fields of a golden case.  A list given
+    as `trace` receives, per octave that is searched, {octave, dog float32 [S + 2, h, w], flags bool [S, h, w]}: the DoG and the
+    candidates before refinement, in the scan order (s, y, x) the device compacts them in."""
     height, width = image.shape
     S, o_min, tp, te = octave_resolution, first_octave, peak_threshold, edge_threshold
     O = num_octaves if num_octaves >= 0 else int(max(math.floor(math.log2(min(width, height))) - o_min - 3, 1))
@@ -426,6 +434,7 @@ def vlfeat(image, num_octaves=4, octave_resolution=3, first_octave=-1, upright=0
         D = np.stack([levels[k + 1] - levels[k] for k in range(S + 2)])
         xper = math.pow(2.0, oc)
         keys = []
+        flags = np.zeros((S, h, w), bool)
         for s in range(S):  # vl_sift_detect: the strict 26-neighbour test, candidates in (s, y, x) order
             v = D[s + 1, 1:-1, 1:-1]
             mx, mn = v.astype(f64) >= 0.8 * tp, v.astype(f64) <= -0.8 * tp
@@ -436,11 +445,14 @@ def vlfeat(image, num_octaves=4, octave_resolution=3, first_octave=-1, upright=0
                             u = D[s + 1 + ds, 1 + dy:h - 1 + dy, 1 + dx:w - 1 + dx]
                             mx &= v > u
                             mn &= v < u
+            flags[s, 1:-1, 1:-1] = mx | mn
             for y, x in zip(*np.nonzero(mx | mn)):
                 r = _refine(D, int(x) + 1, int(y) + 1, s, w, h, S, tp, te)
                 if r is not None:
                     ix, iy, is_, xn, yn, sn = r
                     keys.append((ix, iy, is_, f32(xn * xper), f32(yn * xper), f32(sn), f32(sigma0 * math.pow(2.0, sn / S) * xper)))
+        if trace is not None:
+            trace.append({"octave": oc, "dog": D, "flags": flags})
         grads = {}
         for ix, iy, is_, kx, ky, ks, ksigma in keys:
             if is_ not in grads:

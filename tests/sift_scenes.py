@@ -124,3 +124,86 @@ def cases():
 
 # a peak_threshold that leaves exactly one keypoint on texture(64, 48, 2) (found with tools/make_sift_golden.py --peaks)
 SINGLE_PEAK_THRESHOLD = 0.034
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The second golden file (tests/golden/sift_vlfeat_v2.npz): the octaves, sizes and options cases() leaves out.
+
+
+def coarse(width, height, seed, k):
+    """texture() of 1 / k the size, every pixel repeated k x k, box-blurred with radius k / 2 and stretched: structure large
+    enough to survive first_octave = 2 and 3, with neighbouring pixels that still differ (a sampling offset would show)."""
+    t = texture((width + k - 1) // k, (height + k - 1) // k, seed)
+    big = np.repeat(np.repeat(t, k, axis=0), k, axis=1)[:height, :width]
+    return stretch(box_blur(big, k // 2))
+
+
+def checkerboard(width, height, cell=4):
+    """0 / 255 squares of `cell` pixels: exact symmetries, so equal DoG samples and equal histogram bins."""
+    y, x = np.mgrid[0:height, 0:width]
+    return ((((x // cell) + (y // cell)) & 1) * 255).astype(np.uint8)
+
+
+def dots(width, height, period=8, size=2):
+    """size x size squares of 255 every `period` pixels on 0.  A square of even size has its centre between four pixels, so
+    the DoG extremum over it is shared by equal neighbouring samples."""
+    y, x = np.mgrid[0:height, 0:width]
+    return (((x % period < size) & (y % period < size)) * 255).astype(np.uint8)
+
+
+def binary_noise(width, height, seed):
+    """The lowest bit of hash_field as 0 / 255: every pixel an extremum of something."""
+    return ((hash_field(width, height, seed) & np.uint64(1)) * np.uint64(255)).astype(np.uint8)
+
+
+ZERO_RESULT_V2 = ("line40x1", "line1x40", "rows40x2", "small20x5")
+
+
+def cases_v2():
+    """[(name, image uint8 [h, w], options)]: the runs stored in tests/golden/sift_vlfeat_v2.npz.
+
+    VLFeat's counts, as the tool prints them (it now adds the most orientations any keypoint has):
+      first-2_sq20     14 keypoints,   16 descriptors, octaves [-2, -1, 0], 6 DoG levels, at most 2 orientations
+      first-2_32x24    30 keypoints,   36 descriptors, octaves [-2, -1], 4 DoG levels, at most 2 orientations
+      first-3_sq16     10 keypoints,   11 descriptors, octaves [-3, -2, -1], 5 DoG levels, at most 2 orientations
+      first2_253x191   20 keypoints,   21 descriptors, octaves [2, 3], 5 DoG levels, at most 2 orientations
+      first3_253x191    4 keypoints,    4 descriptors, octaves [3], 2 DoG levels, at most 1 orientations
+      octaves-1       100 keypoints,  117 descriptors, octaves [-1, 0, 1], 9 DoG levels, at most 2 orientations
+      octaves0          0 keypoints,    0 descriptors, octaves [], 0 DoG levels, at most 0 orientations
+      octaves1         87 keypoints,  103 descriptors, octaves [-1], 3 DoG levels, at most 2 orientations
+      octaves10_16x16    4 keypoints,    4 descriptors, octaves [-1], 2 DoG levels, at most 1 orientations
+      line40x1          0 keypoints,    0 descriptors, octaves [], 0 DoG levels, at most 0 orientations
+      line1x40          0 keypoints,    0 descriptors, octaves [], 0 DoG levels, at most 0 orientations
+      rows40x2          0 keypoints,    0 descriptors, octaves [], 0 DoG levels, at most 0 orientations
+      small20x5         0 keypoints,    0 descriptors, octaves [], 0 DoG levels, at most 0 orientations
+      thin44x10         9 keypoints,   10 descriptors, octaves [-1, 0], 4 DoG levels, at most 2 orientations
+      checker40x40    120 keypoints,  368 descriptors, octaves [-1], 2 DoG levels, at most 4 orientations
+      dots40x40        39 keypoints,   81 descriptors, octaves [-1, 0], 3 DoG levels, at most 4 orientations
+      noise64x48       16 keypoints,   25 descriptors, octaves [-1], 2 DoG levels, at most 3 orientations
+      lowthreshold    104 keypoints,  122 descriptors, octaves [-1, 0, 1], 9 DoG levels, at most 2 orientations
+      dense18x48      110 keypoints,  332 descriptors, octaves [-1], 2 DoG levels, at most 4 orientations
+    thin44x10 asks for 6 octaves: 88 x 20, 44 x 10 and 22 x 5 are searched, 11 x 2 is smoothed and skipped (under 3 rows), 5 x 1
+    ends the loop (under 2).  octaves10_16x16 goes 32, 16, 8, 4 (searched), 2 (skipped), 1 (the end)."""
+    mid = texture(64, 48, 2)
+    big = coarse(253, 191, 6, 4)  # 253 >> 2 = 63 and 191 >> 2 = 47 drop a remainder; 31 x 23 at first_octave = 3
+    return [
+        ("first-2_sq20", texture(20, 20, 22), _opts(first_octave=-2)),
+        ("first-2_32x24", texture(32, 24, 23), _opts(first_octave=-2)),  # non-square: the second doubling is scrambled
+        ("first-3_sq16", texture(16, 16, 20), _opts(first_octave=-3)),
+        ("first2_253x191", big, _opts(first_octave=2)),
+        ("first3_253x191", big, _opts(first_octave=3)),
+        ("octaves-1", mid, _opts(num_octaves=-1)),  # automatic: floor(log2(48)) + 1 - 3 = 3 octaves, as many as hold keypoints
+        ("octaves0", mid, _opts(num_octaves=0)),
+        ("octaves1", mid, _opts(num_octaves=1)),
+        ("octaves10_16x16", texture(16, 16, 8), _opts(num_octaves=10)),
+        ("line40x1", texture(40, 1, 3), _opts()),
+        ("line1x40", texture(1, 40, 3), _opts()),
+        ("rows40x2", texture(40, 2, 3), _opts()),
+        ("small20x5", texture(20, 5, 3), _opts()),
+        ("thin44x10", texture(44, 10, 7), _opts(num_octaves=6)),
+        ("checker40x40", checkerboard(40, 40), _opts()),
+        ("dots40x40", dots(40, 40), _opts()),  # ties that decide: samples >= all 26 neighbours and equal to one of them
+        ("noise64x48", binary_noise(64, 48, 5), _opts()),
+        ("lowthreshold", mid, _opts(peak_threshold=1e-4, edge_threshold=100.0)),
+        ("dense18x48", checkerboard(18, 48, 3), _opts()),  # 36 samples a row: a chunk of 256 flags spans 7 rows of close extrema
+    ]

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Regenerates tests/golden/sift_vlfeat_v1.npz: the cases of tests/sift_scenes.py run through the reference's VLFeat.
+"""Regenerates tests/golden/sift_vlfeat_v1.npz and sift_vlfeat_v2.npz: the cases of tests/sift_scenes.py (cases() and
+cases_v2()) run through the reference's VLFeat.
 
 Needs the reference tree (default /root/reference, or --reference DIR); nothing of it is copied into the repository.  The
 driver tools/sift_golden_driver.c is compiled against lib/VLFeat/{sift,imopv,imopv_sse2,generic,host,mathop,mathop_sse2,random}.c
@@ -11,8 +12,8 @@ peak_threshold, edge_threshold), NAME/ints (int32 [n, 4]: o, ix, iy, is), NAME/f
 NAME/num_angles (int32 [n]), NAME/angles (float64 [n, 4]) and NAME/descriptors (float32 [sum num_angles, 128], VLFeat's order).
 The archive is written with fixed time stamps, so a second run gives the same bytes.
 
-  python tools/make_sift_golden.py            # rewrite the golden file, print the counts
-  python tools/make_sift_golden.py --check    # regenerate in memory and compare with the committed file
+  python tools/make_sift_golden.py            # rewrite both golden files, print the counts
+  python tools/make_sift_golden.py --check    # regenerate in memory and compare with the committed files
   python tools/make_sift_golden.py --time W H [--json]  # wall time of the SSE2 build on one core for texture(W, H); --json records
                                                         # it for tools/bench_sift_extraction.py
 """
@@ -33,6 +34,7 @@ sys.path.insert(0, ROOT)
 from tests import sift_scenes  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "sift_vlfeat_v1.npz")
+GOLDEN_V2 = os.path.join(ROOT, "tests", "golden", "sift_vlfeat_v2.npz")
 VL_SOURCES = ["sift", "imopv", "imopv_sse2", "generic", "host", "mathop", "mathop_sse2", "random"]
 OPTION_KEYS = ("num_octaves", "octave_resolution", "first_octave", "upright", "peak_threshold", "edge_threshold")
 
@@ -83,11 +85,11 @@ def parse(blob):
             "descriptors": np.concatenate(desc).astype(np.float32) if n and sum(nang) else z(np.float32, (0, 128))}
 
 
-def generate(reference):
+def generate(reference, cases):
     arrays, counts = {}, []
     with tempfile.TemporaryDirectory() as work:
         exe_sse2, exe_plain = build(reference, work, True), build(reference, work, False)
-        for name, image, options in sift_scenes.cases():
+        for name, image, options in cases:
             a, _ = run(exe_sse2, work, image, options)
             b, _ = run(exe_plain, work, image, options)
             assert a == b, "the SSE2 and the plain build of VLFeat disagree on case %s" % name
@@ -98,8 +100,9 @@ def generate(reference):
                 arrays[name + "/" + k] = v
             octs = sorted(set(rec["ints"][:, 0].tolist()))
             levels = sorted(set(map(tuple, rec["ints"][:, [0, 3]].tolist())))
-            counts.append("  %-14s %4d keypoints, %4d descriptors, octaves %s, %d DoG levels" % (
-                name, len(rec["ints"]), len(rec["descriptors"]), octs, len(levels)))
+            most = int(rec["num_angles"].max()) if len(rec["ints"]) else 0
+            counts.append("  %-14s %4d keypoints, %4d descriptors, octaves %s, %d DoG levels, at most %d orientations" % (
+                name, len(rec["ints"]), len(rec["descriptors"]), octs, len(levels), most))
     return arrays, counts
 
 
@@ -150,17 +153,23 @@ def main():
                 blob, _ = run(exe, work, sift_scenes.texture(64, 48, 2), dict(sift_scenes.DEFAULTS, peak_threshold=t))
                 print(t, struct.unpack_from("<i", blob, 0)[0])
         return
-    arrays, counts = generate(args.reference)
-    data = archive(arrays)
-    print("\n".join(counts))
-    print("%d bytes" % len(data))
+    all_same = True
+    for path, cases in ((GOLDEN, sift_scenes.cases()), (GOLDEN_V2, sift_scenes.cases_v2())):
+        arrays, counts = generate(args.reference, cases)
+        data = archive(arrays)
+        print(os.path.relpath(path, ROOT))
+        print("\n".join(counts))
+        print("%d bytes" % len(data))
+        if args.check:
+            same = os.path.exists(path) and open(path, "rb").read() == data
+            print("identical to the committed file" if same else "DIFFERENT from the committed file")
+            all_same = all_same and same
+            continue
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "wb") as f:
+            f.write(data)
     if args.check:
-        same = os.path.exists(GOLDEN) and open(GOLDEN, "rb").read() == data
-        print("identical to the committed file" if same else "DIFFERENT from the committed file")
-        sys.exit(0 if same else 1)
-    os.makedirs(os.path.dirname(GOLDEN), exist_ok=True)
-    with open(GOLDEN, "wb") as f:
-        f.write(data)
+        sys.exit(0 if all_same else 1)
 
 
 if __name__ == "__main__":
