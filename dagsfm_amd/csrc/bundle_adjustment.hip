@@ -4,7 +4,8 @@
 //   BundleAdjustmentCostFunction                      src/base/cost_functions.h:45-85
 // Levenberg-Marquardt with Jacobi scaling; each step solves the Schur complement over the variable points with a CG
 // preconditioned by the exact diagonal blocks of S, S applied implicitly from the stored per-observation Jacobian blocks.
-// Canonical order: points by id, observations image-major by (image, point rank), each track by (camera, image).  Every sum
+// Canonical order: points by id, the images with observations by content, their cameras by first use (the host relabels
+// both; the rest stays off the device), observations image-major by (image, point rank), each track by (camera, image).  Every sum
 // walks a segment of that order (one thread per point over its track, one 64-lane block per image over its observations with
 // a fixed LDS tree, one block per camera over its images' partial rows), every scalar is a fixed-order sum of per-block
 // partials: no floating-point atomics, the same bytes on every run and for every input order.  Loop control stays on the
@@ -15,6 +16,7 @@
 #include <limits.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <chrono>
@@ -1017,7 +1019,8 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
       o.max_linear_solver_iterations > 1000000 || !fin_nonneg(o.gradient_tolerance) || !fin_nonneg(o.function_tolerance) ||
       !fin_nonneg(o.parameter_tolerance) || o.max_num_consecutive_invalid_steps < 0)
     return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: option out of range");
-  const uint32_t C = num_cameras, N = num_images, P = num_points;
+  uint32_t C = num_cameras, N = num_images;  // the caller's counts; below the canonical order, the problem's
+  const uint32_t P = num_points;
   if (track_offsets[0] != 0) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: track_offsets must start at 0");
   const uint64_t n_obs64 = track_offsets[P];
   if (n_obs64 >= (1ull << 31) || (n_obs64 && (!obs_image || !obs_xy)))
@@ -1025,15 +1028,12 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
   const uint32_t n_obs = (uint32_t)n_obs64;
   // ---- validation
   BaProblem pb;
-  std::vector<uint32_t> poff(C + 1, 0);
-  pb.cam_np.resize(C);
+  std::vector<uint32_t> poff_in(C + 1, 0);  // the caller's cameras
   for (uint32_t c = 0; c < C; ++c) {
     if (!cam_model_exists(camera_model_ids[c])) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: unknown camera model");
-    pb.cam_np[c] = cam_num_params(camera_model_ids[c]);
-    poff[c + 1] = poff[c] + pb.cam_np[c];
+    poff_in[c + 1] = poff_in[c] + cam_num_params(camera_model_ids[c]);
   }
-  const uint32_t n_prm = poff[C];
-  for (uint32_t j = 0; j < n_prm; ++j)
+  for (uint32_t j = 0; j < poff_in[C]; ++j)
     if (!std::isfinite(camera_params[j])) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: non-finite camera parameter");
   for (uint32_t i = 0; i < N; ++i) {
     if (image_camera[i] >= C) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: image camera index out of range");
@@ -1063,6 +1063,92 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
   std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return point_ids[a] < point_ids[b]; });
   for (uint32_t r = 1; r < P; ++r)
     if (point_ids[order[r]] == point_ids[order[r - 1]]) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_bundle_adjust: repeated point id");
+  // the images with observations by content: flags, pose, the camera's model and parameters, then -- only where all of that
+  // ties -- the observations by point rank; the cameras by first use.  Images and cameras without residuals never reach the
+  // device, so neither they nor the caller's order of the lists move a sum (as in local_bundle.hip).
+  std::vector<uint32_t> iorder, corder;  // canonical index -> the caller's
+  {
+    std::vector<uint32_t> ioff(N + 1, 0), iobs(n_obs), orank(n_obs);
+    for (uint32_t a = 0; a < n_obs; ++a) ++ioff[obs_image[a] + 1];
+    for (uint32_t i = 0; i < N; ++i) ioff[i + 1] += ioff[i];
+    std::vector<uint32_t> fill(ioff.begin(), ioff.end() - 1);
+    for (uint32_t r = 0; r < P; ++r)
+      for (uint32_t a = track_offsets[order[r]]; a < track_offsets[order[r] + 1]; ++a) {
+        iobs[fill[obs_image[a]]++] = a;
+        orank[a] = r;
+      }
+    auto bits = [](double v) {
+      uint64_t u;
+      memcpy(&u, &v, sizeof u);
+      return u;
+    };
+    auto head = [&](uint32_t i, uint64_t* ky) {  // 22 words at most
+      const uint32_t cam = image_camera[i];
+      int n = 0;
+      ky[n++] = image_constant_pose && image_constant_pose[i] ? 1 : 0;
+      ky[n++] = image_constant_tvec ? image_constant_tvec[i] : 0;
+      for (int a = 0; a < 4; ++a) ky[n++] = bits(image_qvec[4 * (size_t)i + a]);
+      for (int a = 0; a < 3; ++a) ky[n++] = bits(image_tvec[3 * (size_t)i + a]);
+      ky[n++] = (uint64_t)camera_model_ids[cam];
+      for (uint32_t j = poff_in[cam]; j < poff_in[cam + 1]; ++j) ky[n++] = bits(camera_params[j]);
+      return n;
+    };
+    for (uint32_t i = 0; i < N; ++i)
+      if (ioff[i + 1] > ioff[i]) iorder.push_back(i);
+    std::stable_sort(iorder.begin(), iorder.end(), [&](uint32_t x, uint32_t y) {
+      uint64_t kx[24], ky[24];
+      const int nx = head(x, kx), ny = head(y, ky);
+      if (!std::equal(kx, kx + nx, ky, ky + ny)) return std::lexicographical_compare(kx, kx + nx, ky, ky + ny);
+      const uint32_t lx = ioff[x + 1] - ioff[x], ly = ioff[y + 1] - ioff[y];
+      for (uint32_t k = 0; k < lx && k < ly; ++k) {
+        const uint32_t ax = iobs[ioff[x] + k], ay = iobs[ioff[y] + k];
+        const uint64_t wx[3] = {orank[ax], bits(obs_xy[2 * (size_t)ax]), bits(obs_xy[2 * (size_t)ax + 1])};
+        const uint64_t wy[3] = {orank[ay], bits(obs_xy[2 * (size_t)ay]), bits(obs_xy[2 * (size_t)ay + 1])};
+        for (int a = 0; a < 3; ++a)
+          if (wx[a] != wy[a]) return wx[a] < wy[a];
+      }
+      return lx < ly;
+    });
+  }
+  std::vector<uint32_t> c_icam(iorder.size()), c_oimg(n_obs), poff(1, 0);
+  std::vector<int32_t> c_model;
+  std::vector<double> c_qvec(4 * iorder.size()), c_tvec(3 * iorder.size()), c_prm;
+  std::vector<uint8_t> c_cpose(iorder.size()), c_mask(iorder.size());
+  {
+    std::vector<uint32_t> inew(N, 0), cnew(C, UINT32_MAX);
+    for (uint32_t r = 0; r < iorder.size(); ++r) {
+      const uint32_t i = iorder[r], c = image_camera[i];
+      inew[i] = r;
+      if (cnew[c] == UINT32_MAX) {
+        cnew[c] = (uint32_t)corder.size();
+        corder.push_back(c);
+        c_model.push_back(camera_model_ids[c]);
+        c_prm.insert(c_prm.end(), camera_params + poff_in[c], camera_params + poff_in[c + 1]);
+        poff.push_back((uint32_t)c_prm.size());
+      }
+      c_icam[r] = cnew[c];
+      std::copy(image_qvec + 4 * (size_t)i, image_qvec + 4 * (size_t)i + 4, c_qvec.begin() + 4 * (size_t)r);
+      std::copy(image_tvec + 3 * (size_t)i, image_tvec + 3 * (size_t)i + 3, c_tvec.begin() + 3 * (size_t)r);
+      c_cpose[r] = image_constant_pose && image_constant_pose[i];
+      c_mask[r] = image_constant_tvec ? image_constant_tvec[i] : 0;
+    }
+    for (uint32_t a = 0; a < n_obs; ++a) c_oimg[a] = inew[obs_image[a]];
+  }
+  // from here on the problem in canonical order; the caller's arrays are written once, at the end
+  double *const out_params = camera_params, *const out_qvec = image_qvec, *const out_tvec = image_tvec;
+  N = (uint32_t)iorder.size();
+  C = (uint32_t)corder.size();
+  image_camera = c_icam.data();
+  obs_image = c_oimg.data();
+  camera_model_ids = c_model.data();
+  camera_params = c_prm.data();
+  image_qvec = c_qvec.data();
+  image_tvec = c_tvec.data();
+  image_constant_pose = c_cpose.data();
+  image_constant_tvec = c_mask.data();
+  const uint32_t n_prm = poff[C];
+  pb.cam_np.resize(C);
+  for (uint32_t c = 0; c < C; ++c) pb.cam_np[c] = (int)(poff[c + 1] - poff[c]);
   pb.img_off.assign(N + 1, 0);
   for (uint32_t a = 0; a < n_obs; ++a) ++pb.img_off[obs_image[a] + 1];
   for (uint32_t i = 0; i < N; ++i) pb.img_off[i + 1] += pb.img_off[i];
@@ -1368,12 +1454,11 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
     if (rc == DSM_OK) {
       for (uint32_t r = 0; r < P; ++r)
         for (int m = 0; m < 3; ++m) point_xyz[3 * (size_t)order[r] + m] = Xo[3 * (size_t)r + m];
-      for (uint32_t i = 0; i < N; ++i) {
-        if (pb.img_off[i + 1] == pb.img_off[i]) continue;
-        for (int m = 0; m < 4; ++m) image_qvec[4 * (size_t)i + m] = qo[4 * (size_t)i + m];
-        for (int m = 0; m < 3; ++m) image_tvec[3 * (size_t)i + m] = to[3 * (size_t)i + m];
+      for (uint32_t i = 0; i < N; ++i) {  // images and cameras outside the problem keep their bits
+        for (int m = 0; m < 4; ++m) out_qvec[4 * (size_t)iorder[i] + m] = qo[4 * (size_t)i + m];
+        for (int m = 0; m < 3; ++m) out_tvec[3 * (size_t)iorder[i] + m] = to[3 * (size_t)i + m];
       }
-      std::copy(po.begin(), po.end(), camera_params);
+      for (uint32_t c = 0; c < C; ++c) std::copy(po.begin() + poff[c], po.begin() + poff[c + 1], out_params + poff_in[corder[c]]);
       if (trace) std::copy(tr.begin(), tr.end(), trace);
       if (report) {
         dsm_bundle_adjustment_report rep{};

@@ -90,4 +90,7 @@ def comparisons():
     out.append(("no_variable_camera_side", s, run))
     out.append(("constant_points_mixed", local_scene(93, 5, 3, n_points=50, const_point_frac=0.4), run))
     out.append(("default_options", local_scene(94, 6, 4, n_points=80, noise=2.0), {}))
+    # cameras shared by some of the images, outside ones among them: image i has camera i % len(models), none is constant
+    out.append(("groups_2_cameras", local_scene(96, 6, 3, n_points=60, models=(2, 4), arc=1.0), dict(run, refine_extra_params=0)))
+    out.append(("groups_3_cameras", local_scene(96, 7, 2, n_points=60, models=(0, 3, 1), arc=1.0), dict(run, refine_extra_params=0)))
     return out

@@ -16,7 +16,7 @@ from tests.bundle_adjustment_ref import make_scene, quat_plus
 ULP_SENSITIVITY = 1.2e-10
 # times 16 for what the restatement does not pin (libm's log / sin / cos, the dual numbers' order): the GPU file's tolerance
 CLEAR_TOLERANCE = 16 * ULP_SENSITIVITY
-# A comparison that is not clear (points1, loss_trivial; 37 of the 39 are clear): one ulp moves its final cost by at most 6.9e-16 of its initial cost;
+# A comparison that is not clear (points1, loss_trivial; 39 of the 41 are clear): one ulp moves its final cost by at most 6.9e-16 of its initial cost;
 # held to 8e-16, times 16
 UNCLEAR_COST_SENSITIVITY = 8e-16
 UNCLEAR_COST_TOLERANCE = 16 * UNCLEAR_COST_SENSITIVITY
