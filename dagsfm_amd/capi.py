@@ -189,6 +189,32 @@ class TriangulationReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PairRetriangulationOptions(ctypes.Structure):
+    """dsm_pair_retriangulation_options: the triangulation options plus Retriangulate's re_* settings
+    (src/sfm/incremental_triangulator.h:65-73)."""
+    _fields_ = [("tri", TriangulationOptions), ("re_max_angle_error", ctypes.c_double), ("re_min_ratio", ctypes.c_double),
+                ("re_max_trials", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+PAIR_NOT_UNDER_RECONSTRUCTED, PAIR_CLOSED_BY_ITS_TURN, PAIR_UNREGISTERED, PAIR_TRIALS_EXHAUSTED, PAIR_BOGUS_CAMERA, PAIR_PROCESSED = range(6)
+
+
+class PairRetriangulationReport(ctypes.Structure):
+    _fields_ = [("num_candidates", ctypes.c_uint32), ("num_rounds", ctypes.c_uint32), ("num_pairs_by_status", ctypes.c_uint64 * 6),
+                ("num_correspondences", ctypes.c_uint64), ("num_both", ctypes.c_uint64), ("num_continue_tried", ctypes.c_uint64),
+                ("num_continue_taken", ctypes.c_uint64), ("num_two_view_skipped", ctypes.c_uint64),
+                ("num_create_tried", ctypes.c_uint64), ("num_create_taken", ctypes.c_uint64), ("num_tris", ctypes.c_uint64),
+                ("num_new_points", ctypes.c_uint64), ("num_continued", ctypes.c_uint64), ("min_residual_margin", ctypes.c_double),
+                ("min_angle_margin", ctypes.c_double), ("min_depth_margin", ctypes.c_double), ("min_continue_margin", ctypes.c_double),
+                ("min_bogus_margin", ctypes.c_double), ("setup_ms", ctypes.c_double), ("graph_ms", ctypes.c_double),
+                ("schedule_ms", ctypes.c_double), ("rounds_ms", ctypes.c_double), ("gate_ms", ctypes.c_double), ("solve_ms", ctypes.c_double),
+                ("round_gap_ms", ctypes.c_double), ("download_ms", ctypes.c_double), ("assemble_ms", ctypes.c_double),
+                ("device_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k == "num_pairs_by_status" else getattr(self, k)) for k, _ in self._fields_}
+
+
 BA_CONVERGENCE, BA_NO_CONVERGENCE, BA_FAILURE = 0, 1, 2
 BA_TRACE_COLUMNS = 6  # cost, radius, rho, CG iterations, accepted, gradient max-norm
 
@@ -400,6 +426,11 @@ def lib(check=False):
         L.dsm_retriangulate.argtypes = ([vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32] + [vp] * 8 + [ctypes.c_uint32, vp, vp, ctypes.c_uint32]
                                         + [vp] * 3 + [ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.POINTER(TriangulationOptions)]
                                         + [vp] * 14)
+        L.dsm_default_pair_retriangulation_options.argtypes = [ctypes.POINTER(PairRetriangulationOptions)]
+        L.dsm_default_pair_retriangulation_options.restype = None
+        L.dsm_retriangulate_pairs.argtypes = ([vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32] + [vp] * 8
+                                              + [ctypes.c_uint32, vp, vp, ctypes.c_uint32] + [vp] * 3
+                                              + [ctypes.c_uint64, ctypes.POINTER(PairRetriangulationOptions)] + [vp] * 16)
         L.dsm_default_absolute_pose_options.argtypes = [ctypes.POINTER(AbsolutePoseOptions)]
         L.dsm_default_absolute_pose_options.restype = None
         L.dsm_absolute_pose_seed.argtypes = [ctypes.c_uint32] * 3
@@ -508,6 +539,16 @@ def default_triangulation_options(**kw):
     lib().dsm_default_triangulation_options(ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
+    return o
+
+
+def default_pair_retriangulation_options(**kw):
+    """re_max_angle_error, re_min_ratio, re_max_trials by name; any other keyword is a field of the `tri` member."""
+    o = PairRetriangulationOptions()
+    lib().dsm_default_pair_retriangulation_options(ctypes.byref(o))
+    own = {k for k, _ in PairRetriangulationOptions._fields_}
+    for k, v in kw.items():
+        setattr(o if k in own else o.tri, k, v)
     return o
 
 
@@ -1264,6 +1305,50 @@ class Context:
                 "new_track_obs": nobs[:int(noff[n])].copy(), "continued_obs": cobs[:c].copy(), "continued_point_ids": cid[:c].copy(),
                 "touched_obs": tobs[:t].copy(), "touched_point_ids": tid[:t].copy(),
                 "num_tris_per_separator": sep_tris[:len(seps)].copy(), "num_tris": tris.value, "report": rep}
+
+    def retriangulate_pairs(self, scene, options=None, re_num_trials=None, next_point3D_id=0):
+        """dsm_retriangulate_pairs (IncrementalTriangulator::Retriangulate, DESIGN.md 19).  scene: the dict of retriangulate.
+        re_num_trials [K]: the trials every pair has had, in the order of scene["pairs"]; None = zeros.
+        Returns a dict: new_point_ids, new_xyz [n, 3], new_track_obs [n, 2, 2] ((image_id, point2D_idx) of image1, then image2),
+        continued_obs [c, 2], continued_point_ids [c], touched_obs [t, 2], touched_point_ids [t], pair_num_total_corrs [K],
+        pair_num_tri_corrs [K] (after the call), pair_status [K] (PAIR_*), re_num_trials [K] (updated), num_tris, report."""
+        a = lambda key, dt, shape=-1: np.ascontiguousarray(scene[key], dt).reshape(shape)
+        cam_ids = a("camera_ids", np.uint32)
+        cams = (Camera * max(len(cam_ids), 1))(*scene["cameras"])
+        img_ids, img_cam, reg = a("image_ids", np.uint32), a("image_camera_ids", np.uint32), a("registered", np.uint8)
+        N = len(img_ids)
+        qvec, tvec = a("qvec", np.float64, (N, 4)), a("tvec", np.float64, (N, 3))
+        poff = a("points2D_offsets", np.uint32)
+        xy, p3 = a("points2D_xy", np.float64, (-1, 2)), a("points2D_point3D", np.int32)
+        pids, pxyz = a("point3D_ids", np.uint64), a("point3D_xyz", np.float64, (-1, 3))
+        pairs, moff, m = a("pairs", np.uint32, (-1, 2)), a("match_offsets", np.uint64), a("matches", np.uint32, (-1, 2))
+        K = len(pairs)
+        trials = np.zeros(max(K, 1), np.uint32)
+        if re_num_trials is not None:
+            given = np.ascontiguousarray(re_num_trials, np.uint32).reshape(-1)
+            if len(given) != K:
+                raise DsmError("retriangulate_pairs: re_num_trials must hold one entry per pair")
+            trials[:K] = given
+        T = max(int(poff[-1]) if len(poff) else 0, 1)
+        nid, nxyz, nobs = np.zeros(T, np.uint64), np.zeros((T, 3)), np.zeros((T, 2, 2), np.uint32)
+        cobs, cid = np.zeros((T, 2), np.uint32), np.zeros(T, np.uint64)
+        tobs, tid = np.zeros((T, 2), np.uint32), np.zeros(T, np.uint64)
+        total, tri, status = np.zeros(max(K, 1), np.uint32), np.zeros(max(K, 1), np.uint32), np.zeros(max(K, 1), np.uint8)
+        nn, nc, nt, tris = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rep = PairRetriangulationReport()
+        o = options if options is not None else default_pair_retriangulation_options()
+        ptr = lambda x: x.ctypes.data
+        self._chk(self._L.dsm_retriangulate_pairs(self._h, len(cam_ids), ptr(cam_ids), ctypes.addressof(cams), N, ptr(img_ids),
+                                                  ptr(img_cam), ptr(reg), ptr(qvec), ptr(tvec), ptr(poff), ptr(xy), ptr(p3), len(pids),
+                                                  ptr(pids), ptr(pxyz), K, ptr(pairs), ptr(moff), ptr(m), int(next_point3D_id),
+                                                  ctypes.byref(o), ptr(trials), ptr(nid), ptr(nxyz), ptr(nobs), ctypes.addressof(nn),
+                                                  ptr(cobs), ptr(cid), ctypes.addressof(nc), ptr(tobs), ptr(tid), ctypes.addressof(nt),
+                                                  ptr(total), ptr(tri), ptr(status), ctypes.addressof(tris), ctypes.addressof(rep)))
+        n, c, t = nn.value, nc.value, nt.value
+        return {"new_point_ids": nid[:n].copy(), "new_xyz": nxyz[:n].copy(), "new_track_obs": nobs[:n].copy(),
+                "continued_obs": cobs[:c].copy(), "continued_point_ids": cid[:c].copy(), "touched_obs": tobs[:t].copy(),
+                "touched_point_ids": tid[:t].copy(), "pair_num_total_corrs": total[:K].copy(), "pair_num_tri_corrs": tri[:K].copy(),
+                "pair_status": status[:K].copy(), "re_num_trials": trials[:K].copy(), "num_tris": tris.value, "report": rep}
 
     def estimate_absolute_poses(self, cameras, estimate_focal_length, offsets, points2D, points3D, options=None, seeds=None):
         """dsm_estimate_absolute_poses (EstimateAbsolutePose for a batch of problems).  cameras: a list of Camera

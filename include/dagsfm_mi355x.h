@@ -819,6 +819,100 @@ int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera
                       uint64_t* n_touched, uint32_t* num_tris_per_separator, uint64_t* num_tris_out,
                       dsm_triangulation_report* report);
 
+/* ------------------------------------------------------------------ re-triangulation of under-reconstructed image pairs
+ * IncrementalTriangulator::Retriangulate (src/sfm/incremental_triangulator.cc:289-390), what IterativeGlobalRefinement runs
+ * before every global bundle adjustment of a cluster (src/controllers/incremental_mapper_controller.cc:114-116): for every
+ * image pair whose share of triangulated correspondences is below re_min_ratio at its turn, Continue (threshold
+ * re_max_angle_error) or a two-view Create (threshold create_max_angle_error, :380-382) per correspondence.  The
+ * correspondence graph, ImageToWorld, the two-view triangulation and the tests are those of dsm_retriangulate.
+ *   Rulings: pairs run in ascending (min image id, max image id), i.e. ascending ImagePairToPairId (the
+ *   reference: an unordered_map); image1 is the image with the smaller id however the input pair is written; a pair's
+ *   correspondences run in FindCorrespondencesBetweenImages order, ascending point2D index of image1, not in load order;
+ *   num_total_corrs is the number of matches a pair keeps after the duplicate rule, and a pair that keeps none is skipped
+ *   without a trial (status DSM_PAIR_NOT_UNDER_RECONSTRUCTED); num_tri_corrs is the number of kept matches whose two features
+ *   carry the same point3D (what SetObservationAsTriangulated maintains, reconstruction.cc:2018-2050), recomputed from the
+ *   feature -> point state; per pair, in the reference's order: (double)tri / (double)total >= re_min_ratio skips, an
+ *   unregistered image skips, re_num_trials >= re_max_trials skips, re_num_trials is incremented, a camera with bogus
+ *   parameters skips (the trial stays counted); per correspondence: both features with a point: nothing; exactly one: Continue
+ *   of the other feature onto that point, the angular error through the projection matrix as in dsm_retriangulate; neither:
+ *   Create over {feature of image1, feature of image2}, skipped with ignore_two_view_tracks when IsTwoViewObservation holds
+ *   for the feature of image1 (correspondence_graph.cc:250-261); Create on two views is one LORANSAC trial without local
+ *   optimisation: triangulate, both cheirality depths, the triangulation angle against min_angle, both residuals within the
+ *   threshold, and the new track is (image1, image2); new point ids are handed out from next_point3D_id in sequential
+ *   (pair, correspondence) order however the device schedules the pairs. */
+typedef struct dsm_pair_retriangulation_options {
+  dsm_triangulation_options tri;   /* as dsm_retriangulate reads it; continue_max_angle_error is replaced by re_max_angle_error */
+  double re_max_angle_error;       /* 5.0 degrees */
+  double re_min_ratio;             /* 0.2 */
+  int32_t re_max_trials;           /* 1 */
+  int32_t reserved;
+} dsm_pair_retriangulation_options;
+
+enum {
+  DSM_PAIR_NOT_UNDER_RECONSTRUCTED = 0, /* tri / total >= re_min_ratio when the call started (or no kept match) */
+  DSM_PAIR_CLOSED_BY_ITS_TURN = 1,      /* open when the call started, closed by what earlier pairs of the call added */
+  DSM_PAIR_UNREGISTERED = 2,
+  DSM_PAIR_TRIALS_EXHAUSTED = 3,
+  DSM_PAIR_BOGUS_CAMERA = 4,            /* the trial is counted */
+  DSM_PAIR_PROCESSED = 5
+};
+
+typedef struct dsm_pair_retriangulation_report {
+  uint32_t num_candidates;        /* pairs open on the input state, registered, with trials left, on cameras that pass */
+  uint32_t num_rounds;            /* rounds of the schedule: 1 + the longest chain of candidate pairs sharing features */
+  uint64_t num_pairs_by_status[6];
+  uint64_t num_correspondences;   /* matches kept after the duplicate rule, over all pairs */
+  /* the correspondences of the processed pairs by case; tried = taken + rejected (a two-view skip is not a try) */
+  uint64_t num_both, num_continue_tried, num_continue_taken, num_two_view_skipped, num_create_tried, num_create_taken;
+  uint64_t num_tris;              /* observations added: one per Continue taken, two per point created */
+  uint64_t num_new_points;
+  uint64_t num_continued;
+  /* the margins of dsm_triangulation_report that occur here (INFINITY when never taken): both residuals of a Create,
+     its triangulation angle, its cheirality depths, Continue's error against re_max_angle_error, the bogus ratios */
+  double min_residual_margin, min_angle_margin, min_depth_margin, min_continue_margin, min_bogus_margin;
+  double setup_ms;                /* host validation and canonical order (host clock) */
+  double graph_ms;                /* HIP events: uploads, duplicate rule, ranks, the correspondence lists, the first counts */
+  double schedule_ms;             /* candidates and their rounds: one pass over the candidates' feature sets (host clock) */
+  double rounds_ms;               /* HIP events: the first round's gate to the last round's solve */
+  double gate_ms, solve_ms;       /* HIP events, summed over the rounds; 0 in a call of more than 1024 rounds, which records
+                                     no events per round */
+  double round_gap_ms;            /* rounds_ms outside the kernels (launch gaps); 0 where gate_ms and solve_ms are */
+  double download_ms;             /* HIP events: the final counts and the results back to the host */
+  double assemble_ms;             /* ids, tracks and lists from the results (host clock) */
+  double device_ms;               /* HIP events: first upload to the last download */
+} dsm_pair_retriangulation_report;
+
+void dsm_default_pair_retriangulation_options(dsm_pair_retriangulation_options* o);
+
+/* Retriangulate over the image pairs (host pointers).  The scene arguments are those of dsm_retriangulate, without the
+ * separators.  T = points2D_offsets[num_images].
+ *   re_num_trials[num_pairs]: the trials every pair has had (the reference's re_num_trials_, which persists across calls; here
+ *     the host owns it), in input pair order; read, and written with the trials of this call added.  NULL: zeros, nothing out.
+ * Outputs, each with room for T entries unless its size is given:
+ *   new points in id order: new_point_ids, new_point_xyz (3 each), new_track_obs (4 each: image_id1, point2D_idx1, image_id2,
+ *     point2D_idx2); *n_new_points
+ *   continued_obs (image_id, point2D_idx) with continued_point_ids, in the sequential order; *n_continued
+ *   touched_obs (image_id, point2D_idx) ascending with touched_point_ids: every point2D that received a point; *n_touched
+ *   pair_num_total_corrs[num_pairs], pair_num_tri_corrs[num_pairs] (after the call), pair_status[num_pairs] (DSM_PAIR_*), in
+ *     input pair order; *num_tris_out
+ * Output arrays other than the counts may be NULL.  report may be NULL.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT): everything dsm_retriangulate refuses; a non-finite or non-positive re_max_angle_error; a
+ *   non-finite or negative re_min_ratio; a negative re_max_trials.
+ * The result is the same bytes for any order of the points3D, for any order of the matches inside a pair (when no match of
+ * the pair is dropped as a duplicate), and for a pair written as (image2, image1) with its matches swapped. */
+int dsm_retriangulate_pairs(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
+                            uint32_t num_images, const uint32_t* image_ids, const uint32_t* image_camera_ids,
+                            const uint8_t* image_registered, const double* image_qvec, const double* image_tvec,
+                            const uint32_t* points2D_offsets, const double* points2D_xy, const int32_t* points2D_point3D,
+                            uint32_t num_points3D, const uint64_t* point3D_ids, const double* point3D_xyz, uint32_t num_pairs,
+                            const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
+                            uint64_t next_point3D_id, const dsm_pair_retriangulation_options* options, uint32_t* re_num_trials,
+                            uint64_t* new_point_ids, double* new_point_xyz, uint32_t* new_track_obs, uint64_t* n_new_points,
+                            uint32_t* continued_obs, uint64_t* continued_point_ids, uint64_t* n_continued, uint32_t* touched_obs,
+                            uint64_t* touched_point_ids, uint64_t* n_touched, uint32_t* pair_num_total_corrs,
+                            uint32_t* pair_num_tri_corrs, uint8_t* pair_status, uint64_t* num_tris_out,
+                            dsm_pair_retriangulation_report* report);
+
 /* ------------------------------------------------------------------ absolute pose estimation (image registration)
  * EstimateAbsolutePose (src/estimators/pose.cc:48-158) as IncrementalMapper::RegisterNextImage calls it
  * (src/sfm/incremental_mapper.cc:438-496), for a batch of independent problems: per problem a camera, N
