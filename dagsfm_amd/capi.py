@@ -1096,6 +1096,7 @@ class Context:
         """dsm_align_clusters (SfMAligner::Align up to the transforms, DESIGN.md 11).  clusters: a list of K dicts with
         image_ids [r] (registered images), point_ids [p] (uint64), xyz [p, 3] (float64) and obs [m, 3] (image_id, point2D_idx,
         point index inside the cluster).  seeds: None or a [K, K] uint32 array, seeds[a, b] for the direction a -> b.
+        A non-finite xyz coordinate or threshold raises DsmError ("non-finite"), like every other invalid input.
         Returns a dict: pairs (ALIGN_PAIR_DTYPE records in ascending (i, j)), anchor, in_component [K] bool, mst_parent [K],
         sim3_to_anchor as s [K], R [K, 3, 3], t [K, 3], separators (sorted image ids), report."""
         K = len(clusters)

@@ -629,6 +629,7 @@ extern "C" int dsm_align_clusters(dsm_ctx* ctx, uint32_t K, const uint32_t* imag
     o = *options;
   else
     dsm_default_align_options(&o);
+  if (!std::isfinite(o.threshold)) return fail(DSM_ERR_INVALID_ARGUMENT, "non-finite threshold");
   if (!(o.threshold > 0.0) || !(o.failure_probability > 0.0 && o.failure_probability < 1.0) || !(o.max_reprojection_error >= 0.0) ||
       o.min_iterations < 0 || o.max_iterations < 1 || o.max_iterations < o.min_iterations || o.max_iterations > kAlMaxIterationsCap)
     return fail(DSM_ERR_INVALID_ARGUMENT, "option out of range");
@@ -639,6 +640,9 @@ extern "C" int dsm_align_clusters(dsm_ctx* ctx, uint32_t K, const uint32_t* imag
     return fail(DSM_ERR_INVALID_ARGUMENT, "a repeated point id inside one cluster");
   };
   if (M >= 0x80000000u || P >= 0x80000000u) return fail(DSM_ERR_INVALID_ARGUMENT, "too many points or observations");
+  // a NaN or an infinite coordinate would reach the SVD of every trial that samples it: refused here, before the first launch
+  for (size_t q = 0; q < 3 * (size_t)P; ++q)
+    if (!std::isfinite(point_xyz[q])) return fail(DSM_ERR_INVALID_ARGUMENT, "non-finite point_xyz");
   dsm_align_report rep{};
   rep.num_clusters = K;
   rep.num_observations = M;

@@ -587,7 +587,7 @@ int dsm_get_clustering_spectrum(dsm_ctx* ctx, double* values, uint32_t values_ca
  *   Free choices: no edge for N <= 2 (the reference: NaN / a rotation-only LM); the closed form instead of
  *   Refine_RTS; seeds per (i, j, direction); ties by cluster index. */
 typedef struct dsm_align_options {
-  double threshold;              /* 0.1: PROSAC error_thresh (AlignOptions); <= 0 -> DSM_ERR_INVALID_ARGUMENT */
+  double threshold;              /* 0.1: PROSAC error_thresh (AlignOptions); <= 0 or non-finite -> DSM_ERR_INVALID_ARGUMENT */
   double max_reprojection_error; /* 1.8: larger edge weights are dropped */
   double failure_probability;    /* 0.01 (RansacParameters); outside (0, 1) -> invalid */
   int32_t min_iterations;        /* 100 */
@@ -648,7 +648,8 @@ uint32_t dsm_align_seed(uint32_t i, uint32_t j, uint32_t direction, uint32_t use
  *   obs_offsets[K + 1], obs (3 x uint32 per track element: image_id, point2D_idx, point index inside the cluster)
  *   options  NULL = dsm_default_align_options; seeds NULL = dsm_align_seed, else K * K entries, seeds[a * K + b] for a -> b.
  * Invalid (DSM_ERR_INVALID_ARGUMENT): K == 0 or K > 65536, an observation on an image the cluster has not registered, a point
- * index out of range, a repeated (image_id, point2D_idx) or point id inside one cluster, options out of range.
+ * index out of range, a repeated (image_id, point2D_idx) or point id inside one cluster, options out of range, a non-finite
+ * point_xyz coordinate or threshold (checked on the host before the first launch; the message says "non-finite").
  * Outputs: pairs_out (capacity pairs_capacity; *n_pairs_out = their number, only the first min(number, capacity) written) in
  *   ascending (i, j); *anchor_out; per cluster in_component, mst_parent (-1: the anchor or outside the component) and
  *   sim3_to_anchor (13 doubles: s, R row-major, t; the identity outside the component); separators (capacity: the summed
