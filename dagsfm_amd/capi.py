@@ -99,6 +99,35 @@ class RotationAveragingReport(ctypes.Structure):
         return d
 
 
+NLR_TRACE_COLUMNS = 6  # DSM_NLR_TRACE_COLUMNS: cost, radius, rho, CG iterations, accepted, gradient max-norm
+
+
+class NonlinearRotationOptions(ctypes.Structure):
+    """dsm_nonlinear_rotation_options: NonlinearRotationEstimator (/root/reference/src/rotation_estimation/
+    nonlinear_rotation_estimator.h:86, .cpp:123-125) and ceres::Solver::Options defaults."""
+    _fields_ = [("robust_loss_width", ctypes.c_double), ("max_num_iterations", ctypes.c_int32),
+                ("max_num_consecutive_invalid_steps", ctypes.c_int32), ("function_tolerance", ctypes.c_double),
+                ("gradient_tolerance", ctypes.c_double), ("parameter_tolerance", ctypes.c_double),
+                ("initial_trust_region_radius", ctypes.c_double), ("max_trust_region_radius", ctypes.c_double),
+                ("min_relative_decrease", ctypes.c_double), ("min_lm_diagonal", ctypes.c_double), ("max_lm_diagonal", ctypes.c_double),
+                ("max_num_cg_iterations", ctypes.c_int32), ("reserved", ctypes.c_int32), ("cg_tolerance", ctypes.c_double),
+                ("cg_max_residual", ctypes.c_double), ("max_relative_rotation_difference_degrees", ctypes.c_double)]
+
+
+class NonlinearRotationReport(ctypes.Structure):
+    _fields_ = [("num_components", ctypes.c_uint32), ("num_images", ctypes.c_uint32), ("num_edges", ctypes.c_uint32),
+                ("termination", ctypes.c_int32), ("num_iterations", ctypes.c_uint32), ("num_successful_steps", ctypes.c_uint32),
+                ("num_rejected_steps", ctypes.c_uint32), ("num_invalid_steps", ctypes.c_uint32), ("num_filtered_edges", ctypes.c_uint32),
+                ("num_final_images", ctypes.c_uint32), ("total_cg_iterations", ctypes.c_uint64),
+                ("num_kernel_launches", ctypes.c_uint64), ("initial_cost", ctypes.c_double),
+                ("final_cost", ctypes.c_double), ("final_trust_region_radius", ctypes.c_double),
+                ("max_cg_relative_residual", ctypes.c_double), ("min_rho_margin", ctypes.c_double),
+                ("min_gradient_margin", ctypes.c_double), ("min_function_margin", ctypes.c_double), ("device_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class ClusteringOptions(ctypes.Structure):
     """dsm_clustering_options: ImageClustering::Options defaults (src/clustering/image_clustering.h:126-132)
     and Spectra's compute() stopping rule."""
@@ -407,6 +436,11 @@ def lib(check=False):
         L.dsm_view_graph_rotation_averaging.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.POINTER(RotationAveragingOptions)] + [vp] * 7
         L.dsm_default_rotation_averaging_options.argtypes = [ctypes.POINTER(RotationAveragingOptions)]
         L.dsm_default_rotation_averaging_options.restype = None
+        L.dsm_default_nonlinear_rotation_options.argtypes = [ctypes.POINTER(NonlinearRotationOptions)]
+        L.dsm_default_nonlinear_rotation_options.restype = None
+        L.dsm_view_graph_rotation_averaging_nonlinear.argtypes = ([vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint32, vp, vp,
+                                                                  ctypes.POINTER(NonlinearRotationOptions)] + [vp] * 8)
+        L.dsm_debug_pairwise_rotation_error.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_double, vp, vp, vp]
         L.dsm_view_graph_cluster.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.POINTER(ClusteringOptions)] + [vp] * 8
         L.dsm_default_clustering_options.argtypes = [ctypes.POINTER(ClusteringOptions)]
         L.dsm_default_clustering_options.restype = None
@@ -505,6 +539,14 @@ def default_two_view_options(**kw):
 def default_rotation_averaging_options(**kw):
     o = RotationAveragingOptions()
     lib().dsm_default_rotation_averaging_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_nonlinear_rotation_options(**kw):
+    o = NonlinearRotationOptions()
+    lib().dsm_default_nonlinear_rotation_options(ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -1051,6 +1093,56 @@ class Context:
         k = nimg.value
         return {"image_ids": ids[:k].copy(), "orientations": orient[:k].copy(), "in_final_cc": fin[:k].astype(bool),
                 "edge_state": state[:n].copy(), "relative_rotations": rel[:n].copy(), "report": rep}
+
+    def rotation_averaging_nonlinear(self, pairs, qvecs, use=None, initial=None, options=None):
+        """dsm_view_graph_rotation_averaging_nonlinear (GlobalRotationAveraging with the NONLINEAR estimator: largest component,
+        NonlinearRotationEstimator, orientation filter, largest component).  initial: None (every orientation starts at zero) or a
+        dict with image_ids (ascending) and orientations -- what rotation_averaging returns fits.  Returns the dict of
+        rotation_averaging with a NonlinearRotationReport, plus trace [iterations + 1, NLR_TRACE_COLUMNS].  The orientations
+        carry a free common rotation: compare them relative to one image."""
+        p = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        q = np.ascontiguousarray(qvecs, np.float64).reshape(-1, 4)
+        assert len(p) == len(q)
+        n = len(p)
+        u = None if use is None else np.ascontiguousarray(use, np.uint8).reshape(-1)
+        assert u is None or len(u) == n
+        n_init, init_ids, init_aa = 0, None, None
+        if initial is not None:
+            init_ids = np.ascontiguousarray(initial["image_ids"], np.uint32).reshape(-1)
+            init_aa = np.ascontiguousarray(initial["orientations"], np.float64).reshape(-1, 3)
+            assert len(init_ids) == len(init_aa)
+            n_init = len(init_ids)
+        opts = options if options is not None else default_nonlinear_rotation_options()
+        cap = max(2 * n, 1)
+        ids = np.zeros(cap, np.uint32)
+        orient = np.zeros((cap, 3), np.float64)
+        fin = np.zeros(cap, np.uint8)
+        nimg = ctypes.c_uint32(0)
+        state = np.zeros(max(n, 1), np.uint8)
+        rel = np.zeros((max(n, 1), 3), np.float64)
+        rep = NonlinearRotationReport()
+        trace = np.full((max(int(opts.max_num_iterations), 0) + 1, NLR_TRACE_COLUMNS), np.nan)
+        self._chk(self._L.dsm_view_graph_rotation_averaging_nonlinear(
+            self._h, n, p.ctypes.data, q.ctypes.data, None if u is None else u.ctypes.data, n_init,
+            init_ids.ctypes.data if n_init else None, init_aa.ctypes.data if n_init else None, ctypes.byref(opts), ids.ctypes.data,
+            orient.ctypes.data, fin.ctypes.data, ctypes.addressof(nimg), state.ctypes.data, rel.ctypes.data, ctypes.addressof(rep),
+            trace.ctypes.data))
+        k = nimg.value
+        return {"image_ids": ids[:k].copy(), "orientations": orient[:k].copy(), "in_final_cc": fin[:k].astype(bool),
+                "edge_state": state[:n].copy(), "relative_rotations": rel[:n].copy(), "report": rep,
+                "trace": trace[:rep.num_iterations + 1].copy() if k else trace[:0].copy()}
+
+    def debug_pairwise_rotation_error(self, rotation1, rotation2, relative_rotation, loss_width=0.1):
+        """dsm_debug_pairwise_rotation_error: the per-edge device function of rotation_averaging_nonlinear on n triples of
+        angle-axis rotations.  Returns (residuals [n, 3], jacobians [n, 2, 3, 3] with respect to rotation1 and rotation2, both after
+        the loss corrector, rho [n, 3] = rho, rho', rho'' at the uncorrected |r|^2)."""
+        a = [np.ascontiguousarray(v, np.float64).reshape(-1, 3) for v in (rotation1, rotation2, relative_rotation)]
+        n = len(a[0])
+        assert len(a[1]) == n and len(a[2]) == n
+        res, jac, rho = np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 2, 3, 3)), np.zeros((max(n, 1), 3))
+        self._chk(self._L.dsm_debug_pairwise_rotation_error(self._h, n, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data,
+                                                          float(loss_width), res.ctypes.data, jac.ctypes.data, rho.ctypes.data))
+        return res[:n], jac[:n], rho[:n]
 
     def cluster_view_graph(self, pairs, weights, use=None, labels_in=None, options=None):
         """dsm_view_graph_cluster (ClusteringScenes: SPECTRAL on the device, or Cut + Expand over labels_in).  Returns a dict:

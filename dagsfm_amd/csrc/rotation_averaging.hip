@@ -29,11 +29,9 @@
 #include "ctx.h"
 #include "graph_edges.h"
 #include "rotation_ceres.h"
+#include "rotation_graph.h"
 
 namespace {
-
-constexpr int RA_BLOCK = 256;
-constexpr double kRaDegToRad = 0.017453292519943295;  // M_PI / 180 (util.h DegToRad)
 
 // device-side loop state; every field has one writer per launch and no reader in that launch
 struct RaCtl {
@@ -51,26 +49,6 @@ struct RaCtl {
   double last_step;     // average step of the last L1 / IRLS iteration
   double admm_r, admm_s, admm_pe, admm_de;  // the last ADMM stopping values
 };
-
-// ---------------------------------------------------------------- rotations (ceres' conversions, rotation_ceres.h)
-__device__ inline void aa_to_R(const double* aa, double* R) { ceres_angle_axis_to_rotation(aa, R); }
-__device__ inline void R_to_aa(const double* R, double* aa) {  // RotationMatrixToAngleAxis
-  double q[4];
-  ceres_rotation_to_quaternion(R, q);
-  ceres_quaternion_to_angle_axis(q, aa);
-}
-__device__ inline void matmul3(const double* A, const double* B, double* C) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) C[i * 3 + j] = A[i * 3 + 0] * B[0 * 3 + j] + A[i * 3 + 1] * B[1 * 3 + j] + A[i * 3 + 2] * B[2 * 3 + j];
-}
-// MultiplyRotations (src/math/rotation.cpp:157-167): AngleAxis(R(a) * R(b))
-__device__ inline void mul_rot(const double* a, const double* b, double* out) {
-  double Ra[9], Rb[9], C[9];
-  aa_to_R(a, Ra);
-  aa_to_R(b, Rb);
-  matmul3(Ra, Rb, C);
-  R_to_aa(C, out);
-}
 
 __device__ inline bool gated(const RaCtl* c, int admm_t) { return admm_t >= 0 && admm_t >= c->admm_stop; }
 
@@ -129,34 +107,6 @@ __global__ void __launch_bounds__(RA_BLOCK) k_ra_admm_edges(uint32_t M, const ui
     }
   }
   write_partials<RA_BLOCK, 3>(acc, sh, P);
-}
-
-// FilterViewPairsFromOrientation (filter_view_pairs_from_orientation.cpp:22-35, 71-80): keep iff
-// |MultiplyRotations(-R12, MultiplyRotations(R_j, -R_i))|^2 <= theta^2; a kept edge gets RelativeRotationFromTwoRotations
-// (util.h:97-106) = AngleAxis(R(R_j) * R(R_i)^T)
-__global__ void __launch_bounds__(RA_BLOCK) k_ra_filter(uint32_t M, const uint32_t* __restrict__ ei, const uint32_t* __restrict__ ej,
-                                                        const double* __restrict__ r12, const double* __restrict__ R, double sq_thr,
-                                                        uint8_t* __restrict__ state, double* __restrict__ rel) {
-  const uint32_t e = blockIdx.x * RA_BLOCK + threadIdx.x;
-  if (e >= M) return;
-  const double* Ri = R + 3 * (size_t)ei[e];
-  const double* Rj = R + 3 * (size_t)ej[e];
-  const double* a = r12 + 3 * (size_t)e;
-  double mRi[3] = {-Ri[0], -Ri[1], -Ri[2]}, ma[3] = {-a[0], -a[1], -a[2]}, comp[3], loop[3];
-  mul_rot(Rj, mRi, comp);
-  mul_rot(ma, comp, loop);
-  const bool ok = loop[0] * loop[0] + loop[1] * loop[1] + loop[2] * loop[2] <= sq_thr;
-  state[e] = ok ? 3 : 2;
-  double out[3] = {0.0, 0.0, 0.0};
-  if (ok) {
-    double M1[9], M2[9], T[9];
-    aa_to_R(Ri, M1);
-    aa_to_R(Rj, M2);
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) T[i * 3 + j] = M2[i * 3 + 0] * M1[j * 3 + 0] + M2[i * 3 + 1] * M1[j * 3 + 1] + M2[i * 3 + 2] * M1[j * 3 + 2];
-    R_to_aa(T, out);
-  }
-  for (int c = 0; c < 3; ++c) rel[3 * (size_t)e + c] = out[c];
 }
 
 // ---------------------------------------------------------------- per-image kernels (gathers over the CSR row)
@@ -457,40 +407,6 @@ __global__ void k_ra_fill(double* __restrict__ a, size_t n, double v) {
   if (i < n) a[i] = v;
 }
 
-// ---------------------------------------------------------------- host side
-struct Uf {
-  std::vector<uint32_t> p;
-  explicit Uf(size_t n) : p(n) { std::iota(p.begin(), p.end(), 0u); }
-  uint32_t find(uint32_t x) {
-    while (p[x] != x) x = p[x] = p[p[x]];
-    return x;
-  }
-  void join(uint32_t a, uint32_t b) {
-    a = find(a);
-    b = find(b);
-    if (a != b) p[std::max(a, b)] = std::min(a, b);  // the root is the smallest member
-  }
-};
-
-// the largest component of (verts 0..V-1, edges); ties: the one holding the smallest vertex (vertices ascend with image id).
-// Returns the flag per vertex and the number of components.
-uint32_t largest_component(uint32_t V, const std::vector<std::pair<uint32_t, uint32_t>>& edges, std::vector<uint8_t>& in_cc) {
-  Uf uf(V);
-  for (const auto& e : edges) uf.join(e.first, e.second);
-  std::vector<uint32_t> size(V, 0);
-  uint32_t n_comp = 0;
-  for (uint32_t v = 0; v < V; ++v) {
-    if (uf.find(v) == v) ++n_comp;
-    ++size[uf.find(v)];
-  }
-  uint32_t best = 0;
-  for (uint32_t v = 0; v < V; ++v)  // ascending roots = ascending smallest members: the first maximum wins
-    if (size[v] > size[best]) best = v;
-  in_cc.assign(V, 0);
-  for (uint32_t v = 0; v < V; ++v) in_cc[v] = V && uf.find(v) == best;
-  return n_comp;
-}
-
 }  // namespace
 
 extern "C" void dsm_default_rotation_averaging_options(dsm_rotation_averaging_options* o) {
@@ -538,76 +454,17 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
   dsm_rotation_averaging_report rep{};
   *n_images_out = 0;
   if (report) *report = rep;
-  // argument checks on every used edge before anything is written
-  for (uint32_t e = 0; e < n_pairs; ++e) {
-    if (use && !use[e]) continue;
-    if (pairs[2 * e] == pairs[2 * e + 1]) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_rotation_averaging: image_id1 == image_id2");
-    const double* q = qvecs + 4 * (size_t)e;
-    bool finite = true, zero = true;
-    for (int c = 0; c < 4; ++c) {
-      finite &= std::isfinite(q[c]);
-      zero &= q[c] == 0.0;
-    }
-    if (!finite || zero) return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, "dsm_view_graph_rotation_averaging: non-finite or zero qvec");
-  }
-  for (uint32_t e = 0; e < n_pairs; ++e) {
-    edge_state[e] = 0;
-    for (int c = 0; c < 3; ++c) relative_rotations_out[3 * (size_t)e + c] = 0.0;
-  }
-  // host: unique used edges (the first occurrence of an unordered pair wins, ViewGraph::AddTwoViewGeometry), images renumbered
-  // by ascending id, the first component (ImageGraph::ExtractLargestCC)
-  std::vector<uint32_t> ids;
-  const std::vector<GraphEdge> uniq = graph_unique_edges(n_pairs, pairs, use, ids);
-  if (uniq.empty()) return DSM_OK;
-  const uint32_t V = (uint32_t)ids.size();
-  std::vector<std::pair<uint32_t, uint32_t>> ue;
-  for (const GraphEdge& x : uniq) ue.emplace_back(x.lo, x.hi);
-  std::vector<uint8_t> in1;
-  rep.num_components = largest_component(V, ue, in1);
-  std::vector<uint32_t> cid(V, UINT32_MAX), cimg;  // component renumbering: ascending id, cimg[0] is the constant image
-  for (uint32_t v = 0; v < V; ++v)
-    if (in1[v]) {
-      cid[v] = (uint32_t)cimg.size();
-      cimg.push_back(ids[v]);
-    }
-  const uint32_t N = (uint32_t)cimg.size();
-  std::vector<GraphEdge> ce_edges;  // edges of the component in canonical (lo, hi) order, vertices in component numbering
-  for (const GraphEdge& x : uniq) {
-    if (!in1[x.lo]) {
-      edge_state[x.orig] = 1;
-      continue;
-    }
-    ce_edges.push_back(GraphEdge{cid[x.lo], cid[x.hi], cid[x.i], cid[x.j], x.orig});
-  }
-  const uint32_t M = (uint32_t)ce_edges.size();
+  // step 1 (rotation_graph.h): the checks on every used edge, the unique edges, the first component and its CSR
+  RaGraph g;
+  if (const int grc = ra_build_graph(ctx, "dsm_view_graph_rotation_averaging", n_pairs, pairs, qvecs, use, edge_state, relative_rotations_out, g))
+    return grc;
+  if (g.M == 0) return DSM_OK;
+  const uint32_t N = g.N, M = g.M;
+  const std::vector<uint32_t>&ei = g.ei, &ej = g.ej, &off = g.off, &nb = g.nb, &cev = g.cev;
+  const std::vector<double>& r12 = g.r12;
+  rep.num_components = g.num_components;
   rep.num_images = N;
   rep.num_edges = M;
-  // CSR over images, entries sorted by neighbour; cev: 2 k + 1 where the entry's image is edge k's image j, else 2 k
-  std::vector<uint32_t> ei(M), ej(M), off, nb, cev;
-  graph_neighbour_csr(N, ce_edges, off, nb, cev);
-  for (uint32_t v = 0; v < N; ++v)
-    for (uint32_t p = off[v]; p < off[v + 1]; ++p) {
-      const uint32_t k = cev[p];
-      cev[p] = 2 * k + (ce_edges[k].j == v ? 1u : 0u);
-    }
-  std::vector<double> r12(3 * (size_t)M);
-  for (uint32_t k = 0; k < M; ++k) {
-    const GraphEdge& x = ce_edges[k];
-    ei[k] = x.i;
-    ej[k] = x.j;
-    // QuaternionToAngleAxis (ceres) on the host, the formula of rotation_ceres.h
-    const double* q = qvecs + 4 * (size_t)x.orig;
-    const double q1 = q[1], q2 = q[2], q3 = q[3];
-    const double s2 = q1 * q1 + q2 * q2 + q3 * q3;
-    double kk = 2.0;
-    if (s2 > 0.0) {
-      const double st = sqrt(s2), ct = q[0];
-      kk = 2.0 * ((ct < 0.0) ? atan2(-st, -ct) : atan2(st, ct)) / st;
-    }
-    r12[3 * (size_t)k] = q1 * kk;
-    r12[3 * (size_t)k + 1] = q2 * kk;
-    r12[3 * (size_t)k + 2] = q3 * kk;
-  }
 
   hipError_t he = hipSetDevice(ctx->device);
   if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
@@ -773,26 +630,8 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
   rep.total_cg_iterations = h.cg_total;
   rep.max_cg_relative_residual = h.cg_worst;
   if (rc == DSM_OK) {
-    // the largest component of the surviving edges (:1000-1003), same tie rule
-    std::vector<std::pair<uint32_t, uint32_t>> kept;
-    for (uint32_t k = 0; k < M; ++k) {
-      edge_state[ce_edges[k].orig] = st8[k];
-      if (st8[k] == 3) {
-        kept.emplace_back(ce_edges[k].lo, ce_edges[k].hi);
-        for (int c = 0; c < 3; ++c) relative_rotations_out[3 * (size_t)ce_edges[k].orig + c] = relh[3 * (size_t)k + c];
-      } else {
-        ++rep.num_filtered_edges;
-      }
-    }
-    std::vector<uint8_t> fin;
-    largest_component(N, kept, fin);
-    for (uint32_t v = 0; v < N; ++v) {
-      image_ids_out[v] = cimg[v];
-      for (int c = 0; c < 3; ++c) orientations_out[3 * (size_t)v + c] = Rh[3 * (size_t)v + c];
-      image_in_final_cc[v] = fin[v];
-      rep.num_final_images += fin[v];
-    }
-    *n_images_out = N;
+    ra_write_outputs(g, st8, relh, Rh, image_ids_out, orientations_out, image_in_final_cc, n_images_out, edge_state, relative_rotations_out,
+                     &rep.num_filtered_edges, &rep.num_final_images);
   } else {
     for (uint32_t e = 0; e < n_pairs; ++e) edge_state[e] = 0;
   }

@@ -499,6 +499,89 @@ int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs, const uint
                                       uint32_t* n_images_out, uint8_t* edge_state, double* relative_rotations_out,
                                       dsm_rotation_averaging_report* report);
 
+/* ------------------------------------------------------------------ global rotation averaging, NONLINEAR
+ * GlobalRotationAveraging() with global_rotation_estimator_type = NONLINEAR
+ * (src/controllers/distributed_mapper_controller.cpp:969-986): steps 1, 3 and 4 above, and as step 2
+ * NonlinearRotationEstimator::EstimateRotations (src/rotation_estimation/nonlinear_rotation_estimator.cpp:82-131): one
+ * PairwiseRotationError (src/rotation_estimation/pairwise_rotation_error.h:98-128; weight 1) per edge under one
+ * ceres::SoftLOneLoss(robust_loss_width), no constant block, ceres' Levenberg-Marquardt with max_num_iterations = 200 and
+ * otherwise ceres' defaults.  The trust-region rules are dsm_bundle_adjust's without the Schur part; the
+ * reference's sparse Cholesky of J^T J + D / radius is a conjugate gradient preconditioned by the exact 3 x 3 diagonal
+ * blocks here.  The cost is invariant under one rotation applied to every image and nothing holds that
+ * gauge: compare orientations relative to one image, or as edge rotations, never absolutely. */
+typedef struct dsm_nonlinear_rotation_options {
+  double robust_loss_width;              /* 0.1 (nonlinear_rotation_estimator.h:86); > 0 */
+  int32_t max_num_iterations;            /* 200 (nonlinear_rotation_estimator.cpp:125) */
+  int32_t max_num_consecutive_invalid_steps; /* 5 (ceres) */
+  double function_tolerance;             /* 1e-6 (ceres) */
+  double gradient_tolerance;             /* 1e-10 (ceres) */
+  double parameter_tolerance;            /* 1e-8 (ceres) */
+  double initial_trust_region_radius;    /* 1e4 (ceres) */
+  double max_trust_region_radius;        /* 1e16 (ceres) */
+  double min_relative_decrease;          /* 1e-3 (ceres) */
+  double min_lm_diagonal;                /* 1e-6 (ceres) */
+  double max_lm_diagonal;                /* 1e32 (ceres) */
+  int32_t max_num_cg_iterations;         /* 0: max(1000, 20 * images of the component) per solve */
+  int32_t reserved;
+  double cg_tolerance;                   /* 1e-14: relative residual at which a solve stops.  Tighter than the robust stage's
+                                            1e-12: the reference factorises exactly, and a step solved to 1e-12 moves the cost
+                                            of the iterations in mid-descent by up to 1e-7 relative */
+  double cg_max_residual;                /* 1e-9: a solve that ends above it is DSM_ERR_NOT_CONVERGED */
+  double max_relative_rotation_difference_degrees; /* 5.0 (DistributedMapperController options) */
+} dsm_nonlinear_rotation_options;
+
+typedef struct dsm_nonlinear_rotation_report {
+  uint32_t num_components;          /* connected components of the used edges */
+  uint32_t num_images;              /* images of the largest one */
+  uint32_t num_edges;               /* edges of the largest one (the residual blocks) */
+  int32_t termination;              /* DSM_BA_CONVERGENCE / DSM_BA_NO_CONVERGENCE / DSM_BA_FAILURE: reported, never an
+                                       error -- the reference does not look at ceres' summary either */
+  uint32_t num_iterations;          /* LM iterations (every step counts) */
+  uint32_t num_successful_steps;
+  uint32_t num_rejected_steps;      /* valid steps that did not reduce the cost enough */
+  uint32_t num_invalid_steps;
+  uint32_t num_filtered_edges;      /* edges removed by the orientation filter */
+  uint32_t num_final_images;        /* images of the largest component after the filter */
+  uint64_t total_cg_iterations;
+  uint64_t num_kernel_launches;     /* launches of the estimator, the no-ops past a stop flag included */
+  double initial_cost, final_cost;  /* 1/2 sum rho(|r|^2) */
+  double final_trust_region_radius;
+  double max_cg_relative_residual;  /* largest final relative residual over all solves */
+  double min_rho_margin;            /* |(cost - candidate) - min_relative_decrease * model_cost_change| / cost */
+  double min_gradient_margin;       /* relative distance of the gradient max-norm from gradient_tolerance */
+  double min_function_margin;       /* relative distance of |cost - candidate| from function_tolerance * cost */
+  double device_ms;                 /* HIP events: first upload to the last kernel */
+} dsm_nonlinear_rotation_report;
+
+void dsm_default_nonlinear_rotation_options(dsm_nonlinear_rotation_options* o);
+
+#define DSM_NLR_TRACE_COLUMNS 6  /* DSM_BA_TRACE_COLUMNS: cost, radius, rho, CG iterations, accepted, gradient max-norm */
+
+/* The arrays of dsm_view_graph_rotation_averaging, in and out, and additionally:
+ *   n_initial = 0: every orientation starts at zero, as Run() does (distributed_mapper_controller.cpp:949-952).  Otherwise
+ *     initial_image_ids (n_initial ids, ascending) and initial_orientations (n_initial x 3, angle-axis) -- the image_ids_out /
+ *     orientations_out of dsm_view_graph_rotation_averaging fit -- must hold every image of the first component; ids outside
+ *     it are ignored.  A missing image, a non-finite value, unsorted or repeated ids: DSM_ERR_INVALID_ARGUMENT.
+ *   options NULL = dsm_default_nonlinear_rotation_options; report may be NULL; trace NULL or (max_num_iterations + 1) x
+ *     DSM_NLR_TRACE_COLUMNS doubles (rows past the last iteration untouched).
+ * DSM_OK whatever the termination type, with the last accepted state; only a conjugate-gradient solve that ends above
+ * cg_max_residual fails the call (DSM_ERR_NOT_CONVERGED). */
+int dsm_view_graph_rotation_averaging_nonlinear(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const double* qvecs,
+                                                const uint8_t* use, uint32_t n_initial, const uint32_t* initial_image_ids,
+                                                const double* initial_orientations,
+                                                const dsm_nonlinear_rotation_options* options, uint32_t* image_ids_out,
+                                                double* orientations_out, uint8_t* image_in_final_cc, uint32_t* n_images_out,
+                                                uint8_t* edge_state, double* relative_rotations_out,
+                                                dsm_nonlinear_rotation_report* report, double* trace);
+
+/* The per-edge device function of the call above on n arbitrary triples (a test hook, like dsm_debug_image_to_world):
+ * rotation1, rotation2, relative_rotation n x 3 angle-axis; residuals n x 3 and jacobians n x 18 (3 x 3 row-major with
+ * respect to rotation1, then rotation2) after the loss corrector; rho n x 3 = rho(s), rho'(s), rho''(s) at s = |r|^2 of the
+ * uncorrected residual.  Host pointers. */
+int dsm_debug_pairwise_rotation_error(dsm_ctx* ctx, uint32_t n, const double* rotation1, const double* rotation2,
+                                      const double* relative_rotation, double loss_width, double* residuals, double* jacobians,
+                                      double* rho);
+
 /* ------------------------------------------------------------------ view-graph clustering
  * The step after global rotation averaging: DistributedMapperController::ClusteringScenes
  * (src/controllers/distributed_mapper_controller.cpp:633-657) = ImageClustering::Cut() + Expand()
