@@ -12,6 +12,7 @@ import pytest
 from dagsfm_amd import capi
 from tests import absolute_pose_ref as ref
 from tests import absolute_pose_scenes as scenes
+from tests.absolute_pose_compare import compare, result_bytes, run_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -21,44 +22,6 @@ POSE_TOLERANCE = scenes.POSE_TOLERANCE  # measured on the restatement and re-mea
 @pytest.fixture(scope="module")
 def ctx():
     return capi.Context(0)
-
-
-def run_batch(ctx, problems, options=None, seeds=None):
-    offs = np.concatenate([[0], np.cumsum([len(p["xy"]) for p in problems])]).astype(np.uint64)
-    xy = np.concatenate([p["xy"].reshape(-1, 2) for p in problems] + [np.zeros((0, 2))])
-    X = np.concatenate([p["X"].reshape(-1, 3) for p in problems] + [np.zeros((0, 3))])
-    return ctx.estimate_absolute_poses([p["cam"] for p in problems], [int(p["sweep"]) for p in problems], offs, xy, X, options, seeds), offs
-
-
-def result_bytes(out):
-    return b"".join(bytes(r) for r in out["results"]) + out["inlier_mask"].tobytes()
-
-
-def close(a, b, what):
-    a, b = np.asarray(a, np.float64).ravel(), np.asarray(b, np.float64).ravel()
-    scale = max(float(np.max(np.abs(b))), 1e-300)
-    assert float(np.max(np.abs(a - b))) <= POSE_TOLERANCE * scale, (what, float(np.max(np.abs(a - b))) / scale)
-
-
-def compare(res, mask, margins, want, index):
-    """One problem of a batch against the restatement's record; returns whether it was clear on both sides."""
-    clear = ref.is_clear(want["margins"]) and ref.is_clear(list(margins))
-    assert bool(res.success) == want["success"], index
-    if clear:
-        assert res.factor_index == want["factor_index"], index
-        assert res.num_inliers == want["num_inliers"], index
-        if want["success"]:
-            assert res.num_trials == want["num_trials"], index
-            assert bool(res.model_is_local) == want["model_is_local"], index
-            assert (mask == want["mask"]).all(), index
-            close(list(res.proj_matrix), want["proj_matrix"], "model %d" % index)
-            close(list(res.qvec), want["qvec"], "qvec %d" % index)
-            close(list(res.tvec), want["tvec"], "tvec %d" % index)
-            assert list(res.focal_params) == list(want["focal_params"]), index
-            assert res.focal_length_factor == want["focal_length_factor"], index
-    else:
-        assert abs(int(res.num_inliers) - want["num_inliers"]) <= 0.02 * max(want["num_inliers"], 1) + 0.5, index
-    return clear
 
 
 def test_hand_scenes(ctx):
