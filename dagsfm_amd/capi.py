@@ -387,6 +387,14 @@ class SiftOptions(ctypes.Structure):
                 ("edge_threshold", ctypes.c_double)]
 
 
+class CovariantSiftOptions(ctypes.Structure):
+    """dsm_covariant_sift_options: the fields of SiftExtractionOptions (src/feature/sift.h) ExtractCovariantSiftFeaturesCPU reads."""
+    _fields_ = [("octave_resolution", ctypes.c_int32), ("first_octave", ctypes.c_int32), ("max_num_features", ctypes.c_int32),
+                ("upright", ctypes.c_int32), ("normalization", ctypes.c_int32), ("estimate_affine_shape", ctypes.c_int32),
+                ("domain_size_pooling", ctypes.c_int32), ("dsp_num_scales", ctypes.c_int32), ("peak_threshold", ctypes.c_double),
+                ("edge_threshold", ctypes.c_double), ("dsp_min_scale", ctypes.c_double), ("dsp_max_scale", ctypes.c_double)]
+
+
 def lib(check=False):
     """Loads the shared library (check=True: the check build); raises if it has not been built (no fallback)."""
     if check not in _libs:
@@ -489,6 +497,11 @@ def lib(check=False):
         L.dsm_sift_default_options.argtypes = [ctypes.POINTER(SiftOptions)]
         L.dsm_sift_default_options.restype = None
         L.dsm_extract_sift.argtypes = [vp, ctypes.POINTER(SiftOptions), vp] + [ctypes.c_uint32] * 4 + [vp, vp, u32p]
+        L.dsm_covariant_sift_default_options.argtypes = [ctypes.POINTER(CovariantSiftOptions)]
+        L.dsm_covariant_sift_default_options.restype = None
+        L.dsm_extract_covariant_sift.argtypes = [vp, ctypes.POINTER(CovariantSiftOptions), vp] + [ctypes.c_uint32] * 4 + [vp, vp, u32p]
+        L.dsm_get_covariant_sift_raw.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, u32p]
+        L.dsm_get_covariant_sift_time.argtypes = [vp, vp]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
         L.dsm_default_match_options.restype = None
         L.dsm_default_two_view_options.argtypes = [ctypes.POINTER(TwoViewOptions)]
@@ -621,6 +634,14 @@ def default_point_filter_options(**kw):
 def default_sift_options(**kw):
     o = SiftOptions()
     lib().dsm_sift_default_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_covariant_sift_options(check=False, **kw):
+    o = CovariantSiftOptions()
+    lib(check).dsm_covariant_sift_default_options(ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -1341,6 +1362,61 @@ class Context:
         self._L.dsm_get_sift_time.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._chk(self._L.dsm_get_sift_time(self._h, ctypes.addressof(ms)))
         return dict(zip(self.SIFT_STAGES, list(ms)))
+
+    def extract_covariant_sift(self, image_u8, options=None, descriptors=True, capacity=None, width=None):
+        """dsm_extract_covariant_sift: image_u8 [height, row_stride] grey bytes, of which the first `width` of a
+        row are the image (None: all of them).  Returns (keypoints float32 [n, 6] = (x, y, a11, a12, a21, a22), descriptors uint8
+        [n, 128] in UBC order, or None with descriptors=False).  capacity None: room for 32768 features, and a second call with
+        the count the first one reports where that is too little; a given capacity below the count raises DsmError with the
+        count in .num_features."""
+        im = np.ascontiguousarray(image_u8, np.uint8)
+        height, row_stride = im.shape
+        width = row_stride if width is None else int(width)
+        o = options if options is not None else default_covariant_sift_options()
+        n = ctypes.c_uint32(0)
+
+        def call(cap):
+            kp = np.zeros((max(cap, 1), 6), np.float32)
+            ds = np.zeros((max(cap, 1), 128), np.uint8) if descriptors else None
+            rc = self._L.dsm_extract_covariant_sift(self._h, ctypes.byref(o), im.ctypes.data, width, height, row_stride, cap, kp.ctypes.data,
+                                                    None if ds is None else ds.ctypes.data, ctypes.byref(n))
+            return rc, kp, ds
+
+        rc, kp, ds = call(32768 if capacity is None else int(capacity))
+        if rc == 4 and capacity is None and n.value > 0:
+            rc, kp, ds = call(int(n.value))
+        if rc != 0:
+            err = DsmError("dsm_extract_covariant_sift failed (%d): %s" % (rc, self._L.dsm_last_error(self._handle).decode()))
+            err.num_features = int(n.value)
+            err.status = rc
+            err.outputs = (kp, ds)  # as the library left them
+            raise err
+        return kp[:n.value].copy(), (None if ds is None else ds[:n.value].copy())
+
+    def covariant_sift_raw(self, num_scales=None):
+        """dsm_get_covariant_sift_raw: the last extract_covariant_sift's features in output order as {"octave_scale": int32 [n, 2],
+        "scores": float32 [n, 3] = peak, edge, orientation, "raw": float32 [n, num_scales, 128] = VLFeat's descriptor of every
+        pooling scale before the pooling, in VLFeat's bin order}.  num_scales None: no raw descriptors are fetched."""
+        n = ctypes.c_uint32(0)
+        rc = self._L.dsm_get_covariant_sift_raw(self._h, 0, None, None, None, ctypes.byref(n))
+        if rc not in (0, 4):
+            self._chk(rc)
+        cap = max(int(n.value), 1)
+        os_ = np.zeros((cap, 2), np.int32)
+        sc = np.zeros((cap, 3), np.float32)
+        raw = np.zeros((cap, int(num_scales), 128), np.float32) if num_scales else None
+        self._chk(self._L.dsm_get_covariant_sift_raw(self._h, cap, os_.ctypes.data, sc.ctypes.data, None if raw is None else raw.ctypes.data,
+                                                     ctypes.byref(n)))
+        k = int(n.value)
+        return {"octave_scale": os_[:k].copy(), "scores": sc[:k].copy(), "raw": None if raw is None else raw[:k].copy()}
+
+    COVARIANT_SIFT_STAGES = ("scale_space", "detection", "orientations", "descriptors", "pooling")
+
+    def covariant_sift_time(self):
+        """dsm_get_covariant_sift_time: {stage: ms} of the last extract_covariant_sift (HIP events)."""
+        ms = (ctypes.c_double * len(self.COVARIANT_SIFT_STAGES))()
+        self._chk(self._L.dsm_get_covariant_sift_time(self._h, ctypes.addressof(ms)))
+        return dict(zip(self.COVARIANT_SIFT_STAGES, list(ms)))
 
     @staticmethod
     def apply_point_filter(scene, result):

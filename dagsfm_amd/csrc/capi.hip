@@ -222,6 +222,7 @@ void dsm_ctx_destroy(dsm_ctx* ctx) {
   dsm_retrieval_destroy(ctx);
   (void)hipStreamSynchronize(ctx->stream);
   dsm_sift_destroy(ctx);
+  dsm_covariant_sift_destroy(ctx);
   delete ctx;
 }
 

@@ -219,6 +219,7 @@ struct dsm_ctx {
   uint64_t memory_budget = 0;
 
   struct RetrievalState* retrieval = nullptr;  // vocabulary-tree retrieval (retrieval.hip), created on first use
+  struct CovSiftState* covsift = nullptr;      // the scale space and the last result of dsm_extract_covariant_sift (covariant_sift.hip), created on first use
   struct SiftState* sift = nullptr;            // the scratch of dsm_extract_sift (sift_extraction.hip), created on first use, reused across calls
 
   // the final Ritz values and the k Ritz vectors ([images][k]) of the last dsm_view_graph_cluster that ran the eigen-solver
@@ -249,6 +250,7 @@ struct dsm_ctx {
 void dsm_retrieval_destroy(dsm_ctx* ctx);     // retrieval.hip
 void dsm_retrieval_invalidate(dsm_ctx* ctx);  // retrieval.hip: the resident images changed
 void dsm_sift_destroy(dsm_ctx* ctx);          // sift_extraction.hip
+void dsm_covariant_sift_destroy(dsm_ctx* ctx);  // covariant_sift.hip
 
 // keys dsm_set_debug_option accepts (an unknown key is an error, so a check-only switch fails loudly on the product build)
 static const char* const dsm_product_debug_keys[] = {"DSM_MATCH_CHUNK_ROWS", "DSM_VERIFY_CHUNK_PAIRS", "DSM_VERIFY_LANES", "DSM_VERIFY_INLINE_LO",

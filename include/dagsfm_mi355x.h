@@ -1321,7 +1321,8 @@ int dsm_adjust_local_bundles(dsm_ctx* ctx, uint32_t num_problems, const uint32_t
  * restated in the reference's evaluation order, and COLMAP's loop around them: the groups per DoG level, the first
  * max_num_orientations orientations of a keypoint, L1_ROOT / L2 (src/feature/utils.cc:47-77), the bytes, the VLFeat -> UBC bin
  * order (sift.cc:58-74) and the max_num_features cut (sift.cc:387-398; the level that crosses the limit is kept whole).
- * DESIGN.md 18.  ExtractCovariantSiftFeaturesCPU (estimate_affine_shape, domain_size_pooling) and SiftGPU are not covered. */
+ * DESIGN.md 18.  ExtractCovariantSiftFeaturesCPU (domain_size_pooling) is dsm_extract_covariant_sift below; estimate_affine_shape
+ * and SiftGPU are not covered. */
 enum { DSM_SIFT_L1_ROOT = 0, DSM_SIFT_L2 = 1 };  /* SiftExtractionOptions::Normalization, src/feature/sift.h */
 
 typedef struct dsm_sift_options {  /* SiftExtractionOptions, src/feature/sift.h:36-112 */
@@ -1357,6 +1358,70 @@ int dsm_extract_sift(dsm_ctx* ctx, const dsm_sift_options* options, const uint8_
  * refinement, 4 gradient, 5 orientations, 6 descriptors.  DSM_ERR_NOT_READY before the first call. */
 #define DSM_SIFT_STAGES 7
 int dsm_get_sift_time(dsm_ctx* ctx, double* stage_ms);
+
+/* ---- covariant SIFT feature extraction with domain-size pooling ----
+ * ExtractCovariantSiftFeaturesCPU (src/feature/sift.cc:428-598) with estimate_affine_shape = false: the extractor
+ * SiftExtraction.domain_size_pooling selects (src/feature/extraction.cc:374-380).  VLFeat's scale space (lib/VLFeat/
+ * scalespace.c:669-812, imopv.c:620-679), the DoG detector of covdet (covdet.c:1921-2144 with :1057-1126 and :1206-1318), its
+ * orientations (:2698-2892), its patch extraction (:2166-2446) and vl_sift_calc_raw_descriptor (sift.c:1754-1903) restated in
+ * the reference's evaluation order, and COLMAP's loop around them: the std::sort by (o, s) descending (sift.cc:479-487), the
+ * cut that keeps the crossing (o, s) group whole (:489-513), the pooling scales (:530-553), the mean over them (:577),
+ * L1_ROOT / L2, the bytes and the VLFeat -> UBC bin order.  DESIGN.md 21. */
+typedef struct dsm_covariant_sift_options {  /* SiftExtractionOptions, src/feature/sift.h:36-112 */
+  int32_t octave_resolution;      /* 3 */
+  int32_t first_octave;           /* -1 */
+  int32_t max_num_features;       /* 8192 */
+  int32_t upright;                /* 0 */
+  int32_t normalization;          /* DSM_SIFT_L1_ROOT */
+  int32_t estimate_affine_shape;  /* 0; 1 is DSM_ERR_INVALID_ARGUMENT: vl_covdet_extract_affine_shape is not covered */
+  int32_t domain_size_pooling;    /* 1; 0: one scale of 1, as the reference's function does without it */
+  int32_t dsp_num_scales;         /* 10 */
+  double peak_threshold;          /* 0.02 / octave_resolution */
+  double edge_threshold;          /* 10.0 */
+  double dsp_min_scale;           /* 1.0 / 6.0 */
+  double dsp_max_scale;           /* 3.0 */
+} dsm_covariant_sift_options;
+/* num_octaves and max_num_orientations have no field: covdet reads neither.  The last octave comes from the image
+ * (covdet.c:1699: floor(log2(min(width - 1, height - 1) / 15))), and at most four orientations are kept (covdet.c:1432). */
+
+void dsm_covariant_sift_default_options(dsm_covariant_sift_options* o);
+
+/* One grey image, host pointers: gray_u8 holds height rows of row_stride >= width bytes.  keypoints_out [capacity x 6] receives
+ * (x + 0.5, y + 0.5, a11, a12, a21, a22) as sift.cc:494-501 fills FeatureKeypoint; descriptors_out [capacity x 128] the bytes in
+ * UBC order, NULL where only keypoints are wanted (sift.cc:516).  options NULL = the defaults.
+ * *num_features_out: the number of features found; above capacity the call fails with DSM_ERR_OUT_OF_RANGE, nothing is written
+ * to the outputs and the count is still valid.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT): NULL where data is needed, an empty image, row_stride < width, options that
+ *   SiftExtractionOptions::Check (sift.cc:218-234) rejects (max_num_features, octave_resolution, peak_threshold, edge_threshold,
+ *   dsp_min_scale or dsp_num_scales not positive, dsp_max_scale < dsp_min_scale), an unknown normalization,
+ *   estimate_affine_shape != 0.
+ * DSM_ERR_OUT_OF_RANGE:
+ *   - an image the reference aborts on.  With last = floor(log2(min(width - 1, height - 1) / 15)) the scale space holds the
+ *     octaves first_octave .. last.  The reference needs last >= first_octave (vl_scalespace_new_with_geometry asserts a valid
+ *     geometry) and, for a negative first_octave, last >= 0 (the upsampling chain of _vl_scalespace_start_octave_from_image
+ *     starts at octave 0: the assertion at scalespace.c:396).  So: min(width, height) - 1 < 15 * 2^max(first_octave, 0) is
+ *     refused -- a 12 x 40 image at first_octave = -1, any image under 16 pixels on a side;
+ *   - first_octave outside -4 .. 16, octave_resolution above 64, dsp_num_scales above 64, a first octave of 2^31 samples or
+ *     more over its levels, a scale space whose scratch exceeds dsm_ctx_set_memory_budget (the stage does not tile). */
+int dsm_extract_covariant_sift(dsm_ctx* ctx, const dsm_covariant_sift_options* options, const uint8_t* gray_u8, uint32_t width,
+                               uint32_t height, uint32_t row_stride, uint32_t capacity, float* keypoints_out,
+                               uint8_t* descriptors_out, uint32_t* num_features_out);
+
+/* The features of the last dsm_extract_covariant_sift on this context, in output order, as a test compares them (the final
+ * bytes hide differences below 1 / 512): octave_scale [n x 2] = VlCovDetFeature's (o, s), scores [n x 3] = peakScore, edgeScore,
+ * orientationScore, raw_descriptors [n x num_scales x 128] = vl_sift_calc_raw_descriptor's floats of every pooling scale, in
+ * VLFeat's bin order, before the pooling (num_scales = dsp_num_scales, or 1 without domain_size_pooling).  Any of the three
+ * may be NULL.  *n_out: the count; above capacity DSM_ERR_OUT_OF_RANGE and nothing is written.
+ * DSM_ERR_NOT_READY before the first successful call, and for raw_descriptors after a call without descriptors_out. */
+int dsm_get_covariant_sift_raw(dsm_ctx* ctx, uint32_t capacity, int32_t* octave_scale, float* scores, float* raw_descriptors,
+                               uint32_t* n_out);
+
+/* HIP-event times of the last dsm_extract_covariant_sift on this context, in ms: 0 the scale space (load, up- / downsampling,
+ * every smoothing of every octave), 1 detection (DoG, extremum test, compaction, refinement, summed over the octaves),
+ * 2 orientations, 3 descriptors (patch, gradient and raw descriptor of every (feature, pooling scale)), 4 pooling,
+ * normalisation and bytes.  DSM_ERR_NOT_READY before the first call. */
+#define DSM_COVARIANT_SIFT_STAGES 5
+int dsm_get_covariant_sift_time(dsm_ctx* ctx, double* stage_ms);
 
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
