@@ -536,7 +536,6 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
     HIPCHK(ctx, ctx->d_doutoff.reserve(std::max<uint32_t>(nc, 1) * 8));
     HIPCHK(ctx, ctx->d_pair_dir.reserve(std::max<uint32_t>(nc, 1) * sizeof(uint4)));
     HIPCHK(ctx, ctx->d_m.reserve(std::max<uint64_t>(off, 1) * 4));
-    HIPCHK(ctx, ctx->d_ms.reserve(std::max<uint64_t>(off, 1) * 4));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_dpairs.p, dpairs.data(), nc * sizeof(uint2), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_order.p, order.data(), nc * 4, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_doutoff.p, doff.data(), nc * 8, hipMemcpyHostToDevice, st));
@@ -553,7 +552,7 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
     k1.max_ratio = (float)options->max_ratio;        // narrowed as at sift.cc:164-166
     k1.max_distance = (float)options->max_distance;
     k1.out = ctx->d_m.as<int32_t>();
-    k1.out_s = ctx->d_ms.as<int32_t>();
+    k1.out_s = nullptr;  // (only the two-kernel form of the check build passes K1's second best on)
     k1.order = ctx->d_order.as<uint32_t>();
     k1.entries = nullptr;
     k1.e_off = nullptr;
@@ -563,23 +562,34 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
       HIPCHK(ctx, hipEventCreate(&e.e));
       ctx->ev.push_back(std::move(e));
     }
+    // K1 resolves its flagged rows in its own tail: the resolve interval [1, 2) is empty (and [4, 5) of pass 2 holds the
+    // compaction only); the events stay, so that the four timers still sum to the call.
     // DSM_K1_DOT4=1: the LDS-tiled v_dot4 variant of pass 1 (comparison runs only, profiles/r02_k1_variants.md)
+    // DSM_K1_RESOLVE_KERNEL=1: the two-kernel form of both passes, unfused k1_best_rows + k1_resolve_index with K1's second
+    // best in d_ms / d_out2s between them (the independently scheduled cross-check and A/B partner of the fused tail)
 #ifdef DSM_CHECK_BUILD
     const bool k1_dot4 = ctx->dbg("DSM_K1_DOT4") != nullptr;
-#else
-    const bool k1_dot4 = false;
+    const bool k1_two = ctx->dbg("DSM_K1_RESOLVE_KERNEL") != nullptr;
+    if (k1_two) {
+      HIPCHK(ctx, ctx->d_ms.reserve(std::max<uint64_t>(off, 1) * 4));
+      k1.out_s = ctx->d_ms.as<int32_t>();
+    }
 #endif
     HIPCHK(ctx, hipEventRecord(ctx->ev[ev_used], st));
 #ifdef DSM_CHECK_BUILD
     if (k1_dot4)
       launch_k1_dot4(k1, nc, max_rb, st);
+    else if (k1_two)
+      launch_k1_unfused(k1, nc, max_rb, st);
     else
 #endif
       launch_k1(k1, nc, max_rb, st);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[ev_used + 1], st));
-    if (!k1_dot4) launch_k1_resolve(k1, nc, max_rb, st);
+#ifdef DSM_CHECK_BUILD
+    if (k1_two && !k1_dot4) launch_k1_resolve(k1, nc, max_rb, st);
     HIPCHK(ctx, hipGetLastError());
+#endif
     HIPCHK(ctx, hipEventRecord(ctx->ev[ev_used + 2], st));
     if (max_rb) ctx->k1_launches++;
 
@@ -625,7 +635,6 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
       HIPCHK(ctx, hipStreamSynchronize(st));
       HIPCHK(ctx, ctx->d_entries.reserve(std::max<uint64_t>(etotal, 1) * 8));
       HIPCHK(ctx, ctx->d_out2.reserve(std::max<uint64_t>(etotal, 1) * 4));
-      HIPCHK(ctx, ctx->d_out2s.reserve(std::max<uint64_t>(etotal, 1) * 4));
       k2.matches = ctx->d_entries.as<uint32_t>();
       launch_k2(k2, nc, true, st);
       HIPCHK(ctx, hipGetLastError());
@@ -639,17 +648,29 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
       g.e_off = ctx->d_eoff.as<uint64_t>();
       g.e_cnt = ctx->d_ecnt.as<uint32_t>();
       g.out = ctx->d_out2.as<int32_t>();
-      g.out_s = ctx->d_out2s.as<int32_t>();
+#ifdef DSM_CHECK_BUILD
+      if (k1_two) {
+        HIPCHK(ctx, ctx->d_out2s.reserve(std::max<uint64_t>(etotal, 1) * 4));
+        g.out_s = ctx->d_out2s.as<int32_t>();
+      }
+#endif
       HIPCHK(ctx, hipEventRecord(ctx->ev[ev_used + 3], st));
-      if (etotal) {
-        launch_k1(g, nc, max_rb, st);  // a pair has at most rows(a) entries
+      if (etotal) {  // a pair has at most rows(a) entries
+#ifdef DSM_CHECK_BUILD
+        if (k1_two)
+          launch_k1_unfused(g, nc, max_rb, st);
+        else
+#endif
+          launch_k1(g, nc, max_rb, st);
         HIPCHK(ctx, hipGetLastError());
       }
       HIPCHK(ctx, hipEventRecord(ctx->ev[ev_used + 4], st));
-      if (etotal) {
+#ifdef DSM_CHECK_BUILD
+      if (etotal && k1_two) {
         launch_k1_resolve(g, nc, max_rb, st);
         HIPCHK(ctx, hipGetLastError());
       }
+#endif
       K2eParams ke;
       ke.entries = g.entries;
       ke.e_off = g.e_off;

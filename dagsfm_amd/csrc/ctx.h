@@ -207,7 +207,8 @@ struct dsm_ctx {
   //   libdagsfm_mi355x_check.so  -DDSM_CHECK_BUILD: additionally the independent schedules of the same results that
   //                              tools/check_schedules.py and the schedule-parametrised tests compare the product with
   //                              (legacy one-kernel LO-RANSAC, fused / LDS forms of the 5-point root finder,
-  //                              the v_dot4 K1 and word assignment, counters of DSM_VERIFY_DEBUG / DSM_SCORE_PREFILTER=check)
+  //                              the v_dot4 K1 and word assignment, the two-kernel K1 + k1_resolve_index,
+  //                              counters of DSM_VERIFY_DEBUG / DSM_SCORE_PREFILTER=check)
   std::map<std::string, std::string> debug_options;
   const char* dbg(const char* key) const {
     const auto it = debug_options.find(key);
@@ -256,7 +257,7 @@ void dsm_covariant_sift_destroy(dsm_ctx* ctx);  // covariant_sift.hip
 static const char* const dsm_product_debug_keys[] = {"DSM_MATCH_CHUNK_ROWS", "DSM_VERIFY_CHUNK_PAIRS", "DSM_VERIFY_LANES", "DSM_VERIFY_INLINE_LO",
                                                      "DSM_VERIFY_ITEM_MODE", "DSM_LO_TAIL", "DSM_LO_TAIL_MODE", "DSM_VERIFY_GRID_DIV"};
 #ifdef DSM_CHECK_BUILD
-static const char* const dsm_check_debug_keys[] = {"DSM_K1_DOT4", "DSM_VERIFY_DEBUG", "DSM_SAMPLER_SERIAL", "DSM_LO_PREPARE_WAVE", "DSM_LO_JACOBI_GROUPS",
+static const char* const dsm_check_debug_keys[] = {"DSM_K1_DOT4", "DSM_K1_RESOLVE_KERNEL", "DSM_VERIFY_DEBUG", "DSM_SAMPLER_SERIAL", "DSM_LO_PREPARE_WAVE", "DSM_LO_JACOBI_GROUPS",
                                                    "DSM_ROOTS_LDS", "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT",
                                                    "DSM_DEBUG_SAMPLER_MODE", "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER",
                                                    "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",

@@ -18,8 +18,9 @@ struct K1Params {
   const float* lut;           // acosf(min(d / 2^18, 1)), d = 0..262144, built on the host
   float max_ratio;
   float max_distance;
-  int32_t* out;               // per row: matched column index or -1 (between K1 and K1b: tile * 4 + column set)
-  int32_t* out_s;             // per flagged row, between K1 and K1b: K1's second-best dot product (a lower bound)
+  int32_t* out;               // per row: matched column index or -1 (two-kernel form, between K1 and K1b: tile * 4 + column set)
+  int32_t* out_s;             // two-kernel form only (check build), per flagged row between K1 and K1b: K1's second-best dot
+                              // product (a lower bound); the fused kernel never touches it
   // gathered pass (pass 2 of the cross-check); entries == nullptr: plain pass over an image's rows
   const uint32_t* order;      // optional: blockIdx.x -> directed pair (launch order, sorted by column image)
   const uint2* entries;       // one-way matches (i1, i2) of all pairs; entry k of pair d = row i2 of image dpairs[d].x
@@ -248,7 +249,8 @@ void launch_compact_inliers(const uint64_t* match_off, const uint64_t* inl_off, 
 void launch_k0(const uint8_t* in_u8, int8_t* out_s8, int32_t* rterm, uint64_t n_rows, hipStream_t st);
 void launch_k1(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st);
 void launch_k1_dot4(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st);
-void launch_k1_resolve(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st);
+void launch_k1_unfused(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st);  // check build
+void launch_k1_resolve(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st);  // check build
 void launch_k2(const K2Params& p, uint32_t n_pairs, bool write, hipStream_t st);
 void launch_k2_entries(const K2eParams& p, uint32_t n_pairs, bool write, hipStream_t st);
 void launch_scan(const uint32_t* counts, uint64_t* offsets, uint32_t n, uint64_t* running_total, hipStream_t st);

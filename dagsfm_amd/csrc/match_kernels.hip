@@ -11,14 +11,17 @@
 //                       distance tiles whose accumulators start at the column bias, top-2 VALUES
 //                       per row fused in the epilogue (3 VALU per 2 elements: v_med3, v_max3,
 //                       v_max) plus the 32-column tile in which the best value was reached;
-//                       thresholds (acos LUT, ratio) applied before the single int32 store.
+//                       thresholds (acos LUT, ratio) applied before the single int32 store.  The rows that pass
+//                       them are resolved in the wave's own tail (below the column loop): the lowest column
+//                       of that tile that attains the best value (16 or 32 dot products per row, v_dot4), the
+//                       second best completed, the ratio test repeated -- the store is the column index or -1.
 //                       Cross-check: FindBestMatches only ever reads matches21[matches12[i1]]
 //                       (sift.cc:178-186), so the second pass (GATHER) computes
 //                       FindBestMatchesOneWay(dists.transpose()) for exactly those rows of image b --
 //                       the one-way matches of pass 1, gathered through an entry list -- against
 //                       all columns of image a: ~N/14 rows instead of N at the benchmark shape.
-// K1b k1_resolve_index  for the rows that passed the thresholds only: the lowest column of that
-//                       tile that attains the best value (32 dot products per row, v_dot4).
+// K1b k1_resolve_index  check build only (DSM_K1_RESOLVE_KERNEL): the same resolve as a kernel of its own behind
+//                       the unfused K1 -- the form of rounds 3 - 7, kept as cross-check and A/B partner.
 // K2  k2_cross_compact  mutual check + ordered compaction (ascending idx1) per pair.
 //
 // Exactness of the signed-MFMA trick: a = a' + 128, b = b' + 128,
@@ -35,7 +38,7 @@
 // second-best semantics on values: a duplicate of the best value is the second best
 // (sift.cc:126-132).  The reference's best_i2 is the LOWEST column that attains the maximum
 // (ascending strict-`>` scan): K1 remembers the first tile in which the final best value was
-// reached (a strict increase of the running best), K1b finds the first column inside that tile.
+// reached (a strict increase of the running best), the resolve finds the first column inside that tile.
 // Zero padding rows/columns have dot == 0 and can never beat the initial
 // best_dist = second_best_dist = 0 (sift.cc:122-123).
 #include <hip/hip_runtime.h>
@@ -90,7 +93,7 @@ __global__ __launch_bounds__(256) void k0_prepare(const uint8_t* __restrict__ in
 //   t = max of the 16 values (v_max3 chain);  u = max(t, second);  second = min(u, best);  best = max(u, best)
 // i.e. (best, second) become the two largest of {best, second, t}: the running pair is the top-2 of the TILE MAXIMA
 // of the lane's 16-column sets.  `best` is exact.  `second` misses exactly one candidate -- the second largest value
-// INSIDE the set that holds the best -- and k1_resolve_index, which re-reads that set anyway to find the column,
+// INSIDE the set that holds the best -- and the resolve (k1_resolve_keys), which re-reads that set anyway to find the column,
 // adds it (rows are flagged with this `second`, which is <= the true one: a superset of the rows that pass the ratio
 // test, sift.cc:148-155; the final test runs there).  12 VALU per tile where the exact top-2 tree needed 22: the
 // VALU issue port, not the matrix pipe, was what limited this kernel (2 waves per SIMD x (4 MFMA + 22 VALU) issue
@@ -140,11 +143,109 @@ __device__ __forceinline__ int lds_off(int col, int chunk) {
   return col * 128 + ((chunk ^ ((col >> 1) & 7)) << 4);
 }
 
+// ------------------------------------------------------------------------------------ the resolve of flagged rows
+// K1's pass leaves, for a row that passed the thresholds, the exact best value, the 32-column tile in which it was first
+// reached, the 16-column set of the half-wave that reached it (columns 8q + 4*set + e; set 2 = both) and a `second` that may
+// be too small (k1_epilogue_quarter).  The resolve re-reads those columns -- 2 KB instead of the 4 KB tile -- and
+//   * finds the LOWEST column that attains the best value (the reference's best_i2, strict `>` ascending scan),
+//   * finds the second largest value inside the set, the one candidate K1's `second` lacks, and
+//   * applies the ratio test of sift.cc:148-155 with the completed second best: column index or -1.
+// A whole wave resolves RU rows per trip, their loads issued together (one memory round trip instead of RU); 8 lanes share
+// one dot product: column group lane >> 3, 16-byte chunk lane & 7.  Two functions, shared by the tail of k1_best_rows (the
+// row comes out of LDS) and by the stand-alone k1_resolve_index of the check build (the row comes from global memory): the
+// two forms produce the same bits by construction.
+//   k1_resolve_keys   per row the two largest keys (value << 5 | 31 - column: distinct per column) of the set's columns,
+//                     the same on every lane.  load_row(u) = chunk lane & 7 of row u of the trip.  BOTH = false: no row of
+//                     the trip has set == 2 (two loads per row instead of four: half the registers, so a trip can take more rows).
+//   k1_resolve_final  the completed second best and the ratio test: column index or -1.
+// The sums and the top-2 merge cross the lanes by DPP (one VALU each, no LDS crossbar): the eight lanes of a dot product are
+// half a DPP row, two column groups one row; the four rows meet in scalar registers.  The trip's rows are slots 0 .. n - 1;
+// an empty slot costs a scalar branch.
+template <int CTRL>
+__device__ __forceinline__ int k1_dpp(int v) {  // every lane active
+  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
+}
+template <int RU, bool BOTH, typename LoadRow>
+__device__ __forceinline__ void k1_resolve_keys(const int8_t* bimg, const int32_t* rt_b, int lane, int n, const int (&tile_l)[RU],
+                                                const int (&set_l)[RU], LoadRow&& load_row, int (&k1_l)[RU], int (&k2_l)[RU]) {
+  constexpr int XOR1 = 0xB1, XOR2 = 0x4E, HALF_MIRROR = 0x141, MIRROR = 0x140;  // quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror
+  const int g = lane >> 3;
+  constexpr int NL = BOTH ? 4 : 2;
+  // a set's 16 columns are four runs of four consecutive columns (512 B each): load i covers the eight columns
+  // 8*(2i + (g>>2)) + 4*set + (g&3); both sets (a tie between the half-waves): four loads of eight consecutive columns
+  v4i x[RU], y[RU][NL];
+  int ct[RU][NL], col[RU][NL];
+#pragma unroll
+  for (int u = 0; u < RU; ++u) {
+    if (u >= n) break;  // wave-uniform
+    x[u] = load_row(u);
+    const bool both = BOTH && set_l[u] == 2;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      col[u][i] = both ? i * 8 + g : 8 * (2 * (i & 1) + (g >> 2)) + 4 * set_l[u] + (g & 3);
+      if (i < 2 || both) {  // wave-uniform
+        const int c = tile_l[u] * 32 + col[u][i];
+        y[u][i] = *reinterpret_cast<const v4i*>(bimg + (size_t)c * 128 + (lane & 7) * 16);
+        ct[u][i] = rt_b[c];
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < RU; ++u) {
+    if (u >= n) break;
+    const bool both = BOTH && set_l[u] == 2;
+    int k1 = INT32_MIN, k2 = INT32_MIN;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      if (i < 2 || both) {
+        int acc = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_sdot4(x[u][e], y[u][i][e], acc, false);
+        acc += k1_dpp<XOR1>(acc);
+        acc += k1_dpp<XOR2>(acc);
+        acc += k1_dpp<HALF_MIRROR>(acc);  // (lane i <- lane 7 - i of the half row: the other quad, whose lanes agree by now)
+        const int key = (int)((uint32_t)(acc + ct[u][i]) << 5) | (31 - col[u][i]);  // |S + rterm(j)| <= 2^22
+        k2 = max(k2, min(k1, key));
+        k1 = max(k1, key);
+      }
+    }
+    {  // the other column group of the row of 16 lanes (lane i <- lane 15 - i)
+      const int o1 = k1_dpp<MIRROR>(k1), o2 = k1_dpp<MIRROR>(k2);
+      k2 = max(min(k1, o1), max(k2, o2));
+      k1 = max(k1, o1);
+    }
+    int s1 = __builtin_amdgcn_readlane(k1, 0), s2 = __builtin_amdgcn_readlane(k2, 0);
+#pragma unroll
+    for (int o = 16; o < 64; o += 16) {  // the four rows
+      const int o1 = __builtin_amdgcn_readlane(k1, o), o2 = __builtin_amdgcn_readlane(k2, o);
+      s2 = max(min(s1, o1), max(s2, o2));
+      s1 = max(s1, o1);
+    }
+    k1_l[u] = s1;
+    k2_l[u] = s2;
+  }
+}
+// k1, k2: the row's keys; sap: K1's second-best dot product (a lower bound); rti: the row's bias term
+__device__ __forceinline__ int k1_resolve_final(const K1Params& p, int k1, int k2, int sap, int rti, int tile) {
+  const int bias = rti + (1 << 21);
+  const int best_dot = (k1 >> 5) + bias;
+  const int second_dot = max(sap, (k2 >> 5) + bias);
+  const float bn = p.lut[min(best_dot, 262144)];
+  const float sn = p.lut[min(second_dot, 262144)];
+  const float rhs = __fmul_rn(p.max_ratio, sn);
+  return (bn >= rhs) ? -1 : tile * 32 + (31 - (k1 & 31));  // sift.cc:153
+}
+
 // Workgroup = 4 waves x 128 rows of image a (4 resident 32-row fragments per wave); the columns of
 // image b stream through LDS in 64-column steps (double buffered) together with their bias terms.
 // GATHER: the rows are not an image's rows but the entries [e_off[d], e_off[d] + e_cnt[d]) of the entry list, entry
 // k standing for row entries[k].y of image ab.x (pass 2 of the cross-check); out is indexed like the entry list.
-template <bool GATHER>
+// FUSED: the resolve of the flagged rows runs in the tail of the wave that owns them (below the column loop) and `out`
+// receives the final column index; otherwise `out` / `out_s` receive what k1_resolve_index needs (check build).
+#ifndef K1_TAIL_RU
+#define K1_TAIL_RU 6  // rows per trip of the fused tail: the most at which the tail's registers leave the column loop's schedule alone
+#endif
+template <bool GATHER, bool FUSED>
 __global__ __launch_bounds__(256, 2) void k1_best_rows(const K1Params p) {
   const uint32_t d = p.order ? p.order[blockIdx.x] : blockIdx.x;
   const uint32_t rb = blockIdx.y;
@@ -324,6 +425,7 @@ __global__ __launch_bounds__(256, 2) void k1_best_rows(const K1Params p) {
   const uint64_t out0 = (GATHER ? p.e_off[d] : p.d_out_off[d]) + rb * 512u + wave * 128;
   int32_t* out = p.out + out0;
   int32_t* out_s = p.out_s + out0;
+  int res_f[4], sdot_f[4];  // FUSED: the merged rows, for the tail below
 #pragma unroll
   for (int rt = 0; rt < 4; ++rt) {
     // the two halves of the wave hold disjoint 16-column sets of the same row
@@ -346,23 +448,104 @@ __global__ __launch_bounds__(256, 2) void k1_best_rows(const K1Params p) {
       if (!(bn > p.max_distance)) {  // sift.cc:144
         const float sn = p.lut[min(second_dot, 262144)];
         const float rhs = __fmul_rn(p.max_ratio, sn);
-        if (!(bn >= rhs)) res = T * 4 + set;  // sift.cc:153 with second <= true second; K1b completes the test
+        if (!(bn >= rhs)) res = T * 4 + set;  // sift.cc:153 with second <= true second; the resolve completes the test
       }
     }
-    if (half == (rt & 1) && valid[rt]) {
-      out[rt * 32 + l31] = res;
-      if (res >= 0) out_s[rt * 32 + l31] = second_dot;
+    if constexpr (!FUSED) {
+      if (half == (rt & 1) && valid[rt]) {
+        out[rt * 32 + l31] = res;
+        if (res >= 0) out_s[rt * 32 + l31] = second_dot;
+      }
+    } else {
+      res_f[rt] = res;  // (both halves of the wave hold the same res / second_dot of row l31)
+      sdot_f[rt] = second_dot;
+    }
+  }
+  if constexpr (FUSED) {
+    // The tail: this wave resolves its flagged rows itself.  No wave reads sB any more (the column loop ended at a
+    // barrier), so the wave stages one fragment's 32 rows at a time in ITS quarter of sB (32 x 128 B = 4 KB) -- every lane
+    // the four 16-byte chunks ks*2 + half it holds, chunk c of row r at position c ^ (r & 7) -- and reads them back as a
+    // trip wants them (8 lanes x 16 B = one row).  The slice is private to the wave and a wave's LDS operations complete
+    // in order: no barrier, only the waits of the round trip.  The flagged rows are the low 32 bits of the ballot; they
+    // go up to K1_TAIL_RU per trip, the rare rows whose best value sits in both column sets up to four.  A trip leaves
+    // the keys with the lane pair that owns the row; the ratio test (two LUT reads) then runs once for all four
+    // fragments, every lane for its own rows: one more memory round trip per wave instead of one per trip.
+    // The fragment loop is NOT unrolled (one copy of the trip code): the fragment's registers are picked by wave-uniform
+    // branches.
+    // (the tail's lane-derived values hang on a copy of the lane index made here, so that none of them is computed above
+    // the column loop and lives across it)
+    int lane_t = lane;
+    asm volatile("" : "+v"(lane_t));
+    const int l31_t = lane_t & 31, half_t = lane_t >> 5;
+    int8_t* slice = &sB[0][0] + wave * 4096;
+    int k1v[4] = {0, 0, 0, 0}, k2v[4] = {0, 0, 0, 0};
+#pragma nounroll
+    for (int rt = 0; rt < 4; ++rt) {
+      int res = -1, k1c = 0, k2c = 0;
+      static_for<0, 4>([&](auto RT) {
+        if (rt == RT.value) res = res_f[RT.value];
+      });
+      const uint32_t mask = (uint32_t)__ballot(res >= 0);
+      if (mask == 0u) continue;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the previous fragment's reads are before these writes)
+      static_for<0, 4>([&](auto RT) {
+        if (rt == RT.value) {
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks)
+            *reinterpret_cast<v4i*>(slice + l31_t * 128 + (((ks * 2 + half_t) ^ (l31_t & 7)) << 4)) = afrag[RT.value][ks];
+        }
+      });
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      uint32_t mask_b = (uint32_t)__ballot(res >= 0 && (res & 3) == 2);
+      uint32_t mask_n = mask & ~mask_b;
+      auto trips = [&](auto RU_, auto BOTH_, uint32_t m) {
+        constexpr int RU = decltype(RU_)::value;
+        while (m) {
+          int r_l[RU], tile_l[RU], set_l[RU], k1_l[RU], k2_l[RU];
+          bool on[RU];
+          const int n = min(__popc(m), RU);
+#pragma unroll
+          for (int u = 0; u < RU; ++u) {
+            on[u] = m != 0u;
+            const int r = on[u] ? (__ffs((int)m) - 1) : 0;
+            if (on[u]) m &= m - 1;
+            r_l[u] = r;
+            const int code = on[u] ? __builtin_amdgcn_readlane(res, r) : 0;
+            tile_l[u] = code >> 2;
+            set_l[u] = code & 3;
+          }
+          k1_resolve_keys<RU, decltype(BOTH_)::value>(
+              bimg, rt_b, lane_t, n, tile_l, set_l,
+              [&](int u) { return *reinterpret_cast<const v4i*>(slice + r_l[u] * 128 + (((lane_t & 7) ^ (r_l[u] & 7)) << 4)); }, k1_l, k2_l);
+#pragma unroll
+          for (int u = 0; u < RU; ++u)
+            if (on[u] && l31_t == r_l[u]) {
+              k1c = k1_l[u];
+              k2c = k2_l[u];
+            }
+        }
+      };
+      trips(std::integral_constant<int, K1_TAIL_RU>(), std::false_type(), mask_n);
+      trips(std::integral_constant<int, 4>(), std::true_type(), mask_b);
+      static_for<0, 4>([&](auto RT) {
+        if (rt == RT.value) {
+          k1v[RT.value] = k1c;
+          k2v[RT.value] = k2c;
+        }
+      });
+    }
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) {  // (a row that is not flagged has keys 0: its LUT reads stay inside the table)
+      const int col = k1_resolve_final(p, k1v[rt], k2v[rt], sdot_f[rt], rterm_i[rt], res_f[rt] >> 2);
+      if (half_t == (rt & 1) && valid[rt]) out[rt * 32 + l31_t] = res_f[rt] >= 0 ? col : -1;
     }
   }
 }
 
 // ------------------------------------------------------------------------------------ K1b
-// out[row] = tile * 4 + set for the rows K1 flagged (best value exact, `second` possibly too small): the best value
-// was first reached in that 32-column tile, in the 16-column set of half-wave `set` (columns 8q + 4*set + e; set 2 =
-// both).  This kernel re-reads those columns -- 2 KB instead of the 4 KB tile -- and
-//   * finds the LOWEST column that attains the best value (the reference's best_i2, strict `>` ascending scan),
-//   * finds the second largest value inside the set, the one candidate K1's `second` lacks, and
-//   * applies the ratio test of sift.cc:148-155 with the completed second best: column index or -1.
+// The stand-alone form of the resolve (check build, DSM_K1_RESOLVE_KERNEL: the independently scheduled cross-check and A/B
+// partner of the fused tail): out[row] = tile * 4 + set and out_s[row] = K1's `second` for the rows the unfused
+// k1_best_rows flagged; k1_resolve_trip turns them into the column index or -1.
 // One workgroup per directed pair (the columns it reads all belong to ONE image b, which stays in L2); a wave takes
 // 64 rows at a time and resolves its flagged rows four at a time.
 template <bool GATHER>
@@ -377,7 +560,6 @@ __global__ __launch_bounds__(256) void k1_resolve_index(const K1Params p) {
   const int8_t* bimg = p.desc + (size_t)b_row0 * 128;
   const int32_t* rt_b = p.rterm + b_row0;
   const uint2* ent = GATHER ? p.entries + p.e_off[d] : nullptr;
-  const int g = lane >> 3;  // 8 lanes share one dot product: column group g, 16-byte chunk lane & 7
   for (uint32_t row_w = wave * 64u; row_w < a_rows; row_w += 256u) {  // first row of this wave's chunk
     const uint64_t o0 = (GATHER ? p.e_off[d] : p.d_out_off[d]) + row_w;
     int32_t* out = p.out + o0;
@@ -391,9 +573,10 @@ __global__ __launch_bounds__(256) void k1_resolve_index(const K1Params p) {
     // trip pays one memory round trip instead of four (a wave resolves ~100 rows one after the other)
     constexpr int RU = 4;
     while (mask) {
-      int r_l[RU], tile_l[RU], set_l[RU], sap_l[RU];
+      int r_l[RU], tile_l[RU], set_l[RU], sap_l[RU], rti_l[RU], k1_l[RU], k2_l[RU];
       uint32_t grow_l[RU];
       bool on[RU];
+      const int n = min(__popcll(mask), RU);
 #pragma unroll
       for (int u = 0; u < RU; ++u) {
         on[u] = mask != 0ull;
@@ -405,60 +588,14 @@ __global__ __launch_bounds__(256) void k1_resolve_index(const K1Params p) {
         set_l[u] = code & 3;
         sap_l[u] = __builtin_amdgcn_readlane(s_appr, r);
         grow_l[u] = a_img0 + (uint32_t)__builtin_amdgcn_readlane((int)my_row, r);
+        rti_l[u] = p.rterm[grow_l[u]];
       }
-      // a set's 16 columns are four runs of four consecutive columns (512 B each): load i covers the eight columns
-      // 8*(2i + (g>>2)) + 4*set + (g&3); both sets (a tie between the half-waves): four loads of eight consecutive columns
-      v4i x[RU], y[RU][4];
-      int ct[RU][4], col[RU][4], rti[RU];
+      k1_resolve_keys<RU, true>(bimg, rt_b, lane, n, tile_l, set_l,
+                                [&](int u) { return *reinterpret_cast<const v4i*>(p.desc + (size_t)grow_l[u] * 128 + (lane & 7) * 16); },
+                                k1_l, k2_l);
 #pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        x[u] = *reinterpret_cast<const v4i*>(p.desc + (size_t)grow_l[u] * 128 + (lane & 7) * 16);
-        rti[u] = p.rterm[grow_l[u]];
-        const bool both = set_l[u] == 2;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          col[u][i] = both ? i * 8 + g : 8 * (2 * (i & 1) + (g >> 2)) + 4 * set_l[u] + (g & 3);
-          if (i < 2 || both) {  // wave-uniform
-            const int c = tile_l[u] * 32 + col[u][i];
-            y[u][i] = *reinterpret_cast<const v4i*>(bimg + (size_t)c * 128 + (lane & 7) * 16);
-            ct[u][i] = rt_b[c];
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        const bool both = set_l[u] == 2;
-        int k1 = INT32_MIN, k2 = INT32_MIN;  // the two largest keys (value << 5 | 31 - column: distinct per column)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (i < 2 || both) {
-            int acc = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_sdot4(x[u][e], y[u][i][e], acc, false);
-            acc += __shfl_xor(acc, 1);
-            acc += __shfl_xor(acc, 2);
-            acc += __shfl_xor(acc, 4);
-            const int key = (int)((uint32_t)(acc + ct[u][i]) << 5) | (31 - col[u][i]);  // |S + rterm(j)| <= 2^22
-            k2 = max(k2, min(k1, key));
-            k1 = max(k1, key);
-          }
-        }
-#pragma unroll
-        for (int o = 8; o < 64; o <<= 1) {
-          const int o1 = __shfl_xor(k1, o), o2 = __shfl_xor(k2, o);
-          k2 = max(min(k1, o1), max(k2, o2));
-          k1 = max(k1, o1);
-        }
-        if (lane == 0 && on[u]) {
-          const int bias = rti[u] + (1 << 21);
-          const int best_dot = (k1 >> 5) + bias;
-          const int second_dot = max(sap_l[u], (k2 >> 5) + bias);
-          const float bn = p.lut[min(best_dot, 262144)];
-          const float sn = p.lut[min(second_dot, 262144)];
-          const float rhs = __fmul_rn(p.max_ratio, sn);
-          out[r_l[u]] = (bn >= rhs) ? -1 : tile_l[u] * 32 + (31 - (k1 & 31));  // sift.cc:153
-        }
-      }
+      for (int u = 0; u < RU; ++u)
+        if (lane == 0 && on[u]) out[r_l[u]] = k1_resolve_final(p, k1_l[u], k2_l[u], sap_l[u], rti_l[u], tile_l[u]);
     }
   }
 }
@@ -802,20 +939,23 @@ void launch_k0(const uint8_t* in_u8, int8_t* out_s8, int32_t* rterm, uint64_t n_
 }
 
 // max_row_blocks = largest padded row count of an `a` image / 256
+// `out` receives the final column indices: the flagged rows are resolved in the kernel's tail
 void launch_k1(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st) {
   if (n_directed == 0 || max_row_blocks == 0) return;
   if (p.entries)
-    hipLaunchKernelGGL(k1_best_rows<true>, dim3(n_directed, (max_row_blocks + 1) / 2), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((k1_best_rows<true, true>), dim3(n_directed, (max_row_blocks + 1) / 2), dim3(256), 0, st, p);
   else
-    hipLaunchKernelGGL(k1_best_rows<false>, dim3(n_directed, (max_row_blocks + 1) / 2), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((k1_best_rows<false, true>), dim3(n_directed, (max_row_blocks + 1) / 2), dim3(256), 0, st, p);
 }
 #ifdef DSM_CHECK_BUILD
-// comparison variant (DSM_K1_DOT4): pass 1 on the VALU; writes exact column indices, no resolve pass
-void launch_k1_dot4(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st) {
+// cross-check form (DSM_K1_RESOLVE_KERNEL): the pass without the tail, to be followed by launch_k1_resolve (needs p.out_s)
+void launch_k1_unfused(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st) {
   if (n_directed == 0 || max_row_blocks == 0) return;
-  hipLaunchKernelGGL(k1_best_rows_dot4, dim3(n_directed, (max_row_blocks + 1) / 2), dim3(256), 0, st, p);
+  if (p.entries)
+    hipLaunchKernelGGL((k1_best_rows<true, false>), dim3(n_directed, (max_row_blocks + 1) / 2), dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL((k1_best_rows<false, false>), dim3(n_directed, (max_row_blocks + 1) / 2), dim3(256), 0, st, p);
 }
-#endif
 void launch_k1_resolve(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st) {
   if (n_directed == 0 || max_row_blocks == 0) return;
   if (p.entries)
@@ -823,6 +963,12 @@ void launch_k1_resolve(const K1Params& p, uint32_t n_directed, uint32_t max_row_
   else
     hipLaunchKernelGGL(k1_resolve_index<false>, dim3(n_directed), dim3(256), 0, st, p);
 }
+// comparison variant (DSM_K1_DOT4): pass 1 on the VALU; writes exact column indices, no resolve pass
+void launch_k1_dot4(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st) {
+  if (n_directed == 0 || max_row_blocks == 0) return;
+  hipLaunchKernelGGL(k1_best_rows_dot4, dim3(n_directed, (max_row_blocks + 1) / 2), dim3(256), 0, st, p);
+}
+#endif
 void launch_k2_entries(const K2eParams& p, uint32_t n_pairs, bool write, hipStream_t st) {
   if (n_pairs == 0) return;
   if (write)

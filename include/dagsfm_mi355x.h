@@ -241,13 +241,14 @@ int dsm_match_sift_features(dsm_ctx* ctx, const dsm_match_options* options,
  * last dsm_match_pairs, measured with HIP events on the stream the kernel was
  * launched on: total milliseconds and number of launches. */
 int dsm_get_match_kernel_time(dsm_ctx* ctx, double* total_ms, uint32_t* n_launches);
-/* Same for the small follow-up kernel that turns the best tile of every accepted row into
- * the exact column index (k1_resolve_index). */
+/* Same for the interval behind pass 1 in which the follow-up kernel k1_resolve_index ran (best tile of every accepted row
+ * -> exact column index).  The dominant kernel resolves those rows in its own tail now: the interval is empty (about 0);
+ * only the check build's two-kernel form (DSM_K1_RESOLVE_KERNEL) fills it. */
 int dsm_get_match_resolve_time(dsm_ctx* ctx, double* total_ms);
 /* Same for the gathered second pass of the cross-check (k1_best_rows over the rows matches12 points at). */
 int dsm_get_match_gather_time(dsm_ctx* ctx, double* total_ms);
-/* Same for everything else on the stream: the entry list of pass 2 (k2 + scan between pass 1's resolve and pass 2), pass 2's
- * k1_resolve_index and the compaction of the mutual matches (k2_entries + scan, the host's waits for the totals included) --
+/* Same for everything else on the stream: the entry list of pass 2 (k2 + scan between pass 1 and pass 2) and the compaction
+ * of the mutual matches (k2_entries + scan, the host's waits for the totals included) --
  * without the cross-check: the compaction of the one-way matches -- so that the four match timers sum to the call in both modes. */
 int dsm_get_match_tail_time(dsm_ctx* ctx, double* total_ms);
 

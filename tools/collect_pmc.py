@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Collects PMC counters of the matching kernels (k1_best_rows<false> = pass 1, <true> = gathered pass 2) with
+"""Collects PMC counters of the matching kernels (k1_best_rows<false, ..> = pass 1, <true, ..> = gathered pass 2) with
 rocprofv3, in separate passes as MI355X_MICROARCH.md (section HBM / rocprofv3 PMC slots) prescribes: FETCH_SIZE
 costs 3 TCC slots and WRITE_SIZE 2, so they cannot share a pass; the SQ utilisation counters get passes of their
 own.  Every pass is `rocprofv3 --pmc <counters> --kernel-trace` only (no other trace domain).
@@ -59,7 +59,7 @@ def kname(row):
         return n if n and not n.startswith("k1_") and not n.startswith("__amd") else None
     if "k1_best_rows" not in n:
         return None
-    return "pass2" if "<true>" in n else "pass1"
+    return "pass2" if "k1_best_rows<true" in n else "pass1"  # <GATHER[, FUSED]>
 
 
 def summarize_verify(res):

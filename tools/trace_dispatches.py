@@ -18,7 +18,7 @@ for r in rows:
     grid = int(r.get("Grid_Size_X", r.get("Grid_Size", 0)) or 0)
     ev.append((s, e, name, grid // max(wg, 1), r.get("Queue_Id", "0")))
 ev.sort()
-starts = [s for s, e, n, g, q in ev if "k1_best_rows<false>" in n or "k1_best_rows<(bool)0>" in n]
+starts = [s for s, e, n, g, q in ev if "k1_best_rows<false" in n or "k1_best_rows<(bool)0>" in n]
 t0 = starts[-1]
 ev = [x for x in ev if x[0] >= t0]
 last_end = defaultdict(lambda: t0)

@@ -9,7 +9,7 @@ import sys
 
 rows = list(csv.DictReader(open(sys.argv[1])))
 ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in rows)
-starts = [s for s, e, n in ev if "k1_best_rows<false>" in n or "k1_best_rows<(bool)0>" in n]
+starts = [s for s, e, n in ev if "k1_best_rows<false" in n or "k1_best_rows<(bool)0>" in n]
 t0 = starts[-1]
 ev = [x for x in ev if x[0] >= t0]
 first_verify = min(s for s, e, n in ev if "k_verify_prep" in n)

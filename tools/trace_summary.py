@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarises a rocprofv3 --kernel-trace CSV of a bench.py run: for the LAST step (from the last k1_best_rows<false>
+"""Summarises a rocprofv3 --kernel-trace CSV of a bench.py run: for the LAST step (from the last k1_best_rows<false, ..>
 launch on), the span, the time during which NO kernel was running on any stream (host round trips, launch gaps), the time
 during which only `small` kernels (grid below 256 workgroups = less than one per CU) were running, and the per-kernel
 totals.  Usage: python tools/trace_summary.py <kernel_trace.csv>"""
@@ -16,7 +16,7 @@ for r in rows:
     grid = int(r.get("Grid_Size_X", r.get("Grid_Size", 0)) or 0) * max(1, int(r.get("Grid_Size_Y", 1) or 1))
     ev.append((s, e, name, grid // max(wg, 1)))
 ev.sort()
-starts = [s for s, e, n, g in ev if "k1_best_rows<false>" in n or "k1_best_rows<(bool)0>" in n]
+starts = [s for s, e, n, g in ev if "k1_best_rows<false" in n or "k1_best_rows<(bool)0>" in n]
 t0 = starts[-1]
 ev = [x for x in ev if x[0] >= t0]
 t1 = max(e for s, e, n, g in ev)

@@ -11,7 +11,7 @@ ev = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name
 finals = [i for i, e in enumerate(ev) if e[2].startswith("k_verify_final")]
 t_end = ev[finals[-1]][1]
 # the step starts at the last k1_best_rows<false> before it
-starts = [e[0] for e in ev if e[2].startswith("k1_best_rows<false>") and e[0] < t_end]
+starts = [e[0] for e in ev if e[2].startswith("k1_best_rows<false") and e[0] < t_end]
 t0 = starts[-1]
 seg = [e for e in ev if e[0] >= t0 and e[1] <= t_end]
 queues = sorted({e[3] for e in seg})
