@@ -71,6 +71,7 @@ _libs = {}
 
 
 RA_MAX_L1_ITERATIONS = 8  # DSM_RA_MAX_L1_ITERATIONS
+DSM_ERR_INVALID_ARGUMENT = 1
 DSM_ERR_NOT_CONVERGED = 6
 
 
@@ -395,6 +396,17 @@ class CovariantSiftOptions(ctypes.Structure):
                 ("edge_threshold", ctypes.c_double), ("dsp_min_scale", ctypes.c_double), ("dsp_max_scale", ctypes.c_double)]
 
 
+class UndistortOptions(ctypes.Structure):
+    """dsm_undistort_options: UndistortCameraOptions (src/base/undistortion.h:41-62)."""
+    _fields_ = [("blank_pixels", ctypes.c_double), ("min_scale", ctypes.c_double), ("max_scale", ctypes.c_double),
+                ("max_image_size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("roi_min_x", ctypes.c_double),
+                ("roi_min_y", ctypes.c_double), ("roi_max_x", ctypes.c_double), ("roi_max_y", ctypes.c_double)]
+
+
+CAMERA_SIZE_ONLY = -1  # DSM_CAMERA_SIZE_ONLY: a dsm_camera of which dsm_warp_images reads only width and height
+UNDISTORTION_STAGES = ("border_scan", "points", "warp_upload", "warp_kernel", "warp_download")
+
+
 def lib(check=False):
     """Loads the shared library (check=True: the check build); raises if it has not been built (no fallback)."""
     if check not in _libs:
@@ -502,6 +514,13 @@ def lib(check=False):
         L.dsm_extract_covariant_sift.argtypes = [vp, ctypes.POINTER(CovariantSiftOptions), vp] + [ctypes.c_uint32] * 4 + [vp, vp, u32p]
         L.dsm_get_covariant_sift_raw.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, u32p]
         L.dsm_get_covariant_sift_time.argtypes = [vp, vp]
+        L.dsm_default_undistort_options.argtypes = [ctypes.POINTER(UndistortOptions)]
+        L.dsm_default_undistort_options.restype = None
+        L.dsm_undistort_cameras.argtypes = [vp, ctypes.POINTER(UndistortOptions), ctypes.c_uint32, vp, vp]
+        L.dsm_undistort_points2D.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp]
+        L.dsm_warp_images.argtypes = ([vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_uint64, vp,
+                                       ctypes.c_uint64, ctypes.c_uint64, vp, vp, vp])
+        L.dsm_get_undistortion_time.argtypes = [vp, vp]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
         L.dsm_default_match_options.restype = None
         L.dsm_default_two_view_options.argtypes = [ctypes.POINTER(TwoViewOptions)]
@@ -531,6 +550,11 @@ def camera(model_id, params, width, height, prior=True):
     for k, v in enumerate(params):
         c.params[k] = float(v)
     return c
+
+
+def copy_camera(c):
+    """A Camera of its own memory with c's fields (an element of a ctypes array is a view of the array)."""
+    return Camera.from_buffer_copy(bytes(c))
 
 
 def default_match_options(**kw):
@@ -645,6 +669,19 @@ def default_covariant_sift_options(check=False, **kw):
     for k, v in kw.items():
         setattr(o, k, v)
     return o
+
+
+def default_undistort_options(**kw):
+    o = UndistortOptions()
+    lib().dsm_default_undistort_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def size_only_camera(width, height):
+    """The dsm_camera that gives dsm_warp_images the size of an image of a warp without cameras (WarpImageWithHomography)."""
+    return Camera(model_id=CAMERA_SIZE_ONLY, has_prior_focal_length=0, width=width, height=height)
 
 
 def default_local_bundle_options(**kw):
@@ -1417,6 +1454,100 @@ class Context:
         ms = (ctypes.c_double * len(self.COVARIANT_SIFT_STAGES))()
         self._chk(self._L.dsm_get_covariant_sift_time(self._h, ctypes.addressof(ms)))
         return dict(zip(self.COVARIANT_SIFT_STAGES, list(ms)))
+
+    def _fail(self, name, rc):
+        raise DsmError("%s failed (%d): %s" % (name, rc, self._L.dsm_last_error(self._handle).decode()))
+
+    def undistort_cameras(self, cameras, options=None, **kw):
+        """dsm_undistort_cameras (UndistortCamera): a list of Camera -> the list of their PINHOLE cameras.
+        options: an UndistortOptions, or its fields as keywords over the defaults."""
+        assert options is None or not kw, "pass an UndistortOptions or keywords, not both"
+        o = options if options is not None else default_undistort_options(**kw)
+        n = len(cameras)
+        arr, out = (Camera * max(n, 1))(*cameras), (Camera * max(n, 1))()
+        rc = self._L.dsm_undistort_cameras(self._h, ctypes.byref(o), n, ctypes.addressof(arr), ctypes.addressof(out))
+        if rc != 0:
+            self._fail("dsm_undistort_cameras", rc)
+        return [copy_camera(out[i]) for i in range(n)]
+
+    def undistort_points2D(self, cameras, undistorted_cameras, camera_index, xy):
+        """dsm_undistort_points2D (the loop of UndistortReconstruction): xy [n, 2] of the points of camera camera_index[i] ->
+        the undistorted xy [n, 2] (a new array)."""
+        assert len(cameras) == len(undistorted_cameras)
+        nc = len(cameras)
+        a, b = (Camera * max(nc, 1))(*cameras), (Camera * max(nc, 1))(*undistorted_cameras)
+        idx = np.ascontiguousarray(camera_index, np.uint32).reshape(-1)
+        out = np.array(xy, dtype=np.float64, order="C").reshape(-1, 2)
+        assert len(idx) == len(out)
+        rc = self._L.dsm_undistort_points2D(self._h, nc, ctypes.addressof(a), ctypes.addressof(b), len(out), idx.ctypes.data, out.ctypes.data)
+        if rc != 0:
+            self._fail("dsm_undistort_points2D", rc)
+        return out
+
+    def warp_images(self, source, target, images, H=None, return_map=False, out=None):
+        """dsm_warp_images (src/base/warp.cc).  images: uint8 [n, height, width] (grey), [n, height, width, 3], or
+        one grey image [height, width]; only the pixels of a row have to be contiguous, so a view with a longer row stride is
+        passed as it is.  source / target: Camera; for WarpImageWithHomography (H alone) source is None or a size_only_camera
+        (None: the images' size) and target None or the size_only_camera of the target image.  The size of the images must be
+        the source camera's (DsmError otherwise, as the reference CHECKs).
+        Returns a dict: images (the warp, shaped like the input; at the SOURCE resolution with cameras), scaled_target (Camera),
+        needs_rescale (bool: Bitmap::Rescale to the target camera's width x height is still the caller's to do), and with
+        return_map source_xy [height, width, 2]."""
+        im = np.asarray(images)
+        if im.dtype != np.uint8:
+            raise DsmError("dsm_warp_images: images must be uint8")
+        single = im.ndim == 2
+        if single:
+            im = im[None]
+        if im.ndim not in (3, 4):
+            raise DsmError("dsm_warp_images: images must be [n, height, width] or [n, height, width, channels]")
+        channels = 1 if im.ndim == 3 else im.shape[3]
+        n, height, width = im.shape[:3]
+        if source is None:
+            source = size_only_camera(width, height)
+        if int(source.width) != width or int(source.height) != height:
+            raise DsmError("dsm_warp_images failed (%d): the camera's size %d x %d differs from the images' %d x %d"
+                           % (DSM_ERR_INVALID_ARGUMENT, source.width, source.height, width, height))
+        pix = im.strides[2] if n * height * width else channels
+        inner_ok = pix == channels and (im.ndim == 3 or channels == 1 or im.strides[3] == 1)
+        if not inner_ok or (height > 1 and im.strides[1] < 0) or (n > 1 and im.strides[0] < 0):
+            im = np.ascontiguousarray(im)
+        src_row = im.strides[1] if height > 1 else width * channels
+        src_img = im.strides[0] if n > 1 else src_row * height
+        size_only = int(source.model_id) == CAMERA_SIZE_ONLY
+        tw, th = (int(target.width), int(target.height)) if (size_only and target is not None) else (width, height)
+        if out is None:
+            out = np.zeros((n, th, tw) + ((channels,) if im.ndim == 4 else ()), np.uint8)
+        assert out.dtype == np.uint8 and out.shape[0] == n and out.shape[1:3] == (th, tw)
+        dst_row = out.strides[1] if th > 1 else tw * channels
+        dst_img = out.strides[0] if n > 1 else dst_row * th
+        scaled, owed = Camera(), ctypes.c_int32(0)
+        Hm = None if H is None else np.ascontiguousarray(H, np.float64).reshape(9)
+        smap = np.zeros((th, tw, 2)) if return_map else None
+        rc = self._L.dsm_warp_images(self._h, ctypes.addressof(source), None if target is None else ctypes.addressof(target),
+                                     None if Hm is None else Hm.ctypes.data, n, channels, im.ctypes.data, src_row, src_img,
+                                     out.ctypes.data, dst_row, dst_img, ctypes.addressof(scaled), ctypes.addressof(owed),
+                                     None if smap is None else smap.ctypes.data)
+        if rc != 0:
+            self._fail("dsm_warp_images", rc)
+        res = {"images": out[0] if single else out, "scaled_target": scaled, "needs_rescale": bool(owed.value)}
+        if return_map:
+            res["source_xy"] = smap
+        return res
+
+    def undistort_images(self, images, camera, options=None, **kw):
+        """UndistortImage (undistortion.cc:844-859) for a batch of images of one camera: undistort_cameras, then warp_images
+        into the undistorted camera.  Returns (the warped stack at the SOURCE resolution, the undistorted Camera, whether a
+        rescale of every image to (width, height) of that camera is still owed -- Bitmap::Rescale, the caller's)."""
+        und = self.undistort_cameras([camera], options, **kw)[0]
+        r = self.warp_images(camera, und, images)
+        return r["images"], und, r["needs_rescale"]
+
+    def undistortion_time(self):
+        """dsm_get_undistortion_time: {stage: ms} of the last call of each kind (HIP events)."""
+        ms = (ctypes.c_double * len(UNDISTORTION_STAGES))()
+        self._chk(self._L.dsm_get_undistortion_time(self._h, ctypes.addressof(ms)))
+        return dict(zip(UNDISTORTION_STAGES, list(ms)))
 
     @staticmethod
     def apply_point_filter(scene, result):

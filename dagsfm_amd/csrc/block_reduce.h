@@ -53,6 +53,38 @@ __device__ inline double block_max(double v, double* sh) {
   __syncthreads();
   return out;
 }
+// std::min(a, b) / std::max(a, b) as the C++ library defines them: b only where the comparison holds, so a NaN in b is never
+// taken (fmin / fmax above would not take one in a either)
+__device__ inline double std_min(double a, double b) { return (b < a) ? b : a; }
+__device__ inline double std_max(double a, double b) { return (a < b) ? b : a; }
+// the minima / maxima of v[0..K) over the block under std_min / std_max, back in v in every thread.  No order of the tree
+// changes the result as long as no v is a NaN (up to the sign of a zero that ties with the other zero).
+template <int BS, int K>
+__device__ inline void block_std_min(double* v, double* sh) {
+  const int t = threadIdx.x;
+  for (int k = 0; k < K; ++k) sh[k * BS + t] = v[k];
+  __syncthreads();
+  for (int s = BS / 2; s > 0; s >>= 1) {
+    if (t < s)
+      for (int k = 0; k < K; ++k) sh[k * BS + t] = std_min(sh[k * BS + t], sh[k * BS + t + s]);
+    __syncthreads();
+  }
+  for (int k = 0; k < K; ++k) v[k] = sh[k * BS];
+  __syncthreads();
+}
+template <int BS, int K>
+__device__ inline void block_std_max(double* v, double* sh) {
+  const int t = threadIdx.x;
+  for (int k = 0; k < K; ++k) sh[k * BS + t] = v[k];
+  __syncthreads();
+  for (int s = BS / 2; s > 0; s >>= 1) {
+    if (t < s)
+      for (int k = 0; k < K; ++k) sh[k * BS + t] = std_max(sh[k * BS + t], sh[k * BS + t + s]);
+    __syncthreads();
+  }
+  for (int k = 0; k < K; ++k) v[k] = sh[k * BS];
+  __syncthreads();
+}
 // the K columns of n partials P[k * n + i] reduced by one block: thread t takes i = t, t + BS, ... in order, then the tree.
 // Every block that calls it gets the same bytes.
 template <int BS, int K, typename I>

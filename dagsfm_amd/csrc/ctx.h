@@ -223,6 +223,12 @@ struct dsm_ctx {
   struct CovSiftState* covsift = nullptr;      // the scale space and the last result of dsm_extract_covariant_sift (covariant_sift.hip), created on first use
   struct SiftState* sift = nullptr;            // the scratch of dsm_extract_sift (sift_extraction.hip), created on first use, reused across calls
 
+  // undistortion.hip: the border pixels of dsm_undistort_cameras, the points of dsm_undistort_points2D, a chunk of source and
+  // target images of dsm_warp_images and its map of source points; the HIP-event times of the last call of each
+  DevBuf d_ud_border, d_ud_points, d_ud_src, d_ud_dst, d_ud_map;
+  bool undistortion_ready = false;
+  double undistortion_ms[DSM_UNDISTORTION_STAGES] = {0};
+
   // the final Ritz values and the k Ritz vectors ([images][k]) of the last dsm_view_graph_cluster that ran the eigen-solver
   // (view_graph_clustering.hip)
   std::vector<double> cluster_ritz, cluster_vectors;
@@ -243,7 +249,7 @@ struct dsm_ctx {
                       &d_mm_keep, &d_mm_total})
       f(*b, false);
     for (DevBuf* b : {&d_m, &d_ms, &d_entries, &d_out2, &d_out2s, &d_dpairs, &d_dpairs2, &d_doutoff, &d_pair_dir, &d_order, &d_ecnt, &d_eoff,
-                      &d_vscratch})
+                      &d_vscratch, &d_ud_border, &d_ud_points, &d_ud_src, &d_ud_dst, &d_ud_map})
       f(*b, true);
     for (VerifyLane& L : lanes) L.for_each_buffer([&f](DevBuf& b) { f(b, true); });
   }

@@ -1424,6 +1424,84 @@ int dsm_get_covariant_sift_raw(dsm_ctx* ctx, uint32_t capacity, int32_t* octave_
 #define DSM_COVARIANT_SIFT_STAGES 5
 int dsm_get_covariant_sift_time(dsm_ctx* ctx, double* stage_ms);
 
+/* ---- image and reconstruction undistortion ----
+ * image_undistorter / COLMAPUndistorter's numerical work: UndistortCamera (src/base/undistortion.cc:659-842), the point loop of
+ * UndistortReconstruction (:869-879), UndistortImage -> WarpImageBetweenCameras and the two homography warps
+ * (src/base/warp.cc:51-172) with Bitmap::InterpolateBilinear (src/util/bitmap.cc:225-281) and BitmapColor<float>::Cast<uint8_t>
+ * (src/util/bitmap.h:217-243).  DESIGN.md 22.  All eleven camera models, both directions, bit for bit the CPU path's.
+ *
+ * NOT covered: the Bitmap::Rescale that ends WarpImageBetweenCameras and WarpImageWithHomographyBetweenCameras when the target
+ * camera's size differs from the source's (warp.cc:92-95, 168-171).  It is FreeImage_Rescale; the device delivers the warp at
+ * the source resolution (warp.cc:58-90, 133-166) and reports that the caller's Bitmap::Rescale(target.width, target.height)
+ * is still owed.  Image decoding and writing, RectifyStereoCameras (the caller passes H), the exporters' text files: the host's. */
+typedef struct dsm_undistort_options { /* UndistortCameraOptions, src/base/undistortion.h:41-62 */
+  double blank_pixels;    /* 0.0 */
+  double min_scale;       /* 0.2 */
+  double max_scale;       /* 2.0 */
+  int32_t max_image_size; /* -1 */
+  int32_t reserved;
+  double roi_min_x;       /* 0.0 */
+  double roi_min_y;       /* 0.0 */
+  double roi_max_x;       /* 1.0 */
+  double roi_max_y;       /* 1.0 */
+} dsm_undistort_options;
+
+void dsm_default_undistort_options(dsm_undistort_options* o);
+
+/* UndistortCamera (undistortion.cc:659-842) for n cameras, host pointers; options NULL = the defaults.  out_cameras[i] is the
+ * PINHOLE camera (model 1, no prior focal length) of cameras[i]: the focal lengths copied by the number of focal indices
+ * (:679-688), the ROI arithmetic (:695-726), the border scan (:729-777) on the device for all cameras in one launch, the scalar
+ * tail (:779-839) with Camera::Rescale(scale) (camera.cc:228-247) on the host in the reference's order, std::min / std::max /
+ * Clip with the reference's argument order (a NaN scale clips to min_scale).
+ * Invalid (DSM_ERR_INVALID_ARGUMENT, out_cameras untouched): every CHECK of :661-671 (blank_pixels outside [0, 1], min_scale
+ * <= 0 or > max_scale, max_image_size == 0, a ROI outside [0, 1] or empty; a NaN fails them as it fails the CHECKs), an unknown
+ * model, a camera without pixels or with a side above 2^30, 2^31 border pixels or more in one batch. */
+int dsm_undistort_cameras(dsm_ctx* ctx, const dsm_undistort_options* options, uint32_t n, const dsm_camera* cameras,
+                          dsm_camera* out_cameras);
+
+/* The loop of UndistortReconstruction (undistortion.cc:869-879) over all 2D points of all images, host pointers:
+ * xy[i] <- undistorted_cameras[c].WorldToImage(cameras[c].ImageToWorld(xy[i])) with c = camera_index[i], in place, xy
+ * [n_points x 2].  n_points = 0 is a valid call.
+ * Invalid (xy untouched): NULL where data is needed, an unknown model, a camera index >= n_cameras. */
+int dsm_undistort_points2D(dsm_ctx* ctx, uint32_t n_cameras, const dsm_camera* cameras, const dsm_camera* undistorted_cameras,
+                           uint64_t n_points, const uint32_t* camera_index, double* xy);
+
+/* The warps of src/base/warp.cc for a batch of n_images images of one source camera and size, host pointers.  Images are rows
+ * top-down of interleaved bytes, channels = 1 (grey) or 3 (the channels are independent: their byte order is the caller's);
+ * image k starts at src + k * src_image_stride, its row y at + y * src_row_stride (dst likewise).  The image size is the
+ * source camera's (the reference CHECKs that they agree, warp.cc:54-55).
+ *   H == NULL                     WarpImageBetweenCameras (:51-90), up to but not including the Rescale of :92-95: the target
+ *                                 camera is rescaled to the source size (Camera::Rescale(width, height), camera.cc:249-267)
+ *                                 when the sizes differ; per target pixel ImageToWorld of the scaled target at (x + 0.5, y + 0.5),
+ *                                 WorldToImage of the source, the bilinear sample at (sx - 0.5, sy - 0.5).
+ *   H, both cameras               WarpImageWithHomographyBetweenCameras (:124-166) as written: H * (x + 0.5, y + 0.5, 1),
+ *                                 hnormalized, ImageToWorld of the UNSCALED target_camera (:154), WorldToImage of the source.
+ *   H, a size-only source camera  WarpImageWithHomography (:98-122).  The reference takes no camera there; the sizes come in
+ *                                 cameras whose model_id is DSM_CAMERA_SIZE_ONLY and of which only width and height are read:
+ *                                 source_camera the source image's, target_camera the target image's (NULL: the source's).
+ * H is row-major; each row of H * p is summed left to right (Eigen fixes no order for it).
+ * dst receives the warp at the SOURCE resolution in the two camera modes (dst images are source-sized), at the target size in
+ * the third.  *out_scaled_target_camera (may be NULL): the target camera rescaled to the source size (a copy where the sizes
+ * agree).  *out_needs_rescale (may be NULL): 1 when the reference would now call Bitmap::Rescale(target_camera.width,
+ * target_camera.height) -- the caller's to do with FreeImage -- else 0.  out_source_xy (may be NULL): [height x width x 2]
+ * doubles, the source point (sx, sy) of every target pixel before the - 0.5, so that a wrong map can be told from a wrong sample.
+ * A source coordinate that is NaN or whose floor lies outside int writes 0 (the reference's cast is undefined there).
+ * A batch that does not fit dsm_ctx_set_memory_budget is cut into chunks of images (one image always runs).
+ * Invalid (dst and the outputs untouched): channels other than 1 or 3, a row stride below width * channels, an image stride
+ * below row stride * height (n_images > 1), an unknown model, a camera without pixels or with a side above 2^30, H without
+ * target_camera for a real source camera, a size-only source camera without H or with a real target camera. */
+#define DSM_CAMERA_SIZE_ONLY (-1)
+int dsm_warp_images(dsm_ctx* ctx, const dsm_camera* source_camera, const dsm_camera* target_camera, const double* H,
+                    uint32_t n_images, uint32_t channels, const uint8_t* src, uint64_t src_row_stride, uint64_t src_image_stride,
+                    uint8_t* dst, uint64_t dst_row_stride, uint64_t dst_image_stride, dsm_camera* out_scaled_target_camera,
+                    int32_t* out_needs_rescale, double* out_source_xy);
+
+/* HIP-event times in ms of the last call of each kind on this context: 0 the border scan of dsm_undistort_cameras, 1 the kernel of
+ * dsm_undistort_points2D, and of dsm_warp_images, summed over its chunks, 2 the upload, 3 the warp kernel, 4 the download.
+ * DSM_ERR_NOT_READY before the first of these calls. */
+#define DSM_UNDISTORTION_STAGES 5
+int dsm_get_undistortion_time(dsm_ctx* ctx, double* stage_ms);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
