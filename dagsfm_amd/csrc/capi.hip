@@ -495,6 +495,7 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
   std::vector<uint64_t> doff;
   std::vector<uint4> pdir;
   std::vector<uint32_t> order, cnt_b(ctx->n_images + 1);
+  std::vector<uint32_t> run_first;  // pass 2: first pair of every run of consecutive pairs with the same column image a, + nc
   size_t ev_used = 0;
   uint32_t c0 = 0;
   while (c0 < n_pairs) {
@@ -519,16 +520,20 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
     std::fill(cnt_b.begin(), cnt_b.end(), 0u);
     uint64_t off = 0;
     uint32_t max_rb = 0;
+    run_first.clear();
     for (uint32_t k = 0; k < nc; ++k) {
       const uint32_t a = pairs[2 * (c0 + k)], b = pairs[2 * (c0 + k) + 1];
       dpairs[k] = make_uint2(a, b);
       dpairs2[k] = make_uint2(b, a);  // pass 2: gathered rows of image b vs the columns of image a
+      if (k == 0 || a != dpairs2[k - 1].y) run_first.push_back(k);  // (a chunk boundary ends a run)
       pdir[k] = make_uint4(k, 0, ctx->nfeat[a], ctx->nfeat[b]);
       doff[k] = off;
       off += ctx->rows[a];
       max_rb = std::max(max_rb, ctx->rows[a] / 256);
       cnt_b[b + 1]++;
     }
+    const uint32_t n_runs = (uint32_t)run_first.size();
+    run_first.push_back(nc);
     for (uint32_t k = 0; k < ctx->n_images; ++k) cnt_b[k + 1] += cnt_b[k];
     for (uint32_t k = 0; k < nc; ++k) order[cnt_b[dpairs[k].y]++] = k;
     HIPCHK(ctx, ctx->d_dpairs.reserve(std::max<uint32_t>(nc, 1) * sizeof(uint2)));
@@ -557,6 +562,8 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
     k1.entries = nullptr;
     k1.e_off = nullptr;
     k1.e_cnt = nullptr;
+    k1.gblocks = nullptr;
+    k1.e_grow = nullptr;
     while (ctx->ev.size() < ev_used + 6) {
       DevEvent e;
       HIPCHK(ctx, hipEventCreate(&e.e));
@@ -624,6 +631,26 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
       HIPCHK(ctx, ctx->d_eoff.reserve(((size_t)nc + 1) * 8));
       HIPCHK(ctx, ctx->d_etotal.reserve(8));
       HIPCHK(ctx, hipMemsetAsync(ctx->d_etotal.p, 0, 8, st));
+      // Pass 2: FindBestMatchesOneWay(dists.transpose()) (sift.cc:175-176) for the rows matches12 points at.
+      // The product packs the pass across the pairs of a run (consecutive pairs with the same column image a: the lists the
+      // callers build have long ones): the entry list is contiguous in pair order, so a workgroup takes 512 consecutive entries
+      // of a run whatever pairs they belong to.  The runs' block counts and their scan need e_off only: they are queued in
+      // front of the host's wait for the entry total; etotal / 512 + n_runs then bounds the number of blocks, and the table is
+      // written on the device -- all of it inside the interval of the entry list [2, 3).  The two-kernel form of the check
+      // build keeps the per-pair grid.
+      bool packed = true;
+#ifdef DSM_CHECK_BUILD
+      packed = !k1_two;
+#endif
+      HIPCHK(ctx, ctx->d_dpairs2.reserve(std::max<uint32_t>(nc, 1) * sizeof(uint2)));
+      HIPCHK(ctx, hipMemcpyAsync(ctx->d_dpairs2.p, dpairs2.data(), nc * sizeof(uint2), hipMemcpyHostToDevice, st));
+      if (packed) {
+        HIPCHK(ctx, ctx->d_runs.reserve(((size_t)n_runs + 1) * 4));
+        HIPCHK(ctx, ctx->d_run_blocks.reserve((size_t)n_runs * 4));
+        HIPCHK(ctx, ctx->d_run_blkoff.reserve(((size_t)n_runs + 2) * 8));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_runs.p, run_first.data(), ((size_t)n_runs + 1) * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_run_blkoff.as<uint64_t>() + n_runs + 1, 0, 8, st));  // the scan's running total
+      }
       k2.counts = ctx->d_ecnt.as<uint32_t>();
       k2.offsets = ctx->d_eoff.as<uint64_t>();
       launch_k2(k2, nc, false, st);
@@ -632,15 +659,15 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
       HIPCHK(ctx, hipGetLastError());
       uint64_t etotal = 0;
       HIPCHK(ctx, hipMemcpyAsync(&etotal, ctx->d_etotal.p, 8, hipMemcpyDeviceToHost, st));
+      if (packed) {
+        launch_run_blocks(ctx->d_runs.as<uint32_t>(), n_runs, ctx->d_eoff.as<uint64_t>(), ctx->d_run_blocks.as<uint32_t>(),
+                          ctx->d_run_blkoff.as<uint64_t>(), st);
+        HIPCHK(ctx, hipGetLastError());
+      }
       HIPCHK(ctx, hipStreamSynchronize(st));
       HIPCHK(ctx, ctx->d_entries.reserve(std::max<uint64_t>(etotal, 1) * 8));
       HIPCHK(ctx, ctx->d_out2.reserve(std::max<uint64_t>(etotal, 1) * 4));
-      k2.matches = ctx->d_entries.as<uint32_t>();
-      launch_k2(k2, nc, true, st);
-      HIPCHK(ctx, hipGetLastError());
-      // Pass 2: FindBestMatchesOneWay(dists.transpose()) (sift.cc:175-176) for the rows matches12 points at
-      HIPCHK(ctx, ctx->d_dpairs2.reserve(std::max<uint32_t>(nc, 1) * sizeof(uint2)));
-      HIPCHK(ctx, hipMemcpyAsync(ctx->d_dpairs2.p, dpairs2.data(), nc * sizeof(uint2), hipMemcpyHostToDevice, st));
+      const uint32_t n_slots = (packed && etotal) ? (uint32_t)(etotal / 512) + n_runs : 0u;
       K1Params g = k1;
       g.dpairs = ctx->d_dpairs2.as<uint2>();
       g.order = nullptr;  // list order: the column image a of consecutive pairs rarely changes in the lists the callers build
@@ -648,6 +675,21 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
       g.e_off = ctx->d_eoff.as<uint64_t>();
       g.e_cnt = ctx->d_ecnt.as<uint32_t>();
       g.out = ctx->d_out2.as<int32_t>();
+      if (n_slots) {
+        HIPCHK(ctx, ctx->d_egrow.reserve(etotal * 4));
+        HIPCHK(ctx, ctx->d_gblocks.reserve((size_t)n_slots * sizeof(uint4)));
+        launch_gather_blocks(ctx->d_runs.as<uint32_t>(), n_runs, g.e_off, g.dpairs, ctx->d_run_blkoff.as<uint64_t>(),
+                             ctx->d_gblocks.as<uint4>(), n_slots, st);
+        HIPCHK(ctx, hipGetLastError());
+        g.gblocks = ctx->d_gblocks.as<uint4>();
+        g.e_grow = ctx->d_egrow.as<uint32_t>();
+        k2.e_grow = ctx->d_egrow.as<uint32_t>();  // the write pass stores every entry's descriptor row beside it
+        k2.gpairs = ctx->d_dpairs2.as<uint2>();
+        k2.img_row0 = ctx->d_img_row0.as<uint32_t>();
+      }
+      k2.matches = ctx->d_entries.as<uint32_t>();
+      launch_k2(k2, nc, true, st);
+      HIPCHK(ctx, hipGetLastError());
 #ifdef DSM_CHECK_BUILD
       if (k1_two) {
         HIPCHK(ctx, ctx->d_out2s.reserve(std::max<uint64_t>(etotal, 1) * 4));
@@ -661,7 +703,7 @@ int dsm_match_pairs(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* pairs, const
           launch_k1_unfused(g, nc, max_rb, st);
         else
 #endif
-          launch_k1(g, nc, max_rb, st);
+          launch_k1_gather(g, n_slots, st);
         HIPCHK(ctx, hipGetLastError());
       }
       HIPCHK(ctx, hipEventRecord(ctx->ev[ev_used + 4], st));

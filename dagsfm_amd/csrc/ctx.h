@@ -170,6 +170,9 @@ struct dsm_ctx {
   double k1t_ms = 0.0;  // after pass 2: its k1_resolve_index + the compaction of the mutual matches (host wait for the total included)
   double k1g_ms = 0.0;  // k1_best_rows<GATHER> (pass 2 of the cross-check)
   DevBuf d_order, d_dpairs2, d_ecnt, d_eoff, d_etotal, d_entries, d_out2, d_ms, d_out2s;
+  // the packed gathered pass: the chunk's runs (first pair of each + sentinel), their block counts and the scan of those, the
+  // block table of the grid, and the descriptor row of every entry
+  DevBuf d_runs, d_run_blocks, d_run_blkoff, d_gblocks, d_egrow;
   uint32_t k1_launches = 0;
   std::vector<DevEvent> ev;
 
@@ -249,6 +252,7 @@ struct dsm_ctx {
                       &d_mm_keep, &d_mm_total})
       f(*b, false);
     for (DevBuf* b : {&d_m, &d_ms, &d_entries, &d_out2, &d_out2s, &d_dpairs, &d_dpairs2, &d_doutoff, &d_pair_dir, &d_order, &d_ecnt, &d_eoff,
+                      &d_runs, &d_run_blocks, &d_run_blkoff, &d_gblocks, &d_egrow,
                       &d_vscratch, &d_ud_border, &d_ud_points, &d_ud_src, &d_ud_dst, &d_ud_map})
       f(*b, true);
     for (VerifyLane& L : lanes) L.for_each_buffer([&f](DevBuf& b) { f(b, true); });

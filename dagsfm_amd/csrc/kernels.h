@@ -26,6 +26,11 @@ struct K1Params {
   const uint2* entries;       // one-way matches (i1, i2) of all pairs; entry k of pair d = row i2 of image dpairs[d].x
   const uint64_t* e_off;      // [n_pairs] first entry of every pair (also the pair's offset into `out`)
   const uint32_t* e_cnt;      // [n_pairs] entries of every pair
+  // packed gathered pass (the product's pass 2): a workgroup takes 512 consecutive entries of a RUN -- consecutive pairs with the
+  // same column image -- whatever pairs they belong to (launch_k1_gather); the per-pair grid above remains the check build's
+  const uint4* gblocks;       // per workgroup: {first entry (low, high word), entries from there to the run's end capped at 512
+                              // (0: no block), column image}, written by launch_gather_blocks
+  const uint32_t* e_grow;     // per entry: its descriptor row, img_row0[dpairs[d].x] + entries[k].y (written with the entry list)
 };
 
 // Cross-check on the gathered pass' result: keep entry (i1, i2) when out2 == i1.
@@ -48,6 +53,10 @@ struct K2Params {
   uint32_t* counts;           // [n_pairs] (count pass)
   const uint64_t* offsets;    // [n_pairs] absolute offsets into matches (write pass)
   uint32_t* matches;          // [total][2]
+  // write pass of the entry list of the packed gathered pass: e_grow[k] = img_row0[gpairs[pair].x] + i2 beside matches[k]
+  uint32_t* e_grow = nullptr;
+  const uint2* gpairs = nullptr;      // pass 2's directed pairs {image b, image a}
+  const uint32_t* img_row0 = nullptr;
 };
 
 // Guided matching (MatchGuidedSiftFeaturesCPU, sift.cc:824-875): one directed pass with the geometric filter.
@@ -248,6 +257,16 @@ void launch_compact_inliers(const uint64_t* match_off, const uint64_t* inl_off, 
 
 void launch_k0(const uint8_t* in_u8, int8_t* out_s8, int32_t* rterm, uint64_t n_rows, hipStream_t st);
 void launch_k1(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st);
+// The packed gathered pass.  run_first[0 .. n_runs]: the first pair of every run and the closing sentinel n_pairs.
+// launch_run_blocks gives run r ceil(entries / 512) blocks (run_blocks) and scans them into run_blkoff[0 .. n_runs], whose
+// element n_runs + 1 is the scan's running total and must be zero; it needs e_off only, not the host's copy of the entry total.
+// launch_gather_blocks writes gblocks[0 .. n_slots); n_slots >= the total block count (entries / 512 + n_runs is an upper
+// bound), the slots beyond it get no block.  launch_k1_gather runs one workgroup per slot.
+void launch_run_blocks(const uint32_t* run_first, uint32_t n_runs, const uint64_t* e_off, uint32_t* run_blocks, uint64_t* run_blkoff,
+                       hipStream_t st);
+void launch_gather_blocks(const uint32_t* run_first, uint32_t n_runs, const uint64_t* e_off, const uint2* dpairs, const uint64_t* run_blkoff,
+                          uint4* gblocks, uint32_t n_slots, hipStream_t st);
+void launch_k1_gather(const K1Params& p, uint32_t n_slots, hipStream_t st);
 void launch_k1_dot4(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st);
 void launch_k1_unfused(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st);  // check build
 void launch_k1_resolve(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st);  // check build

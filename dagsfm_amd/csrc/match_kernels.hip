@@ -245,16 +245,35 @@ __device__ __forceinline__ int k1_resolve_final(const K1Params& p, int k1, int k
 #ifndef K1_TAIL_RU
 #define K1_TAIL_RU 6  // rows per trip of the fused tail: the most at which the tail's registers leave the column loop's schedule alone
 #endif
+// PACKED (= GATHER && FUSED, the product's pass 2): the grid is not (pair, row block) but one workgroup per entry of
+// p.gblocks, 512 consecutive entries of a run of pairs that share the column image, whatever pairs they belong to: row r of
+// the block is entry e0 + r of the whole list, its descriptor row is p.e_grow[e0 + r], and `out` is indexed like the entry
+// list anyway.  (A pair of the benchmark has ~ 256 entries: on the per-pair grid three of a pair's four workgroups returned
+// at once and the fourth ran two or three of its four waves.)
 template <bool GATHER, bool FUSED>
 __global__ __launch_bounds__(256, 2) void k1_best_rows(const K1Params p) {
-  const uint32_t d = p.order ? p.order[blockIdx.x] : blockIdx.x;
-  const uint32_t rb = blockIdx.y;
-  const uint2 ab = p.dpairs[d];
-  const uint32_t a_rows = GATHER ? p.e_cnt[d] : p.img_rows[ab.x];
-  if (rb * 512u >= a_rows) return;
-  const uint32_t b_cols = p.img_rows[ab.y];
-  const uint32_t a_row0 = (GATHER ? 0u : p.img_row0[ab.x]) + rb * 512u;  // GATHER: first entry of this block
-  const uint32_t b_row0 = p.img_row0[ab.y];
+  constexpr bool PACKED = GATHER && FUSED;
+  uint32_t d = 0, rb = 0, a_rows, b_img, a_row0;
+  uint64_t e0 = 0;  // PACKED: the block's first entry
+  if constexpr (PACKED) {
+    const uint4 gb = p.gblocks[blockIdx.x];
+    a_rows = gb.z;  // entries of the block
+    if (a_rows == 0u) return;
+    e0 = (uint64_t)gb.y << 32 | gb.x;
+    b_img = gb.w;
+    a_row0 = 0u;
+  } else {
+    d = p.order ? p.order[blockIdx.x] : blockIdx.x;
+    rb = blockIdx.y;
+    const uint2 ab = p.dpairs[d];
+    a_rows = GATHER ? p.e_cnt[d] : p.img_rows[ab.x];
+    if (rb * 512u >= a_rows) return;
+    b_img = ab.y;
+    a_row0 = (GATHER ? 0u : p.img_row0[ab.x]) + rb * 512u;  // GATHER: first entry of this block
+  }
+  // (written so: with b_cols / b_row0 assigned inside the two branches hipcc builds another head for the column loop)
+  const uint32_t b_cols = p.img_rows[b_img];
+  const uint32_t b_row0 = p.img_row0[b_img];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -272,14 +291,18 @@ __global__ __launch_bounds__(256, 2) void k1_best_rows(const K1Params p) {
   int rterm_i[4];
   bool valid[4];  // GATHER: this lane's row of fragment rt is an entry (the last fragments of a pair are ragged)
   {
-    const uint2* ent = GATHER ? p.entries + p.e_off[d] : nullptr;
-    const uint32_t img0 = GATHER ? p.img_row0[ab.x] : 0u;
+    const uint2* ent = (GATHER && !PACKED) ? p.entries + p.e_off[d] : nullptr;
+    const uint32_t img0 = (GATHER && !PACKED) ? p.img_row0[p.dpairs[d].x] : 0u;
+    const uint32_t* e_grow = PACKED ? p.e_grow + e0 : nullptr;
 #pragma unroll
     for (int rt = 0; rt < 4; ++rt) {
-      const uint32_t r = a_row0 + wave * 128 + rt * 32 + l31;  // row of the image / entry of the pair
+      const uint32_t r = a_row0 + wave * 128 + rt * 32 + l31;  // row of the image / entry of the pair / of the block
       valid[rt] = GATHER ? (r < a_rows) : active;
       uint32_t grow = r;
-      if (GATHER) grow = valid[rt] ? img0 + ent[r].y : 0u;
+      if constexpr (PACKED)
+        grow = valid[rt] ? e_grow[r] : 0u;
+      else if (GATHER)
+        grow = valid[rt] ? img0 + ent[r].y : 0u;
       const int8_t* arow = p.desc + (size_t)grow * 128;
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
@@ -422,7 +445,7 @@ __global__ __launch_bounds__(256, 2) void k1_best_rows(const K1Params p) {
   }
 
   if (!active) return;
-  const uint64_t out0 = (GATHER ? p.e_off[d] : p.d_out_off[d]) + rb * 512u + wave * 128;
+  const uint64_t out0 = (PACKED ? e0 : GATHER ? p.e_off[d] : p.d_out_off[d]) + rb * 512u + wave * 128;
   int32_t* out = p.out + out0;
   int32_t* out_s = p.out_s + out0;
   int res_f[4], sdot_f[4];  // FUSED: the merged rows, for the tail below
@@ -825,6 +848,9 @@ __global__ __launch_bounds__(256) void k2_cross_compact(const K2Params p) {
   uint32_t running = 0;
   uint2* dst = nullptr;
   if (WRITE) dst = reinterpret_cast<uint2*>(p.matches) + p.offsets[pi];
+  // the entry list of the packed gathered pass: every entry's descriptor row beside it
+  uint32_t* e_grow = (WRITE && p.e_grow) ? p.e_grow + p.offsets[pi] : nullptr;
+  const uint32_t grow0 = e_grow ? p.img_row0[p.gpairs[pi].x] : 0u;
   for (uint32_t base = 0; base < n1; base += 256) {
     const uint32_t i = base + tid;
     int j = -1;
@@ -845,7 +871,10 @@ __global__ __launch_bounds__(256) void k2_cross_compact(const K2Params p) {
       if (w < wave) wbase += c;
       total += c;
     }
-    if (WRITE && ok) dst[running + wbase + before] = make_uint2(i, (uint32_t)j);
+    if (WRITE && ok) {
+      dst[running + wbase + before] = make_uint2(i, (uint32_t)j);
+      if (e_grow) e_grow[running + wbase + before] = grow0 + (uint32_t)j;
+    }
     running += total;
     __syncthreads();
   }
@@ -930,7 +959,54 @@ __global__ __launch_bounds__(1024) void k_scan_counts(const uint32_t* __restrict
   }
 }
 
+// ------------------------------------------------------------------------------------ the block table of the packed gathered pass
+// A run = consecutive pairs of the chunk with the same column image; its entries [e_off[first], e_off[next run's first]) are
+// contiguous in the entry list (e_off is a scan in pair order).  Run r gets ceil(entries / 512) blocks ...
+__global__ __launch_bounds__(256) void k_run_blocks(const uint32_t* __restrict__ run_first, const uint64_t* __restrict__ e_off,
+                                                    uint32_t n_runs, uint32_t* __restrict__ run_blocks) {
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  if (r >= n_runs) return;
+  run_blocks[r] = (uint32_t)((e_off[run_first[r + 1]] - e_off[run_first[r]] + 511u) >> 9);
+}
+// ... and, after the scan of those counts, slot t of the grid finds its run (the last one whose first block is <= t: runs
+// without entries share their offset with the run behind them) and writes what the workgroup needs in one 16-byte load.
+__global__ __launch_bounds__(256) void k_gather_blocks(const uint32_t* __restrict__ run_first, const uint64_t* __restrict__ e_off,
+                                                       const uint2* __restrict__ dpairs, const uint64_t* __restrict__ run_blkoff,
+                                                       uint32_t n_runs, uint32_t n_slots, uint4* __restrict__ gblocks) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= n_slots) return;
+  uint4 gb = make_uint4(0u, 0u, 0u, 0u);
+  if (t < run_blkoff[n_runs]) {
+    uint32_t lo = 0, hi = n_runs;  // run_blkoff[lo] <= t < run_blkoff[hi]
+    while (hi - lo > 1u) {
+      const uint32_t mid = lo + (hi - lo) / 2u;
+      if (run_blkoff[mid] <= t) lo = mid; else hi = mid;
+    }
+    const uint32_t first = run_first[lo];
+    const uint64_t e0 = e_off[first] + (t - run_blkoff[lo]) * 512u, e1 = e_off[run_first[lo + 1]];
+    gb = make_uint4((uint32_t)e0, (uint32_t)(e0 >> 32), (uint32_t)(e1 - e0 < 512u ? e1 - e0 : 512u), dpairs[first].y);
+  }
+  gblocks[t] = gb;
+}
+
 // ------------------------------------------------------------------------------------ launchers
+void launch_run_blocks(const uint32_t* run_first, uint32_t n_runs, const uint64_t* e_off, uint32_t* run_blocks, uint64_t* run_blkoff,
+                       hipStream_t st) {
+  if (n_runs == 0) return;
+  hipLaunchKernelGGL(k_run_blocks, dim3((n_runs + 255) / 256), dim3(256), 0, st, run_first, e_off, n_runs, run_blocks);
+  launch_scan(run_blocks, run_blkoff, n_runs, run_blkoff + n_runs + 1, st);
+}
+void launch_gather_blocks(const uint32_t* run_first, uint32_t n_runs, const uint64_t* e_off, const uint2* dpairs, const uint64_t* run_blkoff,
+                          uint4* gblocks, uint32_t n_slots, hipStream_t st) {
+  if (n_runs == 0 || n_slots == 0) return;
+  hipLaunchKernelGGL(k_gather_blocks, dim3((n_slots + 255) / 256), dim3(256), 0, st, run_first, e_off, dpairs, run_blkoff, n_runs, n_slots,
+                     gblocks);
+}
+void launch_k1_gather(const K1Params& p, uint32_t n_slots, hipStream_t st) {
+  if (n_slots == 0) return;
+  hipLaunchKernelGGL((k1_best_rows<true, true>), dim3(n_slots), dim3(256), 0, st, p);
+}
+
 void launch_k0(const uint8_t* in_u8, int8_t* out_s8, int32_t* rterm, uint64_t n_rows, hipStream_t st) {
   if (n_rows == 0) return;
   const uint64_t threads = n_rows * 8;
@@ -940,12 +1016,10 @@ void launch_k0(const uint8_t* in_u8, int8_t* out_s8, int32_t* rterm, uint64_t n_
 
 // max_row_blocks = largest padded row count of an `a` image / 256
 // `out` receives the final column indices: the flagged rows are resolved in the kernel's tail
+// (pass 1; the gathered pass of the product is launch_k1_gather)
 void launch_k1(const K1Params& p, uint32_t n_directed, uint32_t max_row_blocks, hipStream_t st) {
   if (n_directed == 0 || max_row_blocks == 0) return;
-  if (p.entries)
-    hipLaunchKernelGGL((k1_best_rows<true, true>), dim3(n_directed, (max_row_blocks + 1) / 2), dim3(256), 0, st, p);
-  else
-    hipLaunchKernelGGL((k1_best_rows<false, true>), dim3(n_directed, (max_row_blocks + 1) / 2), dim3(256), 0, st, p);
+  hipLaunchKernelGGL((k1_best_rows<false, true>), dim3(n_directed, (max_row_blocks + 1) / 2), dim3(256), 0, st, p);
 }
 #ifdef DSM_CHECK_BUILD
 // cross-check form (DSM_K1_RESOLVE_KERNEL): the pass without the tail, to be followed by launch_k1_resolve (needs p.out_s)
