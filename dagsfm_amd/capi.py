@@ -403,6 +403,21 @@ class UndistortOptions(ctypes.Structure):
                 ("roi_min_y", ctypes.c_double), ("roi_max_x", ctypes.c_double), ("roi_max_y", ctypes.c_double)]
 
 
+class VocabularyBuildOptions(ctypes.Structure):
+    """dsm_vocabulary_build_options: VisualIndex::BuildOptions (src/retrieval/visual_index.h:99-118) + the scheduling field."""
+    _fields_ = [("num_visual_words", ctypes.c_int32), ("branching", ctypes.c_int32), ("num_iterations", ctypes.c_int32),
+                ("workgroup_node_max", ctypes.c_int32)]
+
+
+class VocabularyTreeNode(ctypes.Structure):
+    """dsm_vocabulary_tree_node (dsm_get_vocabulary_tree)."""
+    _fields_ = [("parent", ctypes.c_int32), ("first_child", ctypes.c_int32), ("size", ctypes.c_int32),
+                ("variance_bits", ctypes.c_uint32), ("radius_bits", ctypes.c_uint32)]
+
+
+RAND_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p)  # int (*rand_fn)(void* user) of dsm_retrieval_quantize
+VOCABULARY_BUILD_STAGES = ("seeding", "assignment", "centre_update", "statistics", "partition", "embedding")
+
 CAMERA_SIZE_ONLY = -1  # DSM_CAMERA_SIZE_ONLY: a dsm_camera of which dsm_warp_images reads only width and height
 UNDISTORTION_STAGES = ("border_scan", "points", "warp_upload", "warp_kernel", "warp_download")
 
@@ -521,6 +536,12 @@ def lib(check=False):
         L.dsm_warp_images.argtypes = ([vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_uint64, vp,
                                        ctypes.c_uint64, ctypes.c_uint64, vp, vp, vp])
         L.dsm_get_undistortion_time.argtypes = [vp, vp]
+        L.dsm_default_vocabulary_build_options.argtypes = [ctypes.POINTER(VocabularyBuildOptions)]
+        L.dsm_default_vocabulary_build_options.restype = None
+        L.dsm_retrieval_quantize.argtypes = [vp, ctypes.POINTER(VocabularyBuildOptions), vp, ctypes.c_uint64, vp, vp, u32p, vp, vp]
+        L.dsm_get_vocabulary_tree.argtypes = [vp, u32p, vp, vp, ctypes.c_uint32, vp, ctypes.c_uint64]
+        L.dsm_retrieval_train_embedding.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, vp, vp]
+        L.dsm_get_vocabulary_build_time.argtypes = [vp, vp]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
         L.dsm_default_match_options.restype = None
         L.dsm_default_two_view_options.argtypes = [ctypes.POINTER(TwoViewOptions)]
@@ -674,6 +695,14 @@ def default_covariant_sift_options(check=False, **kw):
 def default_undistort_options(**kw):
     o = UndistortOptions()
     lib().dsm_default_undistort_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_vocabulary_build_options(**kw):
+    o = VocabularyBuildOptions()
+    lib().dsm_default_vocabulary_build_options(ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -1113,6 +1142,65 @@ class Context:
         a, b = ctypes.c_double(0), ctypes.c_double(0)
         self._chk(self._L.dsm_get_retrieval_time(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    # ---- training the vocabulary tree (VisualIndex::Build)
+    def retrieval_quantize(self, descriptors, options=None, rand=None, with_centers=False):
+        """dsm_retrieval_quantize: VisualIndex::Quantize of [n, 128] uint8 descriptors.  rand: a callable returning the next
+        rand() value (None: the process's rand()).  Returns words [count, 128] uint8 (and the float centres)."""
+        d = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 128)
+        o = options if options is not None else default_vocabulary_build_options()
+        cap = max(int(o.num_visual_words), 1)
+        words = np.zeros((cap, 128), np.uint8)
+        centers = np.zeros((cap, 128), np.float32) if with_centers else None
+        count = ctypes.c_uint32(0)
+        fn = RAND_FN(lambda user: int(rand())) if rand is not None else None
+        self._chk(self._L.dsm_retrieval_quantize(self._h, ctypes.byref(o), d.ctypes.data, d.shape[0], fn, None, ctypes.byref(count),
+                                                 words.ctypes.data, centers.ctypes.data if with_centers else None))
+        return (words[:count.value], centers[:count.value]) if with_centers else words[:count.value]
+
+    def vocabulary_tree(self):
+        """dsm_get_vocabulary_tree: (parent, first_child, size, variance bits, radius bits, pivot bits [nodes, 128], indices) of
+        the last retrieval_quantize, nodes in depth-first order."""
+        n_nodes = ctypes.c_uint32(0)
+        self._chk(self._L.dsm_get_vocabulary_tree(self._h, ctypes.byref(n_nodes), None, None, 0, None, 0))
+        k = n_nodes.value
+        nodes = (VocabularyTreeNode * k)()
+        pivots = np.zeros((k, 128), np.float32)
+        size_root = ctypes.c_uint32(0)
+        self._chk(self._L.dsm_get_vocabulary_tree(self._h, ctypes.byref(size_root), ctypes.addressof(nodes), pivots.ctypes.data, k, None, 0))
+        a = np.frombuffer(nodes, np.uint32).reshape(k, 5)
+        indices = np.zeros(int(a[0, 2]), np.int32)
+        self._chk(self._L.dsm_get_vocabulary_tree(self._h, None, None, None, 0, indices.ctypes.data, len(indices)))
+        return (a[:, 0].astype(np.int32), a[:, 1].astype(np.int32), a[:, 2].astype(np.int32), a[:, 3].copy(), a[:, 4].copy(),
+                pivots.view(np.uint32), indices)
+
+    def retrieval_train_embedding(self, descriptors, words, projection, word_ids=None):
+        """dsm_retrieval_train_embedding: (thresholds [num_words, 64] float32, has_embedding [num_words] uint8)."""
+        d = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 128)
+        w = np.ascontiguousarray(words, np.uint8).reshape(-1, 128)
+        p = np.ascontiguousarray(projection, np.float32).reshape(64, 128)
+        ids = None if word_ids is None else np.ascontiguousarray(word_ids, np.int32)
+        assert ids is None or ids.shape == (d.shape[0],)
+        thresholds = np.zeros((w.shape[0], 64), np.float32)
+        has = np.zeros(w.shape[0], np.uint8)
+        self._chk(self._L.dsm_retrieval_train_embedding(self._h, d.ctypes.data, d.shape[0], w.ctypes.data, w.shape[0], p.ctypes.data,
+                                                        None if ids is None else ids.ctypes.data, thresholds.ctypes.data, has.ctypes.data))
+        return thresholds, has
+
+    def build_vocabulary(self, descriptors, projection, options=None, word_ids=None, rand=None):
+        """VisualIndex::Build's numerical part: Quantize, then ComputeHammingEmbedding over the same descriptors.  Returns
+        (words, projection, thresholds), what retrieval_set_vocabulary takes.  word_ids: the caller's word of every descriptor
+        among the returned words (a callable is given the words first); None: the exact nearest word."""
+        words = self.retrieval_quantize(descriptors, options, rand)
+        ids = word_ids(words) if callable(word_ids) else word_ids
+        thresholds, _ = self.retrieval_train_embedding(descriptors, words, projection, ids)
+        return words, np.ascontiguousarray(projection, np.float32).reshape(64, 128), thresholds
+
+    def vocabulary_build_time(self):
+        """dsm_get_vocabulary_build_time: {stage: ms} of the last retrieval_quantize / retrieval_train_embedding."""
+        ms = (ctypes.c_double * len(VOCABULARY_BUILD_STAGES))()
+        self._chk(self._L.dsm_get_vocabulary_build_time(self._h, ctypes.addressof(ms)))
+        return dict(zip(VOCABULARY_BUILD_STAGES, list(ms)))
 
     def view_graph_filter_cycles(self, pairs, qvecs, max_loop_error_degrees=5.0):
         """ViewGraph::FilterViewGraphCyclesByRotation over (pairs, qvecs): returns (keep [n] bool, number of triplets)."""

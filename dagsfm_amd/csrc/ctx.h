@@ -232,6 +232,18 @@ struct dsm_ctx {
   bool undistortion_ready = false;
   double undistortion_ms[DSM_UNDISTORTION_STAGES] = {0};
 
+  // vocabulary_build.hip: the descriptors, the indices permutation, the per-position values and the per-job state of a
+  // dsm_retrieval_quantize call, the buffers of dsm_retrieval_train_embedding -- all released when the call ends; the tree of the
+  // last dsm_retrieval_quantize in depth-first order (dsm_get_vocabulary_tree) and the HIP-event times of the last calls
+  DevBuf d_vb_desc, d_vb_idx, d_vb_point, d_vb_node, d_vb_embed;
+  std::vector<dsm_vocabulary_tree_node> vb_nodes;
+  std::vector<float> vb_pivots;
+  std::vector<std::vector<int32_t>> vb_childs;
+  std::vector<int32_t> vb_indices;
+  int32_t vb_branching = 0;
+  bool vocabulary_build_ready = false;
+  double vocabulary_build_ms[DSM_VOCABULARY_BUILD_STAGES] = {0};
+
   // the final Ritz values and the k Ritz vectors ([images][k]) of the last dsm_view_graph_cluster that ran the eigen-solver
   // (view_graph_clustering.hip)
   std::vector<double> cluster_ritz, cluster_vectors;
@@ -249,11 +261,11 @@ struct dsm_ctx {
                       &d_g_nfeat, &d_g_dpairs, &d_g_doff, &d_g_pdir, &d_g_params, &d_g_m, &d_g_counts, &d_g_offsets, &d_g_total, &d_g_matches,
                       &d_g_plan, &d_g_inl, &d_g_inl_off,
                       &d_mm_matches[0], &d_mm_matches[1], &d_mm_off[0], &d_mm_off[1], &d_mm_counts, &d_mm_state, &d_mm_first, &d_mm_acc,
-                      &d_mm_keep, &d_mm_total})
+                      &d_mm_keep, &d_mm_total, &d_vb_desc, &d_vb_idx})
       f(*b, false);
     for (DevBuf* b : {&d_m, &d_ms, &d_entries, &d_out2, &d_out2s, &d_dpairs, &d_dpairs2, &d_doutoff, &d_pair_dir, &d_order, &d_ecnt, &d_eoff,
                       &d_runs, &d_run_blocks, &d_run_blkoff, &d_gblocks, &d_egrow,
-                      &d_vscratch, &d_ud_border, &d_ud_points, &d_ud_src, &d_ud_dst, &d_ud_map})
+                      &d_vscratch, &d_ud_border, &d_ud_points, &d_ud_src, &d_ud_dst, &d_ud_map, &d_vb_point, &d_vb_node, &d_vb_embed})
       f(*b, true);
     for (VerifyLane& L : lanes) L.for_each_buffer([&f](DevBuf& b) { f(b, true); });
   }

@@ -1502,6 +1502,67 @@ int dsm_warp_images(dsm_ctx* ctx, const dsm_camera* source_camera, const dsm_cam
 #define DSM_UNDISTORTION_STAGES 5
 int dsm_get_undistortion_time(dsm_ctx* ctx, double* stage_ms);
 
+/* ---- training the vocabulary tree (vocab_tree_builder, VisualIndex::Build, src/retrieval/visual_index.h:510-536) ----
+ * The two numerical steps of Build, DESIGN.md 23: Quantize (:623-665) = flann::hierarchicalClustering<L2<uint8_t>> with
+ * KMEANSPP seeding -- the WHOLE k-means tree (lib/FLANN/algorithms/kmeans_index.h:329-345, 496-530, 544-713), then
+ * getMinVarianceClusters (:928-969) and std::round -- and InvertedIndex::ComputeHammingEmbedding (inverted_index.h:184-217).
+ * Not covered: flann::AutotunedIndex::buildIndex over the words (it decides by wall-clock timings), the Gaussian + QR
+ * projection (GenerateHammingEmbeddingProjection, Eigen), writing the vocabulary file: the host's. */
+typedef struct dsm_vocabulary_build_options { /* VisualIndex::BuildOptions, visual_index.h:99-118 */
+  int32_t num_visual_words;   /* 65536 */
+  int32_t branching;          /* 256; 2 .. 4096 */
+  int32_t num_iterations;     /* 11; negative: until convergence, as FLANN reads it */
+  int32_t workgroup_node_max; /* scheduling only, never the result: a node of at most this many points is clustered by one
+                                 workgroup (nodes whose draws are known beforehand in batches), a larger one by the whole
+                                 chip, a launch per phase.  0: the default, max(2 * branching - 2, 256) */
+} dsm_vocabulary_build_options;
+void dsm_default_vocabulary_build_options(dsm_vocabulary_build_options* o);
+
+/* VisualIndex::Quantize of n x 128 uint8 descriptors (host memory); options NULL = the defaults.  *num_words_out receives the
+ * number of centres the reference returns (<= num_visual_words: getMinVarianceClusters stops when the next split would pass
+ * it), words [num_visual_words][128] its rounded centres in its order, centers (may be NULL) the float centres.
+ * FLANN draws from the process's rand() (lib/FLANN/util/random.h:62-76); rand_fn(user) stands for it and is called on the host
+ * in the reference's order -- `branching` times per clustered node, depth first -- NULL: rand() itself.  With the same stream
+ * of draws the count, the order and every byte are the reference's.  rand() is the PROCESS's stream, as it is for the
+ * reference: whatever else calls it between the caller's srand() and this call's draws shifts the result (seen on the first
+ * vocabulary call of a process); a caller who needs srand(seed) to fix the words passes rand_fn, or calls once before seeding.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT): the reference's CHECKs -- num_visual_words < branching, n < num_visual_words, branching
+ * < 2 -- and branching > 4096, n > 2^31 - 1, a negative workgroup_node_max, NULL where data is needed; num_iterations == 0
+ * on a node of identical points, which then keeps all of them in one child for ever (the reference recurses until its stack
+ * is gone; with an iteration the empty-cluster repair splits such a node).
+ * DSM_ERR_OUT_OF_RANGE: the descriptors and the tree's state (about 144 bytes per descriptor) do not fit
+ * dsm_ctx_set_memory_budget or the device's free memory.  The device memory of the call is released when it returns. */
+int dsm_retrieval_quantize(dsm_ctx* ctx, const dsm_vocabulary_build_options* options, const uint8_t* descriptors, uint64_t n,
+                           int (*rand_fn)(void*), void* user, uint32_t* num_words_out, uint8_t* words, float* centers);
+
+/* Test hook: the k-means tree of the last dsm_retrieval_quantize, nodes in depth-first order (a node, then the subtrees of
+ * its children in order).  first_child is -1 for a leaf; the other children are the later nodes with this parent, in order.
+ * variance and radius are float bits.  pivots [nodes][128] floats (may be NULL), indices [n] the final permutation
+ * (may be NULL).  *num_nodes (may be NULL) is set before the capacities are checked (DSM_ERR_OUT_OF_RANGE). */
+typedef struct dsm_vocabulary_tree_node {
+  int32_t parent, first_child, size;
+  uint32_t variance_bits, radius_bits;
+} dsm_vocabulary_tree_node;
+int dsm_get_vocabulary_tree(dsm_ctx* ctx, uint32_t* num_nodes, dsm_vocabulary_tree_node* nodes, float* pivots, uint32_t node_capacity,
+                            int32_t* indices, uint64_t indices_capacity);
+
+/* InvertedIndex::ComputeHammingEmbedding (inverted_index.h:184-217, inverted_file.h:275-291) of n training descriptors, host
+ * pointers: thresholds [num_words][64] = Median (util/math.h:211-229) of the word's projected descriptors per dimension,
+ * has_embedding [num_words] = 1 where it was computed.  A word with fewer than 5 descriptors (kMinEntries) keeps zero
+ * thresholds and flag 0.  projection [64][128] row-major is the caller's; each projected value is summed left to right in
+ * float, as dsm_retrieval_index / _query sum it.  word_ids [n] (may be NULL): the caller's word of every descriptor, e.g. the
+ * reference's FLANN answer; NULL: the exact nearest word, ties to the lower id, as dsm_retrieval_index assigns it.
+ * Invalid: NULL where data is needed, num_words == 0, a word id outside the words. */
+int dsm_retrieval_train_embedding(dsm_ctx* ctx, const uint8_t* descriptors, uint64_t n, const uint8_t* words, uint32_t num_words,
+                                  const float* projection, const int32_t* word_ids, float* thresholds, uint8_t* has_embedding);
+
+/* Times in ms of the last dsm_retrieval_quantize (0 seeding, 1 assignment -- and the whole kernel of the workgroup form --, 2
+ * centre update, 3 statistics: the distances to the float centres and the root's chains, 4 partition: the host's swap
+ * partition with its copies) and of the last dsm_retrieval_train_embedding (5).  HIP events, host clock for the host's
+ * pieces.  DSM_ERR_NOT_READY before the first of these calls. */
+#define DSM_VOCABULARY_BUILD_STAGES 6
+int dsm_get_vocabulary_build_time(dsm_ctx* ctx, double* stage_ms);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
