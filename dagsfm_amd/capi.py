@@ -403,6 +403,27 @@ class UndistortOptions(ctypes.Structure):
                 ("roi_min_y", ctypes.c_double), ("roi_max_x", ctypes.c_double), ("roi_max_y", ctypes.c_double)]
 
 
+class PatchMatchOptions(ctypes.Structure):
+    """dsm_patch_match_options: PatchMatchOptions (src/mvs/patch_match.h:59-139) + the seed of the Philox key."""
+    _fields_ = [("window_radius", ctypes.c_int32), ("window_step", ctypes.c_int32), ("num_samples", ctypes.c_int32),
+                ("num_iterations", ctypes.c_int32), ("geom_consistency", ctypes.c_int32), ("filter", ctypes.c_int32),
+                ("filter_min_num_consistent", ctypes.c_int32), ("seed", ctypes.c_uint32), ("sigma_spatial", ctypes.c_double),
+                ("sigma_color", ctypes.c_double), ("ncc_sigma", ctypes.c_double), ("min_triangulation_angle", ctypes.c_double),
+                ("incident_angle_sigma", ctypes.c_double), ("geom_consistency_regularizer", ctypes.c_double),
+                ("geom_consistency_max_cost", ctypes.c_double), ("filter_min_ncc", ctypes.c_double),
+                ("filter_min_triangulation_angle", ctypes.c_double), ("filter_geom_consistency_max_cost", ctypes.c_double)]
+
+
+class MvsImage(ctypes.Structure):
+    """dsm_mvs_image: one image of the undistorted workspace (dsm_patch_match)."""
+    _fields_ = [("data", ctypes.c_void_p), ("row_stride", ctypes.c_uint64), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("K", ctypes.c_float * 9), ("R", ctypes.c_float * 9), ("T", ctypes.c_float * 3), ("reserved", ctypes.c_uint32),
+                ("depth_map", ctypes.c_void_p), ("normal_map", ctypes.c_void_p)]
+
+
+PATCH_MATCH_STAGES = ("upload", "reference_filter", "initial_cost", "sweeps", "rotation", "download")
+
+
 class VocabularyBuildOptions(ctypes.Structure):
     """dsm_vocabulary_build_options: VisualIndex::BuildOptions (src/retrieval/visual_index.h:99-118) + the scheduling field."""
     _fields_ = [("num_visual_words", ctypes.c_int32), ("branching", ctypes.c_int32), ("num_iterations", ctypes.c_int32),
@@ -542,6 +563,10 @@ def lib(check=False):
         L.dsm_get_vocabulary_tree.argtypes = [vp, u32p, vp, vp, ctypes.c_uint32, vp, ctypes.c_uint64]
         L.dsm_retrieval_train_embedding.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, vp, vp]
         L.dsm_get_vocabulary_build_time.argtypes = [vp, vp]
+        L.dsm_default_patch_match_options.argtypes = [ctypes.POINTER(PatchMatchOptions)]
+        L.dsm_default_patch_match_options.restype = None
+        L.dsm_patch_match.argtypes = [vp, ctypes.POINTER(PatchMatchOptions), ctypes.c_uint32, vp, ctypes.c_uint32] + [vp] * 9
+        L.dsm_get_patch_match_time.argtypes = [vp, vp]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
         L.dsm_default_match_options.restype = None
         L.dsm_default_two_view_options.argtypes = [ctypes.POINTER(TwoViewOptions)]
@@ -700,6 +725,56 @@ def default_undistort_options(**kw):
     return o
 
 
+def default_patch_match_options(**kw):
+    o = PatchMatchOptions()
+    lib().dsm_default_patch_match_options(ctypes.byref(o))
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
+def consistency_graph(mask, src_image_idxs):
+    """GetConsistentImageIdxs (src/mvs/patch_match_cuda.cu:1217-1241) of a consistency mask [S][H][W]: the int32 vector
+    col, row, count, ids... of every pixel with at least one consistent source image, pixels in row-major order, the ids
+    (src_image_idxs[slice]) in slice order -- what the reference writes as its consistency graph."""
+    mask = np.asarray(mask)
+    ids = np.asarray(src_image_idxs, dtype=np.int32)
+    assert mask.ndim == 3 and mask.shape[0] == len(ids)
+    on = np.moveaxis(mask != 0, 0, -1)  # [H][W][S]
+    count = on.sum(axis=-1)
+    rows, cols = np.nonzero(count)
+    out = []
+    for r, c in zip(rows.tolist(), cols.tolist()):
+        out += [c, r, int(count[r, c])] + ids[on[r, c]].tolist()
+    return np.array(out, dtype=np.int32)
+
+
+def write_mvs_array(path, array):
+    """Mat<float>::Write (src/mvs/mat.h:179-191): the text header `W&H&C&`, then the floats little-endian, slice by slice.
+    array: [H][W] or [C][H][W] float32 -- the layout of dsm_patch_match's depth and normal maps, readable by stereo_fusion."""
+    a = np.asarray(array, dtype=np.float32)
+    if a.ndim == 2:
+        a = a[None]
+    assert a.ndim == 3
+    with open(path, "wb") as f:
+        f.write(("%d&%d&%d&" % (a.shape[2], a.shape[1], a.shape[0])).encode("ascii"))
+        f.write(np.ascontiguousarray(a).astype("<f4").tobytes())
+
+
+def read_mvs_array(path):
+    """Mat<float>::Read (src/mvs/mat.h:156-177) -> [C][H][W] float32."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    parts = blob.split(b"&", 3)
+    if len(parts) != 4:
+        raise DsmError("%s: no W&H&C& header" % path)
+    w, h, c = (int(p) for p in parts[:3])
+    if w <= 0 or h <= 0 or c <= 0 or len(parts[3]) != 4 * w * h * c:
+        raise DsmError("%s: header %dx%dx%d does not match %d bytes of data" % (path, w, h, c, len(parts[3])))
+    return np.frombuffer(parts[3], dtype="<f4").astype(np.float32).reshape(c, h, w)
+
+
 def default_vocabulary_build_options(**kw):
     o = VocabularyBuildOptions()
     lib().dsm_default_vocabulary_build_options(ctypes.byref(o))
@@ -852,7 +927,7 @@ PRODUCT_OPTION_KEYS = ("DSM_MATCH_CHUNK_ROWS", "DSM_VERIFY_CHUNK_PAIRS", "DSM_VE
 CHECK_OPTION_KEYS = ("DSM_K1_DOT4", "DSM_K1_RESOLVE_KERNEL", "DSM_VERIFY_DEBUG", "DSM_SAMPLER_SERIAL", "DSM_LO_PREPARE_WAVE", "DSM_LO_JACOBI_GROUPS", "DSM_ROOTS_LDS",
                      "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT", "DSM_DEBUG_SAMPLER_MODE",
                      "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER", "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
-                     "DSM_POSE_FULL")
+                     "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES")
 DEBUG_OPTION_KEYS = PRODUCT_OPTION_KEYS  # what a deployer's library knows
 
 
@@ -1636,6 +1711,83 @@ class Context:
         ms = (ctypes.c_double * len(UNDISTORTION_STAGES))()
         self._chk(self._L.dsm_get_undistortion_time(self._h, ctypes.addressof(ms)))
         return dict(zip(UNDISTORTION_STAGES, list(ms)))
+
+    def patch_match(self, images, problems, options=None, return_sel_prob=True, **kw):
+        """dsm_patch_match (PatchMatchCuda::Run, DESIGN.md 24), one pass over a batch of problems.
+        images: a list of dicts -- data [h][w] uint8, K [9], R [9], T [3] and, for geom_consistency, depth_map [h][w] and
+        normal_map [3][h][w] float32.  problems: a list of (ref_image, src_images, depth_min, depth_max).
+        options: a PatchMatchOptions, or its fields as keywords over the defaults.
+        Returns a list of dicts per problem: depth [H][W], normal [3][H][W], sel_prob [S][H][W] (None unless asked for),
+        mask [S][H][W] uint8 (None without filter)."""
+        assert options is None or not kw, "pass a PatchMatchOptions or keywords, not both"
+        o = options if options is not None else default_patch_match_options(**kw)
+        keep = []
+        arr = (MvsImage * max(len(images), 1))()
+        for i, im in enumerate(images):
+            data = np.ascontiguousarray(im["data"], dtype=np.uint8)
+            assert data.ndim == 2
+            keep.append(data)
+            arr[i].data, arr[i].row_stride = data.ctypes.data, data.strides[0]
+            arr[i].height, arr[i].width = data.shape
+            for name, n in (("K", 9), ("R", 9), ("T", 3)):
+                v = np.asarray(im[name], dtype=np.float32).reshape(-1)
+                assert len(v) == n, name
+                setattr(arr[i], name, (ctypes.c_float * n)(*v.tolist()))
+            for name, shape in (("depth_map", data.shape), ("normal_map", (3,) + data.shape)):
+                if im.get(name) is not None:
+                    m = np.ascontiguousarray(im[name], dtype=np.float32)
+                    assert m.shape == shape, name
+                    keep.append(m)
+                    setattr(arr[i], name, m.ctypes.data)
+        n = len(problems)
+        ref = np.array([p[0] for p in problems], dtype=np.uint32)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(p[1]) for p in problems])
+        src = np.array([s for p in problems for s in p[1]], dtype=np.uint32)
+        dmin = np.array([p[2] for p in problems], dtype=np.float32)
+        dmax = np.array([p[3] for p in problems], dtype=np.float32)
+        out = []
+        ptrs = [(ctypes.c_void_p * max(n, 1))() for _ in range(4)]
+        for k, p in enumerate(problems):
+            assert 0 <= p[0] < len(images), "reference image index out of range"
+            h, w = np.asarray(images[p[0]]["data"]).shape
+            S = len(p[1])
+            r = {"depth": np.zeros((h, w), np.float32), "normal": np.zeros((3, h, w), np.float32),
+                 "sel_prob": np.zeros((S, h, w), np.float32) if return_sel_prob else None,
+                 "mask": np.zeros((S, h, w), np.uint8) if o.filter else None}
+            out.append(r)
+            ptrs[0][k], ptrs[1][k] = r["depth"].ctypes.data, r["normal"].ctypes.data
+            ptrs[2][k] = r["sel_prob"].ctypes.data if return_sel_prob else None
+            # (a zero-sized array has no address worth passing: any non-NULL pointer stands for the empty mask)
+            ptrs[3][k] = (r["mask"].ctypes.data or r["depth"].ctypes.data) if o.filter else None
+        rc = self._L.dsm_patch_match(self._h, ctypes.byref(o), len(images), ctypes.addressof(arr), n, ref.ctypes.data, offs.ctypes.data,
+                                     src.ctypes.data if len(src) else None, dmin.ctypes.data, dmax.ctypes.data, ctypes.addressof(ptrs[0]),
+                                     ctypes.addressof(ptrs[1]), ctypes.addressof(ptrs[2]), ctypes.addressof(ptrs[3]))
+        if rc != 0:
+            self._fail("dsm_patch_match", rc)
+        return out
+
+    def patch_match_stereo(self, images, problems, options=None, return_sel_prob=True, **kw):
+        """The controller's two passes (src/mvs/patch_match.cc:201-215), both batched: the photometric pass of ALL problems
+        with geom_consistency = filter = False, then, if geom_consistency is asked for, the geometric pass with the depth and
+        normal maps of the first as the images' maps.  Without geom_consistency: the one pass as given."""
+        assert options is None or not kw, "pass a PatchMatchOptions or keywords, not both"
+        o = options if options is not None else default_patch_match_options(**kw)
+        if not o.geom_consistency:
+            return self.patch_match(images, problems, o, return_sel_prob)
+        photo = PatchMatchOptions.from_buffer_copy(o)
+        photo.geom_consistency, photo.filter = 0, 0
+        first = self.patch_match(images, problems, photo, return_sel_prob=False)
+        fed = [dict(im) for im in images]
+        for p, r in zip(problems, first):
+            fed[p[0]]["depth_map"], fed[p[0]]["normal_map"] = r["depth"], r["normal"]
+        return self.patch_match(fed, problems, o, return_sel_prob)
+
+    def patch_match_time(self):
+        """dsm_get_patch_match_time: {stage: ms} of the last patch_match call (HIP events, summed over its chunks)."""
+        ms = (ctypes.c_double * len(PATCH_MATCH_STAGES))()
+        self._chk(self._L.dsm_get_patch_match_time(self._h, ctypes.addressof(ms)))
+        return dict(zip(PATCH_MATCH_STAGES, list(ms)))
 
     @staticmethod
     def apply_point_filter(scene, result):

@@ -232,6 +232,12 @@ struct dsm_ctx {
   bool undistortion_ready = false;
   double undistortion_ms[DSM_UNDISTORTION_STAGES] = {0};
 
+  // patch_match.hip: the image table, the tables and every map of one chunk of problems of dsm_patch_match; the HIP-event
+  // times of the last call
+  DevBuf d_pm;
+  bool patch_match_ready = false;
+  double patch_match_ms[DSM_PATCH_MATCH_STAGES] = {0};
+
   // vocabulary_build.hip: the descriptors, the indices permutation, the per-position values and the per-job state of a
   // dsm_retrieval_quantize call, the buffers of dsm_retrieval_train_embedding -- all released when the call ends; the tree of the
   // last dsm_retrieval_quantize in depth-first order (dsm_get_vocabulary_tree) and the HIP-event times of the last calls
@@ -265,7 +271,7 @@ struct dsm_ctx {
       f(*b, false);
     for (DevBuf* b : {&d_m, &d_ms, &d_entries, &d_out2, &d_out2s, &d_dpairs, &d_dpairs2, &d_doutoff, &d_pair_dir, &d_order, &d_ecnt, &d_eoff,
                       &d_runs, &d_run_blocks, &d_run_blkoff, &d_gblocks, &d_egrow,
-                      &d_vscratch, &d_ud_border, &d_ud_points, &d_ud_src, &d_ud_dst, &d_ud_map, &d_vb_point, &d_vb_node, &d_vb_embed})
+                      &d_vscratch, &d_ud_border, &d_ud_points, &d_ud_src, &d_ud_dst, &d_ud_map, &d_pm, &d_vb_point, &d_vb_node, &d_vb_embed})
       f(*b, true);
     for (VerifyLane& L : lanes) L.for_each_buffer([&f](DevBuf& b) { f(b, true); });
   }
@@ -283,7 +289,7 @@ static const char* const dsm_check_debug_keys[] = {"DSM_K1_DOT4", "DSM_K1_RESOLV
                                                    "DSM_ROOTS_LDS", "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT",
                                                    "DSM_DEBUG_SAMPLER_MODE", "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER",
                                                    "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
-                                                   "DSM_POSE_FULL"};
+                                                   "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES"};
 #endif
 
 #define HIPCHK(ctx, call)                                                              \

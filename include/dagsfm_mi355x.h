@@ -1563,6 +1563,77 @@ int dsm_retrieval_train_embedding(dsm_ctx* ctx, const uint8_t* descriptors, uint
 #define DSM_VOCABULARY_BUILD_STAGES 6
 int dsm_get_vocabulary_build_time(dsm_ctx* ctx, double* stage_ms);
 
+/* ---- PatchMatch multi-view stereo (patch_match_stereo, PatchMatchCuda, src/mvs/patch_match_cuda.cu) ----
+ * DESIGN.md 24.  The reference has this stage as CUDA only, built with fast math, hardware texture filtering and cuRAND; the
+ * contract here is its algorithm operation for operation in IEEE float, with the points it leaves to the hardware fixed as
+ * DESIGN.md 24 lists them (Philox4x32-10 draws, software bilinear sampling, fminf / fmaxf, the bilateral weight as a product of
+ * two host tables, correctly rounded exp / sin / cos).  tests/patch_match_ref.py is the normative restatement; the device equals
+ * it bit for bit.
+ * NOT covered: source-image selection and depth ranges from the sparse model (the caller names both, as patch-match.cfg does),
+ * max_image_size rescaling, image decoding, the Workspace cache, StereoFusion and meshing: the host's. */
+typedef struct dsm_patch_match_options { /* PatchMatchOptions, src/mvs/patch_match.h:59-139, ranges of Check() :141-168 */
+  int32_t window_radius;                   /* 5; 1 .. 32 */
+  int32_t window_step;                     /* 1; 1 .. 2 */
+  int32_t num_samples;                     /* 15; > 0 */
+  int32_t num_iterations;                  /* 5; > 0 */
+  int32_t geom_consistency;                /* 1 */
+  int32_t filter;                          /* 1 */
+  int32_t filter_min_num_consistent;       /* 2; >= 0 */
+  uint32_t seed;                           /* 0: the first word of the Philox key */
+  double sigma_spatial;                    /* -1; <= 0: window_radius (patch_match.cc:454) */
+  double sigma_color;                      /* 0.2f; > 0 */
+  double ncc_sigma;                        /* 0.6f; > 0 */
+  double min_triangulation_angle;          /* 1.0 degrees; [0, 180) */
+  double incident_angle_sigma;             /* 0.9f; > 0 */
+  double geom_consistency_regularizer;     /* 0.3f; >= 0 */
+  double geom_consistency_max_cost;        /* 3.0; >= 0 */
+  double filter_min_ncc;                   /* 0.1f; [-1, 1] */
+  double filter_min_triangulation_angle;   /* 3.0 degrees; [0, 180] */
+  double filter_geom_consistency_max_cost; /* 1.0; >= 0 */
+} dsm_patch_match_options;
+void dsm_default_patch_match_options(dsm_patch_match_options* o);
+
+/* One image of the undistorted workspace (mvs::Image, src/mvs/image.h): grey bytes, rows top-down, row y at data + y *
+ * row_stride; K, R row-major and T in float as mvs::Image holds them.  depth_map [height][width] and normal_map
+ * [3][height][width] (the slice layout of Mat<float>) are read with geom_consistency only. */
+typedef struct dsm_mvs_image {
+  const uint8_t* data;
+  uint64_t row_stride;
+  uint32_t width, height;
+  float K[9], R[9], T[3];
+  uint32_t reserved;
+  const float* depth_map;
+  const float* normal_map;
+} dsm_mvs_image;
+
+/* PatchMatchCuda::Run for a batch of problems, host pointers; options NULL = the defaults.  Problem p has the reference image
+ * ref_image[p], the source images src_images[src_offsets[p] .. src_offsets[p + 1]) (their order is the order of the slices S
+ * of the outputs) and the depth range [depth_min[p], depth_max[p]].  The Philox key of a problem is (seed, ref_image[p]), so a
+ * problem's bytes depend neither on its place in the batch nor on how the batch is cut.
+ * With geom_consistency the depth and normal map of the reference image initialise the problem and the depth maps of the
+ * source images enter the cost (InitWorkspaceMemory :1614-1656, InitSourceImages :1466-1497): both must be given for every
+ * image a problem names.
+ * Outputs, one pointer per problem: out_depth[p] [H][W], out_normal[p] [3][H][W], out_sel_prob[p] [S][H][W] (out_sel_prob or
+ * an entry of it may be NULL), out_mask[p] [S][H][W] bytes (the consistency mask, written with filter only; out_mask may be
+ * NULL).  H, W: the reference image's.
+ * n_problems = 0 is a valid call that writes nothing.  A problem without source images is valid: no hypothesis has a cost, so
+ * FindMinCost's `<=` keeps the last one (the perturbed depth with the current normal) in every sweep, and with filter and
+ * filter_min_num_consistent > 0 every pixel is filtered to 0; its S-sliced outputs are empty.
+ * The batch is cut into chunks of problems whose maps fit dsm_ctx_set_memory_budget (4 GiB without one; one problem always
+ * runs); the image table is resident for the whole call.  The results do not depend on the cut.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT, outputs untouched): an option outside the range above (a NaN fails it), depth_min <= 0
+ * or depth_min > depth_max, an image index out of range, an image without pixels or with a side above 32768, a row stride
+ * below the width, NULL where data is needed. */
+int dsm_patch_match(dsm_ctx* ctx, const dsm_patch_match_options* options, uint32_t n_images, const dsm_mvs_image* images,
+                    uint32_t n_problems, const uint32_t* ref_image, const uint64_t* src_offsets, const uint32_t* src_images,
+                    const float* depth_min, const float* depth_max, float* const* out_depth, float* const* out_normal,
+                    float* const* out_sel_prob, uint8_t* const* out_mask);
+
+/* HIP-event times in ms of the last dsm_patch_match, summed over its chunks: 0 upload (image table, tables, initial maps), 1
+ * reference filter and initialisation, 2 initial cost, 3 sweeps, 4 rotation, 5 download.  DSM_ERR_NOT_READY before the first call. */
+#define DSM_PATCH_MATCH_STAGES 6
+int dsm_get_patch_match_time(dsm_ctx* ctx, double* stage_ms);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
