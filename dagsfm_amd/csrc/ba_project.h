@@ -2,6 +2,9 @@
 // so that one body gives both the residual (double) and its derivatives (BaDual: forward-mode dual numbers over u, v and the
 // camera parameters).  Restated from the reference's formulas, in the order it writes them; the model table (ids, parameter
 // counts, focal indices) is verify_camera.h's.  One runtime switch on the model id, no instantiation per model.
+// Below it, what the three reprojection solvers (bundle_adjustment.hip, local_bundle.hip, pose_refinement.hip) share around the
+// projection: ceres' quaternion rotation and its matrix, QuaternionParameterization::Plus, the projection seeded for its
+// derivatives, and the chain from the pixel back to the camera-frame point and the quaternion's tangent.
 #ifndef DAGSFM_AMD_CSRC_BA_PROJECT_H_
 #define DAGSFM_AMD_CSRC_BA_PROJECT_H_
 
@@ -214,6 +217,61 @@ __device__ inline void ba_world_to_image(int id, const T* p, T u, T v, T* x, T* 
   ba_distortion<T>(id, p + 4, u, v, &du, &dv);
   *x = p[0] * (u + du) + p[2];
   *y = p[1] * (v + dv) + p[3];
+}
+
+// ceres::UnitQuaternionRotatePoint (rotation.h)
+__device__ inline void ba_rotate(const double* q, const double* X, double* out) {
+  const double t2 = q[0] * q[1], t3 = q[0] * q[2], t4 = q[0] * q[3], t5 = -q[1] * q[1], t6 = q[1] * q[2], t7 = q[1] * q[3];
+  const double t8 = -q[2] * q[2], t9 = q[2] * q[3], t1 = -q[3] * q[3];
+  out[0] = 2.0 * ((t8 + t1) * X[0] + (t6 - t4) * X[1] + (t3 + t7) * X[2]) + X[0];
+  out[1] = 2.0 * ((t4 + t6) * X[0] + (t5 + t1) * X[1] + (t9 - t2) * X[2]) + X[1];
+  out[2] = 2.0 * ((t7 - t3) * X[0] + (t2 + t9) * X[1] + (t5 + t8) * X[2]) + X[2];
+}
+// its matrix, row-major.  Not ba_rotate of the unit vectors: that adds the products with the two zero components first and
+// rounds differently; local_bundle.hip builds its R that way and keeps doing so.
+__device__ inline void ba_quat_R(const double* q, double* R) {
+  const double t2 = q[0] * q[1], t3 = q[0] * q[2], t4 = q[0] * q[3], t5 = -q[1] * q[1], t6 = q[1] * q[2], t7 = q[1] * q[3];
+  const double t8 = -q[2] * q[2], t9 = q[2] * q[3], t1 = -q[3] * q[3];
+  R[0] = 2.0 * (t8 + t1) + 1.0; R[1] = 2.0 * (t6 - t4);       R[2] = 2.0 * (t3 + t7);
+  R[3] = 2.0 * (t4 + t6);       R[4] = 2.0 * (t5 + t1) + 1.0; R[5] = 2.0 * (t9 - t2);
+  R[6] = 2.0 * (t7 - t3);       R[7] = 2.0 * (t2 + t9);       R[8] = 2.0 * (t5 + t8) + 1.0;
+}
+// QuaternionParameterization::Plus: [cos|d|, sin|d| d / |d|] (x) x
+__device__ inline void ba_quat_plus(const double* x, const double* d, double* out) {
+  const double n = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  if (!(n > 0.0)) {
+    for (int i = 0; i < 4; ++i) out[i] = x[i];
+    return;
+  }
+  const double s = sin(n) / n;
+  const double a0 = cos(n), a1 = s * d[0], a2 = s * d[1], a3 = s * d[2];
+  out[0] = a0 * x[0] - a1 * x[1] - a2 * x[2] - a3 * x[3];
+  out[1] = a0 * x[1] + a1 * x[0] + a2 * x[3] - a3 * x[2];
+  out[2] = a0 * x[2] - a1 * x[3] + a2 * x[0] + a3 * x[1];
+  out[3] = a0 * x[3] + a1 * x[2] - a2 * x[1] + a3 * x[0];
+}
+
+// WorldToImage with its derivatives: slots 0 and 1 are u and v, slot 2 + j is camera parameter j (np of them).  The value is
+// the double instantiation's.
+__device__ inline void ba_project_dual(int model, int np, const double* prm, double u, double v, BaDual* x, BaDual* y) {
+  BaDual pd[BA_ND - 2];
+  for (int j = 0; j < BA_ND - 2; ++j) pd[j] = j < np ? bd_var(prm[j], 2 + j) : bd_const(0.0);
+  ba_world_to_image<BaDual>(model, pd, bd_var(u, 0), bd_var(v, 1), x, y);
+}
+
+// From the pixel (x, y) of ba_project_dual at (u, v) = (P[0], P[1]) / P[2], P = w + tvec, w the rotated point:
+// JP = d(x, y) / dP, and Dq = dP / d(delta) = -2 [w]x, the tangent of QuaternionParameterization, row-major.
+__device__ inline void ba_pixel_jacobian(const BaDual& x, const BaDual& y, double P0, double P1, double P2, const double* w,
+                                         double JP[2][3], double* Dq) {
+  const double iz = 1.0 / P2;
+  const double duP[3] = {iz, 0.0, -P0 * iz * iz}, dvP[3] = {0.0, iz, -P1 * iz * iz};
+  for (int a = 0; a < 3; ++a) {
+    JP[0][a] = x.d[0] * duP[a] + x.d[1] * dvP[a];
+    JP[1][a] = y.d[0] * duP[a] + y.d[1] * dvP[a];
+  }
+  Dq[0] = 0.0;         Dq[1] = 2.0 * w[2];  Dq[2] = -2.0 * w[1];
+  Dq[3] = -2.0 * w[2]; Dq[4] = 0.0;         Dq[5] = 2.0 * w[0];
+  Dq[6] = 2.0 * w[1];  Dq[7] = -2.0 * w[0]; Dq[8] = 0.0;
 }
 
 #endif  // DAGSFM_AMD_CSRC_BA_PROJECT_H_

@@ -2,8 +2,9 @@
 //   DistributedMapperController::AdjustGlobalBundle  src/controllers/distributed_mapper_controller.cpp:836-931
 //   BundleAdjuster (ITERATIVE_SCHUR + SCHUR_JACOBI)    src/optim/bundle_adjustment.cc:273-284, 330-456
 //   BundleAdjustmentCostFunction                      src/base/cost_functions.h:45-85
-// Levenberg-Marquardt with Jacobi scaling; each step solves the Schur complement over the variable points with a CG
-// preconditioned by the exact diagonal blocks of S, S applied implicitly from the stored per-observation Jacobian blocks.
+// Levenberg-Marquardt with Jacobi scaling, the step rules of trust_region.h; each step solves the Schur complement over the
+// variable points with a CG preconditioned by the exact diagonal blocks of S, S applied implicitly from the stored
+// per-observation Jacobian blocks.
 // Canonical order: points by id, the images with observations by content, their cameras by first use (the host relabels
 // both; the rest stays off the device), observations image-major by (image, point rank), each track by (camera, image).  Every sum
 // walks a segment of that order (one thread per point over its track, one 64-lane block per image over its observations with
@@ -28,6 +29,7 @@
 #include "ba_project.h"
 #include "block_reduce.h"
 #include "ctx.h"
+#include "trust_region.h"
 
 namespace {
 
@@ -37,23 +39,23 @@ constexpr int BA_JS = 48;   // doubles per observation: r[2] E[2x3] Fq[2x3] Ft[2
 constexpr int J_R = 0, J_E = 2, J_Q = 8, J_T = 14, J_C = 20;
 constexpr int BA_KMAX = 12;
 constexpr int BA_ICAM = 12 + 78;  // per image camera partial row: a k-vector and a packed k x k lower triangle
-constexpr double kEta = 0.1, kMinRelDecrease = 1e-3, kMinDiag = 1e-6, kMaxDiag = 1e32, kMaxRadius = 1e16, kMinRadius = 1e-32;
+constexpr double kEta = 0.1;
+static_assert(TR_CONVERGENCE == DSM_BA_CONVERGENCE && TR_NO_CONVERGENCE == DSM_BA_NO_CONVERGENCE && TR_FAILURE == DSM_BA_FAILURE,
+              "trust_region.h's termination codes are the public ones");
 
-struct BaCtl {
+struct BaCtl : TrState {  // the LM loop's state (trust_region.h), then this solver's own
   // the running CG solve
-  int cg_stop, cg_fail, cg_iters, pad0;
+  int cg_stop, cg_fail, cg_iters, pad1;  // pad1: the latch of k_ba_finalize
   double rho, beta, alpha, Q0;
-  // the LM loop
-  double cost, reproj, cand_cost, cand_reproj, mcc, step2, x2, radius, dec, gnorm, rho_lm;
-  int iter, n_succ, n_invalid, n_invalid_total, accepted, done, term, pad1;
   unsigned long long cg_total;
-  double m_rho, m_cg, m_grad;
+  double reproj, cand_cost, cand_reproj, mcc;
+  double m_cg;
 };
 
 struct BaDev {
   uint32_t n_obs, n_pts, n_img, n_cam, nf;
-  int max_cg, max_iter, max_invalid;
-  double gtol, ftol, ptol;
+  int max_cg;
+  TrOptions tr;
   const uint32_t *o_img, *o_pt, *o_run, *img_off, *trk_off, *trk, *cam_img_off, *cam_imgs, *img_cam, *cam_poff, *cam_foff, *cam_moff;
   const double* o_xy;
   const uint8_t *img_cpose, *img_mask, *pt_var;
@@ -68,12 +70,6 @@ struct BaDev {
 };
 
 __host__ __device__ inline int tri(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
-
-__device__ inline double margin(double a, double thr) {
-  if (!isfinite(a)) return DBL_MAX;
-  const double den = fmax(fabs(a), fabs(thr));
-  return den > 0.0 ? fabs(a - thr) / den : 0.0;
-}
 
 // ---------------------------------------------------------------- small dense algebra
 __device__ inline bool inv3_sym(const double* A, double* Ai) {  // packed lower triangle in, full 3 x 3 out
@@ -111,36 +107,6 @@ __device__ inline void inv_spd(const double* A, int k, double* L, double* out) {
   }
 }
 
-// ceres::UnitQuaternionRotatePoint (rotation.h), its matrix
-__device__ inline void quat_R(const double* q, double* R) {
-  const double t2 = q[0] * q[1], t3 = q[0] * q[2], t4 = q[0] * q[3], t5 = -q[1] * q[1], t6 = q[1] * q[2], t7 = q[1] * q[3];
-  const double t8 = -q[2] * q[2], t9 = q[2] * q[3], t1 = -q[3] * q[3];
-  R[0] = 2.0 * (t8 + t1) + 1.0; R[1] = 2.0 * (t6 - t4);       R[2] = 2.0 * (t3 + t7);
-  R[3] = 2.0 * (t4 + t6);       R[4] = 2.0 * (t5 + t1) + 1.0; R[5] = 2.0 * (t9 - t2);
-  R[6] = 2.0 * (t7 - t3);       R[7] = 2.0 * (t2 + t9);       R[8] = 2.0 * (t5 + t8) + 1.0;
-}
-__device__ inline void rotate(const double* q, const double* X, double* out) {
-  const double t2 = q[0] * q[1], t3 = q[0] * q[2], t4 = q[0] * q[3], t5 = -q[1] * q[1], t6 = q[1] * q[2], t7 = q[1] * q[3];
-  const double t8 = -q[2] * q[2], t9 = q[2] * q[3], t1 = -q[3] * q[3];
-  out[0] = 2.0 * ((t8 + t1) * X[0] + (t6 - t4) * X[1] + (t3 + t7) * X[2]) + X[0];
-  out[1] = 2.0 * ((t4 + t6) * X[0] + (t5 + t1) * X[1] + (t9 - t2) * X[2]) + X[1];
-  out[2] = 2.0 * ((t7 - t3) * X[0] + (t2 + t9) * X[1] + (t5 + t8) * X[2]) + X[2];
-}
-// QuaternionParameterization::Plus: [cos|d|, sin|d| d / |d|] (x) x
-__device__ inline void quat_plus(const double* x, const double* d, double* out) {
-  const double n = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-  if (!(n > 0.0)) {
-    for (int i = 0; i < 4; ++i) out[i] = x[i];
-    return;
-  }
-  const double s = sin(n) / n;
-  const double a0 = cos(n), a1 = s * d[0], a2 = s * d[1], a3 = s * d[2];
-  out[0] = a0 * x[0] - a1 * x[1] - a2 * x[2] - a3 * x[3];
-  out[1] = a0 * x[1] + a1 * x[0] + a2 * x[3] - a3 * x[2];
-  out[2] = a0 * x[2] - a1 * x[3] + a2 * x[0] + a3 * x[1];
-  out[3] = a0 * x[3] + a1 * x[2] - a2 * x[1] + a3 * x[0];
-}
-
 __device__ inline bool cg_gated(const BaCtl* c, int k) { return c->done || k >= c->cg_stop; }
 
 // ---------------------------------------------------------------- residuals and Jacobians
@@ -161,7 +127,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_eval(BaDev d, int mode) {
     const double* prm = (cand ? d.cprm : d.prm) + d.cam_poff[cam];
     const int model = d.cam_model[cam], np = d.cam_np[cam];
     double w[3];
-    rotate(q, X, w);
+    ba_rotate(q, X, w);
     const double P0 = w[0] + tv[0], P1 = w[1] + tv[1], P2 = w[2] + tv[2];
     const double u = P0 / P2, v = P1 / P2;
     double r0, r1;
@@ -171,29 +137,19 @@ __global__ void __launch_bounds__(BA_B) k_ba_eval(BaDev d, int mode) {
       r0 = xx - d.o_xy[2 * (size_t)o];
       r1 = yy - d.o_xy[2 * (size_t)o + 1];
     } else {
-      BaDual pd[BA_KMAX];
-      for (int j = 0; j < BA_KMAX; ++j) pd[j] = j < np ? bd_var(prm[j], 2 + j) : bd_const(0.0);
       BaDual xx, yy;
-      ba_world_to_image<BaDual>(model, pd, bd_var(u, 0), bd_var(v, 1), &xx, &yy);
+      ba_project_dual(model, np, prm, u, v, &xx, &yy);
       r0 = xx.v - d.o_xy[2 * (size_t)o];
       r1 = yy.v - d.o_xy[2 * (size_t)o + 1];
       double* Jo = d.J + (size_t)BA_JS * o;
       Jo[J_R] = r0;
       Jo[J_R + 1] = r1;
-      // d(u, v) / dP
-      const double iz = 1.0 / P2;
-      const double duP[3] = {iz, 0.0, -P0 * iz * iz}, dvP[3] = {0.0, iz, -P1 * iz * iz};
-      double JP[2][3];
-      for (int a = 0; a < 3; ++a) {
-        JP[0][a] = xx.d[0] * duP[a] + xx.d[1] * dvP[a];
-        JP[1][a] = yy.d[0] * duP[a] + yy.d[1] * dvP[a];
-      }
-      double R[9];
-      quat_R(q, R);
+      // dP/dX = R; dP/d(delta) = Dq
+      double JP[2][3], Dq[9], R[9];
+      ba_pixel_jacobian(xx, yy, P0, P1, P2, w, JP, Dq);
+      ba_quat_R(q, R);
       const bool cpose = d.img_cpose[i];
       const uint8_t mask = d.img_mask[i];
-      // dP/dX = R; dP/d(delta) = -2 [w]x (the tangent of QuaternionParameterization, rotation by 2 |delta|)
-      const double Dq[9] = {0.0, 2.0 * w[2], -2.0 * w[1], -2.0 * w[2], 0.0, 2.0 * w[0], 2.0 * w[1], -2.0 * w[0], 0.0};
       for (int row = 0; row < 2; ++row)
         for (int a = 0; a < 3; ++a) {
           const double e = d.pt_var[pt] ? JP[row][0] * R[a] + JP[row][1] * R[3 + a] + JP[row][2] * R[6 + a] : 0.0;
@@ -301,7 +257,7 @@ __global__ void __launch_bounds__(BA_W) k_ba_grad_img(BaDev d, int gate, uint32_
     const double* q = d.q + 4 * (size_t)i;
     const double mg[3] = {-sh[0], -sh[BA_W], -sh[2 * BA_W]};
     double qp[4];
-    quat_plus(q, mg, qp);
+    ba_quat_plus(q, mg, qp);
     for (int j = 0; j < 4; ++j) gm = fmax(gm, fabs(q[j] - qp[j]));
     for (int j = 0; j < 3; ++j) {
       const double x = d.t[3 * (size_t)i + j];
@@ -352,7 +308,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_scale_cols(BaDev d, int first, int 
   const double cn = isE ? d.cne[j] : d.cnf[j];
   if (first) s[j] = 1.0 / (1.0 + sqrt(cn));
   g[j] = s[j] * g[j];
-  (isE ? d.De : d.Df)[j] = fmin(fmax(s[j] * s[j] * cn, kMinDiag), kMaxDiag);
+  (isE ? d.De : d.Df)[j] = fmin(fmax(s[j] * s[j] * cn, kLmMinDiag), kLmMaxDiag);
 }
 
 __global__ void __launch_bounds__(BA_B) k_ba_scale_J(BaDev d, int gate) {
@@ -740,7 +696,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_cg_fin_q(BaDev d, uint32_t nblk, in
   const double Q1 = -sum_partials<BA_B>(d.Pq, nblk, sh);
   if (threadIdx.x) return;
   const double zeta = k * (Q1 - c->Q0) / Q1;
-  c->m_cg = fmin(c->m_cg, margin(zeta, kEta));
+  tr_min(&c->m_cg, tr_margin(zeta, kEta));
   if (zeta < kEta || k >= d.max_cg) {
     c->cg_stop = k + 1;
     c->cg_iters = k;
@@ -806,7 +762,7 @@ __global__ void __launch_bounds__(BA_B) k_ba_cand_f(BaDev d) {
         dq[m] = d.sf[6 * (size_t)e + m] * d.x[6 * (size_t)e + m];
         s2 += dq[m] * dq[m];
       }
-      quat_plus(q, dq, cq);
+      ba_quat_plus(q, dq, cq);
       for (int m = 0; m < 4; ++m) x2 += q[m] * q[m];
       const uint8_t mask = d.img_mask[e];
       for (int m = 0; m < 3; ++m) {
@@ -872,53 +828,9 @@ __global__ void __launch_bounds__(BA_B) k_ba_decide(BaDev d, uint32_t nb_obs, ui
   const double s2 = sum_partials<BA_B>(d.Pe, nb_pts, sh) + sum_partials<BA_B>(d.Pd, nb_f, sh);
   const double x2 = sum_partials<BA_B>(d.Pe + nb_pts, nb_pts, sh) + sum_partials<BA_B>(d.Pd + nb_f, nb_f, sh);
   if (threadIdx.x) return;
-  c->iter += 1;
   c->mcc = mcc;
   c->cg_total += (unsigned long long)c->cg_iters;
-  c->accepted = 0;
-  c->rho_lm = NAN;
-  const bool valid = c->cg_fail == 0 && isfinite(mcc) && mcc > 0.0 && isfinite(s2) && isfinite(c->cand_cost);
-  if (!valid) {
-    c->n_invalid += 1;
-    c->n_invalid_total += 1;
-    if (c->n_invalid >= d.max_invalid) {
-      c->term = DSM_BA_FAILURE;
-      c->done = 1;
-    } else {
-      c->radius /= c->dec;
-      c->dec *= 2.0;
-    }
-    return;
-  }
-  c->n_invalid = 0;
-  const double step_norm = sqrt(s2), x_norm = sqrt(x2);
-  if (step_norm <= d.ptol * (x_norm + d.ptol)) {
-    c->term = DSM_BA_CONVERGENCE;
-    c->done = 1;
-    return;
-  }
-  if (fabs(c->cost - c->cand_cost) <= d.ftol * c->cost) {
-    c->term = DSM_BA_CONVERGENCE;
-    c->done = 1;
-    return;
-  }
-  const double rho = (c->cost - c->cand_cost) / mcc;
-  c->rho_lm = rho;
-  // the distance of the acceptance test from flipping, in cost: |(cost - candidate) - 1e-3 model_cost_change| / cost (near
-  // the optimum the cost change itself is rounding, and so is rho)
-  c->m_rho = fmin(c->m_rho, fabs((c->cost - c->cand_cost) - kMinRelDecrease * mcc) / fmax(c->cost, DBL_MIN));
-  if (rho > kMinRelDecrease) {
-    c->accepted = 1;
-    c->n_succ += 1;
-    c->cost = c->cand_cost;
-    c->reproj = c->cand_reproj;
-    const double tmp = 2.0 * rho - 1.0;
-    c->radius = fmin(kMaxRadius, c->radius / fmax(1.0 / 3.0, 1.0 - tmp * tmp * tmp));
-    c->dec = 2.0;
-  } else {
-    c->radius /= c->dec;
-    c->dec *= 2.0;
-  }
+  if (tr_decide(c, d.tr, c->cg_fail == 0, c->cand_cost, mcc, s2, x2) == TR_ACCEPTED) c->reproj = c->cand_reproj;
 }
 __global__ void __launch_bounds__(BA_B) k_ba_commit(BaDev d) {
   if (d.ctl->done || !d.ctl->accepted) return;
@@ -946,27 +858,12 @@ __global__ void __launch_bounds__(BA_B) k_ba_finalize(BaDev d, uint32_t n_gparts
   if (fresh) gm = max_partials<BA_B>(d.Pg, n_gparts, sh);
   if (threadIdx.x) return;
   if (fresh) c->gnorm = gm;
-  if (!done) {
-    if (c->iter >= d.max_iter) {
-      c->term = DSM_BA_NO_CONVERGENCE;
-      c->done = 1;
-    } else if (fresh) {
-      c->m_grad = fmin(c->m_grad, margin(c->gnorm, d.gtol));
-      if (c->gnorm <= d.gtol) {
-        c->term = DSM_BA_CONVERGENCE;
-        c->done = 1;
-      }
-    }
-    if (!c->done && c->radius < kMinRadius) {
-      c->term = DSM_BA_CONVERGENCE;
-      c->done = 1;
-    }
-  }
+  tr_end_iteration(c, d.tr, fresh);
   if (d.trace) {
     double* row = d.trace + DSM_BA_TRACE_COLUMNS * (size_t)c->iter;
     row[0] = c->cost;
     row[1] = c->radius;
-    row[2] = first ? NAN : c->rho_lm;
+    row[2] = first ? NAN : c->last_rho;
     row[3] = first ? 0.0 : (double)c->cg_iters;
     row[4] = first ? 1.0 : (double)c->accepted;
     row[5] = c->gnorm;
@@ -1323,16 +1220,16 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
   if (trace) alloc(b_trace, 8 * (size_t)DSM_BA_TRACE_COLUMNS * ((size_t)max_iter + 1));
   for (auto& e : ev) HIPTRY(hipEventCreate(&e.e));
   BaCtl init{};
-  init.radius = 1e4;
-  init.dec = 2.0;
-  init.m_rho = init.m_cg = init.m_grad = DBL_MAX;
-  init.rho_lm = NAN;
+  tr_init(&init, kTrInitialRadius);
+  init.m_cg = INFINITY;
   up(b_ctl, &init, sizeof(BaCtl));
 
   BaDev d{};
   d.n_obs = n_obs; d.n_pts = P; d.n_img = N; d.n_cam = C; d.nf = nf;
-  d.max_cg = o.max_linear_solver_iterations; d.max_iter = max_iter; d.max_invalid = o.max_num_consecutive_invalid_steps;
-  d.gtol = o.gradient_tolerance; d.ftol = o.function_tolerance; d.ptol = o.parameter_tolerance;
+  d.max_cg = o.max_linear_solver_iterations;
+  d.tr = tr_ceres_defaults();
+  d.tr.max_iterations = max_iter; d.tr.max_consecutive_invalid_steps = o.max_num_consecutive_invalid_steps;
+  d.tr.gtol = o.gradient_tolerance; d.tr.ftol = o.function_tolerance; d.tr.ptol = o.parameter_tolerance;
   d.o_img = b_oimg.as<uint32_t>(); d.o_pt = b_opt.as<uint32_t>(); d.o_run = b_orun.as<uint32_t>(); d.img_off = b_imgoff.as<uint32_t>();
   d.trk_off = b_trkoff.as<uint32_t>(); d.trk = b_trk.as<uint32_t>(); d.cam_img_off = b_camimgoff.as<uint32_t>();
   d.cam_imgs = b_camimgs.as<uint32_t>(); d.img_cam = b_imgcam.as<uint32_t>(); d.cam_poff = b_campoff.as<uint32_t>();
@@ -1473,9 +1370,10 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
         rep.final_cost = h.cost;
         rep.initial_mean_reprojection_error = initial_reproj;
         rep.final_mean_reprojection_error = h.reproj;
-        rep.min_rho_margin = h.m_rho;
-        rep.min_cg_margin = h.m_cg;
-        rep.min_gradient_margin = h.m_grad;
+        // the shared state starts its margins at infinity; this report's largest value is DBL_MAX
+        rep.min_rho_margin = std::min(h.m_accept, DBL_MAX);
+        rep.min_cg_margin = std::min(h.m_cg, DBL_MAX);
+        rep.min_gradient_margin = std::min(h.m_grad, DBL_MAX);
         rep.setup_ms = setup_ms;
         rep.jacobian_ms = ms_jac;
         rep.cg_ms = ms_cg;

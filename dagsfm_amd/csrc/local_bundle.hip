@@ -1,9 +1,9 @@
 // local_bundle.hip -- batched local bundle adjustment: IncrementalMapper::AdjustLocalBundle's BundleAdjuster::Solve()
 // (src/sfm/incremental_mapper.cc:562-656, src/optim/bundle_adjustment.cc:258-526) with LocalBundleAdjustment()'s options, for a
-// batch of independent problems.  The residual, the parameterisations and the trust-region rulings are
-// DESIGN.md 12's; new here are the robust loss (Ceres' Corrector, first branch), cameras constant per camera, and the DENSE_SCHUR
-// branch: the points are eliminated, the reduced camera system S is formed explicitly in LDS and factored by an unpivoted
-// Cholesky.
+// batch of independent problems.  The residual, the parameterisations (ba_project.h) and the trust-region
+// rulings (trust_region.h) are DESIGN.md 12's; new here are the robust loss (Ceres' Corrector, first branch), cameras
+// constant per camera, and the DENSE_SCHUR branch: the points are eliminated, the reduced camera system S is formed
+// explicitly in LDS and factored by an unpivoted Cholesky.
 //
 // One kernel, k_lb_adjust: a workgroup of 256 threads (four waves) per problem runs the whole Levenberg-Marquardt loop; no host
 // round trip, no floating-point atomics.  Every sum has an order that is a function of the problem alone:
@@ -31,6 +31,7 @@
 
 #include "ba_project.h"
 #include "ctx.h"
+#include "trust_region.h"
 
 namespace {
 
@@ -42,7 +43,6 @@ constexpr int LB_PT = 24;     // workspace doubles per point: E'E 6, E'r 3, scal
 constexpr int LB_RMAX = DSM_LOCAL_BUNDLE_MAX_REDUCED_DIM;
 constexpr int LB_MARGINS = DSM_LOCAL_BUNDLE_MARGINS;
 constexpr int LB_TRACE = DSM_LOCAL_BUNDLE_TRACE_COLUMNS;
-constexpr double kMinRelDecrease = 1e-3, kMinDiag = 1e-6, kMaxDiag = 1e32, kMaxRadius = 1e16, kMinRadius = 1e-32;
 
 // one problem in canonical order; the o* fields are offsets into the batch arrays
 struct LbProblem {
@@ -52,8 +52,9 @@ struct LbProblem {
 
 struct LbParams {
   uint32_t B;
-  int max_iter, max_invalid, loss, rs;  // rs: the LDS stride (the largest R of the batch, rounded up to even)
-  double gtol, ftol, ptol, b, c;
+  int loss, rs;  // rs: the LDS stride (the largest R of the batch, rounded up to even)
+  TrOptions tr;
+  double b, c;
   const LbProblem* prob;
   // the batch arrays; the kernel moves every pointer to its problem's first element (LbView)
   const uint32_t* img_cam;
@@ -86,13 +87,13 @@ struct LbParams {
   double* G;                // R (R + 1) / 2 per problem, packed by columns: (a, b), a <= b, at b (b + 1) / 2 + a
   dsm_local_bundle_result* res;
   double* margins;  // [B][LB_MARGINS]
-  double* trace;    // [B][max_iter + 1][LB_TRACE]
+  double* trace;    // [B][tr.max_iterations + 1][LB_TRACE]
 };
 
-struct LbCtrl {
-  double cost, cand_cost, err, cand_err, gnorm, radius, dec, mcc, s2, x2, rho;
-  double mg[LB_MARGINS];
-  int iter, n_succ, n_invalid, n_invalid_total, term, done, accepted, valid, ok;
+struct LbCtrl : TrState {
+  double cand_cost, err, cand_err, mcc, s2, x2;
+  double m_pivot, m_point;  // the smallest pivot of S, and of a point's block, relative to its diagonal entry
+  int valid, ok;
 };
 
 // one problem as the device functions see it: the batch pointers moved to the problem, its sizes, the LDS arrays
@@ -108,42 +109,13 @@ struct LbView : LbParams {
   int* colinfo;  // owner << 6 | slot << 1 | kind (0: the image's pose, 1: the camera)
 };
 
-__device__ inline double lb_margin(double a, double thr) {
-  if (!isfinite(a)) return INFINITY;
-  const double den = fmax(fabs(a), fabs(thr));
-  return den > 0.0 ? fabs(a - thr) / den : 0.0;
-}
 __device__ inline int lb_idx(int a, int b) { return b * (b + 1) / 2 + a; }  // a <= b
 
-// the one instantiation of the projection this file carries (value and derivatives; the value is the double path's)
+// one copy each of the projection's dual instantiation and of Plus in this file's code (the library's size cap)
 __device__ __noinline__ void lb_project(int model, int np, const double* prm, double u, double v, BaDual* x, BaDual* y) {
-  BaDual pd[12];
-  for (int j = 0; j < 12; ++j) pd[j] = j < np ? bd_var(prm[j], 2 + j) : bd_const(0.0);
-  ba_world_to_image<BaDual>(model, pd, bd_var(u, 0), bd_var(v, 1), x, y);
+  ba_project_dual(model, np, prm, u, v, x, y);
 }
-
-// ceres::UnitQuaternionRotatePoint
-__device__ inline void lb_rotate(const double* q, const double* X, double* out) {
-  const double t2 = q[0] * q[1], t3 = q[0] * q[2], t4 = q[0] * q[3], t5 = -q[1] * q[1], t6 = q[1] * q[2], t7 = q[1] * q[3];
-  const double t8 = -q[2] * q[2], t9 = q[2] * q[3], t1 = -q[3] * q[3];
-  out[0] = 2.0 * ((t8 + t1) * X[0] + (t6 - t4) * X[1] + (t3 + t7) * X[2]) + X[0];
-  out[1] = 2.0 * ((t4 + t6) * X[0] + (t5 + t1) * X[1] + (t9 - t2) * X[2]) + X[1];
-  out[2] = 2.0 * ((t7 - t3) * X[0] + (t2 + t9) * X[1] + (t5 + t8) * X[2]) + X[2];
-}
-// QuaternionParameterization::Plus: [cos|d|, sin|d| d / |d|] (x) x
-__device__ __noinline__ void lb_quat_plus(const double* x, const double* d, double* out) {
-  const double n = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-  if (!(n > 0.0)) {
-    for (int i = 0; i < 4; ++i) out[i] = x[i];
-    return;
-  }
-  const double s = sin(n) / n;
-  const double a0 = cos(n), a1 = s * d[0], a2 = s * d[1], a3 = s * d[2];
-  out[0] = a0 * x[0] - a1 * x[1] - a2 * x[2] - a3 * x[3];
-  out[1] = a0 * x[1] + a1 * x[0] + a2 * x[3] - a3 * x[2];
-  out[2] = a0 * x[2] - a1 * x[3] + a2 * x[0] + a3 * x[1];
-  out[3] = a0 * x[3] + a1 * x[2] - a2 * x[1] + a3 * x[0];
-}
+__device__ __noinline__ void lb_quat_plus(const double* x, const double* d, double* out) { ba_quat_plus(x, d, out); }
 
 // the workgroup's fixed-order sum / max / min (every thread returns it).  op 0: sum, 1: max, 2: min
 __device__ __noinline__ double lb_reduce(double v, double* red, int tid, int op) {
@@ -188,7 +160,7 @@ __device__ __noinline__ void lb_eval(const LbView& v, bool cand, bool jac, int t
     for (int a = 0; a < 4; ++a) q[a] = Q[4 * (size_t)i + a];
     for (int a = 0; a < 3; ++a) X[a] = XX[3 * (size_t)p + a];
     for (int a = 0; a < 12; ++a) prm[a] = PR[12 * (size_t)c + a];
-    lb_rotate(q, X, w);
+    ba_rotate(q, X, w);
     const double P0 = w[0] + T[3 * (size_t)i], P1 = w[1] + T[3 * (size_t)i + 1], P2 = w[2] + T[3 * (size_t)i + 2];
     const double pu = P0 / P2, pv = P1 / P2;
     BaDual xx, yy;
@@ -211,20 +183,14 @@ __device__ __noinline__ void lb_eval(const LbView& v, bool cand, bool jac, int t
     err += sqrt(s);
     if (!jac) continue;
     const double sq = v.loss == DSM_LOSS_TRIVIAL ? 1.0 : sqrt(rho1);
-    const double iz = 1.0 / P2;
-    const double duP[3] = {iz, 0.0, -P0 * iz * iz}, dvP[3] = {0.0, iz, -P1 * iz * iz};
-    double JP[2][3];
-    for (int a = 0; a < 3; ++a) {
-      JP[0][a] = xx.d[0] * duP[a] + xx.d[1] * dvP[a];
-      JP[1][a] = yy.d[0] * duP[a] + yy.d[1] * dvP[a];
-    }
-    // dP / d(delta) = -2 [w]x, the tangent of QuaternionParameterization; dP / dX = R, column a = R e_a
-    const double Dq[9] = {0.0, 2.0 * w[2], -2.0 * w[1], -2.0 * w[2], 0.0, 2.0 * w[0], 2.0 * w[1], -2.0 * w[0], 0.0};
+    double JP[2][3], Dq[9];
+    ba_pixel_jacobian(xx, yy, P0, P1, P2, w, JP, Dq);
+    // dP / dX = R, column a = R e_a (not ba_quat_R: the rotated unit vectors round differently, and these are the bytes)
     double Rm[9];
     for (int a = 0; a < 3; ++a) {
       const double e[3] = {a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0, a == 2 ? 1.0 : 0.0};
       double col[3];
-      lb_rotate(q, e, col);
+      ba_rotate(q, e, col);
       Rm[a] = col[0];
       Rm[3 + a] = col[1];
       Rm[6 + a] = col[2];
@@ -281,7 +247,7 @@ __device__ __noinline__ void lb_normal(const LbView& v, LbCtrl* ct, int tid, boo
     for (int c = 0; c < 3; ++c) {
       if (first) w[(9 + c) * NP] = 1.0 / (1.0 + sqrt(cn[c]));
       const double se = w[(9 + c) * NP];
-      w[(12 + c) * NP] = fmin(fmax((se * se) * cn[c], kMinDiag), kMaxDiag);
+      w[(12 + c) * NP] = fmin(fmax((se * se) * cn[c], kLmMinDiag), kLmMaxDiag);
     }
   }
   // F'F entry (a, b): the observations that carry both columns, in canonical order -- those of a's image when a is a pose
@@ -325,7 +291,7 @@ __device__ __noinline__ void lb_normal(const LbView& v, LbCtrl* ct, int tid, boo
     const double cn = v.G[lb_idx(a, a)];
     if (first) v.s[a] = 1.0 / (1.0 + sqrt(cn));
     v.gs[a] = v.s[a] * v.g[a];
-    v.D[a] = fmin(fmax((v.s[a] * v.s[a]) * cn, kMinDiag), kMaxDiag);
+    v.D[a] = fmin(fmax((v.s[a] * v.s[a]) * cn, kLmMinDiag), kLmMaxDiag);
   }
   // |x - Plus(x, -g)|inf over the variable blocks, g unscaled
   double m = 0.0;
@@ -417,7 +383,7 @@ __device__ __noinline__ void lb_step(const LbView& v, LbCtrl* ct, int tid) {
     ct->valid = 0;
     ct->mcc = 0.0;
     ct->ok = anybad == 0.0;
-    if (pm < ct->mg[3]) ct->mg[3] = pm;
+    tr_min(&ct->m_point, pm);
   }
   __syncthreads();
   if (anybad != 0.0) return;
@@ -505,7 +471,7 @@ __device__ __noinline__ void lb_step(const LbView& v, LbCtrl* ct, int tid) {
     const bool okp = pv > 0.0 && isfinite(pv);
     if (tid == 0) {
       const double mg = isfinite(pv) && v.diag[j] > 0.0 ? fabs(pv) / v.diag[j] : 0.0;
-      if (mg < ct->mg[2]) ct->mg[2] = mg;
+      tr_min(&ct->m_pivot, mg);
       if (!okp) ct->ok = 0;
     }
     if (!okp) break;  // uniform: every thread read the same pivot
@@ -641,83 +607,24 @@ __device__ __noinline__ void lb_step(const LbView& v, LbCtrl* ct, int tid) {
     ct->mcc = -mc;
     ct->s2 = s2;
     ct->x2 = x2;
-    ct->valid = isfinite(ct->mcc) && ct->mcc > 0.0 && isfinite(s2);
+    ct->valid = tr_step_usable(ct->mcc, s2);
   }
   __syncthreads();
 }
 
-// thread 0: the decision of one iteration
-__device__ __noinline__ void lb_decide(LbCtrl* ct, const LbParams& p) {
-  ct->iter += 1;
-  ct->accepted = 0;
-  ct->rho = NAN;
-  if (!(ct->valid && isfinite(ct->cand_cost))) {
-    ct->n_invalid += 1;
-    ct->n_invalid_total += 1;
-    if (ct->n_invalid >= p.max_invalid) {
-      ct->term = DSM_BA_FAILURE;
-      ct->done = 1;
-    } else {
-      ct->radius /= ct->dec;
-      ct->dec *= 2.0;
-    }
-    return;
-  }
-  ct->n_invalid = 0;
-  if (sqrt(ct->s2) <= p.ptol * (sqrt(ct->x2) + p.ptol)) {
-    ct->term = DSM_BA_CONVERGENCE;
-    ct->done = 1;
-    return;
-  }
-  const double change = ct->cost - ct->cand_cost;
-  if (fabs(change) <= p.ftol * ct->cost) {
-    ct->term = DSM_BA_CONVERGENCE;
-    ct->done = 1;
-    return;
-  }
-  const double rho = change / ct->mcc;
-  ct->rho = rho;
-  const double mg = fabs(change - kMinRelDecrease * ct->mcc) / fmax(ct->cost, DBL_MIN);
-  if (mg < ct->mg[0]) ct->mg[0] = mg;
-  if (rho > kMinRelDecrease) {
-    ct->accepted = 1;
-    ct->n_succ += 1;
-    ct->cost = ct->cand_cost;
-    ct->err = ct->cand_err;
-    const double tmp = 2.0 * rho - 1.0;
-    ct->radius = fmin(kMaxRadius, ct->radius / fmax(1.0 / 3.0, 1.0 - tmp * tmp * tmp));
-    ct->dec = 2.0;
-    return;
-  }
-  ct->radius /= ct->dec;
-  ct->dec *= 2.0;
+// thread 0: the decision of one iteration (trust_region.h); the state itself is committed by the whole group
+__device__ __noinline__ void lb_decide(LbCtrl* ct, const TrOptions& o) {
+  if (tr_decide(ct, o, ct->valid != 0, ct->cand_cost, ct->mcc, ct->s2, ct->x2) == TR_ACCEPTED) ct->err = ct->cand_err;
 }
 
-// thread 0: the checks that end an iteration: the cap, the gradient (after an accepted step or at iteration 0), the radius;
-// then the trace row
-__device__ inline void lb_finalize(LbCtrl* ct, const LbParams& p, bool fresh, double* trace) {
-  if (!ct->done) {
-    if (ct->iter >= p.max_iter) {
-      ct->term = DSM_BA_NO_CONVERGENCE;
-      ct->done = 1;
-    } else if (fresh) {
-      const double mg = lb_margin(ct->gnorm, p.gtol);
-      if (mg < ct->mg[1]) ct->mg[1] = mg;
-      if (ct->gnorm <= p.gtol) {
-        ct->term = DSM_BA_CONVERGENCE;
-        ct->done = 1;
-      }
-    }
-    if (!ct->done && ct->radius < kMinRadius) {
-      ct->term = DSM_BA_CONVERGENCE;
-      ct->done = 1;
-    }
-  }
-  if (trace && ct->iter <= p.max_iter) {
+// thread 0: the checks that end an iteration, then the trace row
+__device__ inline void lb_finalize(LbCtrl* ct, const TrOptions& o, bool fresh, double* trace) {
+  tr_end_iteration(ct, o, fresh);
+  if (trace && ct->iter <= o.max_iterations) {
     double* row = trace + (size_t)ct->iter * LB_TRACE;
     row[0] = ct->cost;
     row[1] = ct->radius;
-    row[2] = ct->iter == 0 ? NAN : ct->rho;
+    row[2] = ct->iter == 0 ? NAN : ct->last_rho;
     row[3] = ct->iter == 0 ? 1.0 : (double)ct->accepted;
     row[4] = ct->gnorm;
   }
@@ -752,7 +659,7 @@ __global__ void __launch_bounds__(LB_T) k_lb_adjust(LbParams p) {
   v.mask = reinterpret_cast<unsigned long long*>(at); at += 2 * LB_TP;
   LbCtrl* ct = reinterpret_cast<LbCtrl*>(at); at += (sizeof(LbCtrl) + 7) / 8;
   v.colinfo = reinterpret_cast<int*>(at);
-  double* trace = p.trace ? p.trace + (size_t)b * (size_t)(p.max_iter + 1) * LB_TRACE : nullptr;
+  double* trace = p.trace ? p.trace + (size_t)b * (size_t)(p.tr.max_iterations + 1) * LB_TRACE : nullptr;
   // the columns' owners: pose columns from the images, camera columns from the cameras
   for (int i = tid; i < v.n_img; i += LB_T) {
     const int qc = v.img_qcol[i];
@@ -769,15 +676,9 @@ __global__ void __launch_bounds__(LB_T) k_lb_adjust(LbParams p) {
     for (int j = 0; j < v.cam_k[c]; ++j) v.colinfo[cc + j] = c << 6 | (6 + j) << 1 | 1;
   }
   if (tid == 0) {
-    for (int i = 0; i < LB_MARGINS; ++i) ct->mg[i] = INFINITY;
-    ct->iter = ct->n_succ = ct->n_invalid = ct->n_invalid_total = 0;
-    ct->term = DSM_BA_CONVERGENCE;
-    ct->done = 0;
-    ct->radius = 1e4;
-    ct->dec = 2.0;
-    ct->cost = ct->err = ct->gnorm = 0.0;
-    ct->rho = NAN;
-    ct->accepted = 0;
+    tr_init(ct, kTrInitialRadius);
+    ct->m_pivot = ct->m_point = INFINITY;
+    ct->err = 0.0;
   }
   __syncthreads();
   const uint64_t n_eff = 3ull * pb.n_var_pt + pb.R;
@@ -793,15 +694,12 @@ __global__ void __launch_bounds__(LB_T) k_lb_adjust(LbParams p) {
       ct->cost = c0;
       ct->err = e0;
       if (n_eff == 0) ct->done = 1;  // Ceres reduces the problem to an empty program: CONVERGENCE, zero iterations
-      if (!isfinite(c0)) {
-        ct->term = DSM_BA_FAILURE;
-        ct->done = 1;
-      }
+      if (!isfinite(c0)) tr_finish(ct, TR_FAILURE);
     }
     __syncthreads();
     if (!ct->done) {
       lb_normal(v, ct, tid, true);
-      if (tid == 0) lb_finalize(ct, p, true, trace);
+      if (tid == 0) lb_finalize(ct, v.tr, true, trace);
     } else if (tid == 0 && trace) {
       trace[0] = c0;
       trace[1] = ct->radius;
@@ -810,7 +708,7 @@ __global__ void __launch_bounds__(LB_T) k_lb_adjust(LbParams p) {
       trace[4] = 0.0;
     }
     __syncthreads();
-    while (!ct->done) {  // at most max_iter rounds: lb_decide counts every one, lb_finalize stops at the cap
+    while (!ct->done) {  // at most max_iterations rounds: tr_decide counts every one, tr_end_iteration stops at the cap
       lb_step(v, ct, tid);
       double cc = INFINITY, ce = 0.0;
       const bool valid = ct->valid != 0;
@@ -822,7 +720,7 @@ __global__ void __launch_bounds__(LB_T) k_lb_adjust(LbParams p) {
       if (tid == 0) {
         ct->cand_cost = cc;
         ct->cand_err = ce;
-        lb_decide(ct, p);
+        lb_decide(ct, v.tr);
       }
       __syncthreads();
       const bool acc = ct->accepted != 0;
@@ -840,7 +738,7 @@ __global__ void __launch_bounds__(LB_T) k_lb_adjust(LbParams p) {
         __syncthreads();
         lb_normal(v, ct, tid, false);
       }
-      if (tid == 0) lb_finalize(ct, p, fresh, trace);
+      if (tid == 0) lb_finalize(ct, v.tr, fresh, trace);
       __syncthreads();
     }
   }
@@ -858,7 +756,8 @@ __global__ void __launch_bounds__(LB_T) k_lb_adjust(LbParams p) {
     out->final_cost = ct->cost;
     out->initial_mean_reprojection_error = v.n_obs ? initial_err / v.n_obs : 0.0;
     out->final_mean_reprojection_error = v.n_obs ? ct->err / v.n_obs : 0.0;
-    for (int i = 0; i < LB_MARGINS; ++i) p.margins[(size_t)b * LB_MARGINS + i] = ct->mg[i];
+    const double mg[LB_MARGINS] = {ct->m_accept, ct->m_grad, ct->m_pivot, ct->m_point};
+    for (int i = 0; i < LB_MARGINS; ++i) p.margins[(size_t)b * LB_MARGINS + i] = mg[i];
   }
 }
 
@@ -1208,13 +1107,14 @@ extern "C" int dsm_adjust_local_bundles(dsm_ctx* ctx, uint32_t num_problems, con
   HIPCHK(ctx, hipMemsetAsync(d.trace.p, 0xFF, trace_rows * LB_TRACE * 8, st));  // all ones: NaN
   LbParams prm;
   prm.B = B;
-  prm.max_iter = o.max_num_iterations;
-  prm.max_invalid = o.max_num_consecutive_invalid_steps;
   prm.loss = o.loss_function_type;
   prm.rs = (r_max + 1) & ~1;
-  prm.gtol = o.gradient_tolerance;
-  prm.ftol = o.function_tolerance;
-  prm.ptol = o.parameter_tolerance;
+  prm.tr = tr_ceres_defaults();
+  prm.tr.max_iterations = o.max_num_iterations;
+  prm.tr.max_consecutive_invalid_steps = o.max_num_consecutive_invalid_steps;
+  prm.tr.gtol = o.gradient_tolerance;
+  prm.tr.ftol = o.function_tolerance;
+  prm.tr.ptol = o.parameter_tolerance;
   prm.b = o.loss_function_scale * o.loss_function_scale;  // SoftLOneLoss(a) / CauchyLoss(a): b_(a * a), c_(1 / b_)
   prm.c = 1.0 / prm.b;
   prm.prob = d.prob.as<LbProblem>();

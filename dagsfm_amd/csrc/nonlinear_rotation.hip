@@ -5,8 +5,9 @@
 // One residual block per edge of the first component: r = RotationMatrixToAngleAxis(R(a_j) R(a_i)^T R(a_12)^T), differentiated
 // by forward-mode dual numbers through ceres' conversions (rotation_ceres.h), under ceres::SoftLOneLoss and ceres' corrector.
 // The minimizer is ceres' Levenberg-Marquardt as DESIGN.md 12 states it (Jacobi scaling, D = clamp(diag J^T J), the step
-// rules and their order), without a Schur complement: (J^T J + D / radius) step = -g is solved by a conjugate gradient
-// preconditioned by the exact 3 x 3 diagonal blocks, x0 = 0, to a relative residual of cg_tolerance (1e-14).
+// rules and their order: trust_region.h), without a Schur complement: (J^T J + D / radius) step = -g is solved by a
+// conjugate gradient preconditioned by the exact 3 x 3 diagonal blocks, x0 = 0, to a relative residual of cg_tolerance
+// (1e-14).
 //
 // Layout.  Vectors over images are [N][3]; an edge record is NL_EDGE doubles: the corrected residual r[3], the corrected
 // Jacobian blocks with respect to image 1 and image 2 (3 x 3 row-major each, unscaled), rho(s).  There are two edge buffers:
@@ -37,40 +38,40 @@
 #include "graph_edges.h"
 #include "rotation_ceres.h"
 #include "rotation_graph.h"
+#include "trust_region.h"
 
 namespace {
 
 constexpr int NL_EDGE = 22;               // r[3], J1[9], J2[9], rho(s)
-constexpr int NL_LINEAR_SOLVER_FAILED = 3;  // internal: a CG solve ended above cg_max_residual
-constexpr double NL_MIN_RADIUS = 1e-32;   // ceres' min_trust_region_radius
+constexpr int NL_LINEAR_SOLVER_FAILED = 3;  // internal, beside TR_*: a CG solve ended above cg_max_residual
 
 // device-side loop state; every field has one writer per launch (thread 0 of block 0).  No kernel reads a value that is
 // written in the same launch, with one exception: cg_stop, which k_nl_cg_ap(k) and k_nl_step(k) may set to k while other
 // blocks of that launch read it at their entry (nl_block_read).  Such a block sees INT_MAX or k; with INT_MAX it repeats the
 // stop test on the same partials and ends the same way, with k it returns at once: both are the ended solve, and nothing else
 // depends on which one it saw.
-struct NlCtl {
+struct NlCtl : TrState {  // accepted: the last step was accepted (or this is iteration 0), so the gradient is fresh
   int cur;        // the edge buffer that holds the linearisation of the accepted state
   int cg_stop;    // CG iterations k >= cg_stop are no-ops (INT_MAX while the solve runs)
   int cg_done;    // the solve of this LM iteration has ended: the tail may run
   int cg_last;    // its iterations
-  int term;       // -1 while running, else DSM_BA_* or NL_LINEAR_SOLVER_FAILED
   int pending;    // a decision was taken and its trace row is not written yet
-  int accepted;   // the last step was accepted (or this is iteration 0): the gradient is fresh
-  int iter, n_succ, n_rej, n_invalid_total, n_invalid;
-  double radius, dec, cost, initial_cost, gnorm, rho_lm;
+  double initial_cost;
   double rz[2];   // r.z of CG iteration k at [k & 1]
   double bb;      // ||b||^2 of the running solve
   double last_resid, cg_worst;
   unsigned long long cg_total;
-  double m_rho, m_grad, m_func;
 };
 
 struct NlOpt {
   double loss_b;  // robust_loss_width^2
-  double ftol, gtol, ptol, max_radius, min_rel, min_diag, max_diag, cg_tol, cg_max_resid;
-  int max_iter, max_invalid, cg_max;
+  double min_diag, max_diag, cg_tol, cg_max_resid;
+  int cg_max;
+  TrOptions tr;
 };
+
+// the entry test of every kernel of the loop; the running loop is the path that falls through
+#define nl_ended(ctl) __builtin_expect((ctl)->done, 0)
 
 // a control word that thread 0 of block 0 may write later in the same launch, read once per block: every thread of a block
 // takes the same path to the barriers that follow
@@ -79,12 +80,6 @@ __device__ inline int nl_block_read(const int* word) {
   if (threadIdx.x == 0) w = *(const volatile int*)word;
   __syncthreads();
   return w;
-}
-
-__device__ inline double nl_margin(double a, double thr) {
-  if (!isfinite(a)) return INFINITY;
-  const double den = fmax(fabs(a), fabs(thr));
-  return den > 0.0 ? fabs(a - thr) / den : 0.0;
 }
 
 // ---------------------------------------------------------------- the residual block
@@ -155,7 +150,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_nl_edges(uint32_t M, const uint32_
                                                        const double* __restrict__ x, const double* __restrict__ sc, double loss_b,
                                                        const NlCtl* ctl, int mode, double* __restrict__ E0, double* __restrict__ E1,
                                                        double* __restrict__ P) {
-  if (mode && (ctl->term >= 0 || !ctl->cg_done)) return;
+  if (mode && (nl_ended(ctl) || !ctl->cg_done)) return;
   __shared__ double sh[2 * RA_BLOCK];
   const int cur = ctl->cur;
   const double* Ecur = cur ? E1 : E0;
@@ -206,7 +201,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_nl_linearize(uint32_t N, const uin
                                                            const double* __restrict__ x, double* __restrict__ R, double* __restrict__ sc,
                                                            double* __restrict__ D, double* __restrict__ gs, double* __restrict__ B,
                                                            const NlCtl* ctl, int mode, NlOpt o, double* __restrict__ Pg) {
-  if (ctl->term >= 0 || (mode && (!ctl->pending || !ctl->accepted))) return;
+  if (nl_ended(ctl) || (mode && (!ctl->pending || !ctl->accepted))) return;
   __shared__ double sh[RA_BLOCK];
   const double* E = ctl->cur ? E1 : E0;
   const uint32_t v = blockIdx.x * RA_BLOCK + threadIdx.x;
@@ -263,7 +258,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_nl_cg_init(uint32_t N, const doubl
                                                          const double* __restrict__ B, double* __restrict__ lm, double* __restrict__ Minv,
                                                          double* __restrict__ x, double* __restrict__ r, double* __restrict__ z,
                                                          NlCtl* ctl, double* __restrict__ Pz) {
-  if (ctl->term >= 0) return;
+  if (nl_ended(ctl)) return;
   __shared__ double sh[2 * RA_BLOCK];
   const double radius = ctl->radius;
   const uint32_t v = blockIdx.x * RA_BLOCK + threadIdx.x;
@@ -333,7 +328,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_nl_cg_ap(uint32_t N, int nbv, cons
                                                        const double* __restrict__ pold, double* __restrict__ pnew, double* __restrict__ q,
                                                        NlCtl* ctl, int k, double tol, int cg_max, const double* __restrict__ Pz,
                                                        double* __restrict__ Pq) {
-  if (ctl->term >= 0 || k >= nl_block_read(&ctl->cg_stop)) return;
+  if (nl_ended(ctl) || k >= nl_block_read(&ctl->cg_stop)) return;
   __shared__ double sh[2 * RA_BLOCK];
   double rz, bb, rel;
   const bool ended = nl_cg_ended(Pz, nbv, k, ctl, tol, cg_max, sh, &rz, &bb, &rel);
@@ -386,7 +381,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_nl_cg_xr(uint32_t N, int nbv, cons
                                                        const double* __restrict__ p, const double* __restrict__ q, double* __restrict__ x,
                                                        double* __restrict__ r, double* __restrict__ z, const NlCtl* ctl, int k,
                                                        double* __restrict__ Pz) {
-  if (ctl->term >= 0 || k >= ctl->cg_stop) return;
+  if (nl_ended(ctl) || k >= ctl->cg_stop) return;
   __shared__ double sh[2 * RA_BLOCK];
   double pq[1];
   sum_partials<RA_BLOCK, 1>(Pq, nbv, pq, sh);
@@ -417,7 +412,7 @@ __global__ void __launch_bounds__(RA_BLOCK) k_nl_cg_xr(uint32_t N, int nbv, cons
 __global__ void __launch_bounds__(RA_BLOCK) k_nl_step(uint32_t N, int nbv, const double* __restrict__ R, const double* __restrict__ x,
                                                       const double* __restrict__ sc, NlCtl* ctl, int k_end, double tol, int cg_max,
                                                       const double* __restrict__ Pz, double* __restrict__ Pv) {
-  if (ctl->term >= 0) return;
+  if (nl_ended(ctl)) return;
   __shared__ double sh[2 * RA_BLOCK];
   const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
   if (k_end < nl_block_read(&ctl->cg_stop)) {  // else an earlier iteration has ended the solve
@@ -438,10 +433,10 @@ __global__ void __launch_bounds__(RA_BLOCK) k_nl_step(uint32_t N, int nbv, const
   if (writer) ctl->cg_done = 1;
 }
 
-// ---------------------------------------------------------------- one thread's decisions (the same order)
+// ---------------------------------------------------------------- one thread's decisions (trust_region.h)
 __global__ void __launch_bounds__(RA_BLOCK) k_nl_decide(int nbe, const double* __restrict__ Pe, int nbv, const double* __restrict__ Pv,
                                                         NlCtl* ctl, int mode, NlOpt o, double initial_radius) {
-  if (mode && (ctl->term >= 0 || !ctl->cg_done || ctl->pending)) return;
+  if (mode && (nl_ended(ctl) || !ctl->cg_done || ctl->pending)) return;
   __shared__ double sh[2 * RA_BLOCK];
   double e2[2], v2[2] = {0.0, 0.0};
   sum_partials<RA_BLOCK, 2>(Pe, nbe, e2, sh);
@@ -450,86 +445,35 @@ __global__ void __launch_bounds__(RA_BLOCK) k_nl_decide(int nbe, const double* _
   if (mode == 0) {
     ctl->cost = ctl->initial_cost = e2[0];
     ctl->radius = initial_radius;
-    ctl->dec = 2.0;
     ctl->accepted = 1;
     ctl->pending = 1;
-    ctl->rho_lm = NAN;
-    if (!isfinite(e2[0])) ctl->term = DSM_BA_FAILURE;
+    if (!isfinite(e2[0])) tr_finish(ctl, TR_FAILURE);
     return;
   }
-  const double cand = e2[0], mcc = e2[1], s2 = v2[0], xn2 = v2[1], cost = ctl->cost;
   ctl->cg_done = 0;
   if (!(ctl->last_resid <= o.cg_max_resid)) {
-    ctl->term = NL_LINEAR_SOLVER_FAILED;
+    tr_finish(ctl, NL_LINEAR_SOLVER_FAILED);
     return;
   }
-  ctl->iter += 1;
-  ctl->accepted = 0;
   ctl->pending = 1;
-  ctl->rho_lm = NAN;
-  const bool valid = isfinite(mcc) && mcc > 0.0 && isfinite(s2) && isfinite(cand);
-  if (!valid) {
-    ctl->n_invalid += 1;
-    ctl->n_invalid_total += 1;
-    if (ctl->n_invalid >= o.max_invalid) {
-      ctl->term = DSM_BA_FAILURE;
-    } else {
-      ctl->radius /= ctl->dec;
-      ctl->dec *= 2.0;
-    }
-    return;
-  }
-  ctl->n_invalid = 0;
-  if (sqrt(s2) <= o.ptol * (sqrt(xn2) + o.ptol)) {
-    ctl->term = DSM_BA_CONVERGENCE;
-    return;
-  }
-  ctl->m_func = fmin(ctl->m_func, nl_margin(fabs(cost - cand), o.ftol * cost));
-  if (fabs(cost - cand) <= o.ftol * cost) {
-    ctl->term = DSM_BA_CONVERGENCE;
-    return;
-  }
-  const double rho = (cost - cand) / mcc;
-  ctl->rho_lm = rho;
-  ctl->m_rho = fmin(ctl->m_rho, fabs((cost - cand) - o.min_rel * mcc) / fmax(cost, DBL_MIN));
-  if (rho > o.min_rel) {
-    ctl->accepted = 1;
-    ctl->n_succ += 1;
-    ctl->cost = cand;
-    ctl->cur ^= 1;
-    const double t = 2.0 * rho - 1.0;
-    ctl->radius = fmin(o.max_radius, ctl->radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
-    ctl->dec = 2.0;
-  } else {
-    ctl->n_rej += 1;
-    ctl->radius /= ctl->dec;
-    ctl->dec *= 2.0;
-  }
+  // e2: the candidate's cost and model_cost_change; v2: |delta|^2 and |x|^2.  An accepted candidate is already linearised.
+  if (tr_decide(ctl, o.tr, true, e2[0], e2[1], v2[0], v2[1]) == TR_ACCEPTED) ctl->cur ^= 1;
 }
 
-// after every iteration (and at iteration 0): the iteration cap, then with a fresh gradient the gradient test, then the
-// smallest radius; the trace row
+// after every iteration (and at iteration 0): the gradient max-norm when fresh, the checks that end an iteration, the trace row
 __global__ void __launch_bounds__(RA_BLOCK) k_nl_post(int nbv, const double* __restrict__ Pg, NlCtl* ctl, NlOpt o, double* __restrict__ trace) {
   if (!ctl->pending) return;
   __shared__ double sh[RA_BLOCK];
   const double gm = max_partials<RA_BLOCK>(Pg, (uint32_t)nbv, sh);
   if (threadIdx.x != 0) return;
-  const bool fresh = ctl->accepted && ctl->term < 0;
+  const bool fresh = ctl->accepted && !ctl->done;
   if (fresh) ctl->gnorm = gm;
-  if (ctl->term < 0) {
-    if (ctl->iter >= o.max_iter) {
-      ctl->term = DSM_BA_NO_CONVERGENCE;
-    } else if (fresh) {
-      ctl->m_grad = fmin(ctl->m_grad, nl_margin(ctl->gnorm, o.gtol));
-      if (ctl->gnorm <= o.gtol) ctl->term = DSM_BA_CONVERGENCE;
-    }
-    if (ctl->term < 0 && ctl->radius < NL_MIN_RADIUS) ctl->term = DSM_BA_CONVERGENCE;
-  }
+  tr_end_iteration(ctl, o.tr, fresh);
   if (trace) {
     double* row = trace + (size_t)DSM_NLR_TRACE_COLUMNS * ctl->iter;
     row[0] = ctl->cost;
     row[1] = ctl->radius;
-    row[2] = ctl->rho_lm;
+    row[2] = ctl->last_rho;
     row[3] = ctl->iter ? (double)ctl->cg_last : 0.0;
     row[4] = (double)ctl->accepted;
     row[5] = ctl->gnorm;
@@ -676,8 +620,7 @@ extern "C" int dsm_view_graph_rotation_averaging_nonlinear(dsm_ctx* ctx, uint32_
   HIPTRY(hipEventCreate(&ev0.e));
   HIPTRY(hipEventCreate(&ev1.e));
   NlCtl h{};
-  h.term = -1;
-  h.m_rho = h.m_grad = h.m_func = INFINITY;
+  tr_init(&h, 0.0);  // k_nl_decide(mode 0) sets the radius
   if (rc == DSM_OK) {
     HIPTRY(hipEventRecord(ev0, st));
     HIPTRY(hipMemcpyAsync(d_ei.p, g.ei.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
@@ -703,17 +646,18 @@ extern "C" int dsm_view_graph_rotation_averaging_nonlinear(dsm_ctx* ctx, uint32_
   double* Pz_[2] = {d_Pz0.as<double>(), d_Pz1.as<double>()};
   NlOpt k{};
   k.loss_b = o.robust_loss_width * o.robust_loss_width;
-  k.ftol = o.function_tolerance;
-  k.gtol = o.gradient_tolerance;
-  k.ptol = o.parameter_tolerance;
-  k.max_radius = o.max_trust_region_radius;
-  k.min_rel = o.min_relative_decrease;
+  k.tr.ftol = o.function_tolerance;
+  k.tr.gtol = o.gradient_tolerance;
+  k.tr.ptol = o.parameter_tolerance;
+  k.tr.max_radius = o.max_trust_region_radius;
+  k.tr.min_radius = kTrMinRadius;
+  k.tr.min_relative_decrease = o.min_relative_decrease;
   k.min_diag = o.min_lm_diagonal;
   k.max_diag = o.max_lm_diagonal;
   k.cg_tol = o.cg_tolerance;
   k.cg_max_resid = o.cg_max_residual;
-  k.max_iter = o.max_num_iterations;
-  k.max_invalid = o.max_num_consecutive_invalid_steps;
+  k.tr.max_iterations = o.max_num_iterations;
+  k.tr.max_consecutive_invalid_steps = o.max_num_consecutive_invalid_steps;
   k.cg_max = o.max_num_cg_iterations > 0 ? o.max_num_cg_iterations : (int)std::max<uint32_t>(1000u, 20u * N);
   const dim3 gv(nbv), ge(nbe), one(1), bs(RA_BLOCK);
   auto read_ctl = [&]() {
@@ -737,7 +681,7 @@ extern "C" int dsm_view_graph_rotation_averaging_nonlinear(dsm_ctx* ctx, uint32_
   }
   int budget = std::min(k.cg_max, 48);
   uint64_t launches = 4;
-  while (rc == DSM_OK && h.term < 0) {
+  while (rc == DSM_OK && !h.done) {
     hipLaunchKernelGGL(k_nl_cg_init, gv, bs, 0, st, N, (const double*)D_, (const double*)gs_, (const double*)B_, lm_, Mi_, x_, r_, z_, ctl,
                        Pz_[0]);
     ++launches;
@@ -755,7 +699,7 @@ extern "C" int dsm_view_graph_rotation_averaging_nonlinear(dsm_ctx* ctx, uint32_
       tail(1);
       launches += 2 * (uint64_t)(k1 - k0) + 5;
       read_ctl();
-      if (h.term >= 0 || h.cg_stop != INT_MAX || k1 >= k.cg_max) break;  // the solve ended inside the budget: the tail has run
+      if (h.done || h.cg_stop != INT_MAX || k1 >= k.cg_max) break;  // the solve ended inside the budget: the tail has run
       k0 = k1;
     }
     budget = std::min(k.cg_max, std::max(16, h.cg_last + h.cg_last / 4 + 8));
@@ -783,7 +727,7 @@ extern "C" int dsm_view_graph_rotation_averaging_nonlinear(dsm_ctx* ctx, uint32_
     rep.device_ms = ms;
   }
   if (rc != DSM_OK) (void)hipStreamSynchronize(st);
-  rep.termination = h.term == NL_LINEAR_SOLVER_FAILED || h.term < 0 ? DSM_BA_FAILURE : h.term;
+  rep.termination = h.term == NL_LINEAR_SOLVER_FAILED || !h.done ? DSM_BA_FAILURE : h.term;
   rep.num_iterations = (uint32_t)h.iter;
   rep.num_successful_steps = (uint32_t)h.n_succ;
   rep.num_rejected_steps = (uint32_t)h.n_rej;
@@ -794,7 +738,7 @@ extern "C" int dsm_view_graph_rotation_averaging_nonlinear(dsm_ctx* ctx, uint32_
   rep.final_cost = h.cost;
   rep.final_trust_region_radius = h.radius;
   rep.max_cg_relative_residual = h.cg_worst;
-  rep.min_rho_margin = h.m_rho;
+  rep.min_rho_margin = h.m_accept;
   rep.min_gradient_margin = h.m_grad;
   rep.min_function_margin = h.m_func;
   if (rc == DSM_OK) {

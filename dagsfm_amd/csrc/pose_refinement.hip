@@ -2,7 +2,7 @@
 // IncrementalMapper::RegisterNextImage calls it (src/sfm/incremental_mapper.cc:498-535), for a batch of independent problems
 // (DESIGN.md 15).  BundleAdjustmentCostFunction with the 3D point constant under ceres::CauchyLoss, qvec through
 // QuaternionParameterization, tvec free, the camera's focal / extra parameters free by the problem's flags; the trust-region
-// rulings of DESIGN.md 12, the damped normal equations solved by an unpivoted Cholesky.
+// rulings of DESIGN.md 12 (trust_region.h), the damped normal equations solved by an unpivoted Cholesky.
 //
 // One kernel, k_pr_refine: a one-wave workgroup per problem runs the whole Levenberg-Marquardt loop.  Per evaluation the 64 lanes
 // walk the problem's points (lane l takes points l, l + 64, ...): residual and Jacobian through ba_project.h's dual numbers, the
@@ -22,21 +22,18 @@
 
 #include "ba_project.h"
 #include "ctx.h"
+#include "trust_region.h"
 
 namespace {
 
 constexpr int PR_P = 16;               // free tangent dimensions at most: qvec 3, tvec 3, camera 10 (FULL_OPENCV / THIN_PRISM_FISHEYE)
 constexpr int PR_ROW = 2 * PR_P + 2;   // workspace doubles per point: the two corrected Jacobian rows, the corrected residual
 constexpr int PR_MARGINS = DSM_POSE_REFINEMENT_MARGINS;
-constexpr double kMinRelDecrease = 1e-3, kMinDiag = 1e-6, kMaxDiag = 1e32, kMaxRadius = 1e16, kMinRadius = 1e-32;
-constexpr double kFunctionTolerance = 1e-6, kParameterTolerance = 1e-8;  // ceres::Solver::Options' defaults
-constexpr int kMaxInvalidSteps = 5;                                      // max_num_consecutive_invalid_steps' default
-enum { PR_ACCEPTED = 1, PR_REJECTED = 2, PR_INVALID = 3, PR_TOLERANCE = 4 };
 
 struct PrParams {
   uint32_t B;
-  int max_iter;
-  double gtol, b, c;  // CauchyLoss: b = scale^2, c = 1 / b
+  TrOptions tr;  // ceres' defaults but for gradient_tolerance and max_num_iterations
+  double b, c;   // CauchyLoss: b = scale^2, c = 1 / b
   const dsm_camera* cams;
   const uint64_t* offsets;
   const double* xy;
@@ -48,23 +45,23 @@ struct PrParams {
   double* ws;  // [offsets[B]][PR_ROW], SoA inside a problem
   dsm_pose_refinement_result* res;
   double* margins;  // [B][PR_MARGINS]
-  uint8_t* steps;   // [B][max_iter]
+  uint8_t* steps;   // [B][tr.max_iterations]
 };
 
 struct PrState {
   double q[4], t[3], prm[12];
 };
 
-struct PrShared {
+struct PrShared : TrState {
+  TrOptions opt;  // the kernel's, beside the state: lane 0's device functions take one pointer
   PrState x, cand;
   double A[PR_P * PR_P];  // J'J of the corrected Jacobian (upper triangle from the sums, mirrored), then scaled in place
   double L[PR_P * PR_P];
   double g[PR_P], gs[PR_P], s[PR_P], D[PR_P], step[PR_P], delta[PR_P];
-  double cost, cand_cost, gnorm, radius, dec, mcc;
-  double mg[PR_MARGINS];
-  int fr[PR_P];  // the free camera parameter indices
-  int model, np, k, P, cam_var;
-  int iter, n_succ, n_invalid, n_invalid_total, term, done, accepted, valid;
+  double cand_cost, mcc, s2;
+  double m_pivot;  // the smallest Cholesky pivot relative to its diagonal entry
+  int fr[PR_P];    // the free camera parameter indices
+  int model, np, k, P, cam_var, valid;
 };
 
 struct PrView {
@@ -76,44 +73,11 @@ struct PrView {
   double b, c;
 };
 
-__device__ inline double pr_margin(double a, double thr) {
-  if (!isfinite(a)) return INFINITY;
-  const double den = fmax(fabs(a), fabs(thr));
-  return den > 0.0 ? fabs(a - thr) / den : 0.0;
-}
-__device__ inline void pr_min(double* m, double v) {
-  if (v < *m) *m = v;
-}
-
-// the one instantiation of the projection this file carries: value and derivatives (the value is the double path's, ba_project.h)
+// one copy each of the projection's dual instantiation and of Plus in this file's code (the library's size cap)
 __device__ __noinline__ void pr_project(int model, int np, const double* prm, double u, double v, BaDual* x, BaDual* y) {
-  BaDual pd[12];
-  for (int j = 0; j < 12; ++j) pd[j] = j < np ? bd_var(prm[j], 2 + j) : bd_const(0.0);
-  ba_world_to_image<BaDual>(model, pd, bd_var(u, 0), bd_var(v, 1), x, y);
+  ba_project_dual(model, np, prm, u, v, x, y);
 }
-
-// ceres::UnitQuaternionRotatePoint
-__device__ inline void pr_rotate(const double* q, const double* X, double* out) {
-  const double t2 = q[0] * q[1], t3 = q[0] * q[2], t4 = q[0] * q[3], t5 = -q[1] * q[1], t6 = q[1] * q[2], t7 = q[1] * q[3];
-  const double t8 = -q[2] * q[2], t9 = q[2] * q[3], t1 = -q[3] * q[3];
-  out[0] = 2.0 * ((t8 + t1) * X[0] + (t6 - t4) * X[1] + (t3 + t7) * X[2]) + X[0];
-  out[1] = 2.0 * ((t4 + t6) * X[0] + (t5 + t1) * X[1] + (t9 - t2) * X[2]) + X[1];
-  out[2] = 2.0 * ((t7 - t3) * X[0] + (t2 + t9) * X[1] + (t5 + t8) * X[2]) + X[2];
-}
-// QuaternionParameterization::Plus: [cos|d|, sin|d| d / |d|] (x) x
-__device__ __noinline__ void pr_quat_plus(const double* x, const double* d, double* out) {
-  const double n = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-  if (!(n > 0.0)) {
-    for (int i = 0; i < 4; ++i) out[i] = x[i];
-    return;
-  }
-  const double s = sin(n) / n;
-  const double a0 = cos(n), a1 = s * d[0], a2 = s * d[1], a3 = s * d[2];
-  out[0] = a0 * x[0] - a1 * x[1] - a2 * x[2] - a3 * x[3];
-  out[1] = a0 * x[1] + a1 * x[0] + a2 * x[3] - a3 * x[2];
-  out[2] = a0 * x[2] - a1 * x[3] + a2 * x[0] + a3 * x[1];
-  out[3] = a0 * x[3] + a1 * x[2] - a2 * x[1] + a3 * x[0];
-}
+__device__ __noinline__ void pr_quat_plus(const double* x, const double* d, double* out) { ba_quat_plus(x, d, out); }
 
 __device__ inline double pr_wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -133,7 +97,7 @@ __device__ __noinline__ double pr_eval(const PrView& v, const PrShared* sm, cons
   for (int i = lane; i < v.N; i += 64) {
     if (!v.mask[i]) continue;  // adds +0.0
     double w[3];
-    pr_rotate(q, v.X + 3 * (size_t)i, w);
+    ba_rotate(q, v.X + 3 * (size_t)i, w);
     const double P0 = w[0] + t[0], P1 = w[1] + t[1], P2 = w[2] + t[2];
     const double pu = P0 / P2, pv = P1 / P2;
     BaDual xx, yy;
@@ -145,15 +109,8 @@ __device__ __noinline__ double pr_eval(const PrView& v, const PrShared* sm, cons
     acc += 0.5 * (v.b * log(sum));
     if (!jac) continue;
     const double sq = sqrt(fmax(DBL_MIN, inv));
-    const double iz = 1.0 / P2;
-    const double duP[3] = {iz, 0.0, -P0 * iz * iz}, dvP[3] = {0.0, iz, -P1 * iz * iz};
-    double JP[2][3];
-    for (int a = 0; a < 3; ++a) {
-      JP[0][a] = xx.d[0] * duP[a] + xx.d[1] * dvP[a];
-      JP[1][a] = yy.d[0] * duP[a] + yy.d[1] * dvP[a];
-    }
-    // dP / d(delta) = -2 [w]x, the tangent of QuaternionParameterization
-    const double Dq[9] = {0.0, 2.0 * w[2], -2.0 * w[1], -2.0 * w[2], 0.0, 2.0 * w[0], 2.0 * w[1], -2.0 * w[0], 0.0};
+    double JP[2][3], Dq[9];
+    ba_pixel_jacobian(xx, yy, P0, P1, P2, w, JP, Dq);
     double* row = v.ws + i;
     const size_t N = (size_t)v.N;
     for (int r = 0; r < 2; ++r) {
@@ -213,7 +170,7 @@ __device__ __noinline__ void pr_scale(PrShared* sm, bool first) {
   for (int a = 0; a < P; ++a) {
     for (int b = 0; b < P; ++b) sm->A[a * PR_P + b] = (sm->s[a] * sm->A[a * PR_P + b]) * sm->s[b];
     sm->gs[a] = sm->s[a] * sm->g[a];
-    sm->D[a] = fmin(fmax((sm->s[a] * sm->s[a]) * cn[a], kMinDiag), kMaxDiag);
+    sm->D[a] = fmin(fmax((sm->s[a] * sm->s[a]) * cn[a], kLmMinDiag), kLmMaxDiag);
   }
   // |x - Plus(x, -g)|inf over the variable blocks, g unscaled
   double ng[3] = {-sm->g[0], -sm->g[1], -sm->g[2]}, qp[4], m = 0.0;
@@ -243,7 +200,7 @@ __device__ __noinline__ void pr_step(PrShared* sm) {
       const double diag = s;
       for (int m = 0; m < j; ++m) s -= L[i * PR_P + m] * L[j * PR_P + m];
       if (i == j) {
-        pr_min(&sm->mg[4], isfinite(s) && diag > 0.0 ? fabs(s) / diag : 0.0);
+        tr_min(&sm->m_pivot, isfinite(s) && diag > 0.0 ? fabs(s) / diag : 0.0);
         if (!(s > 0.0) || !isfinite(s)) {
           ok = false;
           break;
@@ -254,7 +211,7 @@ __device__ __noinline__ void pr_step(PrShared* sm) {
       }
     }
   sm->valid = 0;
-  sm->mcc = 0.0;
+  sm->mcc = sm->s2 = 0.0;
   if (!ok) return;
   double w[PR_P];
   for (int i = 0; i < P; ++i) {
@@ -278,84 +235,24 @@ __device__ __noinline__ void pr_step(PrShared* sm) {
     s2 += sm->delta[i] * sm->delta[i];
   }
   sm->mcc = -mcc;
+  sm->s2 = s2;
   sm->cand = sm->x;
   pr_quat_plus(sm->x.q, sm->delta, sm->cand.q);
   for (int i = 0; i < 3; ++i) sm->cand.t[i] = sm->x.t[i] + sm->delta[3 + i];
   for (int j = 0; j < sm->k; ++j) sm->cand.prm[sm->fr[j]] = sm->x.prm[sm->fr[j]] + sm->delta[6 + j];
-  sm->valid = isfinite(sm->mcc) && sm->mcc > 0.0 && isfinite(s2);
+  sm->valid = tr_step_usable(sm->mcc, s2);
 }
 
-// lane 0: the decision of one iteration; returns the step's code
+// lane 0: the decision of one iteration (trust_region.h); returns the step's code
 __device__ __noinline__ int pr_decide(PrShared* sm) {
-  sm->iter += 1;
-  sm->accepted = 0;
-  if (!(sm->valid && isfinite(sm->cand_cost))) {
-    sm->n_invalid += 1;
-    sm->n_invalid_total += 1;
-    if (sm->n_invalid >= kMaxInvalidSteps) {
-      sm->term = DSM_BA_FAILURE;
-      sm->done = 1;
-    } else {
-      sm->radius /= sm->dec;
-      sm->dec *= 2.0;
-    }
-    return PR_INVALID;
-  }
-  sm->n_invalid = 0;
-  double s2 = 0.0, x2 = 0.0;
-  for (int i = 0; i < sm->P; ++i) s2 += sm->delta[i] * sm->delta[i];
+  double x2 = 0.0;
   for (int i = 0; i < 4; ++i) x2 += sm->x.q[i] * sm->x.q[i];
   for (int i = 0; i < 3; ++i) x2 += sm->x.t[i] * sm->x.t[i];
   if (sm->cam_var)
     for (int i = 0; i < sm->np; ++i) x2 += sm->x.prm[i] * sm->x.prm[i];
-  const double step_norm = sqrt(s2), ptol = kParameterTolerance * (sqrt(x2) + kParameterTolerance);
-  pr_min(&sm->mg[3], pr_margin(step_norm, ptol));
-  if (step_norm <= ptol) {
-    sm->term = DSM_BA_CONVERGENCE;
-    sm->done = 1;
-    return PR_TOLERANCE;
-  }
-  const double change = sm->cost - sm->cand_cost;
-  pr_min(&sm->mg[2], pr_margin(fabs(change), kFunctionTolerance * sm->cost));
-  if (fabs(change) <= kFunctionTolerance * sm->cost) {
-    sm->term = DSM_BA_CONVERGENCE;
-    sm->done = 1;
-    return PR_TOLERANCE;
-  }
-  const double rho = change / sm->mcc;
-  pr_min(&sm->mg[0], fabs(change - kMinRelDecrease * sm->mcc) / fmax(sm->cost, DBL_MIN));
-  if (rho > kMinRelDecrease) {
-    sm->accepted = 1;
-    sm->n_succ += 1;
-    sm->x = sm->cand;
-    sm->cost = sm->cand_cost;
-    const double tmp = 2.0 * rho - 1.0;
-    sm->radius = fmin(kMaxRadius, sm->radius / fmax(1.0 / 3.0, 1.0 - tmp * tmp * tmp));
-    sm->dec = 2.0;
-    return PR_ACCEPTED;
-  }
-  sm->radius /= sm->dec;
-  sm->dec *= 2.0;
-  return PR_REJECTED;
-}
-
-// lane 0: the checks that end an iteration: the cap, the gradient (after an accepted step or at iteration 0), the radius
-__device__ inline void pr_finalize(PrShared* sm, const PrParams& p, bool fresh) {
-  if (sm->done) return;
-  if (sm->iter >= p.max_iter) {
-    sm->term = DSM_BA_NO_CONVERGENCE;
-    sm->done = 1;
-  } else if (fresh) {
-    pr_min(&sm->mg[1], pr_margin(sm->gnorm, p.gtol));
-    if (sm->gnorm <= p.gtol) {
-      sm->term = DSM_BA_CONVERGENCE;
-      sm->done = 1;
-    }
-  }
-  if (!sm->done && sm->radius < kMinRadius) {
-    sm->term = DSM_BA_CONVERGENCE;
-    sm->done = 1;
-  }
+  const int code = tr_decide(sm, sm->opt, sm->valid != 0, sm->cand_cost, sm->mcc, sm->s2, x2);
+  if (code == TR_ACCEPTED) sm->x = sm->cand;
+  return code;
 }
 
 __global__ void __launch_bounds__(64) k_pr_refine(PrParams p) {
@@ -378,7 +275,9 @@ __global__ void __launch_bounds__(64) k_pr_refine(PrParams p) {
   for (int o = 32; o > 0; o >>= 1) n_in += __shfl_xor(n_in, o);
   dsm_pose_refinement_result* out = &p.res[b];
   if (lane == 0) {
-    for (int i = 0; i < PR_MARGINS; ++i) sm.mg[i] = INFINITY;
+    tr_init(&sm, kTrInitialRadius);
+    sm.opt = p.tr;
+    sm.m_pivot = INFINITY;
     sm.model = cam.model_id;
     sm.np = cam_num_params(cam.model_id);
     const int nfoc = cam_two_focal(cam.model_id) ? 2 : 1;
@@ -393,12 +292,6 @@ __global__ void __launch_bounds__(64) k_pr_refine(PrParams p) {
     for (int i = 0; i < 4; ++i) sm.x.q[i] = p.q_in[4 * (size_t)b + i];
     for (int i = 0; i < 3; ++i) sm.x.t[i] = p.t_in[3 * (size_t)b + i];
     for (int i = 0; i < 12; ++i) sm.x.prm[i] = i < sm.np ? cam.params[i] : 0.0;
-    sm.iter = sm.n_succ = sm.n_invalid = sm.n_invalid_total = 0;
-    sm.term = DSM_BA_CONVERGENCE;
-    sm.done = 0;
-    sm.radius = 1e4;
-    sm.dec = 2.0;
-    sm.cost = 0.0;
     if (n_in > 0) {  // NormalizeQuaternion (pose.cc:246); an empty problem leaves qvec as it came
       const double n = sqrt(sm.x.q[0] * sm.x.q[0] + sm.x.q[1] * sm.x.q[1] + sm.x.q[2] * sm.x.q[2] + sm.x.q[3] * sm.x.q[3]);
       if (n > 0.0) {
@@ -419,22 +312,21 @@ __global__ void __launch_bounds__(64) k_pr_refine(PrParams p) {
     if (lane == 0) {
       sm.cost = c0;
       if (!isfinite(c0)) {
-        sm.term = DSM_BA_FAILURE;
-        sm.done = 1;
+        tr_finish(&sm, TR_FAILURE);
       } else {
         pr_scale(&sm, true);
-        pr_finalize(&sm, p, true);
+        tr_end_iteration(&sm, sm.opt, true);
       }
     }
     __syncthreads();
-    while (!sm.done) {  // at most max_iter rounds: pr_decide counts every one, pr_finalize stops at the cap
+    while (!sm.done) {  // at most max_iterations rounds: tr_decide counts every one, tr_end_iteration stops at the cap
       if (lane == 0) pr_step(&sm);
       __syncthreads();
       const double cc = sm.valid ? pr_eval(v, &sm, &sm.cand, lane, false) : INFINITY;
       if (lane == 0) {
         sm.cand_cost = cc;
         const int code = pr_decide(&sm);
-        if (p.steps) p.steps[(size_t)b * p.max_iter + (sm.iter - 1)] = (uint8_t)code;
+        if (p.steps) p.steps[(size_t)b * p.tr.max_iterations + (sm.iter - 1)] = (uint8_t)code;
       }
       __syncthreads();
       const bool fresh = sm.accepted && !sm.done;
@@ -444,7 +336,7 @@ __global__ void __launch_bounds__(64) k_pr_refine(PrParams p) {
         pr_normal(v, &sm, lane);
         if (lane == 0) pr_scale(&sm, false);
       }
-      if (lane == 0) pr_finalize(&sm, p, fresh);
+      if (lane == 0) tr_end_iteration(&sm, sm.opt, fresh);
       __syncthreads();
     }
   }
@@ -460,7 +352,8 @@ __global__ void __launch_bounds__(64) k_pr_refine(PrParams p) {
     for (int i = 0; i < 4; ++i) out->qvec[i] = sm.x.q[i];
     for (int i = 0; i < 3; ++i) out->tvec[i] = sm.x.t[i];
     for (int i = 0; i < 12; ++i) out->camera_params[i] = i < sm.np ? sm.x.prm[i] : cam.params[i];
-    for (int i = 0; i < PR_MARGINS; ++i) p.margins[(size_t)b * PR_MARGINS + i] = sm.mg[i];
+    const double mg[PR_MARGINS] = {sm.m_accept, sm.m_grad, sm.m_func, sm.m_param, sm.m_pivot};
+    for (int i = 0; i < PR_MARGINS; ++i) p.margins[(size_t)b * PR_MARGINS + i] = mg[i];
   }
 }
 
@@ -565,8 +458,9 @@ extern "C" int dsm_refine_absolute_poses(dsm_ctx* ctx, uint32_t num_problems, co
   if (steps_bytes) HIPCHK(ctx, hipMemsetAsync(d.steps.p, 0, steps_bytes, st));
   PrParams prm;
   prm.B = B;
-  prm.max_iter = o.max_num_iterations;
-  prm.gtol = o.gradient_tolerance;
+  prm.tr = tr_ceres_defaults();
+  prm.tr.max_iterations = o.max_num_iterations;
+  prm.tr.gtol = o.gradient_tolerance;
   prm.b = o.loss_function_scale * o.loss_function_scale;  // CauchyLoss(a): b_(a * a), c_(1 / b_)
   prm.c = 1.0 / prm.b;
   prm.cams = d.cams.as<dsm_camera>();
