@@ -12,7 +12,8 @@
     Median                                   src/util/math.h:211-229
 
 Every float32 / float64 operation is element-wise numpy in the type the C++ expression has, sums run in the order the loops run.
-tests/test_vocabulary_build_cpu.py pins this file to the reference's own binary; the device is compared with it."""
+tests/test_vocabulary_build_cpu.py and tests/test_vocabulary_build_edges_cpu.py pin this file to the reference's own binary; the
+device is compared with it."""
 import ctypes
 import sys
 
@@ -166,8 +167,9 @@ class Node:
     __slots__ = ("parent", "pivot", "radius", "variance", "size", "childs", "index")
 
 
-def cluster_node(desc, indices, off, m, branching, iterations, rand, node, nodes):
-    """computeClustering (kmeans_index.h:544-713) of indices[off:off + m]; appends the subtree to nodes in depth-first order."""
+def cluster_node(desc, indices, off, m, branching, iterations, rand, node, nodes, stats=None):
+    """computeClustering (kmeans_index.h:544-713) of indices[off:off + m]; appends the subtree to nodes in depth-first order.
+    stats: a list that receives one record per clustered node (what the tests assert their cases reach); it changes no result."""
     node.size = m
     node.childs = []
     if m < branching:
@@ -182,7 +184,7 @@ def cluster_node(desc, indices, off, m, branching, iterations, rand, node, nodes
         radiuses = np.zeros(b, F32)
         np.maximum.at(radiuses, belongs[~np.isnan(sq)], sq[~np.isnan(sq)])
         count = np.bincount(belongs, minlength=b).astype(np.int64)
-        converged, iteration = False, 0
+        converged, iteration, repairs = False, 0, 0
         while not converged and iteration < iterations:
             converged = True
             iteration += 1
@@ -207,7 +209,11 @@ def cluster_node(desc, indices, off, m, branching, iterations, rand, node, nodes
                     count[j] -= 1
                     count[i] += 1
                     converged = False
+                    repairs += 1
         centers = dcenters.astype(F32)
+        if stats is not None:
+            stats.append({"node": node.index, "size": m, "branching": b, "iterations": iteration, "converged": converged,
+                          "repairs": repairs, "nan_centres": int(np.isnan(centers).any(axis=1).sum())})
         dist_var = l2_groups(centers[belongs] - pts.astype(F32))
         order, ranges = swap_partition(np.arange(m), belongs, b)
         indices[off:off + m] = idx[order]
@@ -226,7 +232,7 @@ def cluster_node(desc, indices, off, m, branching, iterations, rand, node, nodes
             child.variance = seq_sum_f32(dist_var[start:end]) / F32(count[c])
             nodes.append(child)
             node.childs.append(child)
-            cluster_node(desc, indices, off + start, end - start, b, iterations, rand, child, nodes)
+            cluster_node(desc, indices, off + start, end - start, b, iterations, rand, child, nodes, stats)
 
 
 def nan_argmin(d):
@@ -245,8 +251,8 @@ def nan_argmin(d):
     return best, sq
 
 
-def build_tree(desc, branching, iterations, rand=libc_rand):
-    """KMeansIndex::buildIndexImpl: (nodes in depth-first order, the final indices permutation)."""
+def build_tree(desc, branching, iterations, rand=libc_rand, stats=None):
+    """KMeansIndex::buildIndexImpl: (nodes in depth-first order, the final indices permutation).  stats: see cluster_node."""
     sys.setrecursionlimit(max(sys.getrecursionlimit(), 20000))
     desc = np.ascontiguousarray(desc, np.uint8)
     n = len(desc)
@@ -264,7 +270,7 @@ def build_tree(desc, branching, iterations, rand=libc_rand):
         root.variance = seq_sum_f32(dist) / F32(n)
         root.pivot = mean
         nodes = [root]
-        cluster_node(desc, indices, 0, n, branching, iterations, rand, root, nodes)
+        cluster_node(desc, indices, 0, n, branching, iterations, rand, root, nodes, stats)
     return nodes, indices
 
 
@@ -300,12 +306,19 @@ def round_half_away(x):
     return np.floor(x.astype(F64) + 0.5).astype(np.uint8)
 
 
-def quantize(desc, num_visual_words, branching, iterations, rand=libc_rand):
-    """VisualIndex::Quantize: (words [count][128] uint8, float centres, nodes, indices)."""
-    nodes, indices = build_tree(desc, branching, iterations, rand)
+def quantize(desc, num_visual_words, branching, iterations, rand=libc_rand, stats=None):
+    """VisualIndex::Quantize: (words [count][128] uint8, float centres, nodes, indices).  stats: see cluster_node."""
+    nodes, indices = build_tree(desc, branching, iterations, rand, stats)
     clusters = min_variance_clusters(nodes, branching, num_visual_words)
     centres = np.stack([c.pivot for c in clusters]).astype(F32)
     return round_half_away(centres), centres, nodes, indices
+
+
+def same_floats(a_bits, b_bits):
+    """Equal float bits; a NaN (the centre of a cluster the last iteration emptied, 0 * inf) equals a NaN: its sign and payload
+    are the processor's, not the algorithm's."""
+    a, b = a_bits.view(np.float32), b_bits.view(np.float32)
+    return a.shape == b.shape and bool(((a_bits == b_bits) | (np.isnan(a) & np.isnan(b))).all())
 
 
 def tree_arrays(nodes):

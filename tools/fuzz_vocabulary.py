@@ -23,13 +23,6 @@ from tests import vocabulary_build_scenes as scenes  # noqa: E402
 SCHEDULES = (1, 2 ** 31 - 1, 0)
 
 
-def same_floats(a_bits, b_bits):
-    """Equal float bits; a NaN (the centre of a cluster the last iteration emptied, 0 * inf) equals a NaN: its sign and payload
-    are the processor's, not the algorithm's."""
-    a, b = a_bits.view(np.float32), b_bits.view(np.float32)
-    return a.shape == b.shape and bool(((a_bits == b_bits) | (np.isnan(a) & np.isnan(b))).all())
-
-
 def run_fuzz(ctx, n_cases, seed, log=lambda *a: print(*a, flush=True)):
     bad = 0
     for c in range(n_cases):
@@ -70,9 +63,9 @@ def run_fuzz(ctx, n_cases, seed, log=lambda *a: print(*a, flush=True)):
             got_words, got_centres = ctx.retrieval_quantize(d, o, rand=replay, with_centers=True)
             got = ctx.vocabulary_tree()
             same = (replay.pos == len(rec.draws) and got_words.shape == words.shape and (got_words == words).all()
-                    and same_floats(got_centres.view(np.uint32), centres.view(np.uint32)) and len(got[0]) == len(tree[0])
+                    and ref.same_floats(got_centres.view(np.uint32), centres.view(np.uint32)) and len(got[0]) == len(tree[0])
                     and all((g == r).all() for g, r in zip(got[:3], tree[:3]))
-                    and all(same_floats(g, r) for g, r in zip(got[3:6], tree[3:])) and (got[6] == indices).all())
+                    and all(ref.same_floats(g, r) for g, r in zip(got[3:6], tree[3:])) and (got[6] == indices).all())
             ok = ok and same
         projection = np.linalg.qr(rng.normal(size=(128, 128)))[0][:64].astype(np.float32)
         thr, has = ctx.retrieval_train_embedding(d, words, projection)
