@@ -927,7 +927,7 @@ PRODUCT_OPTION_KEYS = ("DSM_MATCH_CHUNK_ROWS", "DSM_VERIFY_CHUNK_PAIRS", "DSM_VE
 CHECK_OPTION_KEYS = ("DSM_K1_DOT4", "DSM_K1_RESOLVE_KERNEL", "DSM_VERIFY_DEBUG", "DSM_SAMPLER_SERIAL", "DSM_LO_PREPARE_WAVE", "DSM_LO_JACOBI_GROUPS", "DSM_ROOTS_LDS",
                      "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT", "DSM_DEBUG_SAMPLER_MODE",
                      "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER", "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
-                     "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES")
+                     "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT")
 DEBUG_OPTION_KEYS = PRODUCT_OPTION_KEYS  # what a deployer's library knows
 
 
@@ -1151,6 +1151,16 @@ class Context:
         v = Vocabulary(num_words=self._voc[0].shape[0], reserved=0, words=self._voc[0].ctypes.data, projection=self._voc[1].ctypes.data,
                        thresholds=self._voc[2].ctypes.data)
         self._chk(self._L.dsm_retrieval_set_vocabulary(self._h, ctypes.byref(v)))
+
+    def debug_solver_fallbacks(self):
+        """dsm_debug_solver_fallbacks: waves of the E / F / H minimal solver that ran the exact pivot norms, then all its waves
+        (check build, DSM_VERIFY_DEBUG)."""
+        L = self._L
+        out = np.zeros(6, np.uint32)
+        L.dsm_debug_solver_fallbacks.restype = ctypes.c_int
+        L.dsm_debug_solver_fallbacks.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._chk(L.dsm_debug_solver_fallbacks(self._h, out.ctypes.data))
+        return out
 
     def debug_verify_counters(self):
         """dsm_debug_verify_counters: 16 statistics counters of the last verify call (DSM_VERIFY_DEBUG / DSM_SCORE_PREFILTER=check)."""

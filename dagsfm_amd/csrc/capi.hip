@@ -931,7 +931,8 @@ static int ensure_nt_tables_t(dsm_ctx* ctx, const dsm_two_view_options* o, const
 // area 64 counters on a 128-byte line each (grab_seg, verify_kernels.hip GRAB_*); laid out so that the counters a phase resets are
 // contiguous: one fill per phase, as before
 #define LANE_CTR_AREA (64 * 128)
-#define LANE_CTR_BYTES (LANE_CTR_AREA + 128 + 3 * LANE_CTR_AREA)
+#define LANE_CTR_NORMS (LANE_CTR_AREA + 128 + 3 * LANE_CTR_AREA)  // eight words behind the hand-out counters, zeroed at lane start only: SOLVER_NORM_CTR
+#define LANE_CTR_BYTES (LANE_CTR_NORMS + 32)
 // What the lanes of one dsm_verify_pairs call share
 struct VerifyPlan {
   uint32_t batch[3] = {0, 0, 0}, bmax = 0;
@@ -1128,6 +1129,7 @@ static void verify_lane_run(dsm_ctx* ctx, uint32_t li, VerifyParams vp, VerifyPl
     LANECHK(L, hipGetLastError());
   }
   if (vp.stats) LANECHK(L, hipMemcpyAsync(L.dbg, actr, 128, hipMemcpyDeviceToHost, st));
+  if (vp.stats) LANECHK(L, hipMemcpyAsync(L.dbg_norms, static_cast<char*>(L.active.p) + LANE_CTR_NORMS, 32, hipMemcpyDeviceToHost, st));
   LANECHK(L, hipEventRecord(L.done, st));
   LANECHK(L, hipStreamSynchronize(st));
 }
@@ -1216,6 +1218,7 @@ static int verify_core(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* d_pairs, 
   vp.sums = nullptr;
   vp.first_batch[0] = vp.first_batch[1] = vp.first_batch[2] = 0;
   vp.stats = ctx->dbg("DSM_VERIFY_DEBUG") ? 1 : 0;
+  vp.norms_exact = ctx->dbg("DSM_NORMS_EXACT") ? 1 : 0;  // (a check-build key: the product's kernels do not read it)
   vp.lo_reg_prepare = ctx->dbg("DSM_LO_PREPARE_WAVE") ? 0 : 1;
   vp.rp_cap = std::min<uint32_t>(n_max, 256u);  // RP_CAP (verify_kernels.hip)
   vp.spec_margin[0] = 8;
@@ -1513,6 +1516,7 @@ static int verify_core(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* d_pairs, 
       L.err.clear();
       for (int f = 0; f < 3; ++f) L.rounds[f] = L.lo_iters[f] = 0;
       memset(L.dbg, 0, sizeof(L.dbg));
+      memset(L.dbg_norms, 0, sizeof(L.dbg_norms));
     }
     ctx->verify_lanes = n_lanes;
     HIPCHK(ctx, hipEventRecord(ctx->vev0, st));
@@ -2028,6 +2032,14 @@ int dsm_debug_verify_counters(dsm_ctx* ctx, uint32_t* out16) {
   for (int k = 0; k < 16; ++k) out16[k] = 0;
   for (uint32_t li = 0; li < ctx->verify_lanes && li < DSM_VERIFY_MAX_LANES; ++li)
     for (int k = 0; k < 16; ++k) out16[k] += ctx->lanes[li].dbg[k];
+  return DSM_OK;
+}
+
+int dsm_debug_solver_fallbacks(dsm_ctx* ctx, uint32_t* out6) {
+  if (!ctx || !out6) return DSM_ERR_INVALID_ARGUMENT;
+  for (int k = 0; k < 6; ++k) out6[k] = 0;
+  for (uint32_t li = 0; li < ctx->verify_lanes && li < DSM_VERIFY_MAX_LANES; ++li)
+    for (int k = 0; k < 6; ++k) out6[k] += ctx->lanes[li].dbg_norms[k];
   return DSM_OK;
 }
 

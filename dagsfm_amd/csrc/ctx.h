@@ -127,6 +127,7 @@ struct VerifyLane {
   DevBuf hyp_map;                                           // the round's hypotheses of all pairs for the compact solver grids (verify_kernels.hip hyp_of_lane)
   uint32_t rounds[3] = {0, 0, 0}, lo_iters[3] = {0, 0, 0};
   uint32_t dbg[32] = {0};
+  uint32_t dbg_norms[8] = {0};  // DSM_VERIFY_DEBUG: wave-solves that ran the exact pivot norms, E / F / H, then all wave-solves, E / F / H
   HostBuf host_ctr;  // pinned read-back target of the lane's counters
   std::string err;
   int rc = 0;
@@ -211,6 +212,7 @@ struct dsm_ctx {
   //                              tools/check_schedules.py and the schedule-parametrised tests compare the product with
   //                              (legacy one-kernel LO-RANSAC, fused / LDS forms of the 5-point root finder,
   //                              the v_dot4 K1 and word assignment, the two-kernel K1 + k1_resolve_index,
+  //                              the minimal solvers' exact pivot-norm bookkeeping in every wave (DSM_NORMS_EXACT),
   //                              counters of DSM_VERIFY_DEBUG / DSM_SCORE_PREFILTER=check)
   std::map<std::string, std::string> debug_options;
   const char* dbg(const char* key) const {
@@ -289,7 +291,7 @@ static const char* const dsm_check_debug_keys[] = {"DSM_K1_DOT4", "DSM_K1_RESOLV
                                                    "DSM_ROOTS_LDS", "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT",
                                                    "DSM_DEBUG_SAMPLER_MODE", "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER",
                                                    "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
-                                                   "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES"};
+                                                   "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT"};
 #endif
 
 #define HIPCHK(ctx, call)                                                              \

@@ -191,6 +191,7 @@ struct VerifyParams {
   int dbg_pose_full;           // check build, DSM_POSE_FULL: k_final_pose_full (every candidate checks every inlier) instead of k_final_pose
   int score_prefilter;         // F / H scoring as bound + exact (k_prescore, k_score_needed); 0: plain k_score (DSM_SCORE_PREFILTER=0)
   int stats;                   // DSM_VERIFY_DEBUG: count candidates / local optimisations (one-address atomics) in the replay
+  int norms_exact;             // check build, DSM_NORMS_EXACT: the minimal solvers' exact pivot-norm bookkeeping for every wave (colpiv_norms.h)
   uint32_t spec_margin[3];     // k_sample: trials a later round speculates beyond what the dynamic stop asks for (samples without a model)
   uint32_t* hyp_map;           // E / F rounds after a pair's first: the round's hypotheses of all pairs, listed by k_sample in 64 segments
   uint32_t hyp_seg_cap;        // (verify_kernels.hip hyp_of_lane); nullptr: the solvers run the (pair, block of 64 trials) grid.  Entries per segment

@@ -150,6 +150,10 @@ DSM_DEV int seven_point_t(const double* xs, double* models, double* At_ext) {
 DSM_DEVN int seven_point(const double* xs, double* models) { return seven_point_t<1>(xs, models, nullptr); }
 // seven_point_t with every array in registers (pr_nullspace_9xm, pr_poly_roots): what the batch kernel k_solve<F> runs.
 // models: 3 x 9, slots beyond the returned count are zero.
+// CERTIFIED: the QR's pivot norms as certified decisions (colpiv_norms.h).  Returns -1, for the whole wave and before the
+// cubic, when a lane of it holds a decision that was not certified: the caller then runs the exact form, which writes the
+// same bytes for the lanes that were certain.
+template <bool CERTIFIED = false>
 DSM_DEV int seven_point_reg(const double (&xs)[28], double (&models)[27]) {
   double At[63];  // A^T, 9 x 7 column-major: At[i*9 + c] = A(i, c)
 #pragma unroll
@@ -160,7 +164,10 @@ DSM_DEV int seven_point_reg(const double (&xs)[28], double (&models)[27]) {
     At[i * 9 + 6] = x0; At[i * 9 + 7] = y0; At[i * 9 + 8] = 1;
   }
   double nv[18];
-  pr_nullspace_9xm<7>(At, nv);
+  const bool certain = pr_nullspace_9xm<7, CERTIFIED>(At, nv);
+  if constexpr (CERTIFIED) {
+    if (__any(!certain)) return -1;
+  }
   double f1[9], f2[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
@@ -278,6 +285,31 @@ template <int K>
 struct H4Step {
   // one step of ColPivHouseholderQR::computeInPlace on a[c][r] (column c, row r), rows = 9, cols = 8
   static DSM_DEV void run(double (&a)[8][9], double (&nu)[8], double (&nd)[8], double (&hco)[8]) {
+    pivot(a, nu, nd);
+    householder(a, hco);
+    downdate(a, nu, nd);
+  }
+  // the same step with the pivot norms as certified decisions (colpiv_norms.h): s / sd are the squared norms; `certain` is
+  // cleared where a decision is too close to call.  The Householder arithmetic is the one function both forms call.
+  static DSM_DEV void run_certified(double (&a)[8][9], double (&s)[8], double (&sd)[8], double (&hco)[8], bool& certain) {
+    pivot(a, s, sd);  // first largest of the squares: the same scan and the same swaps
+#pragma unroll
+    for (int j = K + 1; j < 8; ++j) certain = certain && cpn_pivot_clear(s[K], sd[K], s[j], sd[j]);
+    householder(a, hco);
+#pragma unroll
+    for (int j = K + 1; j < 8; ++j) {
+      if (sd[j] != 0.0) {
+        if (cpn_downdate(s[j], sd[j], a[j][K], certain)) {
+          double ss = 0.0;
+#pragma unroll
+          for (int i = K + 1; i < 9; ++i) ss += a[j][i] * a[j][i];
+          s[j] = sd[j] = ss;
+          certain = certain && cpn_range_ok(ss);
+        }
+      }
+    }
+  }
+  static DSM_DEV void pivot(double (&a)[8][9], double (&nu)[8], double (&nd)[8]) {
     int biggest = K;
     double mx = nu[K];
 #pragma unroll
@@ -302,6 +334,8 @@ struct H4Step {
       nd[K] = sw ? u2 : t2;
       nd[j] = sw ? t2 : u2;
     }
+  }
+  static DSM_DEV void householder(double (&a)[8][9], double (&hco)[8]) {
     // makeHouseholderInPlace on a[K][K..8]
     double tail_sq = 0.0;
 #pragma unroll
@@ -345,6 +379,8 @@ struct H4Step {
         for (int i = K + 1; i < 9; ++i) a[j][i] -= tau * a[K][i] * tmp;
       }
     }
+  }
+  static DSM_DEV void downdate(double (&a)[8][9], double (&nu)[8], double (&nd)[8]) {
     // norm downdating
     const double norm_downdate_threshold = sqrt(DBL_EPSILON);
 #pragma unroll
@@ -369,6 +405,9 @@ struct H4Step {
   }
 };
 
+// CERTIFIED: the pivot norms as certified decisions.  Returns -1, for the whole wave and with nothing written, when a lane of it
+// holds a decision that was not certified: the caller then runs the exact form.
+template <bool CERTIFIED = false>
 DSM_DEV int homography_four_point_reg(const double* xs, double* models) {
   double n1[3], n2[3];
   auto ident = [](int i) { return i; };
@@ -426,22 +465,43 @@ DSM_DEV int homography_four_point_reg(const double* xs, double* models) {
     }
   }
   double nu[8], nd[8], hco[8];
+  if constexpr (CERTIFIED) {
+    bool certain = true;
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    double ss = 0.0;
+    for (int c = 0; c < 8; ++c) {
+      double ss = 0.0;
 #pragma unroll
-    for (int r = 0; r < 9; ++r) ss += a[c][r] * a[c][r];
-    nd[c] = sqrt(ss);
-    nu[c] = nd[c];
+      for (int r = 0; r < 9; ++r) ss += a[c][r] * a[c][r];
+      nu[c] = nd[c] = ss;  // the squares: s and sd of colpiv_norms.h
+      certain = certain && cpn_range_ok(ss);
+    }
+    H4Step<0>::run_certified(a, nu, nd, hco, certain);
+    H4Step<1>::run_certified(a, nu, nd, hco, certain);
+    H4Step<2>::run_certified(a, nu, nd, hco, certain);
+    H4Step<3>::run_certified(a, nu, nd, hco, certain);
+    H4Step<4>::run_certified(a, nu, nd, hco, certain);
+    H4Step<5>::run_certified(a, nu, nd, hco, certain);
+    H4Step<6>::run_certified(a, nu, nd, hco, certain);
+    H4Step<7>::run_certified(a, nu, nd, hco, certain);
+    if (__any(!certain)) return -1;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      double ss = 0.0;
+#pragma unroll
+      for (int r = 0; r < 9; ++r) ss += a[c][r] * a[c][r];
+      nd[c] = sqrt(ss);
+      nu[c] = nd[c];
+    }
+    H4Step<0>::run(a, nu, nd, hco);
+    H4Step<1>::run(a, nu, nd, hco);
+    H4Step<2>::run(a, nu, nd, hco);
+    H4Step<3>::run(a, nu, nd, hco);
+    H4Step<4>::run(a, nu, nd, hco);
+    H4Step<5>::run(a, nu, nd, hco);
+    H4Step<6>::run(a, nu, nd, hco);
+    H4Step<7>::run(a, nu, nd, hco);
   }
-  H4Step<0>::run(a, nu, nd, hco);
-  H4Step<1>::run(a, nu, nd, hco);
-  H4Step<2>::run(a, nu, nd, hco);
-  H4Step<3>::run(a, nu, nd, hco);
-  H4Step<4>::run(a, nu, nd, hco);
-  H4Step<5>::run(a, nu, nd, hco);
-  H4Step<6>::run(a, nu, nd, hco);
-  H4Step<7>::run(a, nu, nd, hco);
   double q[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) q[i] = (i == 8) ? 1.0 : 0.0;
@@ -702,8 +762,10 @@ DSM_DEV void five_point_basis(const double* xs, double* Eb) {
   for (int r = 0; r < 9; ++r)
     for (int c = 0; c < 4; ++c) Eb[r * 4 + c] = nv[c * 9 + r];
 }
-// five_point_basis with the 9 x 5 matrix in registers (batch kernels)
-DSM_DEV void five_point_basis_reg(const double (&xs)[20], double (&Eb)[36]) {
+// five_point_basis with the 9 x 5 matrix in registers (batch kernels).  CERTIFIED as in seven_point_reg: false, for the whole
+// wave, when a lane's pivot decision was not certified and the exact form has to run.
+template <bool CERTIFIED = false>
+DSM_DEV bool five_point_basis_reg(const double (&xs)[20], double (&Eb)[36]) {
   double At[45];  // Q^T, 9 x 5
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
@@ -713,12 +775,14 @@ DSM_DEV void five_point_basis_reg(const double (&xs)[20], double (&Eb)[36]) {
     At[i * 9 + 6] = x1_0; At[i * 9 + 7] = x1_1; At[i * 9 + 8] = 1;
   }
   double nv[36];  // columns 5..8 of V, nv[c*9 + r]
-  pr_nullspace_9xm<5>(At, nv);
+  const bool certain = pr_nullspace_9xm<5, CERTIFIED>(At, nv);
 #pragma unroll
   for (int r = 0; r < 9; ++r) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) Eb[r * 4 + c] = nv[c * 9 + r];
   }
+  if constexpr (CERTIFIED) return !__any(!certain);
+  return true;
 }
 DSM_DEVN int five_point_minimal(const double* xs, double* models) {
   double Eb[36];

@@ -1992,6 +1992,32 @@ DSM_DEV bool hyp_of_lane(const VerifyParams& p, int fam, uint32_t& pl, int& t) {
   t = blockIdx.y * 64 + threadIdx.x;
   return t < (int)fs->nb;
 }
+// The lane-per-hypothesis minimal solvers (k_solve<F>, k_solve<H>, k_solve_e_build) run their pivoted QR with the pivot norms as
+// certified decisions (colpiv_norms.h) and, where a lane of the wave holds a decision that was not certified, once more in the
+// exact form: the same slots, the same bytes, one extra solve for that wave.  Check build: DSM_NORMS_EXACT runs the exact form
+// for every wave, and DSM_VERIFY_DEBUG counts the waves (dsm_debug_solver_fallbacks).
+#define SOLVER_NORM_CTR(p) ((p).active_count + 32 + 3 * GRAB_AREA_WORDS)  // capi.hip LANE_CTR_NORMS
+DSM_DEV bool solver_norms_exact(const VerifyParams& p) {
+#ifdef DSM_CHECK_BUILD
+  return p.norms_exact != 0;
+#else
+  return false;
+#endif
+}
+DSM_DEV uint32_t solver_norms_opaque_zero() {  // 0, as a value the optimiser knows nothing about (no instruction)
+  uint32_t z = 0;
+  asm volatile("" : "+v"(z));
+  return z;
+}
+template <int FAM>
+DSM_DEV void solver_norms_count(const VerifyParams& p, bool exact_ran) {
+#ifdef DSM_CHECK_BUILD
+  if (p.stats && (int)threadIdx.x == __ffsll((long long)__ballot(1)) - 1) {  // the wave's first lane with a trial
+    atomicAdd(SOLVER_NORM_CTR(p) + 3 + FAM, 1u);
+    if (exact_ran) atomicAdd(SOLVER_NORM_CTR(p) + FAM, 1u);
+  }
+#endif
+}
 // F and H: solver and inlier counting as two kernels.  k_solve keeps the solver's working set (F: the 9 x 7
 // matrix in lane-interleaved LDS; H: ~220 VGPRs) away from the counting loop, which is pure FP64 VALU work
 // with a 9-double model per lane and wants many resident waves; k_score gives every (trial, model) slot its
@@ -2006,17 +2032,37 @@ __global__ __launch_bounds__(64, 2) void k_solve(const VerifyParams p) {
   const double* pts = p.pts_px + 4 * p.match_off[pi];
   const uint32_t* smp = p.samples + ((size_t)pl * p.batch + t) * 7;
   double xs[F::K * 4];
+  auto load_sample = [&](uint32_t z) {
 #pragma unroll
-  for (int i = 0; i < F::K; ++i) {
-    const double* q = pts + (size_t)smp[i] * 4;
-    xs[i * 4 + 0] = q[0]; xs[i * 4 + 1] = q[1]; xs[i * 4 + 2] = q[2]; xs[i * 4 + 3] = q[3];
-  }
+    for (int i = 0; i < F::K; ++i) {
+      const double* q = pts + (size_t)smp[z + i] * 4;
+      xs[i * 4 + 0] = q[0]; xs[i * 4 + 1] = q[1]; xs[i * 4 + 2] = q[2]; xs[i * 4 + 3] = q[3];
+    }
+  };
   double mloc[F::MAXM * 9];
-  int nm;
-  if constexpr (FAM == FAM_F)
-    nm = seven_point_reg(xs, mloc);  // 9 x 7 pivoted QR, cubic roots: all in registers
-  else
-    nm = fam_minimal<FAM>(xs, mloc);
+  int nm = -1;
+  if (!solver_norms_exact(p)) {
+    load_sample(0);
+    if constexpr (FAM == FAM_F)
+      nm = seven_point_reg<true>(xs, mloc);  // 9 x 7 pivoted QR, cubic roots: all in registers
+    else
+      nm = homography_four_point_reg<true>(xs, mloc);
+  }
+  // The same in every lane, and said so: behind a branch the compiler takes for divergent the certified solve's models would
+  // stay in registers across the whole exact solve (for the lanes that might not take it).
+  const bool exact = __builtin_amdgcn_readfirstlane((int)(nm < 0)) != 0;
+  solver_norms_count<FAM>(p, exact);
+  if (exact) {
+    // The sample is READ again, through an offset the optimiser cannot see through: otherwise it keeps the first read's matrix
+    // alive across the certified solve for this block to reuse, and the solver no longer fits the register file.
+    load_sample(solver_norms_opaque_zero());
+#pragma unroll
+    for (int k = 0; k < F::MAXM * 9; ++k) mloc[k] = 0.0;  // (nothing of the certified solve lives on: seven_point_reg has exits that write no model)
+    if constexpr (FAM == FAM_F)
+      nm = seven_point_reg(xs, mloc);
+    else
+      nm = homography_four_point_reg(xs, mloc);
+  }
   p.nmodels[(size_t)pl * p.batch + t] = nm;
   double* gm = p.models + ((size_t)pl * p.batch + t) * F::MAXM * 9;
 #pragma unroll
@@ -2795,13 +2841,25 @@ __global__ __launch_bounds__(64, 2) void k_solve_e_build(const VerifyParams p) {
   const double* pts = p.pts_norm + 4 * p.match_off[pi];
   const uint32_t* smp = p.samples + ((size_t)pl * p.batch + t) * 7;
   double xs[20];
+  auto load_sample = [&](uint32_t z) {
 #pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    const double* q = pts + (size_t)smp[i] * 4;
-    xs[i * 4 + 0] = q[0]; xs[i * 4 + 1] = q[1]; xs[i * 4 + 2] = q[2]; xs[i * 4 + 3] = q[3];
-  }
+    for (int i = 0; i < 5; ++i) {
+      const double* q = pts + (size_t)smp[z + i] * 4;
+      xs[i * 4 + 0] = q[0]; xs[i * 4 + 1] = q[1]; xs[i * 4 + 2] = q[2]; xs[i * 4 + 3] = q[3];
+    }
+  };
   double Eb[36];
-  five_point_basis_reg(xs, Eb);
+  bool exact = true;
+  if (!solver_norms_exact(p)) {
+    load_sample(0);
+    exact = !five_point_basis_reg<true>(xs, Eb);
+  }
+  exact = __builtin_amdgcn_readfirstlane((int)exact) != 0;  // (wave-uniform, and a fresh read of the sample: see k_solve)
+  solver_norms_count<FAM_E>(p, exact);
+  if (exact) {
+    load_sample(solver_norms_opaque_zero());
+    five_point_basis_reg(xs, Eb);
+  }
   double* slot = p.models + ((size_t)pl * p.batch + t) * 90;
   for (int k = 0; k < 36; ++k) slot[EPOLY_EB + k] = Eb[k];
   // the wave's 64 hypotheses interleaved: element e of lane l at block + e * 64 + l (batch is a multiple of 64)

@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <float.h>
 
+#include "colpiv_norms.h"
+
 #include <type_traits>
 #include <stdint.h>
 
@@ -229,6 +231,57 @@ DSM_DEV void pl_nullspace_9xm(double* At, int m, int first, double* out) {
 // pl_colpiv_qr / pl_householder_q_col / pl_nullspace_9xm for a 9 x M matrix held in registers: every loop is unrolled
 // over its static range and the one data-dependent index -- the pivot column -- becomes a chain of predicated column
 // swaps.  Same operations in the same order as the pl_ routines (which the single-kernel reference schedule keeps).
+// one step of the factorisation proper on a register matrix: pl_make_householder on rows k..8 of column k, then
+// pl_apply_householder_left to the columns behind it.  Shared by the exact and the certified bookkeeping below: the
+// arithmetic that reaches a model is stated once.
+template <int M>
+DSM_DEV void pr_householder_step9(double (&qr)[9 * M], double (&hco)[M], const int k) {
+#define QRE(i, k) qr[(k) * 9 + (i)]
+  // pl_make_householder on rows k..8 of column k
+  double tail_sq = 0.0;
+#pragma unroll
+  for (int i = k + 1; i < 9; ++i) tail_sq += QRE(i, k) * QRE(i, k);
+  const double c0 = QRE(k, k);
+  double tau, beta;
+  if (tail_sq <= DBL_MIN) {
+    tau = 0.0;
+    beta = c0;
+#pragma unroll
+    for (int i = k + 1; i < 9; ++i) QRE(i, k) = 0.0;
+  } else {
+    double b = sqrt(c0 * c0 + tail_sq);
+    if (c0 >= 0.0) b = -b;
+    const SharedDivisor hd = shared_divisor(c0 - b);
+    double mn = 0x1p1000;
+#pragma unroll
+    for (int i = k + 1; i < 9; ++i) mn = fmin(mn, fabs(QRE(i, k)));
+    if (div_shared_group_ok(hd, mn)) {
+#pragma unroll
+      for (int i = k + 1; i < 9; ++i) QRE(i, k) = div_shared_fast(QRE(i, k), hd);
+    } else {
+#pragma unroll
+      for (int i = k + 1; i < 9; ++i) QRE(i, k) = QRE(i, k) / (c0 - b);
+    }
+    tau = (b - c0) / b;
+    beta = b;
+  }
+  hco[k] = tau;
+  QRE(k, k) = beta;
+  if (tau != 0.0) {  // rows k..8 (never a single row: k <= M - 1 <= 7)
+#pragma unroll
+    for (int j = k + 1; j < M; ++j) {
+      double tmp = 0.0;
+#pragma unroll
+      for (int i = k + 1; i < 9; ++i) tmp += QRE(i, k) * QRE(i, j);
+      tmp += QRE(k, j);
+      QRE(k, j) -= tau * tmp;
+#pragma unroll
+      for (int i = k + 1; i < 9; ++i) QRE(i, j) -= tau * QRE(i, k) * tmp;
+    }
+  }
+#undef QRE
+}
+
 template <int M>
 DSM_DEV void pr_colpiv_qr9(double (&qr)[9 * M], double (&hco)[M]) {
 #define QRE(i, k) qr[(k) * 9 + (i)]
@@ -269,48 +322,7 @@ DSM_DEV void pr_colpiv_qr9(double (&qr)[9 * M], double (&hco)[M]) {
       norms_direct[k] = sw ? db : da;
       norms_direct[j] = sw ? da : db;
     }
-    // pl_make_householder on rows k..8 of column k
-    double tail_sq = 0.0;
-#pragma unroll
-    for (int i = k + 1; i < 9; ++i) tail_sq += QRE(i, k) * QRE(i, k);
-    const double c0 = QRE(k, k);
-    double tau, beta;
-    if (tail_sq <= DBL_MIN) {
-      tau = 0.0;
-      beta = c0;
-#pragma unroll
-      for (int i = k + 1; i < 9; ++i) QRE(i, k) = 0.0;
-    } else {
-      double b = sqrt(c0 * c0 + tail_sq);
-      if (c0 >= 0.0) b = -b;
-      const SharedDivisor hd = shared_divisor(c0 - b);
-      double mn = 0x1p1000;
-#pragma unroll
-      for (int i = k + 1; i < 9; ++i) mn = fmin(mn, fabs(QRE(i, k)));
-      if (div_shared_group_ok(hd, mn)) {
-#pragma unroll
-        for (int i = k + 1; i < 9; ++i) QRE(i, k) = div_shared_fast(QRE(i, k), hd);
-      } else {
-#pragma unroll
-        for (int i = k + 1; i < 9; ++i) QRE(i, k) = QRE(i, k) / (c0 - b);
-      }
-      tau = (b - c0) / b;
-      beta = b;
-    }
-    hco[k] = tau;
-    QRE(k, k) = beta;
-    if (tau != 0.0) {  // rows k..8 (never a single row: k <= M - 1 <= 7)
-#pragma unroll
-      for (int j = k + 1; j < M; ++j) {
-        double tmp = 0.0;
-#pragma unroll
-        for (int i = k + 1; i < 9; ++i) tmp += QRE(i, k) * QRE(i, j);
-        tmp += QRE(k, j);
-        QRE(k, j) -= tau * tmp;
-#pragma unroll
-        for (int i = k + 1; i < 9; ++i) QRE(i, j) -= tau * QRE(i, k) * tmp;
-      }
-    }
+    pr_householder_step9<M>(qr, hco, k);
 #pragma unroll
     for (int j = k + 1; j < M; ++j) {
       if (norms_updated[j] != 0.0) {
@@ -334,6 +346,69 @@ DSM_DEV void pr_colpiv_qr9(double (&qr)[9 * M], double (&hco)[M]) {
 #undef QRE
 }
 
+// pr_colpiv_qr9 with the pivot norms kept as certified decisions (colpiv_norms.h): squared norms, one multiply and one subtract
+// per step and column instead of two divisions and a square root.  Returns whether every decision was certified; where it
+// was, qr and hco hold the bits pr_colpiv_qr9 leaves.  Where not, they hold nothing the caller may use.
+template <int M>
+DSM_DEV bool pr_colpiv_qr9_certified(double (&qr)[9 * M], double (&hco)[M]) {
+#define QRE(i, k) qr[(k) * 9 + (i)]
+  double s[M], sd[M];
+  bool certain = true;
+#pragma unroll
+  for (int k = 0; k < M; ++k) {
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) ss += QRE(i, k) * QRE(i, k);
+    s[k] = sd[k] = ss;
+    certain = certain && cpn_range_ok(ss);
+  }
+#pragma unroll
+  for (int k = 0; k < M; ++k) {
+    int biggest = k;
+    double mx = s[k];
+#pragma unroll
+    for (int j = k + 1; j < M; ++j) {
+      if (s[j] > mx) {
+        mx = s[j];
+        biggest = j;
+      }
+    }
+#pragma unroll
+    for (int j = k + 1; j < M; ++j) {
+      const bool sw = (j == biggest);
+#pragma unroll
+      for (int i = 0; i < 9; ++i) {
+        const double a = QRE(i, k), b = QRE(i, j);
+        QRE(i, k) = sw ? b : a;
+        QRE(i, j) = sw ? a : b;
+      }
+      const double ua = s[k], ub = s[j];
+      s[k] = sw ? ub : ua;
+      s[j] = sw ? ua : ub;
+      const double da = sd[k], db = sd[j];
+      sd[k] = sw ? db : da;
+      sd[j] = sw ? da : db;
+    }
+#pragma unroll
+    for (int j = k + 1; j < M; ++j) certain = certain && cpn_pivot_clear(s[k], sd[k], s[j], sd[j]);
+    pr_householder_step9<M>(qr, hco, k);
+#pragma unroll
+    for (int j = k + 1; j < M; ++j) {
+      if (sd[j] != 0.0) {
+        if (cpn_downdate(s[j], sd[j], QRE(k, j), certain)) {
+          double ss = 0.0;
+#pragma unroll
+          for (int i = k + 1; i < 9; ++i) ss += QRE(i, j) * QRE(i, j);
+          s[j] = sd[j] = ss;
+          certain = certain && cpn_range_ok(ss);
+        }
+      }
+    }
+  }
+#undef QRE
+  return certain;
+}
+
 // column J of householderQ() (9 x 9) of the pivoted QR above
 template <int M, int J>
 DSM_DEV void pr_householder_q_col9(const double (&qr)[9 * M], const double (&hco)[M], double (&q)[9]) {
@@ -355,9 +430,11 @@ DSM_DEV void pr_householder_q_col9(const double (&qr)[9 * M], const double (&hco
   }
 }
 
-// pl_nullspace_9xm for an M-column A^T in registers: columns M..8 of V into out[(c - M) * 9 + r]
-template <int M>
-DSM_DEV void pr_nullspace_9xm(double (&At)[9 * M], double (&out)[(9 - M) * 9]) {
+// pl_nullspace_9xm for an M-column A^T in registers: columns M..8 of V into out[(c - M) * 9 + r].
+// CERTIFIED: the pivot norms as certified decisions; returns false where one was not certified (out is then to be discarded
+// and the exact form run: the callers do that for the whole wave).  The exact form returns true.
+template <int M, bool CERTIFIED = false>
+DSM_DEV bool pr_nullspace_9xm(double (&At)[9 * M], double (&out)[(9 - M) * 9]) {
   double scale = 0.0;
 #pragma unroll
   for (int i = 0; i < 9 * M; ++i) {
@@ -379,7 +456,11 @@ DSM_DEV void pr_nullspace_9xm(double (&At)[9 * M], double (&out)[(9 - M) * 9]) {
     }
   }
   double hco[M];
-  pr_colpiv_qr9<M>(At, hco);
+  bool certain = true;
+  if constexpr (CERTIFIED)
+    certain = pr_colpiv_qr9_certified<M>(At, hco);
+  else
+    pr_colpiv_qr9<M>(At, hco);
   double q[9];
   if constexpr (M <= 8) {
     pr_householder_q_col9<M, 8>(At, hco, q);
@@ -401,6 +482,7 @@ DSM_DEV void pr_nullspace_9xm(double (&At)[9 * M], double (&out)[(9 - M) * 9]) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) out[(5 - M) * 9 + i] = q[i];
   }
+  return certain;
 }
 
 // makeJacobi(x, y, z)

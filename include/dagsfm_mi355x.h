@@ -314,6 +314,12 @@ int dsm_debug_sample_sequence(dsm_ctx* ctx, uint32_t seed, uint32_t k, uint32_t 
  * the bound step would have skipped. */
 int dsm_debug_verify_counters(dsm_ctx* ctx, uint32_t* out16);
 
+/* Test hook: how often the minimal solvers of the last dsm_verify_pairs call that ran with DSM_VERIFY_DEBUG fell back from the
+ * certified pivot norms to the exact bookkeeping (6 uint32, summed over the lanes, counted per wave of 64 solves): [0..2] waves
+ * of the E / F / H solver that ran the exact form, [3..5] all waves of that solver.  All zero on the product library, whose
+ * kernels do not count. */
+int dsm_debug_solver_fallbacks(dsm_ctx* ctx, uint32_t* out6);
+
 /* Test hook: Camera::ImageToWorld (src/base/camera.cc:210-214) of n pixel points (x, y) on the device. */
 int dsm_debug_image_to_world(dsm_ctx* ctx, const dsm_camera* camera, uint32_t n, const double* xy, double* out_uv);
 
