@@ -424,6 +424,28 @@ class MvsImage(ctypes.Structure):
 PATCH_MATCH_STAGES = ("upload", "reference_filter", "initial_cost", "sweeps", "rotation", "download")
 
 
+class StereoFusionOptions(ctypes.Structure):
+    """dsm_stereo_fusion_options: StereoFusionOptions (src/mvs/fusion.h:55-85) + the scheduling field lane_capacity."""
+    _fields_ = [("min_num_pixels", ctypes.c_int32), ("max_num_pixels", ctypes.c_int32), ("max_traversal_depth", ctypes.c_int32),
+                ("lane_capacity", ctypes.c_int32), ("max_reproj_error", ctypes.c_double), ("max_depth_error", ctypes.c_double),
+                ("max_normal_error", ctypes.c_double)]
+
+
+class FusionImage(ctypes.Structure):
+    """dsm_fusion_image: the maps, the bitmap and the matrices of one image (dsm_fuse_stereo)."""
+    _fields_ = [("used", ctypes.c_int32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("bitmap_width", ctypes.c_uint32),
+                ("bitmap_height", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("row_stride", ctypes.c_uint64),
+                ("depth_map", ctypes.c_void_p), ("normal_map", ctypes.c_void_p), ("rgb", ctypes.c_void_p),
+                ("P", ctypes.c_float * 12), ("inv_P", ctypes.c_float * 12), ("inv_R", ctypes.c_float * 9),
+                ("bitmap_scale", ctypes.c_float * 2), ("reserved2", ctypes.c_uint32)]
+
+
+FUSED_POINT_DTYPE = np.dtype([("xyz", "<f4", 3), ("normal", "<f4", 3), ("rgb", "u1", 3), ("reserved", "u1")])  # dsm_fused_point
+STEREO_FUSION_STAGES = ("upload", "traversal", "claims_commit", "medians", "download", "rounds", "traversals")
+# the host build of csrc/stereo_fusion.h: StereoFusion::Run on one CPU thread from the kernels' text (DESIGN.md 26)
+FUSION_HOST_LIB_PATH = os.path.join(_HERE, "libdsm_stereo_fusion_host.so")
+
+
 class VocabularyBuildOptions(ctypes.Structure):
     """dsm_vocabulary_build_options: VisualIndex::BuildOptions (src/retrieval/visual_index.h:99-118) + the scheduling field."""
     _fields_ = [("num_visual_words", ctypes.c_int32), ("branching", ctypes.c_int32), ("num_iterations", ctypes.c_int32),
@@ -567,6 +589,12 @@ def lib(check=False):
         L.dsm_default_patch_match_options.restype = None
         L.dsm_patch_match.argtypes = [vp, ctypes.POINTER(PatchMatchOptions), ctypes.c_uint32, vp, ctypes.c_uint32] + [vp] * 9
         L.dsm_get_patch_match_time.argtypes = [vp, vp]
+        L.dsm_default_stereo_fusion_options.argtypes = [ctypes.POINTER(StereoFusionOptions)]
+        L.dsm_default_stereo_fusion_options.restype = None
+        L.dsm_fuse_stereo.argtypes = [vp, ctypes.POINTER(StereoFusionOptions), ctypes.c_uint32, vp, vp, vp, u64p]
+        L.dsm_get_fused_points.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64]
+        L.dsm_get_stereo_fusion_time.argtypes = [vp, vp]
+        L.dsm_get_stereo_fusion_rounds.argtypes = [vp, vp, vp, ctypes.c_uint32]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
         L.dsm_default_match_options.restype = None
         L.dsm_default_two_view_options.argtypes = [ctypes.POINTER(TwoViewOptions)]
@@ -775,6 +803,213 @@ def read_mvs_array(path):
     return np.frombuffer(parts[3], dtype="<f4").astype(np.float32).reshape(c, h, w)
 
 
+def default_stereo_fusion_options(**kw):
+    o = StereoFusionOptions()
+    lib().dsm_default_stereo_fusion_options(ctypes.byref(o))
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
+def fusion_matrices(K, R, T, scale_x=1.0, scale_y=1.0):
+    """P [12], inv_P [12], inv_R [9] float32 as StereoFusion::Run composes them (src/mvs/fusion.cc:220-235) from the float K, R,
+    T of an mvs::Image and the bitmap scales, by the ruling of DESIGN.md 24 / 26 where Eigen fixes no order: K's focal lengths
+    and principal point times the scales in float; P = [K R | K T] with every entry summed left to right in float; inv_P = the
+    top rows of [P; 0 0 0 1]^-1 = [M^-1 | -M^-1 p] with M^-1 the adjugate of P's left block over its determinant in double
+    (entries and the product summed left to right), rounded to float once; inv_R = R^T.  A host with Eigen passes
+    ComposeProjectionMatrix's own bits to dsm_fuse_stereo instead."""
+    f32 = np.float32
+    K = np.asarray(K, dtype=f32).reshape(3, 3).copy()
+    R = np.asarray(R, dtype=f32).reshape(3, 3)
+    T = np.asarray(T, dtype=f32).reshape(3)
+    sx, sy = f32(scale_x), f32(scale_y)
+    K[0, 0] *= sx
+    K[0, 2] *= sx
+    K[1, 1] *= sy
+    K[1, 2] *= sy
+    P = np.zeros((3, 4), dtype=f32)
+    for r in range(3):
+        for c in range(3):
+            P[r, c] = (K[r, 0] * R[0, c] + K[r, 1] * R[1, c]) + K[r, 2] * R[2, c]
+        P[r, 3] = (K[r, 0] * T[0] + K[r, 1] * T[1]) + K[r, 2] * T[2]
+    m = P[:, :3].astype(np.float64)
+    adj = np.zeros((3, 3))
+    for r in range(3):
+        for c in range(3):
+            r1, r2, c1, c2 = (c + 1) % 3, (c + 2) % 3, (r + 1) % 3, (r + 2) % 3
+            adj[r, c] = m[r1, c1] * m[r2, c2] - m[r1, c2] * m[r2, c1]
+    det = (m[0, 0] * adj[0, 0] + m[0, 1] * adj[1, 0]) + m[0, 2] * adj[2, 0]
+    inv = adj / det
+    p = P[:, 3].astype(np.float64)
+    inv_P = np.zeros((3, 4), dtype=f32)
+    inv_P[:, :3] = inv
+    for r in range(3):
+        inv_P[r, 3] = -((inv[r, 0] * p[0] + inv[r, 1] * p[1]) + inv[r, 2] * p[2])
+    return P.reshape(12), inv_P.reshape(12), np.ascontiguousarray(R.T).reshape(9)
+
+
+def overlapping_images(tracks, n_images, num_images):
+    """Model::GetMaxOverlappingImages (src/mvs/model.cc:119-169) with the triangulation-angle gate at fusion's 0 (fusion.cc:
+    171-174), where it passes every image: per image the up to num_images images that share the most sparse points with it
+    (ComputeSharedPoints :218-233; tracks = the image indices of every point, repeats counted as the reference counts them),
+    most shared first.  The reference's std::sort / std::partial_sort leave the order of equal counts open; here a tie goes to
+    the lower image index."""
+    shared = [dict() for _ in range(n_images)]
+    for track in tracks:
+        track = [int(t) for t in track]
+        for i in range(len(track)):
+            for j in range(i):
+                a, b = track[i], track[j]
+                if a != b:
+                    shared[a][b] = shared[a].get(b, 0) + 1
+                    shared[b][a] = shared[b].get(a, 0) + 1
+    return [[b for b, _ in sorted(s.items(), key=lambda kv: (-kv[1], kv[0]))[:int(num_images)]] for s in shared]
+
+
+def write_fused_ply(path, points, normals, colours):
+    """WriteBinaryPlyPoints (src/util/ply.cc:329-381) with normals and colours: its header, then per point x, y, z, nx, ny, nz
+    as little-endian floats and red, green, blue as bytes -- stereo_fusion's fused.ply."""
+    points = np.asarray(points, dtype="<f4").reshape(-1, 3)
+    normals = np.asarray(normals, dtype="<f4").reshape(-1, 3)
+    colours = np.asarray(colours, dtype=np.uint8).reshape(-1, 3)
+    assert len(points) == len(normals) == len(colours)
+    rec = np.zeros(len(points), dtype=np.dtype([("p", "<f4", 3), ("n", "<f4", 3), ("c", "u1", 3)]))
+    rec["p"], rec["n"], rec["c"] = points, normals, colours
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(points)]
+    header += ["property float %s" % k for k in ("x", "y", "z", "nx", "ny", "nz")]
+    header += ["property uchar %s" % k for k in ("red", "green", "blue")] + ["end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def read_fused_ply(path):
+    """What write_fused_ply wrote -> (points [N][3], normals [N][3] float32, colours [N][3] uint8)."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    end = blob.index(b"end_header\n") + len(b"end_header\n")
+    header = blob[:end].decode("ascii").split("\n")
+    n = int([h for h in header if h.startswith("element vertex")][0].split()[2])
+    rec = np.frombuffer(blob[end:], dtype=np.dtype([("p", "<f4", 3), ("n", "<f4", 3), ("c", "u1", 3)]))
+    if len(rec) != n:
+        raise DsmError("%s: %d vertices announced, %d found" % (path, n, len(rec)))
+    return rec["p"].copy(), rec["n"].copy(), rec["c"].copy()
+
+
+def write_points_visibility(path, visibility):
+    """WritePointsVisibility (src/mvs/fusion.cc:475-489, the format of fusion.h:160-171): the number of points as uint64, then
+    per point its number of images and their indices as uint32, little endian -- fused.ply.vis."""
+    with open(path, "wb") as f:
+        f.write(np.array([len(visibility)], dtype="<u8").tobytes())
+        for v in visibility:
+            f.write(np.array([len(v)] + [int(i) for i in v], dtype="<u4").tobytes())
+
+
+def read_points_visibility(path):
+    """What write_points_visibility wrote -> a list of lists of image indices."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    n = int(np.frombuffer(blob[:8], dtype="<u8")[0])
+    words = np.frombuffer(blob[8:], dtype="<u4")
+    out, at = [], 0
+    for _ in range(n):
+        k = int(words[at])
+        out.append(words[at + 1:at + 1 + k].tolist())
+        at += 1 + k
+    if at != len(words):
+        raise DsmError("%s: trailing data" % path)
+    return out
+
+
+def _fusion_call_arguments(images, overlap):
+    """The dsm_fusion_image array and the overlap lists of a fusion call from image dicts: used, depth [h][w], normal [3][h][w]
+    float32, rgb [bh][bw][3] uint8 (any row stride), P [12], inv_P [12], inv_R [9]; scale [2] defaults to the reference's
+    float(width) / bitmap_width (fusion.cc:216-218).  An unused image needs no other key.  -> (array, offsets, indices, keep)."""
+    arr = (FusionImage * max(len(images), 1))()
+    keep = []
+    for i, im in enumerate(images):
+        a = arr[i]
+        a.used = 1 if im.get("used", True) else 0
+        if not a.used and "depth" not in im:
+            continue
+        depth = np.ascontiguousarray(im["depth"], dtype=np.float32)
+        normal = np.ascontiguousarray(im["normal"], dtype=np.float32)
+        rgb = np.asarray(im["rgb"], dtype=np.uint8)
+        assert depth.ndim == 2 and normal.shape == (3,) + depth.shape and rgb.ndim == 3 and rgb.shape[2] == 3
+        if rgb.strides[2] != 1 or rgb.strides[1] != 3:
+            rgb = np.ascontiguousarray(rgb)
+        keep += [depth, normal, rgb]
+        a.height, a.width = depth.shape
+        a.bitmap_height, a.bitmap_width = rgb.shape[:2]
+        a.row_stride = im.get("row_stride", rgb.strides[0])
+        a.depth_map, a.normal_map, a.rgb = depth.ctypes.data, normal.ctypes.data, rgb.ctypes.data
+        a.P[:] = np.asarray(im["P"], dtype=np.float32).reshape(12).tolist()
+        a.inv_P[:] = np.asarray(im["inv_P"], dtype=np.float32).reshape(12).tolist()
+        a.inv_R[:] = np.asarray(im["inv_R"], dtype=np.float32).reshape(9).tolist()
+        scale = im.get("scale")
+        if scale is None:
+            scale = (np.float32(a.width) / np.float32(a.bitmap_width), np.float32(a.height) / np.float32(a.bitmap_height))
+        a.bitmap_scale[:] = [float(np.float32(scale[0])), float(np.float32(scale[1]))]
+    assert len(overlap) == len(images), "one overlap list per image"
+    offs = np.zeros(len(images) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(v) for v in overlap])
+    idx = np.array([int(i) for v in overlap for i in v] + [0], dtype=np.int64)
+    assert idx.min() >= 0 and idx.max() < 2 ** 32
+    idx = idx.astype(np.uint32)
+    keep += [offs, idx]
+    return arr, offs, idx, keep
+
+
+def fusion_host_lib():
+    """libdsm_stereo_fusion_host.so, the host build of csrc/stereo_fusion.h; raises if it has not been built."""
+    if "fusion_host" not in _libs:
+        if not os.path.exists(FUSION_HOST_LIB_PATH):
+            raise DsmError("%s is missing: run make -C dagsfm_amd/csrc" % FUSION_HOST_LIB_PATH)
+        L = ctypes.CDLL(FUSION_HOST_LIB_PATH)
+        vp = ctypes.c_void_p
+        L.dsm_fusion_host_run.argtypes = [ctypes.POINTER(StereoFusionOptions), ctypes.c_uint32, vp, vp, vp, u64p, u64p, ctypes.POINTER(ctypes.c_char_p)]
+        L.dsm_fusion_host_get.argtypes = [vp, vp, vp]
+        L.dsm_fusion_host_get.restype = None
+        L.dsm_fusion_host_default_options.argtypes = [ctypes.POINTER(StereoFusionOptions)]
+        L.dsm_fusion_host_default_options.restype = None
+        _libs["fusion_host"] = L
+    return _libs["fusion_host"]
+
+
+def fusion_host(images, overlap, options=None, **kw):
+    """StereoFusion::Run on one CPU thread by the host build of the kernels' header (no GPU, no context).  The arguments and
+    the first four results are Context.stereo_fusion's; then the final masks of all used images back to back and the number
+    of seed traversals."""
+    L = fusion_host_lib()
+    assert options is None or not kw, "pass a StereoFusionOptions or keywords, not both"
+    o = options
+    if o is None:
+        o = StereoFusionOptions()
+        L.dsm_fusion_host_default_options(ctypes.byref(o))
+        for k, v in kw.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+    arr, offs, idx, keep = _fusion_call_arguments(images, overlap)
+    n, trav, why = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_char_p()
+    rc = L.dsm_fusion_host_run(ctypes.byref(o), len(images), ctypes.addressof(arr), offs.ctypes.data, idx.ctypes.data, ctypes.byref(n),
+                               ctypes.byref(trav), ctypes.byref(why))
+    if rc != 0:
+        err = DsmError("dsm_fusion_host_run failed (%d): %s" % (rc, (why.value or b"").decode()))
+        err.rc = rc
+        raise err
+    n = int(n.value)
+    words = (len(images) + 31) // 32
+    rec = np.zeros(max(n, 1), dtype=FUSED_POINT_DTYPE)
+    bits = np.zeros((max(n, 1), max(words, 1)), dtype=np.uint32)
+    total = sum(int(a.width) * int(a.height) for a in arr[:len(images)] if a.used)
+    masks = np.zeros(max(total, 1), dtype=np.uint8)
+    L.dsm_fusion_host_get(rec.ctypes.data, bits.ctypes.data, masks.ctypes.data)
+    vis = [[i for i in range(len(images)) if int(bits[k, i // 32]) >> (i % 32) & 1] for k in range(n)]
+    rec = rec[:n]
+    return rec["xyz"].copy(), rec["rgb"].copy(), rec["normal"].copy(), vis, masks[:total], int(trav.value)
+
+
 def default_vocabulary_build_options(**kw):
     o = VocabularyBuildOptions()
     lib().dsm_default_vocabulary_build_options(ctypes.byref(o))
@@ -927,7 +1162,7 @@ PRODUCT_OPTION_KEYS = ("DSM_MATCH_CHUNK_ROWS", "DSM_VERIFY_CHUNK_PAIRS", "DSM_VE
 CHECK_OPTION_KEYS = ("DSM_K1_DOT4", "DSM_K1_RESOLVE_KERNEL", "DSM_VERIFY_DEBUG", "DSM_SAMPLER_SERIAL", "DSM_LO_PREPARE_WAVE", "DSM_LO_JACOBI_GROUPS", "DSM_ROOTS_LDS",
                      "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT", "DSM_DEBUG_SAMPLER_MODE",
                      "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER", "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
-                     "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT")
+                     "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT", "DSM_FUSION_SERIAL")
 DEBUG_OPTION_KEYS = PRODUCT_OPTION_KEYS  # what a deployer's library knows
 
 
@@ -1629,7 +1864,9 @@ class Context:
         return dict(zip(self.COVARIANT_SIFT_STAGES, list(ms)))
 
     def _fail(self, name, rc):
-        raise DsmError("%s failed (%d): %s" % (name, rc, self._L.dsm_last_error(self._handle).decode()))
+        err = DsmError("%s failed (%d): %s" % (name, rc, self._L.dsm_last_error(self._handle).decode()))
+        err.rc = rc
+        raise err
 
     def undistort_cameras(self, cameras, options=None, **kw):
         """dsm_undistort_cameras (UndistortCamera): a list of Camera -> the list of their PINHOLE cameras.
@@ -1798,6 +2035,43 @@ class Context:
         ms = (ctypes.c_double * len(PATCH_MATCH_STAGES))()
         self._chk(self._L.dsm_get_patch_match_time(self._h, ctypes.addressof(ms)))
         return dict(zip(PATCH_MATCH_STAGES, list(ms)))
+
+    def stereo_fusion(self, images, overlap, options=None, **kw):
+        """dsm_fuse_stereo (StereoFusion::Run, DESIGN.md 26): the dense point cloud of the depth and normal maps.
+        images: a list of dicts -- used, depth [h][w], normal [3][h][w] float32, rgb [bh][bw][3] uint8, P [12], inv_P [12], inv_R
+        [9] (capi.fusion_matrices), optionally scale [2]; overlap: overlapping_images_, a list of index lists (capi.
+        overlapping_images).  options: a StereoFusionOptions, or its fields as keywords over the defaults.
+        -> (points [N][3] float32, colours [N][3] uint8, normals [N][3] float32, visibility: N ascending index lists), the points
+        in the reference's order."""
+        assert options is None or not kw, "pass a StereoFusionOptions or keywords, not both"
+        o = options if options is not None else default_stereo_fusion_options(**kw)
+        arr, offs, idx, keep = _fusion_call_arguments(images, overlap)
+        n = ctypes.c_uint64(0)
+        rc = self._L.dsm_fuse_stereo(self._h, ctypes.byref(o), len(images), ctypes.addressof(arr), offs.ctypes.data, idx.ctypes.data, ctypes.byref(n))
+        if rc != 0:
+            self._fail("dsm_fuse_stereo", rc)
+        n = int(n.value)
+        rec = np.zeros(max(n, 1), dtype=FUSED_POINT_DTYPE)
+        voff = np.zeros(n + 1, dtype=np.uint64)
+        self._chk(self._L.dsm_get_fused_points(self._h, None, 0, voff.ctypes.data, None, 0))
+        vimg = np.zeros(max(int(voff[-1]), 1), dtype=np.uint32)
+        self._chk(self._L.dsm_get_fused_points(self._h, rec.ctypes.data, len(rec), voff.ctypes.data, vimg.ctypes.data, len(vimg)))
+        rec = rec[:n]
+        vis = [vimg[int(voff[k]):int(voff[k + 1])].tolist() for k in range(n)]
+        return rec["xyz"].copy(), rec["rgb"].copy(), rec["normal"].copy(), vis
+
+    def stereo_fusion_time(self):
+        """dsm_get_stereo_fusion_time: {stage: ms} of the last stereo_fusion call, with its rounds and seed traversals (counts)."""
+        ms = (ctypes.c_double * len(STEREO_FUSION_STAGES))()
+        self._chk(self._L.dsm_get_stereo_fusion_time(self._h, ctypes.addressof(ms)))
+        return dict(zip(STEREO_FUSION_STAGES, list(ms)))
+
+    def stereo_fusion_rounds(self, n_images):
+        """dsm_get_stereo_fusion_rounds -> (order_pos [n_images], rounds [n_images]) of the last stereo_fusion call."""
+        pos = np.zeros(max(n_images, 1), dtype=np.uint32)
+        rounds = np.zeros(max(n_images, 1), dtype=np.uint32)
+        self._chk(self._L.dsm_get_stereo_fusion_rounds(self._h, pos.ctypes.data, rounds.ctypes.data, len(pos)))
+        return pos[:n_images], rounds[:n_images]
 
     @staticmethod
     def apply_point_filter(scene, result):

@@ -240,6 +240,16 @@ struct dsm_ctx {
   bool patch_match_ready = false;
   double patch_match_ms[DSM_PATCH_MATCH_STAGES] = {0};
 
+  // stereo_fusion.hip: the maps, masks and claims of all used images of dsm_fuse_stereo with the bitmaps and the tables
+  // (d_sf_maps), the per-seed state, the lanes' lists and queues and the big slots (d_sf_lanes); the fused points of the last
+  // call with their visibility lists (dsm_get_fused_points) and its times
+  DevBuf d_sf_maps, d_sf_lanes;
+  std::vector<dsm_fused_point> sf_points;
+  std::vector<uint64_t> sf_vis_off;
+  std::vector<uint32_t> sf_vis_images, sf_rounds;
+  bool stereo_fusion_ready = false;
+  double stereo_fusion_ms[DSM_STEREO_FUSION_STAGES] = {0};
+
   // vocabulary_build.hip: the descriptors, the indices permutation, the per-position values and the per-job state of a
   // dsm_retrieval_quantize call, the buffers of dsm_retrieval_train_embedding -- all released when the call ends; the tree of the
   // last dsm_retrieval_quantize in depth-first order (dsm_get_vocabulary_tree) and the HIP-event times of the last calls
@@ -273,7 +283,7 @@ struct dsm_ctx {
       f(*b, false);
     for (DevBuf* b : {&d_m, &d_ms, &d_entries, &d_out2, &d_out2s, &d_dpairs, &d_dpairs2, &d_doutoff, &d_pair_dir, &d_order, &d_ecnt, &d_eoff,
                       &d_runs, &d_run_blocks, &d_run_blkoff, &d_gblocks, &d_egrow,
-                      &d_vscratch, &d_ud_border, &d_ud_points, &d_ud_src, &d_ud_dst, &d_ud_map, &d_pm, &d_vb_point, &d_vb_node, &d_vb_embed})
+                      &d_vscratch, &d_ud_border, &d_ud_points, &d_ud_src, &d_ud_dst, &d_ud_map, &d_pm, &d_vb_point, &d_vb_node, &d_vb_embed, &d_sf_maps, &d_sf_lanes})
       f(*b, true);
     for (VerifyLane& L : lanes) L.for_each_buffer([&f](DevBuf& b) { f(b, true); });
   }
@@ -291,7 +301,7 @@ static const char* const dsm_check_debug_keys[] = {"DSM_K1_DOT4", "DSM_K1_RESOLV
                                                    "DSM_ROOTS_LDS", "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT",
                                                    "DSM_DEBUG_SAMPLER_MODE", "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER",
                                                    "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
-                                                   "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT"};
+                                                   "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT", "DSM_FUSION_SERIAL"};
 #endif
 
 #define HIPCHK(ctx, call)                                                              \

@@ -1576,7 +1576,7 @@ int dsm_get_vocabulary_build_time(dsm_ctx* ctx, double* stage_ms);
  * two host tables, correctly rounded exp / sin / cos).  tests/patch_match_ref.py is the normative restatement; the device equals
  * it bit for bit.
  * NOT covered: source-image selection and depth ranges from the sparse model (the caller names both, as patch-match.cfg does),
- * max_image_size rescaling, image decoding, the Workspace cache, StereoFusion and meshing: the host's. */
+ * max_image_size rescaling, image decoding, the Workspace cache and meshing: the host's. */
 typedef struct dsm_patch_match_options { /* PatchMatchOptions, src/mvs/patch_match.h:59-139, ranges of Check() :141-168 */
   int32_t window_radius;                   /* 5; 1 .. 32 */
   int32_t window_step;                     /* 1; 1 .. 2 */
@@ -1639,6 +1639,78 @@ int dsm_patch_match(dsm_ctx* ctx, const dsm_patch_match_options* options, uint32
  * reference filter and initialisation, 2 initial cost, 3 sweeps, 4 rotation, 5 download.  DSM_ERR_NOT_READY before the first call. */
 #define DSM_PATCH_MATCH_STAGES 6
 int dsm_get_patch_match_time(dsm_ctx* ctx, double* stage_ms);
+
+/* ---- Stereo fusion of depth and normal maps (stereo_fusion, StereoFusion, src/mvs/fusion.cc) ----
+ * DESIGN.md 26.  StereoFusion::Run from "Reading configuration" onward (fusion.cc:169-293) with Fuse() (:295-473): the
+ * fused points in the reference's order, each with the images that see it.  The contract is the reference's loop operation
+ * for operation in IEEE float (matrix rows, the dot product and the squared norm summed left to right, no contraction);
+ * tests/stereo_fusion_ref.py is the normative restatement and the device equals it bit for bit.  The device does not run
+ * seed after seed: it traverses every pending seed of an image against the committed masks at once and commits, in rank
+ * order, the seeds whose pixels nobody of a lower rank claims (DESIGN.md 26 shows why that is the sequential result).
+ * Deviations: a point's visibility list is in ascending image index (the reference copies an unordered_set); P, inv_P and
+ * inv_R are inputs; min_num_pixels < 1 is refused (the reference would CHECK-fail in Median); depths and normals must be
+ * finite, and a NaN that arithmetic produces fails the test it enters and is never an index.
+ * NOT covered: the Workspace (decoding, max_image_size, the cache), fusion.cfg, the PMVS vis.dat reader, check_num_images
+ * and the overlap lists (an input, as patch-match.cfg's lists are), meshing: the host's. */
+typedef struct dsm_stereo_fusion_options { /* StereoFusionOptions, src/mvs/fusion.h:55-85, ranges of Check() fusion.cc:98-108 */
+  int32_t min_num_pixels;      /* 5; >= 1 (the reference: >= 0) and <= max_num_pixels */
+  int32_t max_num_pixels;      /* 10000 */
+  int32_t max_traversal_depth; /* 100; > 0 */
+  int32_t lane_capacity;       /* 0 = the default: pixels and queue entries a seed's lane holds; scheduling only, >= 0 */
+  double max_reproj_error;     /* 2.0f; >= 0 */
+  double max_depth_error;      /* 0.01f; >= 0 */
+  double max_normal_error;     /* 10.0f degrees; >= 0 */
+} dsm_stereo_fusion_options;
+void dsm_default_stereo_fusion_options(dsm_stereo_fusion_options* o);
+
+/* One image of fusion.  used = 0: the image is in no fusion.cfg (its maps are not read; the reference holds a 0 x 0 map).
+ * depth_map [height][width], normal_map [3][height][width] (the slice layout of Mat<float>), rgb: bitmap_height rows of
+ * bitmap_width RGB byte triples, row y at rgb + y * row_stride.  P, inv_P (3 x 4) and inv_R (3 x 3) row-major as
+ * fusion.cc:220-235 composes them (capi.fusion_matrices does so by the ruling of DESIGN.md 24), bitmap_scale = (width /
+ * bitmap_width, height / bitmap_height) in float (:216-218). */
+typedef struct dsm_fusion_image {
+  int32_t used;
+  uint32_t width, height;
+  uint32_t bitmap_width, bitmap_height;
+  uint32_t reserved;
+  uint64_t row_stride;
+  const float* depth_map;
+  const float* normal_map;
+  const uint8_t* rgb;
+  float P[12], inv_P[12], inv_R[9], bitmap_scale[2];
+  uint32_t reserved2;
+} dsm_fusion_image;
+
+typedef struct dsm_fused_point { /* PlyPoint, src/util/ply.h:45-55 */
+  float x, y, z, nx, ny, nz;
+  uint8_t r, g, b, reserved;
+} dsm_fused_point;
+
+/* StereoFusion::Run (fusion.cc:169-293), host pointers; options NULL = the defaults.  overlapping_images_[i] is
+ * overlap_images[overlap_offsets[i] .. overlap_offsets[i + 1]).  *n_points gets the number of fused points; the points stay
+ * in the context for dsm_get_fused_points.
+ * The maps, masks and claims of all used images are resident on the device for the call (depth 4, normal 12, mask 1, claim 4 bytes
+ * per pixel and the bitmaps) next to the lanes' storage; a call that does not fit dsm_ctx_set_memory_budget (when one is set) or the free
+ * memory, or has 2^31 pixels or more, is refused with DSM_ERR_OUT_OF_RANGE.  There is no cache emulation.
+ * n_images = 0 and "no image used" are valid and give 0 points.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT, outputs untouched): an option outside its range (a NaN fails it), an overlap index out
+ * of range or equal to its own image, a used image without pixels or with a side above 32768 (maps or bitmap), a row stride
+ * below 3 x bitmap_width, a depth or normal that is not finite, NULL where data is needed. */
+int dsm_fuse_stereo(dsm_ctx* ctx, const dsm_stereo_fusion_options* options, uint32_t n_images, const dsm_fusion_image* images,
+                    const uint64_t* overlap_offsets, const uint32_t* overlap_images, uint64_t* n_points);
+/* The points of the last dsm_fuse_stereo in the reference's order (fused_points_) and their visibility
+ * (fused_points_visibility_): vis_offsets gets n_points + 1 prefix offsets, vis_images the image indices, ascending per
+ * point.  Same conventions as dsm_get_matches: any pointer may be NULL, the capacities are in points and in indices. */
+int dsm_get_fused_points(dsm_ctx* ctx, dsm_fused_point* points, uint64_t capacity, uint64_t* vis_offsets, uint32_t* vis_images,
+                         uint64_t vis_capacity);
+/* Times in ms of the last dsm_fuse_stereo (HIP events, host clock around the host's pieces): 0 upload, 1 traversal, 2 claims
+ * and commit decisions, 3 medians (the commit kernel), 4 download (scan, gather and copy); 5 the number of rounds, 6 the
+ * number of seed traversals.  DSM_ERR_NOT_READY before the first call. */
+#define DSM_STEREO_FUSION_STAGES 7
+int dsm_get_stereo_fusion_time(dsm_ctx* ctx, double* stage_ms);
+/* Per image of the last dsm_fuse_stereo: its place in the order of FindNextImage (fusion.cc:58-79; 0 for an image the loop
+ * never reached) and the rounds it took (0 for an image without pixels).  Either pointer may be NULL; capacity in images. */
+int dsm_get_stereo_fusion_rounds(dsm_ctx* ctx, uint32_t* order_pos, uint32_t* rounds, uint32_t capacity);
 
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
