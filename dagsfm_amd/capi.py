@@ -570,6 +570,8 @@ def lib(check=False):
         L.dsm_covariant_sift_default_options.argtypes = [ctypes.POINTER(CovariantSiftOptions)]
         L.dsm_covariant_sift_default_options.restype = None
         L.dsm_extract_covariant_sift.argtypes = [vp, ctypes.POINTER(CovariantSiftOptions), vp] + [ctypes.c_uint32] * 4 + [vp, vp, u32p]
+        L.dsm_extract_covariant_sift_affine.argtypes = L.dsm_extract_covariant_sift.argtypes
+        L.dsm_get_affine_shape_stats.argtypes = [vp, u32p, vp, vp]
         L.dsm_get_covariant_sift_raw.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, u32p]
         L.dsm_get_covariant_sift_time.argtypes = [vp, vp]
         L.dsm_default_undistort_options.argtypes = [ctypes.POINTER(UndistortOptions)]
@@ -1837,6 +1839,45 @@ class Context:
             err.outputs = (kp, ds)  # as the library left them
             raise err
         return kp[:n.value].copy(), (None if ds is None else ds[:n.value].copy())
+
+    def extract_covariant_sift_affine(self, image_u8, options=None, descriptors=True, capacity=None, width=None):
+        """dsm_extract_covariant_sift_affine (DESIGN.md 27): extract_covariant_sift's arguments, results and capacity retry;
+        options.estimate_affine_shape = 1 adapts every frame to its patch's second-moment matrix (vl_covdet_extract_affine_shape)
+        in the place of the orientations."""
+        im = np.ascontiguousarray(image_u8, np.uint8)
+        height, row_stride = im.shape
+        width = row_stride if width is None else int(width)
+        o = options if options is not None else default_covariant_sift_options()
+        n = ctypes.c_uint32(0)
+
+        def call(cap):
+            kp = np.zeros((max(cap, 1), 6), np.float32)
+            ds = np.zeros((max(cap, 1), 128), np.uint8) if descriptors else None
+            rc = self._L.dsm_extract_covariant_sift_affine(self._h, ctypes.byref(o), im.ctypes.data, width, height, row_stride, cap,
+                                                           kp.ctypes.data, None if ds is None else ds.ctypes.data, ctypes.byref(n))
+            return rc, kp, ds
+
+        rc, kp, ds = call(32768 if capacity is None else int(capacity))
+        if rc == 4 and capacity is None and n.value > 0:
+            rc, kp, ds = call(int(n.value))
+        if rc != 0:
+            err = DsmError("dsm_extract_covariant_sift_affine failed (%d): %s" % (rc, self._L.dsm_last_error(self._handle).decode()))
+            err.num_features = int(n.value)
+            err.status = rc
+            err.outputs = (kp, ds)  # as the library left them
+            raise err
+        return kp[:n.value].copy(), (None if ds is None else ds[:n.value].copy())
+
+    AFFINE_SHAPE_EXITS = ("diverged", "max_iterations", "zero_moment", "converged")
+
+    def affine_shape_stats(self):
+        """dsm_get_affine_shape_stats: the shape adaptation of the last extract_covariant_sift_affine as {"rounds": launches of
+        the moment kernel, "exits": {why: features} in the order of AFFINE_SHAPE_EXITS, "active": [features in round r] * 14}."""
+        rounds = ctypes.c_uint32(0)
+        exits = (ctypes.c_uint32 * 4)()
+        active = (ctypes.c_uint32 * 14)()
+        self._chk(self._L.dsm_get_affine_shape_stats(self._h, ctypes.byref(rounds), ctypes.addressof(exits), ctypes.addressof(active)))
+        return {"rounds": int(rounds.value), "exits": dict(zip(self.AFFINE_SHAPE_EXITS, list(exits))), "active": list(active)}
 
     def covariant_sift_raw(self, num_scales=None):
         """dsm_get_covariant_sift_raw: the last extract_covariant_sift's features in output order as {"octave_scale": int32 [n, 2],

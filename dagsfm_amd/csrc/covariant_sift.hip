@@ -1,5 +1,5 @@
-// covariant_sift.hip -- ExtractCovariantSiftFeaturesCPU (src/feature/sift.cc:428-598) with estimate_affine_shape = false on the
-// device: VLFeat's covdet (lib/VLFeat/covdet.c, DoG method) over its scalespace (scalespace.c), and
+// covariant_sift.hip -- ExtractCovariantSiftFeaturesCPU (src/feature/sift.cc:428-598) on the device (DESIGN.md 21, and 27 for
+// estimate_affine_shape): VLFeat's covdet (lib/VLFeat/covdet.c, DoG method) over its scalespace (scalespace.c), and
 // vl_sift_calc_raw_descriptor (sift.c:1754-1903) on the warped patches, restated operation for operation in their own evaluation
 // order, float where the source is float and double where it is double, plus COLMAP's loop around them.
 //
@@ -10,6 +10,9 @@
 //   k_cov_orient      a workgroup per feature: the 41 x 41 patch (vl_covdet_extract_patch_helper, :2362-2399), its smoothing, the
 //                     polar gradient, the 36-bin histogram in double -- a lane per bin, walking all samples in order -- and its peaks
 //                     (:2754-2838)
+//   k_cov_affine_moments   a workgroup per feature and round of vl_covdet_extract_affine_shape_for_frame (:2462-2642): the 41 x 41
+//                     patch, vl_imgradient_f, and the three masked sums of the second-moment matrix in double -- a lane per
+//                     sum, walking all samples in order.  The loop around it (vl_svd2, the exits, the update of A) is the host's
 //   k_cov_describe    THE HOT PATH: a workgroup of one wave per (feature, pooling scale).  The 31 x 31 patch is resampled from
 //                     the level through L2 into LDS, its polar gradient stays in LDS, and a lane per (spatial cell, pair of
 //                     orientation bins) walks that cell's samples in the reference's order from one constant table: no two
@@ -376,6 +379,51 @@ __global__ void __launch_bounds__(COV_WAVE) k_cov_orient(const CovOrientJob* __r
   out[blockIdx.x] = r;
 }
 
+// One pass of vl_covdet_extract_affine_shape_for_frame between its two vl_svd2 (covdet.c:2530-2562) for one feature: the patch
+// (aaAccurateSmoothing is off: no smoothing), vl_imgradient_f (imopv.c:722-829) and lxx, lyy, lxy -- out[3 f .. 3 f + 2] in that
+// order.  Each sum is one lane's chain over the 1681 addends in sample order; the products lx * lx * mask (left to right, the
+// floats widened) do not depend on the chain, so the chain costs one FP64 addition an addend.  A zeroed patch (padded == 2)
+// gives three exact zeros: every addend is + 0.
+__global__ void __launch_bounds__(COV_WAVE) k_cov_affine_moments(const CovPatch* __restrict__ jobs, const float* __restrict__ gss,
+                                                                 const double* __restrict__ hat, const float* __restrict__ mask,
+                                                                 double* __restrict__ out) {
+  __shared__ float patch[COV_OR_N], gx[COV_OR_N], gy[COV_OR_N];
+  const CovPatch& p = jobs[blockIdx.x];
+  const int lane = (int)threadIdx.x;
+  cov_resample<COV_OR_SIDE>(patch, gss, p, hat);
+  __syncthreads();
+  for (int k = lane; k < COV_OR_N; k += COV_WAVE) {
+    const int x = k % COV_OR_SIDE, y = k / COV_OR_SIDE;
+    const float* src = patch + k;
+    float dx, dy;
+    if (x == 0)
+      dx = src[1] - src[0];
+    else if (x == COV_OR_SIDE - 1)
+      dx = src[0] - src[-1];
+    else
+      dx = (float)(0.5 * (src[1] - src[-1]));
+    if (y == 0)
+      dy = src[COV_OR_SIDE] - src[0];
+    else if (y == COV_OR_SIDE - 1)
+      dy = src[0] - src[-COV_OR_SIDE];
+    else
+      dy = (float)(0.5 * (src[COV_OR_SIDE] - src[-COV_OR_SIDE]));
+    gx[k] = dx;
+    gy[k] = dy;
+  }
+  __syncthreads();
+  if (lane >= 3) return;
+  const float* u = lane == 1 ? gy : gx;  // lane 0: lx lx, lane 1: ly ly, lane 2: lx ly
+  const float* v = lane == 0 ? gx : gy;
+  double acc = 0;
+  #pragma unroll 8
+  for (int k = 0; k < COV_OR_N; ++k) {
+    const double a = u[k], b = v[k], m = mask[k];
+    acc += a * b * m;
+  }
+  out[3 * (size_t)blockIdx.x + lane] = acc;
+}
+
 // normalize_histogram (sift.c:1702-1718): the sum of squares left to right by one lane, the division by all
 __device__ inline void cov_normalize(float* descr, float* norm_slot) {
   if (threadIdx.x == 0) {
@@ -610,6 +658,51 @@ void cov_svd2(double* S, double* U, double* V, const double* M) {
   V[0] = cv2, V[1] = sv2, V[2] = -sv2, V[3] = cv2;
 }
 
+// vl_solve_linear_system_2 over vl_gaussian_elimination (mathop.c:872-1016) for a 2 x 3 system, column major: a singular
+// matrix leaves x with what stands in the last column when the elimination gives up
+void cov_solve2(double* x, const double* A, const double* b) {
+  double M[2 * 3] = {A[0], A[1], A[2], A[3], b[0], b[1]};
+  const int numRows = 2, numColumns = 3;
+#define Mat(i, j) M[(i) + (j)*numRows]
+  bool ok = true;
+  for (int j = 0; j < numRows && ok; ++j) {
+    double maxa = 0, maxabsa = 0, tmp;
+    int maxi = -1;
+    for (int i = j; i < numRows; ++i) {
+      const double a = Mat(i, j), absa = std::fabs(a);
+      if (absa > maxabsa) {
+        maxa = a;
+        maxabsa = absa;
+        maxi = i;
+      }
+    }
+    if (maxabsa < 1e-10) {
+      ok = false;
+      break;
+    }
+    const int i = maxi;
+    for (int jj = j; jj < numColumns; ++jj) {
+      tmp = Mat(i, jj);
+      Mat(i, jj) = Mat(j, jj);
+      Mat(j, jj) = tmp;
+      Mat(j, jj) /= maxa;
+    }
+    for (int ii = j + 1; ii < numRows; ++ii) {
+      const double f = Mat(ii, j);
+      for (int jj = j; jj < numColumns; ++jj) Mat(ii, jj) -= f * Mat(j, jj);
+    }
+  }
+  if (ok)
+    for (int i = numRows - 1; i > 0; --i)
+      for (int ii = i - 1; ii >= 0; --ii) {
+        const double f = Mat(ii, i);
+        for (int j = numRows; j < numColumns; ++j) Mat(ii, j) -= f * Mat(i, j);
+      }
+#undef Mat
+  x[0] = M[4];
+  x[1] = M[5];
+}
+
 struct CovGeom {  // VlScaleSpaceGeometry of the detector's scale space (covdet.c:1699-1718)
   int width = 0, height = 0, first = 0, last = 0, R = 0, smin = -1, smax = 0;
   double base = 0;
@@ -706,11 +799,14 @@ struct CovSiftState {
   size_t at_hat31 = 0, at_hat41 = 0, at_mask = 0, at_counts = 0;  // byte offsets in consts
   DevEvent ev[8];
   double stage_ms[DSM_COVARIANT_SIFT_STAGES] = {0};
-  // the last successful call
+  // the last successful call of either entry
   bool valid = false, have_raw = false;
   uint32_t n = 0, scales = 0;
   std::vector<int32_t> os;
   std::vector<float> scores;
+  // the shape adaptation of the last successful dsm_extract_covariant_sift_affine
+  bool affine_valid = false;
+  uint32_t affine_rounds = 0, affine_exits[4] = {0}, affine_active[DSM_AFFINE_SHAPE_MAX_ROUNDS] = {0};
 };
 
 void dsm_covariant_sift_destroy(dsm_ctx* ctx) {
@@ -836,9 +932,10 @@ int cov_upload_consts(dsm_ctx* ctx, CovSiftState& d, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int dsm_extract_covariant_sift(dsm_ctx* ctx, const dsm_covariant_sift_options* options, const uint8_t* gray_u8, uint32_t width,
-                                          uint32_t height, uint32_t row_stride, uint32_t capacity, float* keypoints_out,
-                                          uint8_t* descriptors_out, uint32_t* num_features_out) {
+// both entries: dsm_extract_covariant_sift refuses estimate_affine_shape, dsm_extract_covariant_sift_affine (affine_entry) honours it
+static int cov_extract(dsm_ctx* ctx, const dsm_covariant_sift_options* options, const uint8_t* gray_u8, uint32_t width, uint32_t height,
+                       uint32_t row_stride, uint32_t capacity, float* keypoints_out, uint8_t* descriptors_out, uint32_t* num_features_out,
+                       bool affine_entry) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
   auto fail = [&](int code, const char* msg) { return dsm_fail(ctx, code, msg); };
   dsm_covariant_sift_options o;
@@ -849,7 +946,7 @@ extern "C" int dsm_extract_covariant_sift(dsm_ctx* ctx, const dsm_covariant_sift
   if (num_features_out) *num_features_out = 0;
   if (!gray_u8 || !num_features_out || (capacity && !keypoints_out)) return fail(DSM_ERR_INVALID_ARGUMENT, "NULL argument");
   if (width == 0 || height == 0 || row_stride < width) return fail(DSM_ERR_INVALID_ARGUMENT, "an empty image or row_stride below width");
-  if (o.estimate_affine_shape)
+  if (o.estimate_affine_shape && !affine_entry)
     return fail(DSM_ERR_INVALID_ARGUMENT, "estimate_affine_shape is not covered: vl_covdet_extract_affine_shape stays with the reference");
   // SiftExtractionOptions::Check (sift.cc:218-234)
   if (!(o.max_num_features > 0) || !(o.octave_resolution > 0) || !(o.peak_threshold > 0.0) || !(o.edge_threshold > 0.0) ||
@@ -900,6 +997,8 @@ extern "C" int dsm_extract_covariant_sift(dsm_ctx* ctx, const dsm_covariant_sift
   typedef CovSiftState B;
   d.valid = false;
   d.have_raw = false;
+  uint32_t aff_rounds = 0, aff_exits[4] = {0, 0, 0, 0}, aff_active[DSM_AFFINE_SHAPE_MAX_ROUNDS] = {0};
+  if (affine_entry) d.affine_valid = false;
   if (!d.consts_ready) {
     const int rc = cov_upload_consts(ctx, d, st);
     if (rc != DSM_OK) return rc;
@@ -1110,8 +1209,141 @@ extern "C" int dsm_extract_covariant_sift(dsm_ctx* ctx, const dsm_covariant_sift
     features.resize(j);
   }
 
+  // ---- sift.cc:467-473: vl_covdet_extract_affine_shape (covdet.c:2462-2668) in the place of the orientations.  The loop of
+  // every feature advances in rounds: the host runs a pass's head (vl_svd2, the anisotropy test, the rescaling, the iteration
+  // limit) and plans the patch, one launch computes the three sums of every active feature, the host reads them and runs the
+  // pass's tail (the zero test, vl_svd2, the convergence test, the update of A).  At most 14 rounds: the 15th head leaves.
+  if (o.estimate_affine_shape && !o.upright && !features.empty()) {
+    enum { DIVERGED = 0, MAX_ITER = 1, ZERO_MOMENT = 2, CONVERGED = 3 };
+    struct Shape {
+      double A[4], T[2], D0, D3, referenceScale;
+      int iter;
+      CovFeature adapted;
+    };
+    const size_t nf = features.size();
+    if (ctx->memory_budget && scratch + nf * (sizeof(CovPatch) + 24) > ctx->memory_budget)
+      return fail(DSM_ERR_OUT_OF_RANGE, "the shape adaptation's scratch exceeds the memory budget");
+    std::vector<Shape> shapes(nf);
+    std::vector<uint32_t> active, next;
+    auto head = [&](uint32_t i) {  // covdet.c:2495-2528; true: the pass goes on to the patch
+      Shape& h = shapes[i];
+      double U[4], V[4], D[4], factor;
+      cov_svd2(D, U, V, h.A);
+      const double r0 = D[0] / D[3], r1 = D[3] / D[0];
+      const double anisotropy = r0 > r1 ? r0 : r1;  // VL_MAX
+      if (anisotropy > 5.0) {  // VL_COVDET_AA_MAX_ANISOTROPY
+        aff_exits[DIVERGED] += 1;
+        return false;
+      }
+      if (h.iter == 0) {
+        h.referenceScale = D[0] < D[3] ? D[0] : D[3];  // VL_MIN
+        factor = 1.0;
+      } else {
+        factor = h.referenceScale / (D[0] < D[3] ? D[0] : D[3]);
+      }
+      D[0] *= factor;
+      D[3] *= factor;
+      h.A[0] = U[0] * D[0];
+      h.A[1] = U[1] * D[0];
+      h.A[2] = U[2] * D[3];
+      h.A[3] = U[3] * D[3];
+      h.adapted.a11 = h.A[0];
+      h.adapted.a21 = h.A[1];
+      h.adapted.a12 = h.A[2];
+      h.adapted.a22 = h.A[3];
+      h.D0 = D[0];
+      h.D3 = D[3];
+      if (++h.iter >= 15) {  // VL_COVDET_AA_MAX_NUM_ITERATIONS
+        aff_exits[MAX_ITER] += 1;
+        return false;
+      }
+      return true;
+    };
+    for (size_t i = 0; i < nf; ++i) {
+      const CovFeature& f = features[i];
+      Shape& h = shapes[i];
+      h.A[0] = f.a11, h.A[1] = f.a21, h.A[2] = f.a12, h.A[3] = f.a22;
+      h.T[0] = f.x, h.T[1] = f.y;
+      h.D0 = h.D3 = h.referenceScale = 0;
+      h.iter = 0;
+      h.adapted = f;
+      if (head((uint32_t)i)) active.push_back((uint32_t)i);
+    }
+    std::vector<CovPatch> jobs;
+    std::vector<double> sums;
+    COV_CHK(d.buf[B::ojobs].reserve(active.size() * sizeof(CovPatch)));
+    COV_CHK(d.buf[B::oout].reserve(active.size() * 24));
+    while (!active.empty()) {
+      if (aff_rounds >= DSM_AFFINE_SHAPE_MAX_ROUNDS) return fail(DSM_ERR_OUT_OF_RANGE, "the shape adaptation ran past its 14 rounds");
+      const size_t na = active.size();
+      aff_active[aff_rounds++] = (uint32_t)na;
+      jobs.resize(na);
+      sums.resize(3 * na);
+      for (size_t j = 0; j < na; ++j) {
+        const Shape& h = shapes[active[j]];
+        cov_plan_patch(g, &jobs[j], nullptr, nullptr, COV_OR_EXTENT, 1.0 /* VL_COVDET_AA_RELATIVE_DERIVATIVE_SIGMA */, h.A, h.T, h.D0, h.D3);
+      }
+      COV_CHK(hipMemcpyAsync(d.buf[B::ojobs].p, jobs.data(), na * sizeof(CovPatch), hipMemcpyHostToDevice, st));
+      COV_CHK(mark(4));
+      hipLaunchKernelGGL(k_cov_affine_moments, dim3((uint32_t)na), dim3(COV_WAVE), 0, st, (const CovPatch*)d.buf[B::ojobs].as<CovPatch>(), (const float*)gss, hat41,
+                         mask, d.buf[B::oout].as<double>());
+      COV_CHK(mark(5));
+      COV_CHK(hipGetLastError());
+      COV_CHK(hipMemcpyAsync(sums.data(), d.buf[B::oout].p, na * 24, hipMemcpyDeviceToHost, st));
+      COV_CHK(hipStreamSynchronize(st));
+      COV_CHK(took(2, 4));
+      next.clear();
+      for (size_t j = 0; j < na; ++j) {  // covdet.c:2559-2598
+        const uint32_t i = active[j];
+        Shape& h = shapes[i];
+        const double lxx = sums[3 * j], lyy = sums[3 * j + 1], lxy = sums[3 * j + 2];
+        const double M[4] = {lxx, lxy, lxy, lyy};
+        if (lxx == 0 || lyy == 0) {
+          h.adapted = features[i];
+          aff_exits[ZERO_MOMENT] += 1;
+          continue;
+        }
+        double Q[4], P[4], P_[4];
+        cov_svd2(Q, P, P_, M);
+        if (Q[3] / Q[0] < 1.001 && Q[0] / Q[3] < 1.001) {  // VL_COVDET_AA_CONVERGENCE_THRESHOLD
+          aff_exits[CONVERGED] += 1;
+          continue;
+        }
+        double Ap[4];
+        const double q0 = std::sqrt(Q[0]), q1 = std::sqrt(Q[3]);
+        Ap[0] = (h.A[0] * P[0] + h.A[2] * P[1]) / q0;
+        Ap[1] = (h.A[1] * P[0] + h.A[3] * P[1]) / q0;
+        Ap[2] = (h.A[0] * P[2] + h.A[2] * P[3]) / q1;
+        Ap[3] = (h.A[1] * P[2] + h.A[3] * P[3]) / q1;
+        memcpy(h.A, Ap, sizeof(Ap));
+        if (head(i)) next.push_back(i);
+      }
+      active.swap(next);
+    }
+    for (size_t i = 0; i < nf; ++i) {  // make upright, covdet.c:2610-2639 (transposed is false): reads the adapted frame's floats
+      const CovFeature& ad = shapes[i].adapted;
+      const double A[4] = {ad.a11, ad.a21, ad.a12, ad.a22};
+      const double ref[2] = {0, 1};
+      double ref_[2];
+      cov_solve2(ref_, A, ref);
+      const double angle = std::atan2(ref[1], ref[0]);
+      const double angle_ = std::atan2(ref_[1], ref_[0]);
+      const double dangle = angle_ - angle;
+      // one sincos call, as the reference's compiler emits for cos and sin of one argument (gcc -O2): glibc's sincos and its sin
+      // differ in the last bit of the sine for some arguments, and a12 is the residual of a cancellation that shows it
+      double r1, r2;
+      ::sincos(dangle, &r2, &r1);
+      CovFeature& f = features[i];
+      f = ad;
+      f.a11 = +A[0] * r1 + A[2] * r2;
+      f.a21 = +A[1] * r1 + A[3] * r2;
+      f.a12 = -A[0] * r2 + A[2] * r1;
+      f.a22 = -A[1] * r2 + A[3] * r1;
+    }
+  }
+
   // ---- vl_covdet_extract_orientations (covdet.c:2857-2892) unless upright (sift.cc:467-473)
-  if (!o.upright && !features.empty()) {
+  if (!o.estimate_affine_shape && !o.upright && !features.empty()) {
     const size_t nf = features.size();
     std::vector<CovOrientJob> jobs(nf);
     std::vector<double> theta0(nf);
@@ -1276,6 +1508,35 @@ extern "C" int dsm_extract_covariant_sift(dsm_ctx* ctx, const dsm_covariant_sift
   }
   if (kept && descriptors_out) memcpy(descriptors_out, desc_host.data(), kept * 128);
   d.valid = true;
+  if (affine_entry) {
+    d.affine_rounds = aff_rounds;
+    memcpy(d.affine_exits, aff_exits, sizeof(aff_exits));
+    memcpy(d.affine_active, aff_active, sizeof(aff_active));
+    d.affine_valid = true;
+  }
+  return DSM_OK;
+}
+
+extern "C" int dsm_extract_covariant_sift(dsm_ctx* ctx, const dsm_covariant_sift_options* options, const uint8_t* gray_u8, uint32_t width,
+                                          uint32_t height, uint32_t row_stride, uint32_t capacity, float* keypoints_out,
+                                          uint8_t* descriptors_out, uint32_t* num_features_out) {
+  return cov_extract(ctx, options, gray_u8, width, height, row_stride, capacity, keypoints_out, descriptors_out, num_features_out, false);
+}
+
+extern "C" int dsm_extract_covariant_sift_affine(dsm_ctx* ctx, const dsm_covariant_sift_options* options, const uint8_t* gray_u8,
+                                                 uint32_t width, uint32_t height, uint32_t row_stride, uint32_t capacity,
+                                                 float* keypoints_out, uint8_t* descriptors_out, uint32_t* num_features_out) {
+  return cov_extract(ctx, options, gray_u8, width, height, row_stride, capacity, keypoints_out, descriptors_out, num_features_out, true);
+}
+
+extern "C" int dsm_get_affine_shape_stats(dsm_ctx* ctx, uint32_t* rounds, uint32_t exits[4], uint32_t active[DSM_AFFINE_SHAPE_MAX_ROUNDS]) {
+  if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
+  if (!ctx->covsift || !ctx->covsift->affine_valid)
+    return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_get_affine_shape_stats: no successful dsm_extract_covariant_sift_affine call yet");
+  const CovSiftState& d = *ctx->covsift;
+  if (rounds) *rounds = d.affine_rounds;
+  if (exits) memcpy(exits, d.affine_exits, sizeof(d.affine_exits));
+  if (active) memcpy(active, d.affine_active, sizeof(d.affine_active));
   return DSM_OK;
 }
 
@@ -1284,7 +1545,7 @@ extern "C" int dsm_get_covariant_sift_raw(dsm_ctx* ctx, uint32_t capacity, int32
   if (!ctx || !n_out) return DSM_ERR_INVALID_ARGUMENT;
   *n_out = 0;
   if (!ctx->covsift || !ctx->covsift->valid)
-    return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_get_covariant_sift_raw: no successful dsm_extract_covariant_sift call yet");
+    return dsm_fail(ctx, DSM_ERR_NOT_READY, "dsm_get_covariant_sift_raw: no successful dsm_extract_covariant_sift or dsm_extract_covariant_sift_affine call yet");
   CovSiftState& d = *ctx->covsift;
   *n_out = d.n;
   if (raw_descriptors && !d.have_raw && d.n)

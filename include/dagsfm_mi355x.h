@@ -1328,8 +1328,8 @@ int dsm_adjust_local_bundles(dsm_ctx* ctx, uint32_t num_problems, const uint32_t
  * restated in the reference's evaluation order, and COLMAP's loop around them: the groups per DoG level, the first
  * max_num_orientations orientations of a keypoint, L1_ROOT / L2 (src/feature/utils.cc:47-77), the bytes, the VLFeat -> UBC bin
  * order (sift.cc:58-74) and the max_num_features cut (sift.cc:387-398; the level that crosses the limit is kept whole).
- * DESIGN.md 18.  ExtractCovariantSiftFeaturesCPU (domain_size_pooling) is dsm_extract_covariant_sift below; estimate_affine_shape
- * and SiftGPU are not covered. */
+ * DESIGN.md 18.  ExtractCovariantSiftFeaturesCPU is below: dsm_extract_covariant_sift (domain_size_pooling) and
+ * dsm_extract_covariant_sift_affine (estimate_affine_shape as well).  SiftGPU is not covered. */
 enum { DSM_SIFT_L1_ROOT = 0, DSM_SIFT_L2 = 1 };  /* SiftExtractionOptions::Normalization, src/feature/sift.h */
 
 typedef struct dsm_sift_options {  /* SiftExtractionOptions, src/feature/sift.h:36-112 */
@@ -1380,7 +1380,8 @@ typedef struct dsm_covariant_sift_options {  /* SiftExtractionOptions, src/featu
   int32_t max_num_features;       /* 8192 */
   int32_t upright;                /* 0 */
   int32_t normalization;          /* DSM_SIFT_L1_ROOT */
-  int32_t estimate_affine_shape;  /* 0; 1 is DSM_ERR_INVALID_ARGUMENT: vl_covdet_extract_affine_shape is not covered */
+  int32_t estimate_affine_shape;  /* 0; 1: dsm_extract_covariant_sift_affine runs vl_covdet_extract_affine_shape, and
+                                   * dsm_extract_covariant_sift answers DSM_ERR_INVALID_ARGUMENT */
   int32_t domain_size_pooling;    /* 1; 0: one scale of 1, as the reference's function does without it */
   int32_t dsp_num_scales;         /* 10 */
   double peak_threshold;          /* 0.02 / octave_resolution */
@@ -1414,8 +1415,27 @@ int dsm_extract_covariant_sift(dsm_ctx* ctx, const dsm_covariant_sift_options* o
                                uint32_t height, uint32_t row_stride, uint32_t capacity, float* keypoints_out,
                                uint8_t* descriptors_out, uint32_t* num_features_out);
 
-/* The features of the last dsm_extract_covariant_sift on this context, in output order, as a test compares them (the final
- * bytes hide differences below 1 / 512): octave_scale [n x 2] = VlCovDetFeature's (o, s), scores [n x 3] = peakScore, edgeScore,
+/* ExtractCovariantSiftFeaturesCPU with every option: dsm_extract_covariant_sift's arguments, outputs and errors, except that
+ * estimate_affine_shape is honoured (src/feature/sift.cc:467-473).  With the option and without upright,
+ * vl_covdet_extract_affine_shape (lib/VLFeat/covdet.c:2462-2668) runs in the place of vl_covdet_extract_orientations: every
+ * feature's frame is adapted to the second-moment matrix of its 41 x 41 patch in at most 14 passes and then rotated so that
+ * the y axis keeps its direction; no feature is dropped or copied, and the orientation scores keep their detection value, 0.
+ * With the option at 0, or with upright, the call returns exactly what dsm_extract_covariant_sift returns.  DESIGN.md 27. */
+int dsm_extract_covariant_sift_affine(dsm_ctx* ctx, const dsm_covariant_sift_options* options, const uint8_t* gray_u8,
+                                      uint32_t width, uint32_t height, uint32_t row_stride, uint32_t capacity, float* keypoints_out,
+                                      uint8_t* descriptors_out, uint32_t* num_features_out);
+
+/* The shape adaptation of the last successful dsm_extract_covariant_sift_affine on this context: *rounds = the launches of the
+ * moment kernel (at most DSM_AFFINE_SHAPE_MAX_ROUNDS); exits = the features that left vl_covdet_extract_affine_shape_for_frame
+ * as diverged (anisotropy above 5), at the iteration limit, with a zero moment, and converged, in that order -- they sum to the
+ * features after the suppression; active[r] = the features whose moments round r computed, 0 from *rounds on.  All zero where
+ * the call ran no adaptation (the option at 0, upright, no feature).  Any pointer may be NULL.
+ * DSM_ERR_NOT_READY before such a call. */
+#define DSM_AFFINE_SHAPE_MAX_ROUNDS 14
+int dsm_get_affine_shape_stats(dsm_ctx* ctx, uint32_t* rounds, uint32_t exits[4], uint32_t active[DSM_AFFINE_SHAPE_MAX_ROUNDS]);
+
+/* The features of the last successful dsm_extract_covariant_sift or dsm_extract_covariant_sift_affine on this context, in
+ * output order, as a test compares them (the final bytes hide differences below 1 / 512): octave_scale [n x 2] = VlCovDetFeature's (o, s), scores [n x 3] = peakScore, edgeScore,
  * orientationScore, raw_descriptors [n x num_scales x 128] = vl_sift_calc_raw_descriptor's floats of every pooling scale, in
  * VLFeat's bin order, before the pooling (num_scales = dsp_num_scales, or 1 without domain_size_pooling).  Any of the three
  * may be NULL.  *n_out: the count; above capacity DSM_ERR_OUT_OF_RANGE and nothing is written.
@@ -1423,9 +1443,10 @@ int dsm_extract_covariant_sift(dsm_ctx* ctx, const dsm_covariant_sift_options* o
 int dsm_get_covariant_sift_raw(dsm_ctx* ctx, uint32_t capacity, int32_t* octave_scale, float* scores, float* raw_descriptors,
                                uint32_t* n_out);
 
-/* HIP-event times of the last dsm_extract_covariant_sift on this context, in ms: 0 the scale space (load, up- / downsampling,
- * every smoothing of every octave), 1 detection (DoG, extremum test, compaction, refinement, summed over the octaves),
- * 2 orientations, 3 descriptors (patch, gradient and raw descriptor of every (feature, pooling scale)), 4 pooling,
+/* HIP-event times of the last dsm_extract_covariant_sift or dsm_extract_covariant_sift_affine on this context, in ms: 0 the
+ * scale space (load, up- / downsampling, every smoothing of every octave), 1 detection (DoG, extremum test, compaction,
+ * refinement, summed over the octaves), 2 what stands at sift.cc:467-473: the orientations, or the shape adaptation's moment
+ * kernel summed over its rounds, 3 descriptors (patch, gradient and raw descriptor of every (feature, pooling scale)), 4 pooling,
  * normalisation and bytes.  DSM_ERR_NOT_READY before the first call. */
 #define DSM_COVARIANT_SIFT_STAGES 5
 int dsm_get_covariant_sift_time(dsm_ctx* ctx, double* stage_ms);

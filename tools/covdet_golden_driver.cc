@@ -5,7 +5,10 @@
 // feature and pooling scale.  The project's own source; it includes covdet.h and sift.h alone and is compiled against the
 // reference's VLFeat sources by tools/make_covdet_golden.py, into a temporary directory.
 //
-//   usage: covdet_golden_driver request.bin result.bin
+//   usage: covdet_golden_driver request.bin result.bin [affine]
+//   With the third argument (the word affine) the one call at sift.cc:467-473 is vl_covdet_extract_affine_shape instead of
+//   vl_covdet_extract_orientations -- estimate_affine_shape = true -- and the third list holds the adapted features; everything
+//   else is the same.  Without it the output is what it always was.
 //   request: int32 width, height, octave_resolution, first_octave, max_num_features, upright, domain_size_pooling,
 //            dsp_num_scales; double peak_threshold, edge_threshold, dsp_min_scale, dsp_max_scale; width * height grey bytes
 //   result:  int32 n_detected, n_suppressed (VLFeat's counter), n_after_suppression, n_oriented, n_kept, num_scales, 0, 0;
@@ -66,7 +69,9 @@ double now() {
 int main(int argc, char** argv) {
   int32_t hdr[8];
   double thr[4];
-  if (argc != 3) return 2;
+  if (argc != 3 && argc != 4) return 2;
+  const bool affine = argc == 4;
+  if (affine && strcmp(argv[3], "affine") != 0) return 2;
   FILE* f = fopen(argv[1], "rb");
   if (!f || fread(hdr, 4, 8, f) != 8 || fread(thr, 8, 4, f) != 4) return 3;
   const size_t n = (size_t)hdr[0] * (size_t)hdr[1];
@@ -92,7 +97,12 @@ int main(int argc, char** argv) {
   counts[1] = (int32_t)vl_covdet_get_num_non_extrema_suppressed(covdet);
   counts[2] = (int32_t)vl_covdet_get_num_features(covdet);
   write_features(out, vl_covdet_get_features(covdet), counts[2]);
-  if (!hdr[5]) vl_covdet_extract_orientations(covdet);  // sift.cc:467-473
+  if (!hdr[5]) {  // sift.cc:467-473
+    if (affine)
+      vl_covdet_extract_affine_shape(covdet);
+    else
+      vl_covdet_extract_orientations(covdet);
+  }
   const int num_features = (int)vl_covdet_get_num_features(covdet);
   VlCovDetFeature* features = (VlCovDetFeature*)vl_covdet_get_features(covdet);
   counts[3] = num_features;

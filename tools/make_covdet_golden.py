@@ -61,7 +61,8 @@ def build(reference, out_dir, sse2):
     return exe
 
 
-def run(exe, work, image, o):
+def run(exe, work, image, o, extra=()):
+    """One run of the driver; `extra` are further arguments (tools/make_covdet_affine_golden.py passes the third one)."""
     h, w = image.shape
     req, res = os.path.join(work, "request.bin"), os.path.join(work, "result.bin")
     with open(req, "wb") as f:
@@ -69,7 +70,7 @@ def run(exe, work, image, o):
                             o["domain_size_pooling"], o["dsp_num_scales"]))
         f.write(struct.pack("<4d", o["peak_threshold"], o["edge_threshold"], o["dsp_min_scale"], o["dsp_max_scale"]))
         f.write(np.ascontiguousarray(image, np.uint8).tobytes())
-    subprocess.check_call([exe, req, res])
+    subprocess.check_call([exe, req, res] + list(extra))
     return open(res, "rb").read()
 
 
