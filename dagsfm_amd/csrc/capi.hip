@@ -1164,12 +1164,16 @@ static int verify_core(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* d_pairs, 
   HIPCHK(ctx, ctx->d_pair_state.reserve(std::max<size_t>(n_pairs, 1) * 1280 * 4));
   HIPCHK(ctx, ctx->d_pts_px.reserve(tm * 32));
   HIPCHK(ctx, ctx->d_pts_norm.reserve(tm * 32));
+  const uint64_t f32_stride = total_matches + 3ull * std::max<uint32_t>(n_pairs, 1);  // (kernels.h pts_f32: 16 bytes per match and point set + 48 per pair)
+  HIPCHK(ctx, ctx->d_pts_f32.reserve(2 * f32_stride * 16));
   HIPCHK(ctx, ctx->d_reports.reserve(std::max<size_t>(n_pairs, 1) * 3 * sizeof(RansacReport)));
   HIPCHK(ctx, ctx->d_masks.reserve(tm * 3));
   VerifyParams vp;
   vp.pair_state = ctx->d_pair_state.as<uint32_t>();
   vp.pts_px = ctx->d_pts_px.as<double>();
   vp.pts_norm = ctx->d_pts_norm.as<double>();
+  vp.pts_f32 = ctx->d_pts_f32.as<float4>();
+  vp.pts_f32_stride = f32_stride;
   vp.reports = ctx->d_reports.as<RansacReport>();
   vp.masks = ctx->d_masks.as<unsigned char>();
   vp.mask_stride = tm;
@@ -1241,9 +1245,11 @@ static int verify_core(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* d_pairs, 
   vp.score_prefilter = ctx->dbg("DSM_SCORE_PREFILTER") ? atoi(ctx->dbg("DSM_SCORE_PREFILTER")) : 1;
   // "check": every slot is scored exactly AND held against its bounds (counters [14] violations, [15] slots the filter
   // would have skipped; dsm_debug_verify_counters); the statistics counters stay alive across the rounds
+  // "check65": the same over the bound steps of =65 (the packed-f32 loops with their in-kernel staging)
   const bool prefilter_check = ctx->dbg("DSM_SCORE_PREFILTER") && strcmp(ctx->dbg("DSM_SCORE_PREFILTER"), "check") == 0;
-  if (prefilter_check) {
-    vp.score_prefilter = 5;
+  const bool prefilter_check65 = ctx->dbg("DSM_SCORE_PREFILTER") && strcmp(ctx->dbg("DSM_SCORE_PREFILTER"), "check65") == 0;
+  if (prefilter_check || prefilter_check65) {
+    vp.score_prefilter = prefilter_check65 ? 5 + 64 : 5;
     vp.stats = 1;
   }  // =1: the round-2 kernel (matrix in global scratch) for every problem
   vp.models = nullptr;

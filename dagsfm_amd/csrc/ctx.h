@@ -180,7 +180,7 @@ struct dsm_ctx {
   // last dsm_verify_pairs
   bool verified = false;
   DevBuf d_cams, d_pairs_dev, d_seeds, d_tvg, d_inl, d_inl_counts, d_inl_off, d_inl_compact, d_vscratch, d_inl_total;
-  DevBuf d_nt_table, d_nt_off, d_nt_off_t, d_pair_state, d_pts_px, d_pts_norm, d_reports, d_masks;
+  DevBuf d_nt_table, d_nt_off, d_nt_off_t, d_pair_state, d_pts_px, d_pts_norm, d_pts_f32, d_reports, d_masks;
   DevBuf d_fam_state, d_sidx, d_lo_inl;
   DevBuf d_nt_table_t, d_wm_redo, d_wm_total, d_wm_count, d_lo_inl_pool, d_pose_jobs;
   VerifyLane lanes[DSM_VERIFY_MAX_LANES];
@@ -274,7 +274,7 @@ struct dsm_ctx {
   void for_each_buffer(F f) {
     for (DevBuf* b : {&d_desc, &d_rterm, &d_kp, &d_img_row0, &d_img_rows, &d_lut, &d_stage, &d_counts, &d_offsets, &d_matches, &d_total, &d_etotal,
                       &d_cams, &d_pairs_dev, &d_seeds, &d_tvg, &d_inl, &d_inl_counts, &d_inl_off, &d_inl_compact, &d_inl_total, &d_nt_table,
-                      &d_nt_off, &d_nt_off_t, &d_pair_state, &d_pts_px, &d_pts_norm, &d_reports, &d_masks, &d_fam_state, &d_sidx, &d_lo_inl,
+                      &d_nt_off, &d_nt_off_t, &d_pair_state, &d_pts_px, &d_pts_norm, &d_pts_f32, &d_reports, &d_masks, &d_fam_state, &d_sidx, &d_lo_inl,
                       &d_nt_table_t, &d_wm_redo, &d_wm_total, &d_wm_count, &d_lo_inl_pool, &d_pose_jobs,
                       &d_g_nfeat, &d_g_dpairs, &d_g_doff, &d_g_pdir, &d_g_params, &d_g_m, &d_g_counts, &d_g_offsets, &d_g_total, &d_g_matches,
                       &d_g_plan, &d_g_inl, &d_g_inl_off,

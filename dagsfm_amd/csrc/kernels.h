@@ -175,6 +175,11 @@ struct VerifyParams {
   uint32_t* pair_state;        // [n_pairs][640]: MT19937 state (624 words) + index
   double* pts_px;              // [total][4] matched pixel points x1 y1 x2 y2
   double* pts_norm;            // [total][4] the same through Camera::ImageToWorld (calibrated pairs)
+  // what the bound steps' packed-f32 loops read, written once per call by k_verify_prep (verify_kernels.hip pair_f32): point set s
+  // (0: pts_px, 1: pts_norm) of pair pi at 16-byte unit s * pts_f32_stride + match_off[pi] + 3 * pi -- two units of maxima (four
+  // doubles: max |x1|, |y1|, |x2|, |y2|), then the points as f32, 32 bytes per two points
+  float4* pts_f32;             // [2][pts_f32_stride]
+  uint64_t pts_f32_stride;     // total + 3 * n_pairs
   RansacReport* reports;       // [n_pairs][3] E, F, H
   unsigned char* masks;        // [3][mask_stride] inlier masks of the three families
   uint64_t mask_stride;
@@ -190,6 +195,7 @@ struct VerifyParams {
   int dbg_jacobi_groups, dbg_roots_lds, dbg_final_waves;  // dsm_set_debug_option switches the launch helpers read
   int dbg_pose_full;           // check build, DSM_POSE_FULL: k_final_pose_full (every candidate checks every inlier) instead of k_final_pose
   int score_prefilter;         // F / H scoring as bound + exact (k_prescore, k_score_needed); 0: plain k_score (DSM_SCORE_PREFILTER=0)
+                               // check build: bit 64 (=65) runs the packed-f32 bound steps with their in-kernel staging (k_prescore_*_staged)
   int stats;                   // DSM_VERIFY_DEBUG: count candidates / local optimisations (one-address atomics) in the replay
   int norms_exact;             // check build, DSM_NORMS_EXACT: the minimal solvers' exact pivot-norm bookkeeping for every wave (colpiv_norms.h)
   uint32_t spec_margin[3];     // k_sample: trials a later round speculates beyond what the dynamic stop asks for (samples without a model)

@@ -965,7 +965,7 @@ DSM_DEVN int decompose_homography(const double* H, const double* K1, const doubl
 // The verification of a pair list runs as five launches over the same grid-stride pair loop so that
 // each phase gets its own register allocation (the 5-point solver would otherwise pin the whole
 // pipeline at one wave per SIMD):
-//   k_verify_prep      gather matched points (+ ImageToWorld), seed the pair's MT19937
+//   k_verify_prep      gather matched points (+ ImageToWorld; + their maxima and f32 records for the bound steps), seed the pair's MT19937
 //   k_ransac<E|F|H>    one LO-RANSAC family each, in the stream order E -> F -> H; the generator
 //                      state travels between the launches through pair_state
 //   k_verify_final     decision tree, inlier extraction, watermark, relative pose, output
@@ -1064,6 +1064,32 @@ DSM_DEV WgScratch wg_scratch(const VerifyParams& p) {
   return w;
 }
 
+// The per-pair set-up of the bound steps with a packed-f32 first stage (kernels.h pts_f32): point set `set` (0: pts_px, 1: pts_norm) of
+// pair pi starts with two 16-byte units that hold max |x1|, |y1|, |x2|, |y2| as doubles (what stage_points_with_maxima returns: max is
+// exact and order-free); behind them the points as f32, two per 32-byte record (x1a, x1b, y1a, y1b, x2a, x2b, y2a, y2b), an odd last point twice.
+DSM_DEV float4* pair_f32(const VerifyParams& p, int set, uint32_t pi, uint64_t moff) { return p.pts_f32 + (size_t)set * p.pts_f32_stride + moff + 3 * (size_t)pi; }
+DSM_DEV void store_f32_point(float* rec, int i, bool twice, double x1, double y1, double x2, double y2, double m[4]) {
+  float* r = rec + (size_t)(i >> 1) * 8 + (i & 1);
+  const float f[4] = {(float)x1, (float)y1, (float)x2, (float)y2};
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    r[2 * c] = f[c];
+    if (twice) r[2 * c + 1] = f[c];
+  }
+  m[0] = fmax(m[0], fabs(x1));
+  m[1] = fmax(m[1], fabs(y1));
+  m[2] = fmax(m[2], fabs(x2));
+  m[3] = fmax(m[3], fabs(y2));
+}
+DSM_DEV void store_f32_maxima(double* dst, double m[4], int lane) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) m[c] = fmax(m[c], __shfl_xor(m[c], o));
+  }
+  if (lane < 4) dst[lane] = lane == 0 ? m[0] : (lane == 1 ? m[1] : (lane == 2 ? m[2] : m[3]));
+}
+
 __global__ __launch_bounds__(64) void k_verify_prep(const VerifyParams p) {
   __shared__ MtState sm;
   const int lane = threadIdx.x;
@@ -1092,18 +1118,28 @@ __global__ __launch_bounds__(64) void k_verify_prep(const VerifyParams p) {
     const double* kp2 = p.kp + (size_t)p.img_row0[im2] * 2;
     double* pts_px = p.pts_px + 4 * moff;
     double* pts_norm = p.pts_norm + 4 * moff;
+    // what every wave of the bound steps' packed-f32 loops needs of the pair (k_prescore_h2, k_prescore_compact2), once per call: the
+    // four maxima and the points as f32 records (pair_f32).  A lane writes its own point's half of a record, an odd last point both halves
+    float* rec_px = reinterpret_cast<float*>(pair_f32(p, 0, pi, moff) + 2);
+    float* rec_norm = reinterpret_cast<float*>(pair_f32(p, 1, pi, moff) + 2);
+    double mpx[4] = {0.0, 0.0, 0.0, 0.0}, mnorm[4] = {0.0, 0.0, 0.0, 0.0};
     for (int i = lane; i < n; i += 64) {
       const uint32_t i1 = matches[2 * i], i2 = matches[2 * i + 1];
       const double x1 = kp1[2 * (size_t)i1], y1 = kp1[2 * (size_t)i1 + 1];
       const double x2 = kp2[2 * (size_t)i2], y2 = kp2[2 * (size_t)i2 + 1];
       pts_px[4 * i + 0] = x1; pts_px[4 * i + 1] = y1; pts_px[4 * i + 2] = x2; pts_px[4 * i + 3] = y2;
+      const bool twice = i == n - 1 && !(i & 1);
+      store_f32_point(rec_px, i, twice, x1, y1, x2, y2, mpx);
       if (calibrated) {
         double u1, v1, u2, v2;
         image_to_world(cam1, x1, y1, &u1, &v1);
         image_to_world(cam2, x2, y2, &u2, &v2);
         pts_norm[4 * i + 0] = u1; pts_norm[4 * i + 1] = v1; pts_norm[4 * i + 2] = u2; pts_norm[4 * i + 3] = v2;
+        store_f32_point(rec_norm, i, twice, u1, v1, u2, v2, mnorm);
       }
     }
+    store_f32_maxima(reinterpret_cast<double*>(pair_f32(p, 0, pi, moff)), mpx, lane);
+    if (calibrated) store_f32_maxima(reinterpret_cast<double*>(pair_f32(p, 1, pi, moff)), mnorm, lane);
     wv_sync();
     uint32_t* st = p.pair_state + (size_t)pi * PAIR_STATE_WORDS;
     if (p.reseed) {  // a later pass of EstimateMultiple continues the pair's stream instead
@@ -2409,7 +2445,213 @@ DSM_DEV dsm_f32x2 pk2(float x) {
   return v;
 }
 #define PRESCORE_LIST_CAP 24
+// ---- what the packed-f32 bound steps share (k_prescore_h2, k_prescore_compact2)
+// The pair's f32 records from the per-pair buffer of k_verify_prep into the LDS: four loads of a lane in flight, addresses clamped.
+DSM_DEV void copy_f32_records(const float4* rec, int nrec, float4* s32v, int lane) {
+  for (int j0 = 0; j0 < nrec; j0 += 256) {
+    float4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = rec[j0 + u * 64 + lane < nrec ? j0 + u * 64 + lane : nrec - 1];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (j0 + u * 64 + lane < nrec) s32v[j0 + u * 64 + lane] = v[u];
+  }
+}
+// One trip of the drain: W listed points per lane in FP64, their loads issued together (a trip pays one memory round trip, not W).
+// DECIDED: lb counts the points the test decides either way, not only the surely-in ones (k_prescore_compact2's bookkeeping).
+template <int FAM, int W, bool DECIDED>
+DSM_DEV void drain_trip(const double* M, const PreBounds& b, const double* gpts, const uint16_t* lst, int lane, int k0, int cnt, int& lb, int& sure_out) {
+  double q[W][4];
+  bool on[W];
+#pragma unroll
+  for (int u = 0; u < W; ++u) {
+    on[u] = k0 + u < cnt;
+    const double* src = gpts + (size_t)(on[u] ? lst[(k0 + u) * 64 + lane] : 0) * 4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) q[u][c] = src[c];
+  }
+#pragma unroll
+  for (int u = 0; u < W; ++u) {
+    bool in, out;
+    prescore_flags<FAM>(M, b, q[u], in, out);
+    lb += (on[u] && (in || (DECIDED && out))) ? 1 : 0;
+    sure_out += (on[u] && out) ? 1 : 0;
+  }
+}
+// The lanes' lists of band points in FP64.  The wave loops to its longest list; a trip is as wide as what is left of it (4, 2 or 1
+// points, chosen by wave-uniform branches), not four predicated tests whatever the length.
+template <int FAM, bool DECIDED>
+DSM_DEV void drain_lists(const double* M, const PreBounds& b, const double* gpts, const uint16_t* lst, int lane, int cnt, int& lb, int& sure_out) {
+  int maxc = cnt;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) maxc = max(maxc, __shfl_xor(maxc, o));
+  maxc = __builtin_amdgcn_readfirstlane(maxc);
+  int k0 = 0;
+  for (; maxc - k0 > 2; k0 += 4) drain_trip<FAM, 4, DECIDED>(M, b, gpts, lst, lane, k0, cnt, lb, sure_out);
+  if (maxc - k0 == 2) drain_trip<FAM, 2, DECIDED>(M, b, gpts, lst, lane, k0, cnt, lb, sure_out);
+  if (maxc - k0 == 1) drain_trip<FAM, 1, DECIDED>(M, b, gpts, lst, lane, k0, cnt, lb, sure_out);
+}
+// The packed loops keep their compare results as what the hardware makes of them: 64-bit lane masks in scalar registers (v_cmp
+// writes one), combined by scalar and / or.  As per-lane bools the compiler turned them into 0 / 1 values and back wherever a mask
+// was needed (a v_cndmask and a v_cmp_ne each time).  The compares are the ordered ones of the C operators >=, > and <.
+typedef unsigned long long lane_mask;
+DSM_DEV lane_mask mask_ge(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 3); }  // ordered >=
+DSM_DEV lane_mask mask_gt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 2); }  // ordered >
+DSM_DEV lane_mask mask_lt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 4); }  // ordered <
+DSM_DEV bool in_mask(lane_mask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }  // this lane's bit (the mask becomes the execution mask: no VALU)
+// acc += (this lane's bit of m) as ONE VALU instruction: the mask goes in as the carry of an add with 0.  (From `acc += c ? 1 : 0`
+// the compiler makes a v_cndmask 0 / 1 per compare and a v_add3 per two of them.)
+DSM_DEV void add_mask(int& acc, lane_mask m) {
+  lane_mask carry;
+  asm("v_addc_co_u32_e64 %0, %1, 0, %0, %2" : "+v"(acc), "=&s"(carry) : "s"(m));
+}
+// wave-uniform: does the predicate hold in any lane?  (__any takes an int: a v_cndmask and a v_cmp_ne to get the mask back)
+DSM_DEV bool any_lane(bool m) { return __builtin_amdgcn_ballot_w64(m) != 0ull; }
+
+#define H2_GROUP 8
+struct H2Model {
+  dsm_f32x2 h0, h1, h2, h3, h4, h5, h6, h7, h8, ko, ki;
+  float g;
+};
+// One trip of k_prescore_h2's packed loop: the two points of record `rec` (BOTH = false: the odd last point, the record's first half).
+// A point is surely out, surely in or listed; only the surely-out points and the listed ones are counted (the caller has the rest).
+// One wave-uniform test covers the listing of both points: its body runs a few times per model.
+template <bool BOTH>
+DSM_DEV void h2_trip(const H2Model& m, lane_mask active, const float4* rec, int i0, uint16_t* lst, int lane, int& sure_out, int& cnt) {
+  const float4 lo = rec[0], hi = rec[1];
+  const dsm_f32x2 s0 = {lo.x, lo.y}, s1 = {lo.z, lo.w}, d0 = {hi.x, hi.y}, d1 = {hi.z, hi.w};
+  const dsm_f32x2 p0 = pk_fma(m.h0, s0, pk_fma(m.h1, s1, m.h2));
+  const dsm_f32x2 p1 = pk_fma(m.h3, s0, pk_fma(m.h4, s1, m.h5));
+  const dsm_f32x2 p2 = pk_fma(m.h6, s0, pk_fma(m.h7, s1, m.h8));
+  const dsm_f32x2 e0 = pk_fma(d0, p2, -p0);
+  const dsm_f32x2 e1 = pk_fma(d1, p2, -p1);
+  const dsm_f32x2 L = pk_fma(e0, e0, e1 * e1);
+  const dsm_f32x2 Q = p2 * p2;
+  const dsm_f32x2 QO = m.ko * Q, QI = m.ki * Q;
+  const lane_mask ok_a = mask_ge(fabsf(p2.x), m.g), gt_a = mask_gt(L.x, QO.x);
+  const lane_mask io_a = ok_a & (gt_a | mask_lt(L.x, QI.x));  // surely in or surely out
+  add_mask(sure_out, ok_a & gt_a);
+  lane_mask decided = io_a, io_b = 0;
+  if (BOTH) {
+    const lane_mask ok_b = mask_ge(fabsf(p2.y), m.g), gt_b = mask_gt(L.y, QO.y);
+    io_b = ok_b & (gt_b | mask_lt(L.y, QI.y));
+    add_mask(sure_out, ok_b & gt_b);
+    decided &= io_b;
+  }
+  if (decided != active) {  // some lane has a point inside the band (or unguarded): the FP64 test decides, later
+    if (in_mask(active & ~io_a)) {
+      if (cnt < PRESCORE_LIST_CAP) lst[cnt * 64 + lane] = (uint16_t)i0;
+      ++cnt;
+    }
+    if (BOTH && in_mask(active & ~io_b)) {
+      if (cnt < PRESCORE_LIST_CAP) lst[cnt * 64 + lane] = (uint16_t)(i0 + 1);
+      ++cnt;
+    }
+  }
+}
 __global__ __launch_bounds__(64, 6) void k_prescore_h2(const VerifyParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float4* s32v = reinterpret_cast<float4*>(smem_raw);  // the points as f32 pairs (16 bytes per point), then the lanes' lists; the FP64 points stay in global memory / L2
+  // (with the FP64 copy in the LDS as well -- 15 KB per 256 points -- the kernel runs at 2.5 waves per SIMD: 57 ms instead of 33)
+  const uint32_t pl = blockIdx.x;
+  const uint32_t pi = p.pair0 + pl;
+  const FamState* fs = p.fam_state + (size_t)pi * 3 + FAM_H;
+  if (!fs->active) return;
+  const int lane = threadIdx.x;
+  const int nb = (int)fs->nb;
+  const int t = blockIdx.y * 64 + lane;
+  if ((int)(blockIdx.y * 64) >= nb) return;
+  const uint64_t moff = p.match_off[pi];
+  const int n = (int)(p.match_off[pi + 1] - moff);
+  const double* gpts = p.pts_px + 4 * moff;
+  const bool in_lds = n <= VP_LDS_PTS;
+  const double T = p.opt.max_error * p.opt.max_error;
+  const bool has_slot = t < nb;
+  const bool has_model = has_slot && 0 < p.nmodels[(size_t)pl * p.batch + (has_slot ? t : 0)];
+  const double* gm = p.models + ((size_t)pl * p.batch + (has_slot ? t : 0)) * 9;
+  double M[9];
+  for (int k = 0; k < 9; ++k) M[k] = has_model ? gm[k] : 0.0;
+  int lb = 0, sure_out = n + 1;
+  // the pair's maxima and f32 records: written once per call by k_verify_prep (28 waves per pair and round used to redo them)
+  const float4* rec = pair_f32(p, 0, pi, moff);
+  double mx[4];
+  for (int c = 0; c < 4; ++c) mx[c] = reinterpret_cast<const double*>(rec)[c];
+  if (!in_lds) {  // the points do not fit the LDS: the FP64 loop over wave-uniform global addresses, as k_prescore<H>
+    if (has_model) {
+      const PreBounds b = prescore_bounds<FAM_H>(M, mx, T);
+      sure_out = 0;
+#pragma unroll 4
+      for (int i = 0; i < n; ++i) prescore_point<FAM_H>(M, b, gpts + (size_t)i * 4, lb, sure_out);
+    }
+  } else {
+    const int npair = (n + 1) / 2;
+    uint16_t* lst = reinterpret_cast<uint16_t*>(s32v + (size_t)2 * npair);  // entry k of lane l at [k * 64 + l]
+    copy_f32_records(rec + 2, 2 * npair, s32v, lane);
+    __syncthreads();
+    const PreBounds b = prescore_bounds<FAM_H>(M, mx, T);
+    // ---- the model in f32 (largest entry scaled into [1, 2)), the guard g, the band's constants
+    float H[9], g = __builtin_inff(), k_out = __builtin_inff(), k_in = -1.0f;
+    {
+      double big = 0.0;
+      for (int k = 0; k < 9; ++k) big = fmax(big, fabs(M[k]));
+      const bool usable = has_model && (b.c0 == b.c0) && big >= 0x1p-900 && big <= 0x1p900;  // (c0 is NaN when t_ok / x_ok fail)
+      const double sc = usable ? ldexp(1.0, -ilogb(big)) : 0.0;
+      double Ms[9];
+      for (int k = 0; k < 9; ++k) {
+        Ms[k] = M[k] * sc;
+        H[k] = (float)Ms[k];
+      }
+      const double A0 = fabs(Ms[0]) * mx[0] + fabs(Ms[1]) * mx[1] + fabs(Ms[2]);
+      const double A1 = fabs(Ms[3]) * mx[0] + fabs(Ms[4]) * mx[1] + fabs(Ms[5]);
+      const double A2 = fabs(Ms[6]) * mx[0] + fabs(Ms[7]) * mx[1] + fabs(Ms[8]);
+      const double G = 6.01 * (mx[2] + mx[3]) * A2 + 5.0 * (A0 + A1 + 2.0 * A2);
+      const double gd = fmax(fmax(0x1p-24 * (58.0 * A2 + 8.6 * G / sqrt(T)), 0x1p-16 * A2), fmax(0x1p-24 * fmax(A0, A1), 0x1p-60)) * 1.001;
+      if (usable && gd <= 0x1p100) {
+        g = (float)gd * 1.0001f;                                     // rounded up
+        k_out = (float)(1.265625 * T * (1.0 + 0x1p-8)) * 1.0001f;      // rounded up
+        k_in = (float)(0.765625 * T * (1.0 - 0x1p-8)) * 0.9999f;       // rounded down
+      }
+    }
+    int cnt = 0;
+    if (has_model) {
+      sure_out = 0;
+      const H2Model hm = {pk2(H[0]), pk2(H[1]), pk2(H[2]), pk2(H[3]), pk2(H[4]), pk2(H[5]), pk2(H[6]), pk2(H[7]), pk2(H[8]), pk2(k_out), pk2(k_in), g};
+      const lane_mask active = __builtin_amdgcn_ballot_w64(true);  // the lanes with a model
+      const int nfull = n >> 1;
+      // groups unrolled by hand: the group's LDS address lives in a vector register the compiler cannot see through (from a scalar
+      // one it re-made the address with a v_mov on every trip), the trips read at immediate offsets from it
+      int j = 0, off = 0;
+      asm volatile("" : "+v"(off));
+      for (; j + H2_GROUP <= nfull; j += H2_GROUP, off += 32 * H2_GROUP) {
+        const float4* grp = reinterpret_cast<const float4*>(smem_raw + off);
+#pragma unroll
+        for (int u = 0; u < H2_GROUP; ++u) h2_trip<true>(hm, active, grp + 2 * u, 2 * (j + u), lst, lane, sure_out, cnt);
+      }
+      for (; j < nfull; ++j) h2_trip<true>(hm, active, s32v + 2 * j, 2 * j, lst, lane, sure_out, cnt);
+      if (n & 1) h2_trip<false>(hm, active, s32v + 2 * nfull, 2 * nfull, lst, lane, sure_out, cnt);  // the odd last point, outside the loop
+      lb = n - sure_out - cnt;  // surely in: neither surely out nor listed
+    }
+    // ---- the listed points in FP64; a lane whose list overflowed (a model the f32 stage cannot judge) redoes all of its points
+    const bool overflow = cnt > PRESCORE_LIST_CAP;
+    if (overflow) {
+      lb = 0;
+      sure_out = 0;
+      for (int i = 0; i < n; ++i) prescore_point<FAM_H>(M, b, gpts + (size_t)i * 4, lb, sure_out);
+      cnt = 0;
+    }
+    drain_lists<FAM_H, false>(M, b, gpts, lst, lane, cnt, lb, sure_out);
+  }
+  if (has_slot) {
+    p.counts[(size_t)pl * p.batch + t] = n - sure_out;  // -1: no model in this slot
+    reinterpret_cast<int32_t*>(p.sums + (size_t)pl * p.batch + t)[0] = lb;
+  }
+}
+
+#ifdef DSM_CHECK_BUILD
+// The form before the per-pair buffer (DSM_SCORE_PREFILTER=65, check build): every wave stages the pair's points itself -- FP64 reads, the
+// maxima across the wave, the conversions -- and the packed loop counts both bounds and tests `two` on every trip.  Same bounds, bit for
+// bit (tests/test_bound_loops_gpu.py, tools/check_schedules.py staged_loops).
+__global__ __launch_bounds__(64, 6) void k_prescore_h2_staged(const VerifyParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   float* s32 = reinterpret_cast<float*>(smem_raw);  // the points as f32 pairs (16 bytes per point), then the lanes' lists; the FP64 points stay in global memory / L2
   // (with the FP64 copy in the LDS as well -- 15 KB per 256 points -- the kernel runs at 2.5 waves per SIMD: 57 ms instead of 33)
@@ -2552,6 +2794,7 @@ __global__ __launch_bounds__(64, 6) void k_prescore_h2(const VerifyParams p) {
     reinterpret_cast<int32_t*>(p.sums + (size_t)pl * p.batch + t)[0] = lb;
   }
 }
+#endif  // DSM_CHECK_BUILD
 
 #ifdef DSM_CHECK_BUILD
 // ------------------------------------------------------------------------------------ the H bound step on the matrix pipe (round 5)
@@ -3252,10 +3495,194 @@ __global__ __launch_bounds__(64, 8) void k_prescore_compact(const VerifyParams p
 // tools/check_score_bounds.py (DSM_SCORE_PREFILTER=check) holds every slot's exact count against [lower, upper]; DSM_SCORE_PREFILTER=33
 // (check build) runs the pure FP64 k_prescore_compact instead.
 #ifndef K_PRESCORE_C2_WAVES
-#define K_PRESCORE_C2_WAVES 5  // 96 VGPRs + 24 bytes of scratch per lane: 12.5 + 10.5 ms against 13.1 + 10.8 at four waves per SIMD (100 VGPRs); six spill the stretch loop
+#define K_PRESCORE_C2_WAVES 5  // 96 VGPRs, no scratch since the loop's bookkeeping was trimmed (before: + 24 bytes per lane, and 12.5 + 10.5 ms against 13.1 + 10.8 at four waves per SIMD, 100 VGPRs; six spilled the stretch loop)
 #endif
+#define C2_GROUP 4
+struct C2Model {
+  dsm_f32x2 f0, f1, f2, f3, f4, f5, f6, f7, f8, ko, ki;
+  float gd2;
+};
+// One trip of k_prescore_compact2's packed loop: the two points of record `rec` (BOTH = false: the odd last point, the record's first
+// half).  As h2_trip: surely-out points and listed points are counted, one wave-uniform test covers the listing of both points.
+template <bool BOTH>
+DSM_DEV void c2_trip(const C2Model& m, lane_mask active, const float4* rec, int i0, uint16_t* lst, int lane, int& sure_out, int& cnt) {
+  const float4 lo = rec[0], hi = rec[1];
+  const dsm_f32x2 x10 = {lo.x, lo.y}, x11 = {lo.z, lo.w}, x20 = {hi.x, hi.y}, x21 = {hi.z, hi.w};
+  const dsm_f32x2 g0 = pk_fma(m.f0, x10, pk_fma(m.f1, x11, m.f2));
+  const dsm_f32x2 g1 = pk_fma(m.f3, x10, pk_fma(m.f4, x11, m.f5));
+  const dsm_f32x2 g2 = pk_fma(m.f6, x10, pk_fma(m.f7, x11, m.f8));
+  const dsm_f32x2 h0 = pk_fma(m.f0, x20, pk_fma(m.f3, x21, m.f6));
+  const dsm_f32x2 h1 = pk_fma(m.f1, x20, pk_fma(m.f4, x21, m.f7));
+  const dsm_f32x2 C = pk_fma(x20, g0, pk_fma(x21, g1, g2));
+  const dsm_f32x2 num = C * C;
+  const dsm_f32x2 D = pk_fma(g0, g0, pk_fma(g1, g1, pk_fma(h0, h0, h1 * h1)));
+  const dsm_f32x2 DO = m.ko * D, DI = m.ki * D;
+  const lane_mask ok_a = mask_ge(D.x, m.gd2), gt_a = mask_gt(num.x, DO.x);
+  const lane_mask io_a = ok_a & (gt_a | mask_lt(num.x, DI.x));  // surely in or surely out
+  add_mask(sure_out, ok_a & gt_a);
+  lane_mask decided = io_a, io_b = 0;
+  if (BOTH) {
+    const lane_mask ok_b = mask_ge(D.y, m.gd2), gt_b = mask_gt(num.y, DO.y);
+    io_b = ok_b & (gt_b | mask_lt(num.y, DI.y));
+    add_mask(sure_out, ok_b & gt_b);
+    decided &= io_b;
+  }
+  if ((active & ~decided) != 0) {  // some lane with a model has a point inside the band (or unguarded): the FP64 test decides, at the end of the stretch
+    if (in_mask(active & ~io_a)) {
+      lst[cnt * 64 + lane] = (uint16_t)i0;
+      ++cnt;
+    }
+    if (BOTH && in_mask(active & ~io_b)) {
+      lst[cnt * 64 + lane] = (uint16_t)(i0 + 1);
+      ++cnt;
+    }
+  }
+}
 template <int FAM>
 __global__ __launch_bounds__(64, K_PRESCORE_C2_WAVES) void k_prescore_compact2(const VerifyParams p) {
+  typedef Fam<FAM> F;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __shared__ uint16_t s_map[64];
+  // (dynamic LDS: the points as f32 pairs, 16 bytes per point, then the lanes' lists)
+  const uint32_t pl = blockIdx.x;
+  const uint32_t pi = p.pair0 + pl;
+  const FamState* fs = p.fam_state + (size_t)pi * 3 + FAM;
+  if (!fs->active) return;
+  const int lane = threadIdx.x;
+  const int nb = (int)fs->nb;
+  const int c0 = (int)blockIdx.y * 64;  // first compacted entry of this workgroup
+  if (c0 >= nb * F::MAXM) return;
+  const int32_t* nmod = p.nmodels + (size_t)pl * p.batch;
+  int run = 0;
+  for (int base = 0; base < nb; base += 64) {
+    const int t = base + lane;
+    const int nm = t < nb ? nmod[t] : 0;
+    int incl = nm;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o);
+      if (lane >= o) incl += v;
+    }
+    const int off = run + incl - nm;  // compacted index of this hypothesis' first model
+    if (off < c0 + 64 && off + nm > c0) {
+      for (int m = 0; m < nm; ++m) {
+        const int c = off + m - c0;
+        if (c >= 0 && c < 64) s_map[c] = (uint16_t)(t * F::MAXM + m);
+      }
+    }
+    run += __shfl(incl, 63);
+    if (run >= c0 + 64) break;  // (wave-uniform) the later hypotheses' models belong to later workgroups
+  }
+  if (c0 >= run) return;  // wave-uniform: no model of the pair is left for this workgroup
+  const uint64_t moff = p.match_off[pi];
+  const int n = (int)(p.match_off[pi + 1] - moff);
+  const double* gpts = (FAM == FAM_E ? p.pts_norm : p.pts_px) + 4 * moff;
+  const bool in_lds = n <= VP_LDS_PTS;
+  double T = p.opt.max_error * p.opt.max_error;
+  if (FAM == FAM_E) {
+    const double max_error = (image_to_world_threshold(p.cams[p.pairs[2 * pi]], p.opt.max_error) +
+                              image_to_world_threshold(p.cams[p.pairs[2 * pi + 1]], p.opt.max_error)) / 2;
+    T = max_error * max_error;
+  }
+  // the pair's maxima and f32 records: written once per call by k_verify_prep (every workgroup of every round used to redo them)
+  const float4* rec = pair_f32(p, FAM == FAM_E ? 1 : 0, pi, moff);
+  double mx[4];
+  for (int c = 0; c < 4; ++c) mx[c] = reinterpret_cast<const double*>(rec)[c];
+  const int npair = (n + 1) / 2;
+  float4* s32v = reinterpret_cast<float4*>(smem_raw);
+  uint16_t* lst = reinterpret_cast<uint16_t*>(s32v + (size_t)2 * (in_lds ? npair : 0));  // entry k of lane l at [k * 64 + l]
+  if (in_lds) copy_f32_records(rec + 2, 2 * npair, s32v, lane);
+  __syncthreads();  // (also publishes s_map)
+  const bool has_model = c0 + lane < run;
+  const int slot = has_model ? (int)s_map[lane] : 0;
+  const double* gm = p.models + ((size_t)pl * p.batch * F::MAXM + (size_t)slot) * 9;
+  double M[9];
+  for (int k = 0; k < 9; ++k) M[k] = has_model ? gm[k] : 0.0;
+  const PreBounds b = prescore_bounds<FAM>(M, mx, T);
+  int lb = 0, sure_out = 0;
+  if (!in_lds) {  // the points do not fit the LDS: the FP64 loop over wave-uniform global addresses, as k_prescore_compact
+    if (has_model) {
+#pragma unroll 4
+      for (int i = 0; i < n; ++i) prescore_point<FAM>(M, b, gpts + (size_t)i * 4, lb, sure_out);
+    }
+  } else {
+    // ---- the model in f32 (largest entry scaled into [1, 2)), the guard, the band's constants
+    float Ff[9], gd2 = __builtin_inff(), k_out = __builtin_inff(), k_in = -1.0f;
+    {
+      double big = 0.0;
+      for (int k = 0; k < 9; ++k) big = fmax(big, fabs(M[k]));
+      const bool usable = has_model && (b.c0 == b.c0) && big >= 0x1p-900 && big <= 0x1p900 && T >= 0x1p-40 && T <= 0x1p40;  // (c0 is NaN when t_ok / x_ok fail)
+      const double sc = usable ? ldexp(1.0, -ilogb(big)) : 0.0;
+      double Ms[9];
+      for (int k = 0; k < 9; ++k) {
+        Ms[k] = M[k] * sc;
+        Ff[k] = (float)Ms[k];
+      }
+      const double B0 = fabs(Ms[0]) * mx[0] + fabs(Ms[1]) * mx[1] + fabs(Ms[2]);
+      const double B1 = fabs(Ms[3]) * mx[0] + fabs(Ms[4]) * mx[1] + fabs(Ms[5]);
+      const double B2 = fabs(Ms[6]) * mx[0] + fabs(Ms[7]) * mx[1] + fabs(Ms[8]);
+      const double Bt0 = fabs(Ms[0]) * mx[2] + fabs(Ms[3]) * mx[3] + fabs(Ms[6]);
+      const double Bt1 = fabs(Ms[1]) * mx[2] + fabs(Ms[4]) * mx[3] + fabs(Ms[7]);
+      const double e = 5.0 * 0x1p-24 * (B0 + B1 + Bt0 + Bt1);
+      const double EC = 8.1 * 0x1p-24 * (mx[2] * B0 + mx[3] * B1 + B2);
+      const double gD = fmax(1.01 * (10.2 * e + 8.2 * EC / sqrt(T)), 0x1p-40);
+      if (usable && gD <= 0x1p40) {
+        gd2 = (float)(gD * gD * 1.001) * 1.0001f;                      // rounded up
+        k_out = (float)(1.265625 * T * (1.0 + 0x1p-8)) * 1.0001f;      // rounded up
+        k_in = (float)(0.765625 * T * (1.0 - 0x1p-8)) * 0.9999f;       // rounded down
+      }
+    }
+    // The WAVE walks the points in stretches: the packed-f32 loop runs until some lane's list of band points is about to fill up (or to
+    // the end), then all lanes work their lists off in FP64 together and the loop goes on where it stopped.  (The first form redid ALL
+    // points of a lane in FP64 once its list overflowed: with the ~500-match pairs of configs[4] -- 8 192 features -- most lanes
+    // overflow, and the step was 25 % slower than pure FP64: profiles/r06_prescore_ef_f32_stage.txt.  At config 2's 256 matches a
+    // list almost never fills: one stretch, one drain.)  The loop goes in groups of C2_GROUP trips and tests the cap once per group: a
+    // group adds at most 2 C2_GROUP entries to a list, so a stretch ends once a list is within that of PRESCORE_LIST_CAP; the trips
+    // left over at the end (fewer than a group, and the odd last point) follow a passed test as well.
+    const C2Model cm = {pk2(Ff[0]), pk2(Ff[1]), pk2(Ff[2]), pk2(Ff[3]), pk2(Ff[4]), pk2(Ff[5]), pk2(Ff[6]), pk2(Ff[7]), pk2(Ff[8]), pk2(k_out), pk2(k_in), gd2};
+    const lane_mask active = __builtin_amdgcn_ballot_w64(has_model);  // the lanes with a model: only they list points
+    const int nfull = n >> 1;
+    bool tail = (n & 1) != 0;
+    // Bookkeeping without a counter of its own for the surely-in points: sure_out takes the surely-out points of both stages, lb the
+    // listed points the FP64 test decides (either way) less all listed points -- minus the points still open; the rest of n is surely in.
+    int j = 0, off = 0;
+    asm volatile("" : "+v"(off));
+    while (j < nfull || tail) {
+      int cnt = 0;
+      bool full = false;
+      while (j + C2_GROUP <= nfull) {
+        const float4* grp = reinterpret_cast<const float4*>(smem_raw + off);  // (off = 32 j in a vector register, as in k_prescore_h2)
+#pragma unroll
+        for (int u = 0; u < C2_GROUP; ++u) c2_trip<true>(cm, active, grp + 2 * u, 2 * (j + u), lst, lane, sure_out, cnt);
+        j += C2_GROUP;
+        off += 32 * C2_GROUP;
+        if (any_lane(cnt > PRESCORE_LIST_CAP - 2 * C2_GROUP)) {
+          full = true;
+          break;
+        }
+      }
+      if (!full) {
+        for (; j < nfull; ++j) c2_trip<true>(cm, active, s32v + 2 * j, 2 * j, lst, lane, sure_out, cnt);
+        if (tail) c2_trip<false>(cm, active, s32v + 2 * nfull, 2 * nfull, lst, lane, sure_out, cnt);  // the odd last point, outside the loop
+        tail = false;
+      }
+      lb -= cnt;
+      // ---- the listed points in FP64
+      drain_lists<FAM, true>(M, b, gpts, lst, lane, cnt, lb, sure_out);
+    }
+    lb += n - sure_out;
+  }
+  if (has_model) {
+    p.counts[(size_t)pl * p.batch * F::MAXM + slot] = n - sure_out;
+    reinterpret_cast<int32_t*>(p.sums + (size_t)pl * p.batch * F::MAXM + slot)[0] = lb;
+  }
+}
+
+#ifdef DSM_CHECK_BUILD
+// The form before the per-pair buffer (DSM_SCORE_PREFILTER=65, check build), as k_prescore_h2_staged: in-kernel staging, both bounds
+// counted, `two` and the cap tested on every trip.  Same bounds, bit for bit.
+template <int FAM>
+__global__ __launch_bounds__(64, K_PRESCORE_C2_WAVES) void k_prescore_compact2_staged(const VerifyParams p) {
   typedef Fam<FAM> F;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __shared__ uint16_t s_map[64];
@@ -3431,6 +3858,8 @@ __global__ __launch_bounds__(64, K_PRESCORE_C2_WAVES) void k_prescore_compact2(c
     reinterpret_cast<int32_t*>(p.sums + (size_t)pl * p.batch * F::MAXM + slot)[0] = lb;
   }
 }
+
+#endif  // DSM_CHECK_BUILD
 
 // the inlier counts of ALL models of the block's 64 hypotheses (built by k_roots_e) with the lanes spread over the
 // correspondences (a hypothesis has 0..10 models: scoring them
@@ -5371,6 +5800,8 @@ void launch_vp_solve_score(const VerifyParams& p, int fam, hipStream_t st) {
 #ifdef DSM_CHECK_BUILD
       if (p.score_prefilter & 32)
         hipLaunchKernelGGL(k_prescore_compact<FAM_E>, dim3(p.n_chunk, (p.batch * 10 + 63) / 64), dim3(64), smem, st, p);
+      else if (p.score_prefilter & 64)  // =65: the packed-f32 loops with their in-kernel staging
+        hipLaunchKernelGGL(k_prescore_compact2_staged<FAM_E>, dim3(p.n_chunk, (p.batch * 10 + 63) / 64), dim3(64), smem_c2, st, p);
       else
 #endif
         hipLaunchKernelGGL(k_prescore_compact2<FAM_E>, dim3(p.n_chunk, (p.batch * 10 + 63) / 64), dim3(64), smem_c2, st, p);
@@ -5398,6 +5829,8 @@ void launch_vp_solve_score(const VerifyParams& p, int fam, hipStream_t st) {
 #ifdef DSM_CHECK_BUILD
       else if (p.score_prefilter & 32)
         hipLaunchKernelGGL(k_prescore_compact<FAM_F>, dim3(p.n_chunk, (p.batch * 3 + 63) / 64), dim3(64), smem, st, p);
+      else if (p.score_prefilter & 64)
+        hipLaunchKernelGGL(k_prescore_compact2_staged<FAM_F>, dim3(p.n_chunk, (p.batch * 3 + 63) / 64), dim3(64), smem_c2, st, p);
 #endif
       else
         hipLaunchKernelGGL(k_prescore_compact2<FAM_F>, dim3(p.n_chunk, (p.batch * 3 + 63) / 64), dim3(64), smem_c2, st, p);
@@ -5412,13 +5845,15 @@ void launch_vp_solve_score(const VerifyParams& p, int fam, hipStream_t st) {
     if (p.score_prefilter && p.batch <= 65535 && smem2 <= 64 * 1024) {
       // the bound step with its packed-f32 first stage (k_prescore_h2: the points once more as f32 behind the FP64 copy in the LDS).
       // Check build: DSM_SCORE_PREFILTER=17 the pure FP64 k_prescore<H> (round 4's form), =9 its K = 3 products on the FP64 matrix
-      // pipe (k_prescore_h_mfma: measured slower)
+      // pipe (k_prescore_h_mfma: measured slower), =65 the packed-f32 loops before the per-pair buffer (k_prescore_*_staged)
       const size_t smem_h2 = (size_t)(p.n_max < VP_LDS_PTS ? (p.n_max > 0 ? p.n_max : 1) : VP_LDS_PTS) * 16 + 32 + (size_t)PRESCORE_LIST_CAP * 64 * 2;
 #ifdef DSM_CHECK_BUILD
       if (p.score_prefilter & 8)
         hipLaunchKernelGGL(k_prescore_h_mfma, grid, dim3(64), smem, st, p);
       else if (p.score_prefilter & 16)
         hipLaunchKernelGGL(k_prescore<FAM_H>, grid, dim3(64), smem, st, p);
+      else if (p.score_prefilter & 64)
+        hipLaunchKernelGGL(k_prescore_h2_staged, grid, dim3(64), smem_h2, st, p);
       else
 #endif
         hipLaunchKernelGGL(k_prescore_h2, grid, dim3(64), smem_h2, st, p);

@@ -17,7 +17,9 @@ run on the PRODUCT library, the * schedules on a second context of the check lib
 one is compared with the product's `batched` records -- so the comparison also shows that the two builds agree.
   * no_prefilter, e_fused, final_1wave, legacy, h_mfma (DSM_SCORE_PREFILTER=9: the H bound step's products on the FP64 matrix pipe),
     h_f64 (=17: the pure FP64 H bound step of round 4; the product's has a packed-f32 first stage), ef_f64 (=33: the pure FP64 E / F
-    bound step k_prescore_compact; the product's k_prescore_compact2 has a packed-f32 first stage since round 6), replay_legacy (DSM_REPLAY_LEGACY:
+    bound step k_prescore_compact; the product's k_prescore_compact2 has a packed-f32 first stage since round 6), staged_loops (=65: the
+    packed-f32 bound steps as before the per-pair buffer of k_verify_prep -- every wave stages the points itself, and the packed loops
+    count both bounds and test the odd last point on every trip; k_prescore_h2_staged, k_prescore_compact2_staged), replay_legacy (DSM_REPLAY_LEGACY:
     the replay scans of rounds 2 - 5, k_replay_lo<fam, 0 / 2>, points and residuals through global memory; the product's k_replay_rp
     keeps the pair in LDS), elu_lds (DSM_ELU_LDS: the 5-point solver's 10 x 10 elimination in lane-interleaved LDS, rounds 2 - 5; the
     product's k_solve_e_lu_reg keeps the matrix in registers), hyp_pair_grid (DSM_HYP_GRID=pair: the lane-per-hypothesis solvers of E / F on the
@@ -59,6 +61,8 @@ def run(ctx, opts, schedule):
         os.environ["DSM_SCORE_PREFILTER"] = "17"
     if schedule == "ef_f64":
         os.environ["DSM_SCORE_PREFILTER"] = "33"
+    if schedule == "staged_loops":
+        os.environ["DSM_SCORE_PREFILTER"] = "65"
     os.environ.pop("DSM_FINAL_WAVES", None)
     if schedule == "final_1wave":
         os.environ["DSM_FINAL_WAVES"] = "1"
@@ -118,8 +122,8 @@ def main():
     opts = capi.default_two_view_options()
     r0 = run(ctxs[False], opts, "batched")
     ok = True
-    CHECK_ONLY = ("no_prefilter", "e_fused", "final_1wave", "legacy", "h_mfma", "h_f64", "ef_f64", "replay_legacy", "elu_lds", "hyp_pair_grid", "lo_prepare_wave", "pose_full")
-    for name in ["batched_check_build", "pose_full", "replay_legacy", "elu_lds", "hyp_pair_grid", "lo_prepare_wave", "no_prefilter", "e_fused", "h_mfma", "h_f64", "ef_f64", "one_lane", "no_tail", "tail_inline", "final_1wave", "inline"] + (["legacy"] if a.legacy else []):
+    CHECK_ONLY = ("no_prefilter", "e_fused", "final_1wave", "legacy", "h_mfma", "h_f64", "ef_f64", "staged_loops", "replay_legacy", "elu_lds", "hyp_pair_grid", "lo_prepare_wave", "pose_full")
+    for name in ["batched_check_build", "pose_full", "replay_legacy", "elu_lds", "hyp_pair_grid", "lo_prepare_wave", "no_prefilter", "e_fused", "h_mfma", "h_f64", "ef_f64", "staged_loops", "one_lane", "no_tail", "tail_inline", "final_1wave", "inline"] + (["legacy"] if a.legacy else []):
         use_check = name in CHECK_ONLY or name == "batched_check_build"
         r1 = run(ctxs[use_check], opts, "batched" if name == "batched_check_build" else name)
         for k in capi.CHECK_OPTION_KEYS:  # the product context must not see a check-only switch
