@@ -446,6 +446,18 @@ STEREO_FUSION_STAGES = ("upload", "traversal", "claims_commit", "medians", "down
 FUSION_HOST_LIB_PATH = os.path.join(_HERE, "libdsm_stereo_fusion_host.so")
 
 
+class SourceSelectionOptions(ctypes.Structure):
+    """dsm_source_selection_options: the arguments of Model::GetMaxOverlappingImages (src/mvs/model.cc:119-129)."""
+    _fields_ = [("max_num_src_images", ctypes.c_int32), ("triangulation_angle_percentile", ctypes.c_float),
+                ("min_triangulation_angle", ctypes.c_double)]
+
+
+IMAGE_OVERLAP_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("count", "<u4"), ("angle", "<f4")])  # dsm_image_overlap
+SOURCE_SELECTION_STAGES = ("upload", "depths", "items", "sort", "pairs_select", "download", "items_count", "pairs", "nan_items")
+# the host build of csrc/source_selection.h: the queries of mvs::Model on one CPU thread from the kernels' text (DESIGN.md 28)
+SELECTION_HOST_LIB_PATH = os.path.join(_HERE, "libdsm_source_selection_host.so")
+
+
 class VocabularyBuildOptions(ctypes.Structure):
     """dsm_vocabulary_build_options: VisualIndex::BuildOptions (src/retrieval/visual_index.h:99-118) + the scheduling field."""
     _fields_ = [("num_visual_words", ctypes.c_int32), ("branching", ctypes.c_int32), ("num_iterations", ctypes.c_int32),
@@ -597,6 +609,13 @@ def lib(check=False):
         L.dsm_get_fused_points.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64]
         L.dsm_get_stereo_fusion_time.argtypes = [vp, vp]
         L.dsm_get_stereo_fusion_rounds.argtypes = [vp, vp, vp, ctypes.c_uint32]
+        L.dsm_default_source_selection_options.argtypes = [ctypes.POINTER(SourceSelectionOptions)]
+        L.dsm_default_source_selection_options.restype = None
+        L.dsm_select_source_images.argtypes = [vp, ctypes.POINTER(SourceSelectionOptions), ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, vp,
+                                               u64p, u64p]
+        L.dsm_get_source_images.argtypes = [vp, vp, vp, ctypes.c_uint64]
+        L.dsm_get_image_overlap.argtypes = [vp, vp, ctypes.c_uint64]
+        L.dsm_get_source_selection_time.argtypes = [vp, vp]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
         L.dsm_default_match_options.restype = None
         L.dsm_default_two_view_options.argtypes = [ctypes.POINTER(TwoViewOptions)]
@@ -867,6 +886,171 @@ def overlapping_images(tracks, n_images, num_images):
                     shared[a][b] = shared[a].get(b, 0) + 1
                     shared[b][a] = shared[b].get(a, 0) + 1
     return [[b for b, _ in sorted(s.items(), key=lambda kv: (-kv[1], kv[0]))[:int(num_images)]] for s in shared]
+
+
+def default_source_selection_options(**kw):
+    """The defaults of dsm_source_selection_options with keywords over them.  Needs no device library: the host build has them."""
+    o = SourceSelectionOptions()
+    selection_host_lib().dsm_ss_host_default_options(ctypes.byref(o))
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
+def _selection_call_arguments(R, T, xyz, tracks, candidate_mask):
+    """The arrays of dsm_select_source_images from R [n][9], T [n][3], xyz [m][3] and tracks (a list of index lists, or the CSR
+    pair (offsets, images))."""
+    R = np.ascontiguousarray(np.asarray(R, dtype=np.float32).reshape(-1, 9))
+    T = np.ascontiguousarray(np.asarray(T, dtype=np.float32).reshape(-1, 3))
+    xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float32).reshape(-1, 3))
+    assert len(R) == len(T), "one R and one T per image"
+    if isinstance(tracks, tuple):
+        offs = np.ascontiguousarray(tracks[0], dtype=np.uint64)
+        idx = np.ascontiguousarray(tracks[1], dtype=np.uint32)
+    else:
+        offs = np.zeros(len(tracks) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(t) for t in tracks])
+        idx = np.array([int(i) for t in tracks for i in t], dtype=np.uint32)
+    assert len(offs) == len(xyz) + 1, "one track per point"
+    mask = None
+    if candidate_mask is not None:
+        mask = np.ascontiguousarray(np.asarray(candidate_mask) != 0, dtype=np.uint8)
+        assert len(mask) == len(R), "one mask byte per image"
+    return R, T, xyz, offs, idx, mask
+
+
+def _selection_result(n, ranges, loff, limg, rec, stats):
+    return {"sources": [limg[int(loff[a]):int(loff[a + 1])].tolist() for a in range(n)], "depth_ranges": ranges[:n].copy(),
+            "pairs": (rec["a"].copy(), rec["b"].copy(), rec["count"].copy(), rec["angle"].copy()), "stats": stats}
+
+
+def selection_host_lib():
+    """libdsm_source_selection_host.so, the host build of csrc/source_selection.h; raises if it has not been built."""
+    if "selection_host" not in _libs:
+        if not os.path.exists(SELECTION_HOST_LIB_PATH):
+            raise DsmError("%s is missing: run make -C dagsfm_amd/csrc" % SELECTION_HOST_LIB_PATH)
+        L = ctypes.CDLL(SELECTION_HOST_LIB_PATH)
+        vp, u64, u64p = ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)
+        for f in (L.dsm_ss_host_run, L.dsm_ss_host_run_serial):
+            f.argtypes = [ctypes.POINTER(SourceSelectionOptions), ctypes.c_uint32, vp, vp, u64, vp, vp, vp, vp, vp, u64p, u64p, vp,
+                          ctypes.POINTER(ctypes.c_char_p)]
+        L.dsm_ss_host_get.argtypes = [vp, vp, vp]
+        L.dsm_ss_host_get.restype = None
+        L.dsm_ss_host_default_options.argtypes = [ctypes.POINTER(SourceSelectionOptions)]
+        L.dsm_ss_host_default_options.restype = None
+        L.dsm_ss_host_acos.argtypes = [ctypes.c_double]
+        L.dsm_ss_host_acos.restype = ctypes.c_double
+        L.dsm_ss_host_decode_item.argtypes = [u64, u64p, u64p]
+        L.dsm_ss_host_decode_item.restype = None
+        L.dsm_ss_host_encode_item.argtypes = [u64, u64]
+        L.dsm_ss_host_encode_item.restype = u64
+        L.dsm_ss_host_depth_index.argtypes = [u64, ctypes.c_float]
+        L.dsm_ss_host_depth_index.restype = u64
+        L.dsm_ss_host_percentile_index.argtypes = [ctypes.c_float, u64]
+        L.dsm_ss_host_percentile_index.restype = u64
+        L.dsm_ss_host_min_angle_rad.argtypes = [ctypes.c_double]
+        L.dsm_ss_host_min_angle_rad.restype = ctypes.c_float
+        L.dsm_ss_host_angle_bits.argtypes = [vp, vp, vp]
+        L.dsm_ss_host_angle_bits.restype = ctypes.c_uint32
+        _libs["selection_host"] = L
+    return _libs["selection_host"]
+
+
+def selection_host(R, T, xyz, tracks, options=None, candidate_mask=None, serial=False, **kw):
+    """dsm_select_source_images' results on one CPU thread by the host build of the kernels' header (no GPU, no context): the
+    dict of Context.select_source_images, its "stats" holding items, pairs and nan_items.  serial: the reference's loops over
+    dense tables in place of the sorted schedule."""
+    L = selection_host_lib()
+    assert options is None or not kw, "pass a SourceSelectionOptions or keywords, not both"
+    o = options if options is not None else default_source_selection_options(**kw)
+    R, T, xyz, offs, idx, mask = _selection_call_arguments(R, T, xyz, tracks, candidate_mask)
+    n = len(R)
+    ranges = np.zeros((max(n, 1), 2), dtype=np.float32)
+    n_list, n_pairs, why = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_char_p()
+    counters = np.zeros(3, dtype=np.uint64)
+    rc = (L.dsm_ss_host_run_serial if serial else L.dsm_ss_host_run)(
+        ctypes.byref(o), n, R.ctypes.data, T.ctypes.data, len(xyz), xyz.ctypes.data, offs.ctypes.data, idx.ctypes.data,
+        None if mask is None else mask.ctypes.data, ranges.ctypes.data, ctypes.byref(n_list), ctypes.byref(n_pairs), counters.ctypes.data,
+        ctypes.byref(why))
+    if rc != 0:
+        err = DsmError("dsm_ss_host_run failed (%d): %s" % (rc, (why.value or b"").decode()))
+        err.rc = rc
+        raise err
+    loff = np.zeros(n + 1, dtype=np.uint64)
+    limg = np.zeros(max(int(n_list.value), 1), dtype=np.uint32)
+    rec = np.zeros(max(int(n_pairs.value), 1), dtype=IMAGE_OVERLAP_DTYPE)
+    L.dsm_ss_host_get(loff.ctypes.data, limg.ctypes.data, rec.ctypes.data)
+    stats = {"items": int(counters[0]), "pairs": int(counters[1]), "nan_items": int(counters[2])}
+    return _selection_result(n, ranges, loff, limg, rec[:int(n_pairs.value)], stats)
+
+
+def parse_patch_match_config(lines, image_names):
+    """patch-match.cfg as PatchMatchController::ReadProblems reads it (src/mvs/patch_match.cc:284-305): lines are trimmed, blank
+    lines and lines that start with `#` are skipped, and the rest alternate between a reference image's name and its source
+    specification -- `__all__`, `__auto__, N`, or a comma-separated list of image names.  A reference name without a
+    specification after it is dropped, as in the reference.  image_names: the model's names in index order.
+    -> a list of (ref_index, spec) with spec = ("all",), ("auto", N) or ("list", [indices])."""
+    index = {name: i for i, name in enumerate(image_names)}
+
+    def image(name):
+        if name not in index:
+            raise DsmError("patch-match.cfg names an image the model does not have: %r" % name)
+        return index[name]
+
+    out, ref = [], None
+    for line in lines:
+        line = line.strip()
+        if not line or line[0] == "#":
+            continue
+        if ref is None:
+            ref = line
+            continue
+        names = [v.strip() for v in line.split(",")]  # CSVToVector<std::string>: split at commas, trimmed, empty fields dropped
+        names = [v for v in names if v]
+        if len(names) == 1 and names[0] == "__all__":
+            spec = ("all",)
+        elif len(names) == 2 and names[0] == "__auto__":
+            spec = ("auto", int(names[1]))
+        else:
+            spec = ("list", [image(v) for v in names])
+        out.append((image(ref), spec))
+        ref = None
+    return out
+
+
+def patch_match_problems_from(selection, config, depth_min=-1.0, depth_max=-1.0):
+    """ReadProblems' second loop (patch_match.cc:307-388) and the depth limits of ProcessProblem (:455-464) over the results of a
+    source selection run with the mask of the configured reference images: -> [(ref, src_images, depth_min, depth_max)], what
+    Context.patch_match_stereo takes.  `__all__`: the other configured reference images -- the reference iterates an
+    std::unordered_set there, whose order is unspecified; this binding's order is ascending image index.  `__auto__, N`: the
+    first N of the selection's list.  A reference image whose source list is empty is dropped.  depth_min / depth_max: the
+    options' values; a negative one is replaced by the image's depth range."""
+    refs = sorted({ref for ref, _ in config})
+    out = []
+    for ref, spec in config:
+        if spec[0] == "all":
+            src = [i for i in refs if i != ref]
+        elif spec[0] == "auto":
+            src = list(selection["sources"][ref][:max(int(spec[1]), 0)])
+        else:
+            src = list(spec[1])
+        if not src:
+            continue
+        lo = float(depth_min) if depth_min >= 0 else float(selection["depth_ranges"][ref][0])
+        hi = float(depth_max) if depth_max >= 0 else float(selection["depth_ranges"][ref][1])
+        out.append((ref, src, lo, hi))
+    return out
+
+
+def patch_match_selection_arguments(config, n_images):
+    """(candidate_mask, max_num_src_images) of the source selection ReadProblems needs for `config`: the mask of the configured
+    reference images (ref_image_idxs) and the largest N of its `__auto__, N` entries."""
+    mask = np.zeros(n_images, dtype=np.uint8)
+    for ref, _ in config:
+        mask[ref] = 1
+    autos = [int(spec[1]) for _, spec in config if spec[0] == "auto"]
+    return mask, max([0] + autos)
 
 
 def write_fused_ply(path, points, normals, colours):
@@ -1164,7 +1348,7 @@ PRODUCT_OPTION_KEYS = ("DSM_MATCH_CHUNK_ROWS", "DSM_VERIFY_CHUNK_PAIRS", "DSM_VE
 CHECK_OPTION_KEYS = ("DSM_K1_DOT4", "DSM_K1_RESOLVE_KERNEL", "DSM_VERIFY_DEBUG", "DSM_SAMPLER_SERIAL", "DSM_LO_PREPARE_WAVE", "DSM_LO_JACOBI_GROUPS", "DSM_ROOTS_LDS",
                      "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT", "DSM_DEBUG_SAMPLER_MODE",
                      "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER", "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
-                     "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT", "DSM_FUSION_SERIAL")
+                     "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT", "DSM_FUSION_SERIAL", "DSM_SOURCE_SELECTION_SERIAL")
 DEBUG_OPTION_KEYS = PRODUCT_OPTION_KEYS  # what a deployer's library knows
 
 
@@ -2076,6 +2260,57 @@ class Context:
         ms = (ctypes.c_double * len(PATCH_MATCH_STAGES))()
         self._chk(self._L.dsm_get_patch_match_time(self._h, ctypes.addressof(ms)))
         return dict(zip(PATCH_MATCH_STAGES, list(ms)))
+
+    def select_source_images(self, R, T, xyz, tracks, options=None, candidate_mask=None, **kw):
+        """dsm_select_source_images (DESIGN.md 28): Model::GetMaxOverlappingImages, ComputeDepthRanges, ComputeSharedPoints and
+        ComputeTriangulationAngles of one sparse model.  R [n][9], T [n][3], xyz [m][3] float32; tracks: the image indices of
+        every point (a list of lists, or the CSR pair (offsets, images)); candidate_mask: only images with a non-zero entry may
+        be chosen as sources (ReadProblems' condition); options: a SourceSelectionOptions, or its fields as keywords.
+        -> {"sources": a list per image, most shared points first, "depth_ranges": [n][2] float32, "pairs": (a, b, count, angle)
+        arrays in ascending (a, b) with a < b, "stats": the counts items, pairs and nan_items}."""
+        assert options is None or not kw, "pass a SourceSelectionOptions or keywords, not both"
+        o = options if options is not None else default_source_selection_options(**kw)
+        R, T, xyz, offs, idx, mask = _selection_call_arguments(R, T, xyz, tracks, candidate_mask)
+        n = len(R)
+        ranges = np.zeros((max(n, 1), 2), dtype=np.float32)
+        n_list, n_pairs = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = self._L.dsm_select_source_images(self._h, ctypes.byref(o), n, R.ctypes.data, T.ctypes.data, len(xyz), xyz.ctypes.data, offs.ctypes.data,
+                                              idx.ctypes.data, None if mask is None else mask.ctypes.data, ranges.ctypes.data,
+                                              ctypes.byref(n_list), ctypes.byref(n_pairs))
+        if rc != 0:
+            self._fail("dsm_select_source_images", rc)
+        loff = np.zeros(n + 1, dtype=np.uint64)
+        limg = np.zeros(max(int(n_list.value), 1), dtype=np.uint32)
+        rec = np.zeros(max(int(n_pairs.value), 1), dtype=IMAGE_OVERLAP_DTYPE)
+        self._chk(self._L.dsm_get_source_images(self._h, loff.ctypes.data, limg.ctypes.data, len(limg)))
+        self._chk(self._L.dsm_get_image_overlap(self._h, rec.ctypes.data, len(rec)))
+        times = self.source_selection_time()
+        stats = {"items": int(times["items_count"]), "pairs": int(times["pairs"]), "nan_items": int(times["nan_items"])}
+        return _selection_result(n, ranges, loff, limg, rec[:int(n_pairs.value)], stats)
+
+    def source_selection_time(self):
+        """dsm_get_source_selection_time: {stage: ms} of the last select_source_images call, with its counts items_count, pairs
+        and nan_items."""
+        ms = (ctypes.c_double * len(SOURCE_SELECTION_STAGES))()
+        self._chk(self._L.dsm_get_source_selection_time(self._h, ctypes.addressof(ms)))
+        return dict(zip(SOURCE_SELECTION_STAGES, list(ms)))
+
+    def patch_match_problems(self, model, config, options=None, select=None):
+        """PatchMatchController::ReadWorkspace's depth ranges and ReadProblems (src/mvs/patch_match.cc:255, 258-393) on the device:
+        the (ref, src_images, depth_min, depth_max) tuples Context.patch_match_stereo takes.  model: a dict with R, T, xyz,
+        tracks and either image_names or nothing (then the names are "0", "1", ...); config: the lines of patch-match.cfg, or
+        the list parse_patch_match_config returns; options: a dict with min_triangulation_angle (default 1.0), depth_min and
+        depth_max (default -1: from the depth ranges).  The rules are patch_match_problems_from's.  select: the selection to run
+        in place of the device's (the CPU tests pass capi.selection_host)."""
+        options = dict(options or {})
+        n = len(np.asarray(model["R"]).reshape(-1, 9))
+        if config and isinstance(config[0], str):
+            config = parse_patch_match_config(config, model.get("image_names") or [str(i) for i in range(n)])
+        mask, max_num = patch_match_selection_arguments(config, n)
+        run = select if select is not None else self.select_source_images
+        selection = run(model["R"], model["T"], model["xyz"], model["tracks"], candidate_mask=mask, max_num_src_images=max_num,
+                        min_triangulation_angle=float(options.get("min_triangulation_angle", 1.0)))
+        return patch_match_problems_from(selection, config, options.get("depth_min", -1.0), options.get("depth_max", -1.0))
 
     def stereo_fusion(self, images, overlap, options=None, **kw):
         """dsm_fuse_stereo (StereoFusion::Run, DESIGN.md 26): the dense point cloud of the depth and normal maps.

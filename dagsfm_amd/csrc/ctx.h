@@ -250,6 +250,16 @@ struct dsm_ctx {
   bool stereo_fusion_ready = false;
   double stereo_fusion_ms[DSM_STEREO_FUSION_STAGES] = {0};
 
+  // source_selection.hip: the model and the tables (d_ss_model), the keys of the items and their second buffer, reused for
+  // the depth keys (d_ss_keys), rocPRIM's temporary storage (d_ss_tmp), the first items of the pairs, the pair table, the edges
+  // and the lists on the device (d_ss_pairs); the lists, the pair table and the times of the last dsm_select_source_images
+  DevBuf d_ss_model, d_ss_keys, d_ss_tmp, d_ss_pairs;
+  std::vector<uint64_t> ss_list_off;
+  std::vector<uint32_t> ss_list_img;
+  std::vector<dsm_image_overlap> ss_pairs;
+  bool source_selection_ready = false;
+  double source_selection_ms[DSM_SOURCE_SELECTION_STAGES] = {0};
+
   // vocabulary_build.hip: the descriptors, the indices permutation, the per-position values and the per-job state of a
   // dsm_retrieval_quantize call, the buffers of dsm_retrieval_train_embedding -- all released when the call ends; the tree of the
   // last dsm_retrieval_quantize in depth-first order (dsm_get_vocabulary_tree) and the HIP-event times of the last calls
@@ -283,7 +293,8 @@ struct dsm_ctx {
       f(*b, false);
     for (DevBuf* b : {&d_m, &d_ms, &d_entries, &d_out2, &d_out2s, &d_dpairs, &d_dpairs2, &d_doutoff, &d_pair_dir, &d_order, &d_ecnt, &d_eoff,
                       &d_runs, &d_run_blocks, &d_run_blkoff, &d_gblocks, &d_egrow,
-                      &d_vscratch, &d_ud_border, &d_ud_points, &d_ud_src, &d_ud_dst, &d_ud_map, &d_pm, &d_vb_point, &d_vb_node, &d_vb_embed, &d_sf_maps, &d_sf_lanes})
+                      &d_vscratch, &d_ud_border, &d_ud_points, &d_ud_src, &d_ud_dst, &d_ud_map, &d_pm, &d_vb_point, &d_vb_node, &d_vb_embed, &d_sf_maps, &d_sf_lanes,
+                      &d_ss_model, &d_ss_keys, &d_ss_tmp, &d_ss_pairs})
       f(*b, true);
     for (VerifyLane& L : lanes) L.for_each_buffer([&f](DevBuf& b) { f(b, true); });
   }
@@ -301,7 +312,8 @@ static const char* const dsm_check_debug_keys[] = {"DSM_K1_DOT4", "DSM_K1_RESOLV
                                                    "DSM_ROOTS_LDS", "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT",
                                                    "DSM_DEBUG_SAMPLER_MODE", "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER",
                                                    "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
-                                                   "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT", "DSM_FUSION_SERIAL"};
+                                                   "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT", "DSM_FUSION_SERIAL",
+                                                   "DSM_SOURCE_SELECTION_SERIAL"};
 #endif
 
 #define HIPCHK(ctx, call)                                                              \

@@ -1733,6 +1733,55 @@ int dsm_get_stereo_fusion_time(dsm_ctx* ctx, double* stage_ms);
  * never reached) and the rounds it took (0 for an image without pixels).  Either pointer may be NULL; capacity in images. */
 int dsm_get_stereo_fusion_rounds(dsm_ctx* ctx, uint32_t* order_pos, uint32_t* rounds, uint32_t capacity);
 
+/* ---- Source images and depth ranges of PatchMatch's problems (mvs::Model, src/mvs/model.cc) ----
+ * DESIGN.md 28.  The queries of mvs::Model that turn a sparse model into patch_match's problems, in one call:
+ * GetMaxOverlappingImages (model.cc:119-169) with ReadProblems' condition on the candidates (src/mvs/patch_match.cc:349),
+ * ComputeDepthRanges (:176-216), ComputeSharedPoints (:218-233) and ComputeTriangulationAngles (:235-274) with
+ * ComputeProjectionCenter (src/mvs/image.cc:125-130), CalculateTriangulationAngle (src/base/triangulation.cc:122-145), DegToRad
+ * and Percentile (src/util/math.h:194-200, 231-246).  The contract is the reference's operations in its evaluation order
+ * (entries Eigen leaves open summed left to right, no contraction) with the correctly rounded acos (csrc/exact_acos.h);
+ * tests/source_selection_ref.py is the normative restatement and the device equals it bit for bit.
+ * Rulings: equal counts go to the lower image index (the reference's sorts leave them open); an item whose acos argument left
+ * [-1, 1] has the angle NaN, which orders above every number and fails `>=` (the reference's behaviour there is unspecified).
+ * At most 65536 images (DSM_ERR_OUT_OF_RANGE beyond). */
+typedef struct dsm_source_selection_options {
+  int32_t max_num_src_images;           /* 20: patch-match.cfg's `__auto__, 20` (src/base/undistortion.cc:243); >= 0 */
+  float triangulation_angle_percentile; /* 75 (model.cc:127, patch_match.cc:333); in [0, 100] */
+  double min_triangulation_angle;       /* 1.0 degrees (PatchMatchOptions, src/mvs/patch_match.h); fusion passes 0 */
+} dsm_source_selection_options;
+void dsm_default_source_selection_options(dsm_source_selection_options* o);
+
+typedef struct dsm_image_overlap { /* one entry of ComputeSharedPoints and ComputeTriangulationAngles: a < b */
+  uint32_t a, b, count;
+  float angle; /* the percentile element of the pair's angles, radians */
+} dsm_image_overlap;
+
+/* Host pointers; options NULL = the defaults.  R [n_images][9] row-major and T [n_images][3] as in dsm_mvs_image, xyz
+ * [n_points][3], the track of point p = track_images[track_offsets[p] .. track_offsets[p + 1]) (an image may repeat: every
+ * repeat counts, as in the reference).  candidate_mask NULL: Model::GetMaxOverlappingImages; else [n_images] bytes, and only
+ * images with a non-zero byte may be chosen as sources (ReadProblems' ref_image_idxs.count, patch_match.cc:349).
+ * depth_ranges gets [n_images][2] = ComputeDepthRanges' (first, second), (-1, -1) for an image without a positive depth;
+ * *n_list_entries and *n_pairs (either may be NULL) the sizes for dsm_get_source_images and dsm_get_image_overlap.
+ * Every pair of elements of every track is one item of 8 bytes, sorted on the device; a call whose items and tables do not fit
+ * dsm_ctx_set_memory_budget (when one is set) or the free device memory is refused with DSM_ERR_OUT_OF_RANGE and a message
+ * that names the need and the budget -- never a partial result.  n_images = 0 and n_points = 0 are valid.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT, outputs untouched): max_num_src_images < 0, a percentile outside [0, 100], a NaN angle,
+ * offsets that do not start at 0 or decrease, an image index out of range, NULL where data is needed. */
+int dsm_select_source_images(dsm_ctx* ctx, const dsm_source_selection_options* options, uint32_t n_images, const float* R, const float* T,
+                             uint64_t n_points, const float* xyz, const uint64_t* track_offsets, const uint32_t* track_images,
+                             const uint8_t* candidate_mask, float* depth_ranges, uint64_t* n_list_entries, uint64_t* n_pairs);
+/* The lists of the last dsm_select_source_images: list_offsets gets n_images + 1 prefix offsets, list_images the source
+ * images of every image, most shared points first.  Either pointer may be NULL; capacity in indices. */
+int dsm_get_source_images(dsm_ctx* ctx, uint64_t* list_offsets, uint32_t* list_images, uint64_t capacity);
+/* The pair table of the last dsm_select_source_images in ascending (a, b): what ComputeSharedPoints and
+ * ComputeTriangulationAngles return for both directions of a pair (patch_match.cc:330-335 calls them directly). */
+int dsm_get_image_overlap(dsm_ctx* ctx, dsm_image_overlap* pairs, uint64_t capacity);
+/* HIP-event times in ms of the last dsm_select_source_images: 0 upload, 1 depths (kernel, sort, ranges), 2 items (count, scan,
+ * angles), 3 the sort of the items, 4 pair statistics and selection, 5 download; then the counts 6 items (pairs of track
+ * elements with different images), 7 pairs, 8 nan_items.  DSM_ERR_NOT_READY before the first call. */
+#define DSM_SOURCE_SELECTION_STAGES 9
+int dsm_get_source_selection_time(dsm_ctx* ctx, double* stage_ms);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
