@@ -458,6 +458,32 @@ SOURCE_SELECTION_STAGES = ("upload", "depths", "items", "sort", "pairs_select", 
 SELECTION_HOST_LIB_PATH = os.path.join(_HERE, "libdsm_source_selection_host.so")
 
 
+class InitialPairOptions(ctypes.Structure):
+    """dsm_initial_pair_options (IncrementalMapper::Options, incremental_mapper.h:68-81; DESIGN.md 29)."""
+    _fields_ = [("init_min_num_inliers", ctypes.c_int32), ("init_max_reg_trials", ctypes.c_int32), ("init_max_error", ctypes.c_double),
+                ("init_max_forward_motion", ctypes.c_double), ("init_min_tri_angle", ctypes.c_double), ("user_seed", ctypes.c_uint32),
+                ("speculation_window", ctypes.c_uint32)]
+
+
+class InitialPairResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("image_id1", ctypes.c_uint32), ("image_id2", ctypes.c_uint32), ("num_tried", ctypes.c_uint32),
+                ("num_points", ctypes.c_uint64), ("two_view_geometry", TwoViewGeometry)]
+
+
+class InitialPairReport(ctypes.Structure):
+    _fields_ = [("num_rounds", ctypes.c_uint32), ("num_batches", ctypes.c_uint32), ("num_candidates", ctypes.c_uint64),
+                ("num_verified", ctypes.c_uint64), ("num_speculated", ctypes.c_uint64), ("min_tri_angle_margin", ctypes.c_double),
+                ("min_forward_motion_margin", ctypes.c_double), ("min_point_angle_margin", ctypes.c_double),
+                ("min_point_depth_margin", ctypes.c_double), ("setup_ms", ctypes.c_double), ("graph_ms", ctypes.c_double),
+                ("gather_ms", ctypes.c_double), ("verify_ms", ctypes.c_double), ("pose_ms", ctypes.c_double),
+                ("triangulate_ms", ctypes.c_double), ("device_ms", ctypes.c_double)]
+
+
+NO_IMAGE = 0xFFFFFFFF  # DSM_NO_IMAGE
+INITIAL_PAIR_NONE, INITIAL_PAIR_FOUND = 0, 1
+INITIAL_PAIR_HOST_LIB_PATH = os.path.join(_HERE, "libdsm_initial_pair_host.so")
+
+
 class VocabularyBuildOptions(ctypes.Structure):
     """dsm_vocabulary_build_options: VisualIndex::BuildOptions (src/retrieval/visual_index.h:99-118) + the scheduling field."""
     _fields_ = [("num_visual_words", ctypes.c_int32), ("branching", ctypes.c_int32), ("num_iterations", ctypes.c_int32),
@@ -616,6 +642,11 @@ def lib(check=False):
         L.dsm_get_source_images.argtypes = [vp, vp, vp, ctypes.c_uint64]
         L.dsm_get_image_overlap.argtypes = [vp, vp, ctypes.c_uint64]
         L.dsm_get_source_selection_time.argtypes = [vp, vp]
+        L.dsm_default_initial_pair_options.argtypes = [ctypes.POINTER(InitialPairOptions)]
+        L.dsm_default_initial_pair_options.restype = None
+        L.dsm_find_initial_pairs.argtypes = ([vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_uint32, vp, vp, vp,
+                                              ctypes.c_uint32] + [vp] * 8 + [ctypes.POINTER(InitialPairOptions), vp, vp, vp, ctypes.c_uint64,
+                                                                             vp, vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, vp])
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
         L.dsm_default_match_options.restype = None
         L.dsm_default_two_view_options.argtypes = [ctypes.POINTER(TwoViewOptions)]
@@ -1196,6 +1227,91 @@ def fusion_host(images, overlap, options=None, **kw):
     return rec["xyz"].copy(), rec["rgb"].copy(), rec["normal"].copy(), vis, masks[:total], int(trav.value)
 
 
+def default_initial_pair_options(**kw):
+    o = InitialPairOptions()
+    lib().dsm_default_initial_pair_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def _initial_pair_problem_arguments(scene, problems):
+    """The problems of find_initial_pairs as the C arrays: offsets, ids, num_registrations, init_num_reg_trials, tried offsets and
+    pairs, the two seeds; and the bounds of the outputs (tried pairs, points)."""
+    ids, regs, trials, tried, poff, toff, s1, s2 = [], [], [], [], [0], [0], [], []
+    for pr in problems:
+        im = [int(x) for x in pr["image_ids"]]
+        ids += im
+        regs += [int(x) for x in pr.get("num_registrations", [0] * len(im))]
+        trials += [int(x) for x in pr.get("init_num_reg_trials", [0] * len(im))]
+        tried += [int(x) for t in pr.get("tried_pairs", []) for x in t]
+        poff.append(len(ids))
+        toff.append(len(tried) // 2)
+        s1.append(NO_IMAGE if pr.get("seed_image1") is None else int(pr["seed_image1"]))
+        s2.append(NO_IMAGE if pr.get("seed_image2") is None else int(pr["seed_image2"]))
+    if len(regs) != len(ids) or len(trials) != len(ids):
+        raise DsmError("find_initial_pairs: num_registrations and init_num_reg_trials must align with a problem's image_ids")
+    pairs = np.ascontiguousarray(scene["pairs"], np.int64).reshape(-1, 2)
+    counts = np.diff(np.ascontiguousarray(scene["match_offsets"], np.int64))
+    max_tried, max_points = 0, 0
+    for pr in problems:
+        inside = np.isin(pairs[:, 0], pr["image_ids"]) & np.isin(pairs[:, 1], pr["image_ids"]) if len(pairs) else np.zeros(0, bool)
+        max_tried += max(int(inside.sum()), 1)
+        max_points += int(counts[inside].max()) if inside.any() else 0
+    u32 = lambda x: np.ascontiguousarray(x, np.uint32).reshape(-1)
+    return (u32(poff), u32(ids), u32(regs), u32(trials), np.ascontiguousarray(toff, np.uint64), u32(tried + [0, 0]), u32(s1), u32(s2),
+            max_tried, max_points)
+
+
+def initial_pair_host_lib():
+    """libdsm_initial_pair_host.so: the host build of csrc/initial_pair.h (the candidate order, the angle, Median, the gates)."""
+    if "initial_pair_host" not in _libs:
+        if not os.path.exists(INITIAL_PAIR_HOST_LIB_PATH):
+            raise DsmError("%s is missing: run make -C dagsfm_amd/csrc" % INITIAL_PAIR_HOST_LIB_PATH)
+        L = ctypes.CDLL(INITIAL_PAIR_HOST_LIB_PATH)
+        vp, dbl = ctypes.c_void_p, ctypes.c_double
+        L.dsm_ip_host_acos.argtypes, L.dsm_ip_host_acos.restype = [dbl], dbl
+        L.dsm_ip_host_default_options.argtypes, L.dsm_ip_host_default_options.restype = [ctypes.POINTER(InitialPairOptions)], None
+        L.dsm_ip_host_min_tri_angle_rad.argtypes, L.dsm_ip_host_min_tri_angle_rad.restype = [dbl], dbl
+        L.dsm_ip_host_tri_angle.argtypes, L.dsm_ip_host_tri_angle.restype = [vp, vp, vp], dbl
+        L.dsm_ip_host_median.argtypes, L.dsm_ip_host_median.restype = [vp, ctypes.c_uint64], dbl
+        L.dsm_ip_host_pose.argtypes, L.dsm_ip_host_pose.restype = [vp] * 5, None
+        L.dsm_ip_host_accept.argtypes = [ctypes.c_uint32, dbl, dbl, ctypes.POINTER(InitialPairOptions), vp]
+        L.dsm_ip_host_point_gates.argtypes = [vp, vp, vp, dbl, vp, vp]
+        L.dsm_ip_host_candidates.argtypes = ([ctypes.c_uint32, vp, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint32] + [vp] * 8
+                                             + [ctypes.POINTER(InitialPairOptions), ctypes.c_int, vp, vp, ctypes.c_uint64, vp,
+                                                ctypes.POINTER(ctypes.c_char_p)])
+        _libs["initial_pair_host"] = L
+    return _libs["initial_pair_host"]
+
+
+def initial_pair_host_candidates(scene, problems, options=None, sorted_schedule=False):
+    """The candidate lists of find_initial_pairs from the host build: per problem a list of (image_id1, image_id2) in trial order,
+    and the matches every pair keeps after the duplicate rule.  sorted_schedule: the device's packed keys instead of the
+    reference's nested loops.  Raises DsmError with the library's message on invalid arguments."""
+    L = initial_pair_host_lib()
+    o = options if options is not None else default_initial_pair_options()
+    a = lambda key, dt, shape=-1: np.ascontiguousarray(scene[key], dt).reshape(shape)
+    cam_of = {int(c): k for k, c in enumerate(a("camera_ids", np.uint32))}
+    img_ids, img_cam = a("image_ids", np.uint32), a("image_camera_ids", np.uint32)
+    prior = np.array([scene["cameras"][cam_of[int(c)]].has_prior_focal_length != 0 for c in img_cam], np.uint8)
+    poff = a("points2D_offsets", np.uint32)
+    pairs, moff, m = a("pairs", np.uint32, (-1, 2)), a("match_offsets", np.uint64), a("matches", np.uint32, (-1, 2))
+    prob_off, prob_ids, regs, trials, toff, tried, s1, s2, max_tried, _ = _initial_pair_problem_arguments(scene, problems)
+    out_off = np.zeros(len(problems) + 1, np.uint64)
+    out = np.zeros((max(max_tried, 1), 2), np.uint32)
+    cnt = np.zeros(max(len(pairs), 1), np.uint32)
+    why = ctypes.c_char_p()
+    ptr = lambda x: x.ctypes.data
+    rc = L.dsm_ip_host_candidates(len(img_ids), ptr(img_ids), ptr(prior), ptr(poff), len(pairs), ptr(pairs), ptr(moff), ptr(m), len(problems),
+                                  ptr(prob_off), ptr(prob_ids), ptr(regs), ptr(trials), ptr(toff), ptr(tried), ptr(s1), ptr(s2), ctypes.byref(o),
+                                  int(bool(sorted_schedule)), ptr(out_off), ptr(out), len(out), ptr(cnt), ctypes.byref(why))
+    if rc != 0:
+        raise DsmError("dsm_ip_host_candidates failed (%d): %s" % (rc, (why.value or b"").decode()))
+    lists = [[(int(x), int(y)) for x, y in out[int(out_off[k]):int(out_off[k + 1])]] for k in range(len(problems))]
+    return lists, cnt[:len(pairs)].copy()
+
+
 def default_vocabulary_build_options(**kw):
     o = VocabularyBuildOptions()
     lib().dsm_default_vocabulary_build_options(ctypes.byref(o))
@@ -1348,7 +1464,8 @@ PRODUCT_OPTION_KEYS = ("DSM_MATCH_CHUNK_ROWS", "DSM_VERIFY_CHUNK_PAIRS", "DSM_VE
 CHECK_OPTION_KEYS = ("DSM_K1_DOT4", "DSM_K1_RESOLVE_KERNEL", "DSM_VERIFY_DEBUG", "DSM_SAMPLER_SERIAL", "DSM_LO_PREPARE_WAVE", "DSM_LO_JACOBI_GROUPS", "DSM_ROOTS_LDS",
                      "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT", "DSM_DEBUG_SAMPLER_MODE",
                      "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER", "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
-                     "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT", "DSM_FUSION_SERIAL", "DSM_SOURCE_SELECTION_SERIAL")
+                     "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT", "DSM_FUSION_SERIAL", "DSM_SOURCE_SELECTION_SERIAL",
+                     "DSM_INITIAL_PAIR_SERIAL")
 DEBUG_OPTION_KEYS = PRODUCT_OPTION_KEYS  # what a deployer's library knows
 
 
@@ -2449,6 +2566,50 @@ class Context:
                 "continued_obs": cobs[:c].copy(), "continued_point_ids": cid[:c].copy(), "touched_obs": tobs[:t].copy(),
                 "touched_point_ids": tid[:t].copy(), "pair_num_total_corrs": total[:K].copy(), "pair_num_tri_corrs": tri[:K].copy(),
                 "pair_status": status[:K].copy(), "re_num_trials": trials[:K].copy(), "num_tris": tris.value, "report": rep}
+
+    def find_initial_pairs(self, scene, problems, options=None, **kw):
+        """dsm_find_initial_pairs (FindInitialImagePair, EstimateInitialTwoViewGeometry and the triangulation of
+        RegisterInitialImagePair for a batch of reconstructions).  scene: the dict of retriangulate (camera_ids,
+        cameras, image_ids, image_camera_ids, points2D_offsets, points2D_xy, pairs, match_offsets, matches; its other keys are
+        not read).  problems: a list of dicts with image_ids and, optionally, num_registrations and init_num_reg_trials (aligned
+        with image_ids), tried_pairs [(id, id)], seed_image1, seed_image2 (None = no seed).
+        Returns a dict: results (a list of dicts per problem: found, image_id1, image_id2, two_view_geometry, inlier_matches
+        [i, 2], num_tried, tried_pairs [t, 2] in trial order with the successful pair last, new_xyz [n, 3] and new_track_obs [n, 2, 2]
+        ((image_id, point2D_idx) of image 1, then image 2, as retriangulate_pairs returns new points)) and report."""
+        assert options is None or not kw, "pass an InitialPairOptions or keywords, not both"
+        o = options if options is not None else default_initial_pair_options(**kw)
+        a = lambda key, dt, shape=-1: np.ascontiguousarray(scene[key], dt).reshape(shape)
+        cam_ids = a("camera_ids", np.uint32)
+        cams = (Camera * max(len(cam_ids), 1))(*scene["cameras"])
+        img_ids, img_cam = a("image_ids", np.uint32), a("image_camera_ids", np.uint32)
+        poff, xy = a("points2D_offsets", np.uint32), a("points2D_xy", np.float64, (-1, 2))
+        pairs, moff, m = a("pairs", np.uint32, (-1, 2)), a("match_offsets", np.uint64), a("matches", np.uint32, (-1, 2))
+        prob_off, prob_ids, regs, trials, toff, tried, s1, s2, max_tried, max_points = _initial_pair_problem_arguments(scene, problems)
+        B = len(problems)
+        res = (InitialPairResult * max(B, 1))()
+        out_toff, out_tried = np.zeros(B + 1, np.uint64), np.zeros((max(max_tried, 1), 2), np.uint32)
+        out_poff, out_xyz, out_obs = np.zeros(B + 1, np.uint64), np.zeros((max(max_points, 1), 3)), np.zeros((max(max_points, 1), 2), np.uint32)
+        out_ioff, out_inl = np.zeros(B + 1, np.uint64), np.zeros((max(max_points, 1), 2), np.uint32)
+        rep = InitialPairReport()
+        ptr = lambda x: x.ctypes.data
+        self._chk(self._L.dsm_find_initial_pairs(self._h, len(cam_ids), ptr(cam_ids), ctypes.addressof(cams), len(img_ids), ptr(img_ids),
+                                                 ptr(img_cam), ptr(poff), ptr(xy), len(pairs), ptr(pairs), ptr(moff), ptr(m), B, ptr(prob_off),
+                                                 ptr(prob_ids), ptr(regs), ptr(trials), ptr(toff), ptr(tried), ptr(s1), ptr(s2), ctypes.byref(o),
+                                                 ctypes.addressof(res), ptr(out_toff), ptr(out_tried), len(out_tried), ptr(out_poff),
+                                                 ptr(out_xyz), ptr(out_obs), len(out_xyz), ptr(out_ioff), ptr(out_inl), len(out_inl),
+                                                 ctypes.addressof(rep)))
+        results = []
+        for k in range(B):
+            r = res[k]
+            t0, t1, p0, p1 = int(out_toff[k]), int(out_toff[k + 1]), int(out_poff[k]), int(out_poff[k + 1])
+            obs = np.zeros((p1 - p0, 2, 2), np.uint32)
+            obs[:, 0, 0], obs[:, 1, 0] = r.image_id1, r.image_id2
+            obs[:, 0, 1], obs[:, 1, 1] = out_obs[p0:p1, 0], out_obs[p0:p1, 1]
+            results.append({"found": r.status == INITIAL_PAIR_FOUND, "image_id1": int(r.image_id1), "image_id2": int(r.image_id2),
+                            "two_view_geometry": TwoViewGeometry.from_buffer_copy(bytes(r.two_view_geometry)),
+                            "inlier_matches": out_inl[int(out_ioff[k]):int(out_ioff[k + 1])].copy(), "num_tried": int(r.num_tried),
+                            "tried_pairs": out_tried[t0:t1].copy(), "new_xyz": out_xyz[p0:p1].copy(), "new_track_obs": obs})
+        return {"results": results, "report": rep}
 
     def estimate_absolute_poses(self, cameras, estimate_focal_length, offsets, points2D, points3D, options=None, seeds=None):
         """dsm_estimate_absolute_poses (EstimateAbsolutePose for a batch of problems).  cameras: a list of Camera

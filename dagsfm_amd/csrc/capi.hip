@@ -2116,3 +2116,32 @@ int dsm_get_match_resolve_time(dsm_ctx* ctx, double* total_ms) {
 }
 
 }  // extern "C"
+
+// The verifier's device entry for another stage of the library (initial_pair.hip, declared in ctx.h): verify_core_plain on the
+// leaf context of `ctx`, so that the results of the caller's last dsm_verify_pairs stay where they are.  Every array is on the
+// device except `counts`; the results stay on the leaf until its next use: *d_tvg [n_pairs], *d_inl_off [n_pairs + 1] and
+// *d_inl (2 per inlier match), *total_inliers.
+int dsm_verify_on_leaf(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* d_pairs, const uint64_t* d_match_off, const uint32_t* d_matches,
+                       uint64_t total_matches, const std::vector<uint32_t>& counts, const double* d_kp, const uint32_t* d_img_row0,
+                       const dsm_camera* d_cams, const dsm_two_view_options* o, const uint32_t* d_seeds, const dsm_two_view_geometry** d_tvg,
+                       const uint64_t** d_inl_off, const uint32_t** d_inl, uint64_t* total_inliers, double* kernel_ms) {
+  if (!ctx->leaf) {
+    int rc = dsm_ctx_create(ctx->device, &ctx->leaf);
+    if (rc != DSM_OK) return dsm_fail(ctx, rc, dsm_last_error(nullptr));
+  }
+  dsm_ctx* lf = ctx->leaf;
+  lf->debug_options = ctx->debug_options;
+  lf->memory_budget = ctx->memory_budget;
+  lf->n_pairs = n_pairs;
+  const int rc = verify_core_plain(lf, n_pairs, d_pairs, d_match_off, d_matches, total_matches, counts, d_kp, d_img_row0, d_cams, o, d_seeds, 0);
+  if (rc != DSM_OK) {
+    ctx->err = lf->err;
+    return rc;
+  }
+  *d_tvg = lf->d_tvg.as<dsm_two_view_geometry>();
+  *d_inl_off = lf->d_inl_off.as<uint64_t>();
+  *d_inl = lf->d_inl_compact.as<uint32_t>();
+  *total_inliers = lf->total_inliers;
+  if (kernel_ms) *kernel_ms = lf->verify_ms;
+  return DSM_OK;
+}

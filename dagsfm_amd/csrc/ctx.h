@@ -303,6 +303,11 @@ void dsm_retrieval_destroy(dsm_ctx* ctx);     // retrieval.hip
 void dsm_retrieval_invalidate(dsm_ctx* ctx);  // retrieval.hip: the resident images changed
 void dsm_sift_destroy(dsm_ctx* ctx);          // sift_extraction.hip
 void dsm_covariant_sift_destroy(dsm_ctx* ctx);  // covariant_sift.hip
+// capi.hip: verify_core_plain on the leaf context (device arrays but `counts`); the results stay on the leaf until its next use
+int dsm_verify_on_leaf(dsm_ctx* ctx, uint32_t n_pairs, const uint32_t* d_pairs, const uint64_t* d_match_off, const uint32_t* d_matches,
+                       uint64_t total_matches, const std::vector<uint32_t>& counts, const double* d_kp, const uint32_t* d_img_row0,
+                       const dsm_camera* d_cams, const dsm_two_view_options* o, const uint32_t* d_seeds, const dsm_two_view_geometry** d_tvg,
+                       const uint64_t** d_inl_off, const uint32_t** d_inl, uint64_t* total_inliers, double* kernel_ms);
 
 // keys dsm_set_debug_option accepts (an unknown key is an error, so a check-only switch fails loudly on the product build)
 static const char* const dsm_product_debug_keys[] = {"DSM_MATCH_CHUNK_ROWS", "DSM_VERIFY_CHUNK_PAIRS", "DSM_VERIFY_LANES", "DSM_VERIFY_INLINE_LO",
@@ -313,7 +318,7 @@ static const char* const dsm_check_debug_keys[] = {"DSM_K1_DOT4", "DSM_K1_RESOLV
                                                    "DSM_DEBUG_SAMPLER_MODE", "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER",
                                                    "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
                                                    "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT", "DSM_FUSION_SERIAL",
-                                                   "DSM_SOURCE_SELECTION_SERIAL"};
+                                                   "DSM_SOURCE_SELECTION_SERIAL", "DSM_INITIAL_PAIR_SERIAL"};
 #endif
 
 #define HIPCHK(ctx, call)                                                              \

@@ -1782,6 +1782,111 @@ int dsm_get_image_overlap(dsm_ctx* ctx, dsm_image_overlap* pairs, uint64_t capac
 #define DSM_SOURCE_SELECTION_STAGES 9
 int dsm_get_source_selection_time(dsm_ctx* ctx, double* stage_ms);
 
+/* ---- The initial image pair of a batch of reconstructions (IncrementalMapper, src/sfm/incremental_mapper.cc) ----
+ * DESIGN.md 29.  What brings up a cluster's reconstruction, for many clusters (problems) over one scene in one call:
+ * FindInitialImagePair (incremental_mapper.cc:146-200) with FindFirstInitialImage / FindSecondInitialImage (:791-930),
+ * EstimateInitialTwoViewGeometry (:1121-1176) = TwoViewGeometry::EstimateCalibrated + EstimateRelativePose
+ * (src/estimators/two_view_geometry.cc:292-380, 169-230), and the two-view triangulation of RegisterInitialImagePair
+ * (:289-339).  A problem sees the pairs whose two images are both in its subset: the per-cluster DatabaseCache of
+ * src/controllers/distributed_mapper_controller.cpp:688-702.
+ *   Rulings: the first images run in (prior focal length first, NumCorrespondences descending, image id
+ *   ascending), the second images of a first image in (prior focal length first, correspondences with the first descending,
+ *   image id ascending) -- the reference iterates unordered maps and sorts unstably, so its ties are open; a first image needs
+ *   more than 0 correspondences in the problem, init_num_reg_trials < init_max_reg_trials and num_registrations == 0, a second
+ *   image num_registrations == 0 and at least init_min_num_inliers correspondences with the first; the counts are the matches
+ *   a pair keeps after the duplicate rule of CorrespondenceGraph::AddCorrespondences (dsm_retriangulate's), an image's
+ *   NumCorrespondences their sum over its pairs in the problem; the candidates are the directed pairs in that nested order,
+ *   every undirected pair once (its first occurrence), without the input tried set; with one seed image the first list is
+ *   that image alone (:152-164, no test of the first image), with both the single pair (seed_image1, seed_image2) whatever
+ *   the tried set says (the controller's direct RegisterInitialImagePair); a candidate's matches are
+ *   FindCorrespondencesBetweenImages(id1, id2): ascending point2D index of image 1, oriented as found; EstimateCalibrated is
+ *   forced (both cameras count as having a prior) with TwoViewGeometry::Options' defaults, min_num_trials 30 and max_error
+ *   init_max_error, on a fresh MT19937 stream per candidate seeded with dsm_pair_seed(id1, id2, user_seed) -- the reference
+ *   continues a thread-local stream; EstimateRelativePose: UNDEFINED, DEGENERATE and WATERMARK fail, the pose comes from E for
+ *   CALIBRATED / UNCALIBRATED and from H otherwise, tri_angle = Median(CalculateTriangulationAngles(0, -R^T t, points3D))
+ *   (src/base/triangulation.cc:147-181, Median of src/util/math.h:211-229), 0 without a point in front of both cameras, R the
+ *   rotation matrix of the returned qvec; accepted (:1166-1169) with inliers >= init_min_num_inliers, |tvec.z| <
+ *   init_max_forward_motion and tri_angle > DegToRad(init_min_tri_angle); the triangulation has image 1 at the identity and
+ *   image 2's projection matrix and centre through its quaternion (ComposeProjectionMatrix(qvec, tvec),
+ *   ProjectionCenterFromPose), per correspondence ImageToWorld twice, TriangulatePoint, CalculateTriangulationAngle >= the
+ *   minimum and HasPointPositiveDepth for both, the survivors in correspondence order.
+ * The candidates of all unfinished problems are verified speculation_window at a time; the first accepted candidate in list
+ * order wins, and candidates behind it were speculated: they are counted and do not enter the tried list.  No result depends
+ * on speculation_window, the batch, the memory budget or the order of the problems. */
+typedef struct dsm_initial_pair_options {
+  int32_t init_min_num_inliers;   /* 100  (IncrementalMapper::Options, src/sfm/incremental_mapper.h:68-81); >= 0 */
+  int32_t init_max_reg_trials;    /* 2; >= 1 */
+  double init_max_error;          /* 4.0 pixels; > 0 */
+  double init_max_forward_motion; /* 0.95; in [0, 1] */
+  double init_min_tri_angle;      /* 16.0 degrees; >= 0 */
+  uint32_t user_seed;             /* 0 */
+  uint32_t speculation_window;    /* 64; candidates per problem and round; scheduling only, never the result; >= 1 */
+} dsm_initial_pair_options;
+void dsm_default_initial_pair_options(dsm_initial_pair_options* o);
+
+#define DSM_NO_IMAGE 0xFFFFFFFFu /* kInvalidImageId: no seed image, no pair found */
+enum { DSM_INITIAL_PAIR_NONE = 0, DSM_INITIAL_PAIR_FOUND = 1 };
+
+typedef struct dsm_initial_pair_result { /* one per problem */
+  int32_t status;                /* DSM_INITIAL_PAIR_* */
+  uint32_t image_id1, image_id2; /* in the order the search found them; DSM_NO_IMAGE without a pair (:196-197) */
+  uint32_t num_tried;            /* pairs tried in this call, the successful one included */
+  uint64_t num_points;           /* points the triangulation kept */
+  dsm_two_view_geometry two_view_geometry; /* prev_init_two_view_geometry_ of the pair found, tri_angle as EstimateRelativePose
+                                              computes it; zero without a pair.  Its inlier matches: inlier_matches. */
+} dsm_initial_pair_result;
+
+typedef struct dsm_initial_pair_report {
+  uint32_t num_rounds;        /* speculation rounds */
+  uint32_t num_batches;       /* verifier calls: more than num_rounds where the memory budget cut a round by problems */
+  uint64_t num_candidates;    /* candidates of all problems' lists */
+  uint64_t num_verified;      /* candidates that went through the verifier */
+  uint64_t num_speculated;    /* of those, behind their problem's success */
+  /* the smallest relative margin of every decision rounding could flip (INFINITY when never taken), over the candidates up to
+     and including each problem's success: tri_angle against its threshold, |tvec.z| against init_max_forward_motion; over
+     the correspondences of the pairs found: the angle gate and the two depths */
+  double min_tri_angle_margin, min_forward_motion_margin, min_point_angle_margin, min_point_depth_margin;
+  double setup_ms;            /* host validation, the problems' pair lists (host clock) */
+  double graph_ms;            /* HIP events: uploads, the duplicate rule, the counts, the candidate order */
+  double gather_ms, verify_ms, pose_ms; /* HIP events summed over the batches: match lists, the verifier, k_ip_relative_pose */
+  double triangulate_ms;      /* HIP events: k_ip_triangulate and the download of the points */
+  double device_ms;           /* HIP events: first upload to the last download */
+} dsm_initial_pair_report;
+
+/* Host pointers, the conventions of dsm_retriangulate.
+ *   cameras: camera_ids[num_cameras] (unique), cameras (the eleven models)
+ *   images: image_ids[num_images] (unique, none DSM_NO_IMAGE), image_camera_ids, points2D_offsets[num_images + 1] (<= 262144 per
+ *     image), points2D_xy (2 per point2D)
+ *   pairs, in load order: pair_image_ids (2 per pair), match_offsets[num_pairs + 1] (uint64), matches (idx1, idx2 per match):
+ *     what DatabaseCache::Load kept (src/base/database_cache.cc); min_num_matches and the watermark filter stay with the host
+ *   problems: problem_image_offsets[num_problems + 1] (CSR, as dsm_align_clusters takes clusters), problem_image_ids;
+ *     num_registrations and init_num_reg_trials aligned with problem_image_ids (NULL: zeros); tried_offsets[num_problems + 1]
+ *     (uint64) and tried_pairs (2 image ids per pair, either order; init_image_pairs_), both NULL: none; seed_image1 and
+ *     seed_image2 [num_problems] (DSM_NO_IMAGE = none), NULL: none
+ * Outputs: results[num_problems]; tried_out_offsets[num_problems + 1] and tried_out_pairs (2 ids per pair, as tried, in trial
+ *   order, the successful pair last) with room for tried_capacity pairs -- the pairs of the problems' subsets bound it;
+ *   point_offsets[num_problems + 1], point_xyz (3 each) and point_obs (point2D_idx1, point2D_idx2) in correspondence order with
+ *   room for point_capacity points -- the sum over the problems of the largest match count of a pair bounds it;
+ *   inlier_offsets[num_problems + 1] and inlier_matches (point2D_idx1, point2D_idx2): the inlier matches of the geometry of
+ *   the pair found, with room for inlier_capacity matches (the same bound).  A capacity that is too small is
+ *   DSM_ERR_OUT_OF_RANGE.  tried_out_pairs, point_xyz, point_obs, inlier_offsets and inlier_matches may be NULL (nothing is
+ *   written and no capacity is needed), report may be NULL, options NULL = the defaults.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT, outputs untouched): what dsm_retriangulate refuses of these arguments; a problem image
+ *   that is not an image of the scene; a repeated image inside a problem; a seed image outside its problem, or twice the same;
+ *   options out of range.  More than 2^20 problem images or 2^19 kept matches of one pair is DSM_ERR_OUT_OF_RANGE. */
+int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
+                           uint32_t num_images, const uint32_t* image_ids, const uint32_t* image_camera_ids,
+                           const uint32_t* points2D_offsets, const double* points2D_xy, uint32_t num_pairs,
+                           const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
+                           uint32_t num_problems, const uint32_t* problem_image_offsets, const uint32_t* problem_image_ids,
+                           const uint32_t* num_registrations, const uint32_t* init_num_reg_trials, const uint64_t* tried_offsets,
+                           const uint32_t* tried_pairs, const uint32_t* seed_image1, const uint32_t* seed_image2,
+                           const dsm_initial_pair_options* options, dsm_initial_pair_result* results,
+                           uint64_t* tried_out_offsets, uint32_t* tried_out_pairs, uint64_t tried_capacity,
+                           uint64_t* point_offsets, double* point_xyz, uint32_t* point_obs, uint64_t point_capacity,
+                           uint64_t* inlier_offsets, uint32_t* inlier_matches, uint64_t inlier_capacity,
+                           dsm_initial_pair_report* report);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
