@@ -484,6 +484,39 @@ INITIAL_PAIR_NONE, INITIAL_PAIR_FOUND = 0, 1
 INITIAL_PAIR_HOST_LIB_PATH = os.path.join(_HERE, "libdsm_initial_pair_host.so")
 
 
+class NextImagesOptions(ctypes.Structure):
+    """dsm_next_images_options (IncrementalMapper::Options, incremental_mapper.h:87-131; DESIGN.md 30)."""
+    _fields_ = [("image_selection_method", ctypes.c_int32), ("abs_pose_min_num_inliers", ctypes.c_int32), ("max_reg_trials", ctypes.c_int32)]
+
+
+class NextImagesReport(ctypes.Structure):
+    _fields_ = [("num_eligible", ctypes.c_uint64), ("num_first_bucket", ctypes.c_uint64), ("num_second_bucket", ctypes.c_uint64),
+                ("num_batches", ctypes.c_uint32), ("setup_ms", ctypes.c_double), ("graph_ms", ctypes.c_double),
+                ("visibility_ms", ctypes.c_double), ("score_ms", ctypes.c_double), ("rank_ms", ctypes.c_double), ("device_ms", ctypes.c_double)]
+
+
+class LocalBundleSelectionOptions(ctypes.Structure):
+    """dsm_local_bundle_selection_options (IncrementalMapper::Options, incremental_mapper.h:98-102; DESIGN.md 30)."""
+    _fields_ = [("local_ba_num_images", ctypes.c_int32), ("local_ba_min_tri_angle", ctypes.c_double)]
+
+
+class LocalBundleSelectionReport(ctypes.Structure):
+    _fields_ = [("num_copied", ctypes.c_uint64), ("num_chained", ctypes.c_uint64), ("num_angles", ctypes.c_uint64), ("num_filled", ctypes.c_uint64),
+                ("min_tri_angle_margin", ctypes.c_double), ("num_batches", ctypes.c_uint32), ("setup_ms", ctypes.c_double),
+                ("tracks_ms", ctypes.c_double), ("overlap_ms", ctypes.c_double), ("angles_ms", ctypes.c_double), ("device_ms", ctypes.c_double)]
+
+
+# the arguments dsm_find_local_bundles and its host build share, from num_images to the overlap capacity
+_LOCAL_BUNDLES_ARGTYPES = ([ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 9 + [ctypes.c_uint32]
+                           + [ctypes.c_void_p] * 2 + [ctypes.POINTER(LocalBundleSelectionOptions), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+                           + [ctypes.c_void_p] * 4 + [ctypes.c_uint64])
+NEXT_IMAGE_MAX_VISIBLE_POINTS_NUM, NEXT_IMAGE_MAX_VISIBLE_POINTS_RATIO, NEXT_IMAGE_MIN_UNCERTAINTY = 0, 1, 2
+NEXT_IMAGES_HOST_LIB_PATH = os.path.join(_HERE, "libdsm_next_images_host.so")
+# the arguments dsm_find_next_images and its host build share, from num_cameras to slot_filtered
+_NEXT_IMAGES_SCENE_ARGTYPES = ([ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 4 + [ctypes.c_uint32]
+                               + [ctypes.c_void_p] * 3 + [ctypes.c_uint32] + [ctypes.c_void_p] * 7)
+
+
 class VocabularyBuildOptions(ctypes.Structure):
     """dsm_vocabulary_build_options: VisualIndex::BuildOptions (src/retrieval/visual_index.h:99-118) + the scheduling field."""
     _fields_ = [("num_visual_words", ctypes.c_int32), ("branching", ctypes.c_int32), ("num_iterations", ctypes.c_int32),
@@ -647,6 +680,13 @@ def lib(check=False):
         L.dsm_find_initial_pairs.argtypes = ([vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_uint32, vp, vp, vp,
                                               ctypes.c_uint32] + [vp] * 8 + [ctypes.POINTER(InitialPairOptions), vp, vp, vp, ctypes.c_uint64,
                                                                              vp, vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, vp])
+        L.dsm_default_next_images_options.argtypes = [ctypes.POINTER(NextImagesOptions)]
+        L.dsm_default_next_images_options.restype = None
+        L.dsm_find_next_images.argtypes = ([vp] + _NEXT_IMAGES_SCENE_ARGTYPES + [ctypes.POINTER(NextImagesOptions), vp, vp, ctypes.c_uint64,
+                                                                                 vp, vp, vp, vp])
+        L.dsm_default_local_bundle_selection_options.argtypes = [ctypes.POINTER(LocalBundleSelectionOptions)]
+        L.dsm_default_local_bundle_selection_options.restype = None
+        L.dsm_find_local_bundles.argtypes = [vp] + _LOCAL_BUNDLES_ARGTYPES + [vp]
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
         L.dsm_default_match_options.restype = None
         L.dsm_default_two_view_options.argtypes = [ctypes.POINTER(TwoViewOptions)]
@@ -1312,6 +1352,188 @@ def initial_pair_host_candidates(scene, problems, options=None, sorted_schedule=
     return lists, cnt[:len(pairs)].copy()
 
 
+def default_next_images_options(**kw):
+    o = NextImagesOptions()
+    lib().dsm_default_next_images_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def _next_images_arguments(scene, problems):
+    """The arguments dsm_find_next_images and its host build share, as the C arrays (kept alive by the returned list), and the
+    number of slots.  scene: the dict of find_initial_pairs.  problems: a list of dicts with image_ids, registered (0 / 1 per
+    image), obs_point3D (one int32 array per image: the point of every point2D or -1) and, optionally, num_reg_trials and
+    filtered (per image), obs_offsets (the slots' running sum over the whole call, overriding the one computed here)."""
+    a = lambda key, dt, shape=-1: np.ascontiguousarray(scene[key], dt).reshape(shape)
+    cam_ids = a("camera_ids", np.uint32)
+    cams = (Camera * max(len(cam_ids), 1))(*scene["cameras"])
+    img_ids, img_cam = a("image_ids", np.uint32), a("image_camera_ids", np.uint32)
+    poff, xy = a("points2D_offsets", np.uint32), a("points2D_xy", np.float64, (-1, 2))
+    pairs, moff, m = a("pairs", np.uint32, (-1, 2)), a("match_offsets", np.uint64), a("matches", np.uint32, (-1, 2))
+    ids, reg, trials, filt, obs, prob_off, obs_off = [], [], [], [], [], [0], [0]
+    for pr in problems:
+        im = [int(x) for x in pr["image_ids"]]
+        ids += im
+        reg += [int(x) for x in pr["registered"]]
+        trials += [int(x) for x in pr.get("num_reg_trials", [0] * len(im))]
+        filt += [int(x) for x in pr.get("filtered", [0] * len(im))]
+        for o3 in pr["obs_point3D"]:
+            obs.append(np.ascontiguousarray(o3, np.int32).reshape(-1))
+            obs_off.append(obs_off[-1] + len(obs[-1]))
+        prob_off.append(len(ids))
+    if not (len(reg) == len(trials) == len(filt) == len(ids) == len(obs_off) - 1):
+        raise DsmError("find_next_images: registered, num_reg_trials, filtered and obs_point3D must align with a problem's image_ids")
+    for pr in problems:
+        if "obs_offsets" in pr:
+            obs_off = list(pr["obs_offsets"])
+    u32 = lambda x: np.ascontiguousarray(x, np.uint32).reshape(-1)
+    arrays = [cam_ids, cams, img_ids, img_cam, poff, xy, pairs, moff, m, u32(prob_off), u32(ids + [0]), np.ascontiguousarray(reg + [0], np.uint8),
+              np.ascontiguousarray(obs_off, np.uint64), np.concatenate(obs + [np.zeros(1, np.int32)]), u32(trials + [0]),
+              np.ascontiguousarray(filt + [0], np.uint8)]
+    ptr = lambda x: ctypes.addressof(x) if isinstance(x, ctypes.Array) else x.ctypes.data
+    args = [len(cam_ids), ptr(cam_ids), ptr(cams), len(img_ids), ptr(img_ids), ptr(img_cam), ptr(poff), ptr(xy), len(pairs), ptr(pairs), ptr(moff),
+            ptr(m), len(problems)] + [ptr(x) for x in arrays[9:]]
+    return args, arrays, len(ids)
+
+
+def _next_images_result(problems, n_slots, off, out, nv, no, score):
+    res, s = [], 0
+    for k, pr in enumerate(problems):
+        n = len(pr["image_ids"])
+        res.append({"next_image_ids": [int(x) for x in out[int(off[k]):int(off[k + 1])]], "num_visible": nv[s:s + n].copy(),
+                    "num_observations": no[s:s + n].copy(), "score": score[s:s + n].copy()})
+        s += n
+    return res
+
+
+def next_images_host_lib():
+    """libdsm_next_images_host.so: the host build of csrc/next_images.h (the cell, the score, the rank key, the whole call)."""
+    if "next_images_host" not in _libs:
+        if not os.path.exists(NEXT_IMAGES_HOST_LIB_PATH):
+            raise DsmError("%s is missing: run make -C dagsfm_amd/csrc" % NEXT_IMAGES_HOST_LIB_PATH)
+        L = ctypes.CDLL(NEXT_IMAGES_HOST_LIB_PATH)
+        vp = ctypes.c_void_p
+        L.dsm_ni_host_default_options.argtypes, L.dsm_ni_host_default_options.restype = [ctypes.POINTER(NextImagesOptions)], None
+        L.dsm_ni_host_cell.argtypes, L.dsm_ni_host_cell.restype = [ctypes.c_double, ctypes.c_uint64], ctypes.c_uint32
+        L.dsm_ni_host_score.argtypes, L.dsm_ni_host_score.restype = [vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64], ctypes.c_uint64
+        L.dsm_ni_host_rank.argtypes, L.dsm_ni_host_rank.restype = [ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64], ctypes.c_float
+        L.dsm_ni_host_key.argtypes, L.dsm_ni_host_key.restype = [ctypes.c_uint32, ctypes.c_int, ctypes.c_float, ctypes.c_uint32], ctypes.c_uint64
+        L.dsm_lb_host_default_options.argtypes, L.dsm_lb_host_default_options.restype = [ctypes.POINTER(LocalBundleSelectionOptions)], None
+        L.dsm_lb_host_percentile_index.argtypes, L.dsm_lb_host_percentile_index.restype = [ctypes.c_uint64], ctypes.c_uint64
+        L.dsm_lb_host_percentile.argtypes, L.dsm_lb_host_percentile.restype = [vp, ctypes.c_uint64], ctypes.c_double
+        L.dsm_lb_host_find_local_bundles.argtypes = _LOCAL_BUNDLES_ARGTYPES + [vp, ctypes.POINTER(ctypes.c_char_p)]
+        L.dsm_ni_host_find_next_images.argtypes = (_NEXT_IMAGES_SCENE_ARGTYPES + [ctypes.POINTER(NextImagesOptions), ctypes.c_int, vp, vp,
+                                                                                  ctypes.c_uint64, vp, vp, vp, ctypes.POINTER(ctypes.c_char_p)])
+        _libs["next_images_host"] = L
+    return _libs["next_images_host"]
+
+
+def next_images_host(scene, problems, options=None, sorted_schedule=False, capacity=None, **kw):
+    """dsm_find_next_images from the host build on one CPU thread: the list find_next_images returns, without the report.
+    sorted_schedule: the device's packed keys under a sort instead of the sequential selection.  Raises DsmError with the
+    library's message on invalid arguments."""
+    L = next_images_host_lib()
+    if options is None:
+        options = NextImagesOptions()
+        L.dsm_ni_host_default_options(ctypes.byref(options))
+        for k, v in kw.items():
+            setattr(options, k, v)
+    args, keep, S = _next_images_arguments(scene, problems)
+    B = len(problems)
+    off, out = np.zeros(B + 1, np.uint64), np.zeros(max(S if capacity is None else capacity, 1), np.uint32)
+    nv, no, score = np.zeros(max(S, 1), np.uint32), np.zeros(max(S, 1), np.uint32), np.zeros(max(S, 1), np.uint64)
+    why = ctypes.c_char_p()
+    ptr = lambda x: x.ctypes.data
+    rc = L.dsm_ni_host_find_next_images(*args, ctypes.byref(options), int(bool(sorted_schedule)), ptr(off), ptr(out),
+                                        S if capacity is None else capacity, ptr(nv), ptr(no), ptr(score), ctypes.byref(why))
+    if rc != 0:
+        e = DsmError("dsm_ni_host_find_next_images failed (%d): %s" % (rc, (why.value or b"").decode()))
+        e.code, e.outputs = rc, (off, out, nv, no, score)
+        raise e
+    return _next_images_result(problems, S, off, out, nv, no, score)
+
+
+def default_local_bundle_selection_options(**kw):
+    o = LocalBundleSelectionOptions()
+    lib().dsm_default_local_bundle_selection_options(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def _local_bundles_arguments(scene, problems, queries, capacities):
+    """The arguments dsm_find_local_bundles and its host build share (from num_images to the overlap capacity, the options
+    left out), the arrays that keep them alive, and the outputs.  scene: image_ids and points2D_offsets are read.  problems: as
+    find_next_images takes them, with qvec [n, 4] and tvec [n, 3] per image (read for registered images) and point_xyz [m, 3].
+    queries: [(problem index, image id)]."""
+    a = lambda key, dt: np.ascontiguousarray(scene[key], dt).reshape(-1)
+    img_ids, poff = a("image_ids", np.uint32), a("points2D_offsets", np.uint32)
+    ids, reg, obs, qv, tv, xyz, prob_off, obs_off, pt_off = [], [], [], [], [], [], [0], [0], [0]
+    for pr in problems:
+        im = [int(x) for x in pr["image_ids"]]
+        ids += im
+        reg += [int(x) for x in pr["registered"]]
+        for o3 in pr["obs_point3D"]:
+            obs.append(np.ascontiguousarray(o3, np.int32).reshape(-1))
+            obs_off.append(obs_off[-1] + len(obs[-1]))
+        qv.append(np.asarray(pr.get("qvec", np.tile([1.0, 0, 0, 0], (len(im), 1))), np.float64).reshape(-1, 4))
+        tv.append(np.asarray(pr.get("tvec", np.zeros((len(im), 3))), np.float64).reshape(-1, 3))
+        xyz.append(np.asarray(pr.get("point_xyz", np.zeros((0, 3))), np.float64).reshape(-1, 3))
+        prob_off.append(len(ids))
+        pt_off.append(pt_off[-1] + len(xyz[-1]))
+    if not (len(reg) == len(ids) == len(obs_off) - 1 == sum(len(x) for x in qv) == sum(len(x) for x in tv)):
+        raise DsmError("find_local_bundles: registered, obs_point3D, qvec and tvec must align with a problem's image_ids")
+    for pr in problems:
+        if "obs_offsets" in pr:
+            obs_off = list(pr["obs_offsets"])
+    u32 = lambda x: np.ascontiguousarray(x, np.uint32).reshape(-1)
+    Q = len(queries)
+    S_rows = sum(len(problems[p]["image_ids"]) for p, _ in queries if 0 <= p < len(problems))
+    cap_b, cap_o = capacities
+    out = [np.zeros(Q + 1, np.uint64), np.zeros(max(Q * 64 if cap_b is None else cap_b, 1), np.uint32), np.zeros(Q + 1, np.uint64),
+           np.zeros(max(S_rows if cap_o is None else cap_o, 1), np.uint32), np.zeros(max(S_rows if cap_o is None else cap_o, 1), np.uint32),
+           np.zeros(max(S_rows if cap_o is None else cap_o, 1), np.float64)]
+    arrays = [img_ids, poff, u32(prob_off), u32(ids + [0]), np.ascontiguousarray(reg + [0], np.uint8), np.ascontiguousarray(obs_off, np.uint64),
+              np.concatenate(obs + [np.zeros(1, np.int32)]), np.concatenate(qv + [np.zeros((1, 4))]), np.concatenate(tv + [np.zeros((1, 3))]),
+              np.ascontiguousarray(pt_off, np.uint64), np.concatenate(xyz + [np.zeros((1, 3))]), u32([p for p, _ in queries] + [0]),
+              u32([i for _, i in queries] + [0])]
+    ptr = lambda x: x.ctypes.data
+    head = [len(img_ids), ptr(arrays[0]), ptr(arrays[1]), len(problems)] + [ptr(x) for x in arrays[2:11]] + [Q, ptr(arrays[11]), ptr(arrays[12])]
+    tail = [ptr(out[0]), ptr(out[1]), len(out[1]) if cap_b is None else cap_b, ptr(out[2]), ptr(out[3]), ptr(out[4]), ptr(out[5]),
+            len(out[3]) if cap_o is None else cap_o]
+    return head, tail, arrays, out
+
+
+def _local_bundles_result(queries, out):
+    boff, bids, ooff, oids, oshared, oangle = out
+    res = []
+    for k in range(len(queries)):
+        b0, b1, o0, o1 = int(boff[k]), int(boff[k + 1]), int(ooff[k]), int(ooff[k + 1])
+        res.append({"bundle_image_ids": [int(x) for x in bids[b0:b1]], "overlap_image_ids": [int(x) for x in oids[o0:o1]],
+                    "overlap_shared": [int(x) for x in oshared[o0:o1]], "overlap_tri_angle": oangle[o0:o1].copy()})
+    return res
+
+
+def local_bundles_host(scene, problems, queries, options=None, bundle_capacity=None, overlap_capacity=None, **kw):
+    """dsm_find_local_bundles from the host build on one CPU thread: (the list find_local_bundles returns as results, the
+    smallest tri_angle margin).  Raises DsmError with the library's message on invalid arguments."""
+    L = next_images_host_lib()
+    if options is None:
+        options = LocalBundleSelectionOptions()
+        L.dsm_lb_host_default_options(ctypes.byref(options))
+        for k, v in kw.items():
+            setattr(options, k, v)
+    head, tail, keep, out = _local_bundles_arguments(scene, problems, queries, (bundle_capacity, overlap_capacity))
+    why, margin = ctypes.c_char_p(), ctypes.c_double(0.0)
+    rc = L.dsm_lb_host_find_local_bundles(*head, ctypes.byref(options), *tail, ctypes.addressof(margin), ctypes.byref(why))
+    if rc != 0:
+        e = DsmError("dsm_lb_host_find_local_bundles failed (%d): %s" % (rc, (why.value or b"").decode()))
+        e.code, e.outputs = rc, out
+        raise e
+    return _local_bundles_result(queries, out), margin.value
+
+
 def default_vocabulary_build_options(**kw):
     o = VocabularyBuildOptions()
     lib().dsm_default_vocabulary_build_options(ctypes.byref(o))
@@ -1465,7 +1687,7 @@ CHECK_OPTION_KEYS = ("DSM_K1_DOT4", "DSM_K1_RESOLVE_KERNEL", "DSM_VERIFY_DEBUG",
                      "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT", "DSM_DEBUG_SAMPLER_MODE",
                      "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER", "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
                      "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT", "DSM_FUSION_SERIAL", "DSM_SOURCE_SELECTION_SERIAL",
-                     "DSM_INITIAL_PAIR_SERIAL")
+                     "DSM_INITIAL_PAIR_SERIAL", "DSM_NEXT_IMAGES_SERIAL")
 DEBUG_OPTION_KEYS = PRODUCT_OPTION_KEYS  # what a deployer's library knows
 
 
@@ -2610,6 +2832,47 @@ class Context:
                             "inlier_matches": out_inl[int(out_ioff[k]):int(out_ioff[k + 1])].copy(), "num_tried": int(r.num_tried),
                             "tried_pairs": out_tried[t0:t1].copy(), "new_xyz": out_xyz[p0:p1].copy(), "new_track_obs": obs})
         return {"results": results, "report": rep}
+
+    def find_next_images(self, scene, problems, options=None, capacity=None, **kw):
+        """dsm_find_next_images (IncrementalMapper::FindNextImages for a batch of reconstructions, stateless; DESIGN.md 30).
+        scene: the dict of find_initial_pairs.  problems: a list of dicts with image_ids, registered (0 / 1 per image),
+        obs_point3D (one int32 array per image: the point of every point2D or -1) and, optionally, num_reg_trials and filtered
+        (per image).  Returns a dict: results (per problem a dict: next_image_ids in the order to try them, and per image of
+        the problem num_visible, num_observations, score) and report.  On an error the DsmError carries the output arrays as
+        .outputs (untouched by an invalid call)."""
+        assert options is None or not kw, "pass a NextImagesOptions or keywords, not both"
+        o = options if options is not None else default_next_images_options(**kw)
+        args, keep, S = _next_images_arguments(scene, problems)
+        B = len(problems)
+        off, out = np.zeros(B + 1, np.uint64), np.zeros(max(S if capacity is None else capacity, 1), np.uint32)
+        nv, no, score = np.zeros(max(S, 1), np.uint32), np.zeros(max(S, 1), np.uint32), np.zeros(max(S, 1), np.uint64)
+        rep = NextImagesReport()
+        ptr = lambda x: x.ctypes.data
+        try:
+            self._chk(self._L.dsm_find_next_images(self._h, *args, ctypes.byref(o), ptr(off), ptr(out), S if capacity is None else capacity,
+                                                   ptr(nv), ptr(no), ptr(score), ctypes.addressof(rep)))
+        except DsmError as e:
+            e.outputs = (off, out, nv, no, score)
+            raise
+        return {"results": _next_images_result(problems, S, off, out, nv, no, score), "report": rep}
+
+    def find_local_bundles(self, scene, problems, queries, options=None, bundle_capacity=None, overlap_capacity=None, **kw):
+        """dsm_find_local_bundles (IncrementalMapper::FindLocalBundle for a batch of registered images, stateless; DESIGN.md
+        30).  scene: image_ids and points2D_offsets are read.  problems: as find_next_images takes them, with qvec [n, 4] and
+        tvec [n, 3] per image and point_xyz [m, 3].  queries: [(problem index, image id)].  Returns a dict: results (per query
+        a dict: bundle_image_ids, and the overlap list in overlap order: overlap_image_ids, overlap_shared, overlap_tri_angle
+        with -1 where no threshold could reach the image) and report.  On an error the DsmError carries the output arrays as
+        .outputs (untouched by an invalid call)."""
+        assert options is None or not kw, "pass a LocalBundleSelectionOptions or keywords, not both"
+        o = options if options is not None else default_local_bundle_selection_options(**kw)
+        head, tail, keep, out = _local_bundles_arguments(scene, problems, queries, (bundle_capacity, overlap_capacity))
+        rep = LocalBundleSelectionReport()
+        try:
+            self._chk(self._L.dsm_find_local_bundles(self._h, *head, ctypes.byref(o), *tail, ctypes.addressof(rep)))
+        except DsmError as e:
+            e.outputs = out
+            raise
+        return {"results": _local_bundles_result(queries, out), "report": rep}
 
     def estimate_absolute_poses(self, cameras, estimate_focal_length, offsets, points2D, points3D, options=None, seeds=None):
         """dsm_estimate_absolute_poses (EstimateAbsolutePose for a batch of problems).  cameras: a list of Camera

@@ -131,14 +131,19 @@ IP_HD double ip_bits_double(uint64_t u) {
   return x;
 }
 IP_HD double ip_median_of(double mid, double below, uint64_t n) { return n % 2 == 0 ? (mid + below) / 2.0 : mid; }
-IP_HD double ip_median_serial(const double* a, uint64_t n) {
+// the element of rank k (0 .. n - 1) of n such elements: what nth_element leaves at position k (Median here, Percentile in
+// next_images.h)
+IP_HD double ip_rank_serial(const double* a, uint64_t n, uint64_t k) {
   auto count_below = [&](uint64_t v) {
     uint64_t c = 0;
     for (uint64_t i = 0; i < n; ++i) c += ip_double_bits(a[i]) < v;
     return c;
   };
-  const double mid = ip_bits_double(ip_select_bits(n / 2, count_below));
-  const double below = n % 2 == 0 ? ip_bits_double(ip_select_bits(n / 2 - 1, count_below)) : 0.0;
+  return ip_bits_double(ip_select_bits(k, count_below));
+}
+IP_HD double ip_median_serial(const double* a, uint64_t n) {
+  const double mid = ip_rank_serial(a, n, n / 2);
+  const double below = n % 2 == 0 ? ip_rank_serial(a, n, n / 2 - 1) : 0.0;
   return ip_median_of(mid, below, n);
 }
 

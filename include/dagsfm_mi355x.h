@@ -1887,6 +1887,132 @@ int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* c
                            uint64_t* inlier_offsets, uint32_t* inlier_matches, uint64_t inlier_capacity,
                            dsm_initial_pair_report* report);
 
+/* ---- the next images of a batch of reconstructions: IncrementalMapper::FindNextImages ----
+ * src/sfm/incremental_mapper.cc:202-256 with the ranks of :46-73, over the state the reference keeps incrementally in
+ * Image::Increment / DecrementCorrespondenceHasPoint3D (src/base/image.cc:113-137) and VisibilityPyramid
+ * (src/base/visibility_pyramid.cc:53-106), recomputed here from the scene arrays: the call is stateless.
+ *   A slot is one (problem, image) incidence in the order of problem_image_ids.  A problem sees the pairs whose two images are
+ *   both in it; correspondences are the matches a pair keeps after the duplicate rule of
+ *   CorrespondenceGraph::AddCorrespondences.  A point2D of a slot is visible when at least one of its correspondences in the
+ *   problem ends on an observation that has a point in that problem; NumVisiblePoints3D counts the visible points2D,
+ *   NumObservations the points2D with at least one correspondence in the problem.  The visibility score is the six-level
+ *   pyramid's over the visible points2D: cell cx = Clip(size_t(64 * x / width), 0, 63) in double in that order (cy alike, with
+ *   the camera's width and height), level l = 0 .. 5 has the cells (cx >> (5 - l), cy >> (5 - l)), score = the sum over the
+ *   levels of occupied cells * 4^(l + 1).  An image is eligible when it is not registered, NumVisiblePoints3D >=
+ *   abs_pose_min_num_inliers and num_reg_trials < max_reg_trials; the first bucket holds the eligible images that are not
+ *   filtered and have num_reg_trials == 0, the second the rest; each bucket is sorted by the reference's float rank
+ *   descending, then by image id ascending (the reference's unstable sort of an unordered map's content leaves ties open).
+ * No result depends on the order of the problems, of the pairs, of the matches of a pair none of which is a duplicate, on the
+ * batch or on the memory budget. */
+enum { DSM_NEXT_IMAGE_MAX_VISIBLE_POINTS_NUM = 0, DSM_NEXT_IMAGE_MAX_VISIBLE_POINTS_RATIO = 1, DSM_NEXT_IMAGE_MIN_UNCERTAINTY = 2 };
+
+typedef struct dsm_next_images_options {
+  int32_t image_selection_method;   /* 2 = MIN_UNCERTAINTY (IncrementalMapper::Options, src/sfm/incremental_mapper.h:87-131); 0 .. 2 */
+  int32_t abs_pose_min_num_inliers; /* 30; > 0 */
+  int32_t max_reg_trials;           /* 3; >= 1 */
+} dsm_next_images_options;
+void dsm_default_next_images_options(dsm_next_images_options* o);
+
+typedef struct dsm_next_images_report {
+  uint64_t num_eligible;      /* images in the lists of all problems */
+  uint64_t num_first_bucket;  /* of those: not filtered and never tried */
+  uint64_t num_second_bucket; /* the rest */
+  uint32_t num_batches;       /* more than 1 where the memory budget cut the call by problems */
+  double setup_ms;            /* host validation, the problems' pair lists (host clock) */
+  double graph_ms;            /* HIP events: the scene's uploads and the duplicate rule */
+  double visibility_ms;       /* HIP events summed over the batches: the state's upload and the bitmaps */
+  double score_ms;            /* the counts, the pyramid scores and the keys */
+  double rank_ms;             /* the placement and the downloads */
+  double device_ms;           /* HIP events: first upload to the last download */
+} dsm_next_images_report;
+
+/* Host pointers; cameras, images, pairs and problems as dsm_find_initial_pairs takes them (width and height of a camera feed
+ * the pyramid).  Per slot: slot_registered (0 / 1), slot_obs_offsets[num_slots + 1] (uint64; must equal the running sum of the
+ * images' point2D counts: the caller's layout is checked, not guessed), slot_num_reg_trials and slot_filtered (NULL: zeros).
+ * Per observation: slot_obs_point3D, an index into the problem's points or -1.
+ * Outputs: next_offsets[num_problems + 1] and next_image_ids with room for next_capacity ids (the unregistered slots bound it;
+ *   too small: DSM_ERR_OUT_OF_RANGE, nothing written); slot_num_visible, slot_num_observations and slot_score [num_slots] may
+ *   each be NULL (slot_score is 0 for a registered slot: only a candidate's pyramid is evaluated); report may be NULL,
+ *   options NULL = the defaults.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT, outputs untouched): what dsm_find_initial_pairs refuses of these arguments; a
+ *   slot_registered other than 0 / 1; slot_obs_offsets that are not that running sum; a point index below -1; an observation
+ *   with a point on a slot that is not registered (the reference CHECKs it); negative points2D coordinates, or a camera
+ *   without width or height, on an image of a slot that is not registered; options out of range.  More than 2^31
+ *   observations over all slots is DSM_ERR_OUT_OF_RANGE. */
+int dsm_find_next_images(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
+                         uint32_t num_images, const uint32_t* image_ids, const uint32_t* image_camera_ids,
+                         const uint32_t* points2D_offsets, const double* points2D_xy, uint32_t num_pairs,
+                         const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
+                         uint32_t num_problems, const uint32_t* problem_image_offsets, const uint32_t* problem_image_ids,
+                         const uint8_t* slot_registered, const uint64_t* slot_obs_offsets, const int32_t* slot_obs_point3D,
+                         const uint32_t* slot_num_reg_trials, const uint8_t* slot_filtered,
+                         const dsm_next_images_options* options, uint64_t* next_offsets, uint32_t* next_image_ids,
+                         uint64_t next_capacity, uint32_t* slot_num_visible, uint32_t* slot_num_observations,
+                         uint64_t* slot_score, dsm_next_images_report* report);
+
+/* ---- the local bundles of a batch of registered images: IncrementalMapper::FindLocalBundle ----
+ * src/sfm/incremental_mapper.cc:932-1099 with CalculateTriangulationAngles (src/base/triangulation.cc:147-181) and Percentile
+ * (src/util/math.h:231-246), stateless over the observations' points.
+ *   A point's track is the set of observations of its problem that reference it.  The shared count of another image is the
+ *   number of (query point2D with a point, track element on that image) incidences as the reference's loop counts them: a
+ *   point referenced by two points2D of the query counts twice, and so do two track elements on the same other image.  The
+ *   overlapping images are sorted by shared count descending, then image id ascending (the reference's unstable sort of an
+ *   unordered map's content leaves ties open).  No more of them than local_ba_num_images - 1: they are the answer in that
+ *   order, no angle is computed.  Otherwise the eight thresholds of :1001-1010 apply as written there -- the doubles
+ *   0.6 * NumPoints3D etc. against the count converted to double, NumPoints3D the query's points2D with a point, the inner
+ *   loop breaking at the first image below the overlap threshold -- then the fill-up in overlap order.  tri_angle is
+ *   Percentile(CalculateTriangulationAngles(centre(query), centre(other), the xyz of every query point2D with a point, in
+ *   point2D order, repeats included), 75): the reference's text, not its comment -- it depends on the other image through its
+ *   projection centre only.  Centres are ProjectionCenterFromPose as dsm_find_initial_pairs evaluates it, the angle uses
+ *   the correctly rounded acos, Percentile's index is round(75.0 / 100 * (n - 1)) clamped to 0 .. n - 1; a NaN angle orders
+ *   behind every number.  Which angles get computed is scheduling: the device computes them for every overlapping image at
+ *   or above the loosest overlap threshold (0.1 * NumPoints3D) of a query that enters the chain. */
+typedef struct dsm_local_bundle_selection_options {
+  int32_t local_ba_num_images;   /* 6 (IncrementalMapper::Options, src/sfm/incremental_mapper.h:98-102); >= 2 */
+  double local_ba_min_tri_angle; /* 6.0 degrees; >= 0 and finite */
+} dsm_local_bundle_selection_options;
+void dsm_default_local_bundle_selection_options(dsm_local_bundle_selection_options* o);
+
+typedef struct dsm_local_bundle_selection_report {
+  uint64_t num_copied;         /* queries answered by the copy path (:983-988) */
+  uint64_t num_chained;        /* queries that went through the thresholds */
+  uint64_t num_angles;         /* tri_angles computed on the device */
+  uint64_t num_filled;         /* images taken by the fill-up (:1080-1096) */
+  double min_tri_angle_margin; /* the smallest |tri_angle - threshold| / max(threshold, DBL_EPSILON) over the comparisons the
+                                  chains made; INFINITY when none was made */
+  uint32_t num_batches;        /* more than 1 where the memory budget cut the call by queries */
+  double setup_ms;             /* host validation (host clock) */
+  double tracks_ms;            /* HIP events: uploads, the centres, the inversion of the observations into tracks */
+  double overlap_ms;           /* summed over the batches: the shared counts and the sorted overlap lists */
+  double angles_ms;            /* the angles and their percentiles */
+  double device_ms;            /* HIP events: first upload to the last download */
+} dsm_local_bundle_selection_report;
+
+/* Host pointers.  Images (image_ids, points2D_offsets), problems and the per-slot / per-observation state as
+ * dsm_find_next_images takes them; FindLocalBundle reads no camera, no pair and no point2D coordinate, so none is passed.
+ *   slot_qvec (4 per slot), slot_tvec (3 per slot): read for registered slots only
+ *   points: point_offsets[num_problems + 1] (uint64, CSR over the problems), point_xyz (3 per point); slot_obs_point3D indexes
+ *     its problem's points
+ *   queries: query_problem[num_queries], query_image_id[num_queries]; a query image must be registered in its problem
+ * Outputs: bundle_offsets[num_queries + 1] and bundle_image_ids with room for bundle_capacity ids (num_queries *
+ *   (local_ba_num_images - 1) bounds it); optionally (all four or none) the overlap lists: overlap_offsets[num_queries + 1],
+ *   overlap_image_ids, overlap_shared (the counts) and overlap_tri_angle (-1 for a candidate no threshold could reach, and for
+ *   every candidate of a query on the copy path) with room for overlap_capacity entries (the sum over the queries of their
+ *   problem's images less one bounds it).  A capacity that is too small is DSM_ERR_OUT_OF_RANGE and nothing is written.
+ *   report may be NULL, options NULL = the defaults.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT, outputs untouched): what dsm_find_next_images refuses of these arguments; a point index
+ *   outside its problem's points; a non-finite pose of a registered slot or point; a query on an unknown problem, or on an
+ *   image that is not in the problem or not registered there; options out of range.  More than 2^31 observations or points is
+ *   DSM_ERR_OUT_OF_RANGE. */
+int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_images, const uint32_t* image_ids, const uint32_t* points2D_offsets,
+                           uint32_t num_problems, const uint32_t* problem_image_offsets, const uint32_t* problem_image_ids,
+                           const uint8_t* slot_registered, const uint64_t* slot_obs_offsets, const int32_t* slot_obs_point3D,
+                           const double* slot_qvec, const double* slot_tvec, const uint64_t* point_offsets, const double* point_xyz,
+                           uint32_t num_queries, const uint32_t* query_problem, const uint32_t* query_image_id,
+                           const dsm_local_bundle_selection_options* options, uint64_t* bundle_offsets, uint32_t* bundle_image_ids,
+                           uint64_t bundle_capacity, uint64_t* overlap_offsets, uint32_t* overlap_image_ids, uint32_t* overlap_shared,
+                           double* overlap_tri_angle, uint64_t overlap_capacity, dsm_local_bundle_selection_report* report);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
