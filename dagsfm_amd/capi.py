@@ -203,6 +203,32 @@ class TriangulationOptions(ctypes.Structure):
                 ("max_transitivity", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class TrackUpdateOptions(ctypes.Structure):
+    """dsm_track_update_options: of `tri` only the three bogus-parameter limits are read."""
+    _fields_ = [("tri", TriangulationOptions), ("complete_max_reproj_error", ctypes.c_double),
+                ("merge_max_reproj_error", ctypes.c_double), ("complete_max_transitivity", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class TrackUpdateReport(ctypes.Structure):
+    _fields_ = [("num_points", ctypes.c_uint32), ("num_steps", ctypes.c_uint32), ("complete_rounds", ctypes.c_uint32),
+                ("complete_serial_steps", ctypes.c_uint32), ("num_components", ctypes.c_uint32), ("largest_component", ctypes.c_uint32),
+                ("num_correspondences", ctypes.c_uint64), ("complete_trials", ctypes.c_uint64), ("merge_trials", ctypes.c_uint64),
+                ("num_completed", ctypes.c_uint64), ("num_merged", ctypes.c_uint64), ("num_merge_events", ctypes.c_uint64),
+                ("min_complete_error_margin", ctypes.c_double), ("min_merge_error_margin", ctypes.c_double),
+                ("min_depth_margin", ctypes.c_double), ("min_bogus_margin", ctypes.c_double), ("setup_ms", ctypes.c_double),
+                ("graph_ms", ctypes.c_double), ("complete_ms", ctypes.c_double), ("components_ms", ctypes.c_double),
+                ("schedule_ms", ctypes.c_double), ("merge_ms", ctypes.c_double), ("download_ms", ctypes.c_double),
+                ("device_ms", ctypes.c_double)]
+
+
+TRACKS_MERGE, TRACKS_COMPLETE = 0, 1  # DSM_TRACKS_*
+_TRACK_UPDATE_ARGTYPES = ([ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 7
+                          + [ctypes.c_uint32] + [ctypes.c_void_p] * 3 + [ctypes.c_uint32] + [ctypes.c_void_p] * 4
+                          + [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                             ctypes.POINTER(TrackUpdateOptions)] + [ctypes.c_void_p] * 9)
+
+
 class TriangulationReport(ctypes.Structure):
     _fields_ = [("num_separators", ctypes.c_uint32), ("num_rounds", ctypes.c_uint32), ("num_problems", ctypes.c_uint64),
                 ("num_deferred", ctypes.c_uint64), ("num_correspondences", ctypes.c_uint64), ("ransac_trials", ctypes.c_uint64),
@@ -512,6 +538,7 @@ _LOCAL_BUNDLES_ARGTYPES = ([ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, c
                            + [ctypes.c_void_p] * 4 + [ctypes.c_uint64])
 NEXT_IMAGE_MAX_VISIBLE_POINTS_NUM, NEXT_IMAGE_MAX_VISIBLE_POINTS_RATIO, NEXT_IMAGE_MIN_UNCERTAINTY = 0, 1, 2
 NEXT_IMAGES_HOST_LIB_PATH = os.path.join(_HERE, "libdsm_next_images_host.so")
+TRACK_UPDATE_HOST_LIB_PATH = os.path.join(_HERE, "libdsm_track_update_host.so")
 # the arguments dsm_find_next_images and its host build share, from num_cameras to slot_filtered
 _NEXT_IMAGES_SCENE_ARGTYPES = ([ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 4 + [ctypes.c_uint32]
                                + [ctypes.c_void_p] * 3 + [ctypes.c_uint32] + [ctypes.c_void_p] * 7)
@@ -687,6 +714,9 @@ def lib(check=False):
         L.dsm_default_local_bundle_selection_options.argtypes = [ctypes.POINTER(LocalBundleSelectionOptions)]
         L.dsm_default_local_bundle_selection_options.restype = None
         L.dsm_find_local_bundles.argtypes = [vp] + _LOCAL_BUNDLES_ARGTYPES + [vp]
+        L.dsm_default_track_update_options.argtypes = [ctypes.POINTER(TrackUpdateOptions)]
+        L.dsm_default_track_update_options.restype = None
+        L.dsm_update_tracks.argtypes = [vp] + _TRACK_UPDATE_ARGTYPES
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
         L.dsm_default_match_options.restype = None
         L.dsm_default_two_view_options.argtypes = [ctypes.POINTER(TwoViewOptions)]
@@ -1407,6 +1437,108 @@ def _next_images_result(problems, n_slots, off, out, nv, no, score):
     return res
 
 
+def _track_update_options(L, default_name, kw):
+    """A TrackUpdateOptions with library L's defaults: the struct's own fields by name, any other keyword a field of `tri`."""
+    o = TrackUpdateOptions()
+    getattr(L, default_name)(ctypes.byref(o))
+    own = {k for k, _ in TrackUpdateOptions._fields_}
+    for k, v in kw.items():
+        setattr(o if k in own else o.tri, k, v)
+    return o
+
+
+def default_track_update_options(**kw):
+    """complete_max_reproj_error, merge_max_reproj_error, complete_max_transitivity by name; any other keyword is a field of `tri`."""
+    return _track_update_options(lib(), "dsm_default_track_update_options", kw)
+
+
+def track_update_host_lib():
+    """libdsm_track_update_host.so: the host build of csrc/track_update.h (dsm_update_tracks on one CPU thread)."""
+    if "track_update_host" not in _libs:
+        if not os.path.exists(TRACK_UPDATE_HOST_LIB_PATH):
+            raise DsmError("%s is missing: run make -C dagsfm_amd/csrc" % TRACK_UPDATE_HOST_LIB_PATH)
+        L = ctypes.CDLL(TRACK_UPDATE_HOST_LIB_PATH)
+        L.dsm_tu_host_default_options.argtypes, L.dsm_tu_host_default_options.restype = [ctypes.POINTER(TrackUpdateOptions)], None
+        L.dsm_tu_host_update_tracks.argtypes = _TRACK_UPDATE_ARGTYPES
+        _libs["track_update_host"] = L
+    return _libs["track_update_host"]
+
+
+def _update_tracks(call, scene, steps, selected, next_point3D_id, options):
+    """The marshalling dsm_update_tracks and its host build share.  call(args) -> the return code."""
+    a = lambda key, dt, shape=-1: np.ascontiguousarray(scene[key], dt).reshape(shape)
+    cam_ids = a("camera_ids", np.uint32)
+    cams = (Camera * max(len(cam_ids), 1))(*scene["cameras"])
+    img_ids, img_cam, reg = a("image_ids", np.uint32), a("image_camera_ids", np.uint32), a("registered", np.uint8)
+    N = len(img_ids)
+    qvec, tvec = a("qvec", np.float64, (N, 4)), a("tvec", np.float64, (N, 3))
+    poff, xy = a("points2D_offsets", np.uint32), a("points2D_xy", np.float64, (-1, 2))
+    pairs, moff, m = a("pairs", np.uint32, (-1, 2)), a("match_offsets", np.uint64), a("matches", np.uint32, (-1, 2))
+    pids, pxyz = a("point3D_ids", np.uint64), a("point3D_xyz", np.float64, (-1, 3))
+    toff, tobs = a("track_offsets", np.uint64), a("track_obs", np.uint32, (-1, 2))
+    st = np.ascontiguousarray(steps, np.int32).reshape(-1)
+    sel = None if selected is None else np.ascontiguousarray(selected, np.uint64).reshape(-1)
+    P, T = len(pids), int(poff[-1]) if len(poff) else 0
+    oid, oxyz, ooff = np.zeros(max(P, 1), np.uint64), np.zeros((max(P, 1), 3)), np.zeros(P + 1, np.uint64)
+    oobs, omod, counts = np.zeros((max(T, 1), 2), np.uint32), np.zeros(max(P, 1), np.uint64), np.zeros(max(len(st), 1), np.uint64)
+    n, nm = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rep = TrackUpdateReport()
+    o = options if options is not None else default_track_update_options()
+    ptr = lambda x: x.ctypes.data
+    rc = call([len(cam_ids), ptr(cam_ids), ctypes.addressof(cams), N, ptr(img_ids), ptr(img_cam), ptr(reg), ptr(qvec), ptr(tvec),
+               ptr(poff), ptr(xy), len(pairs), ptr(pairs), ptr(moff), ptr(m), P, ptr(pids), ptr(pxyz), ptr(toff), ptr(tobs),
+               len(st), ptr(st), 0 if sel is None else len(sel), None if sel is None else ptr(sel), int(next_point3D_id),
+               ctypes.byref(o), ctypes.addressof(n), ptr(oid), ptr(oxyz), ptr(ooff), ptr(oobs), ctypes.addressof(nm), ptr(omod),
+               ptr(counts), ctypes.addressof(rep)])
+    k = n.value
+    return rc, {"point_ids": oid[:k].copy(), "xyz": oxyz[:k].copy(), "track_offsets": ooff[:k + 1].copy(),
+                "track_obs": oobs[:int(ooff[k])].copy(), "modified": omod[:nm.value].copy(), "step_counts": counts[:len(st)].copy(),
+                "report": rep}
+
+
+def update_tracks_host(scene, steps, selected=None, next_point3D_id=0, options=None, **kw):
+    """dsm_update_tracks from the host build on one CPU thread; the dict Context.update_tracks returns."""
+    assert options is None or not kw, "pass a TrackUpdateOptions or keywords, not both"
+    L = track_update_host_lib()
+    if options is None:
+        options = _track_update_options(L, "dsm_tu_host_default_options", kw)
+    rc, out = _update_tracks(lambda args: L.dsm_tu_host_update_tracks(*args), scene, steps, selected, next_point3D_id, options)
+    if rc != 0:
+        raise DsmError("dsm_tu_host_update_tracks failed (%d)" % rc)
+    return out
+
+
+def apply_track_update(scene, result):
+    """The scene with the result of update_tracks written back: point3D_ids, point3D_xyz, track_offsets, track_obs replaced, and
+    points2D_point3D (the index of every point2D's point in the new point list, or -1) as dsm_retriangulate_pairs takes it.
+    bundle_arrays(scene) gives the arrays dsm_filter_points3D and dsm_bundle_adjust take."""
+    out = dict(scene)
+    out["point3D_ids"], out["point3D_xyz"] = result["point_ids"].copy(), result["xyz"].copy()
+    out["track_offsets"], out["track_obs"] = result["track_offsets"].copy(), result["track_obs"].copy()
+    poff = np.asarray(scene["points2D_offsets"], np.int64).reshape(-1)
+    img_of = {int(i): k for k, i in enumerate(np.asarray(scene["image_ids"]).reshape(-1))}
+    p3 = np.full(int(poff[-1]) if len(poff) else 0, -1, np.int32)
+    toff = np.asarray(result["track_offsets"], np.int64)
+    owner = np.repeat(np.arange(len(toff) - 1), toff[1:] - toff[:-1])
+    for (im, idx), p in zip(np.asarray(result["track_obs"], np.int64).reshape(-1, 2), owner):
+        p3[poff[img_of[int(im)]] + idx] = p
+    out["points2D_point3D"] = p3
+    return out
+
+
+def bundle_arrays(scene):
+    """The point arrays of a track scene as dsm_bundle_adjust and dsm_filter_points3D take them: xyz, track_offsets, obs_image
+    (image index) and obs_xy per track element."""
+    poff = np.asarray(scene["points2D_offsets"], np.int64).reshape(-1)
+    xy = np.asarray(scene["points2D_xy"], np.float64).reshape(-1, 2)
+    img_of = {int(i): k for k, i in enumerate(np.asarray(scene["image_ids"]).reshape(-1))}
+    tobs = np.asarray(scene["track_obs"], np.int64).reshape(-1, 2)
+    oimg = np.array([img_of[int(i)] for i in tobs[:, 0]], np.uint32)
+    return {"xyz": np.asarray(scene["point3D_xyz"], np.float64).reshape(-1, 3).copy(),
+            "track_offsets": np.asarray(scene["track_offsets"], np.uint32).copy(), "obs_image": oimg,
+            "obs_xy": xy[poff[oimg.astype(np.int64)] + tobs[:, 1]].reshape(-1, 2).copy()}
+
+
 def next_images_host_lib():
     """libdsm_next_images_host.so: the host build of csrc/next_images.h (the cell, the score, the rank key, the whole call)."""
     if "next_images_host" not in _libs:
@@ -1687,7 +1819,7 @@ CHECK_OPTION_KEYS = ("DSM_K1_DOT4", "DSM_K1_RESOLVE_KERNEL", "DSM_VERIFY_DEBUG",
                      "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT", "DSM_DEBUG_SAMPLER_MODE",
                      "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER", "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
                      "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT", "DSM_FUSION_SERIAL", "DSM_SOURCE_SELECTION_SERIAL",
-                     "DSM_INITIAL_PAIR_SERIAL", "DSM_NEXT_IMAGES_SERIAL")
+                     "DSM_INITIAL_PAIR_SERIAL", "DSM_NEXT_IMAGES_SERIAL", "DSM_TRACK_UPDATE_SERIAL")
 DEBUG_OPTION_KEYS = PRODUCT_OPTION_KEYS  # what a deployer's library knows
 
 
@@ -2788,6 +2920,26 @@ class Context:
                 "continued_obs": cobs[:c].copy(), "continued_point_ids": cid[:c].copy(), "touched_obs": tobs[:t].copy(),
                 "touched_point_ids": tid[:t].copy(), "pair_num_total_corrs": total[:K].copy(), "pair_num_tri_corrs": tri[:K].copy(),
                 "pair_status": status[:K].copy(), "re_num_trials": trials[:K].copy(), "num_tris": tris.value, "report": rep}
+
+    def update_tracks(self, scene, steps, selected=None, next_point3D_id=0, options=None, **kw):
+        """dsm_update_tracks (CompleteTracks / MergeTracks).  scene: the dict of retriangulate (points2D_point3D is not
+        read) with track_offsets [P + 1] and track_obs [n, 2] ((image_id, point2D_idx) per element, in track order).  steps: a list
+        of TRACKS_MERGE / TRACKS_COMPLETE; selected: point3D ids (None = all points, a snapshot per step).
+        Returns a dict in ascending id: point_ids, xyz [n, 3], track_offsets [n + 1], track_obs [m, 2], modified (ids),
+        step_counts (num_merged / num_completed per step), report."""
+        assert options is None or not kw, "pass a TrackUpdateOptions or keywords, not both"
+        o = options if options is not None else default_track_update_options(**kw)
+        rc, out = _update_tracks(lambda args: self._L.dsm_update_tracks(self._h, *args), scene, steps, selected, next_point3D_id, o)
+        self._chk(rc)
+        return out
+
+    def complete_and_merge_tracks(self, scene, **kw):
+        """IncrementalMapper::CompleteAndMergeTracks: COMPLETE, then MERGE, over all points."""
+        return self.update_tracks(scene, [TRACKS_COMPLETE, TRACKS_MERGE], None, **kw)
+
+    def merge_and_complete_tracks(self, scene, ids, **kw):
+        """The order of AdjustLocalBundle: MERGE, then COMPLETE, over one id set."""
+        return self.update_tracks(scene, [TRACKS_MERGE, TRACKS_COMPLETE], ids, **kw)
 
     def find_initial_pairs(self, scene, problems, options=None, **kw):
         """dsm_find_initial_pairs (FindInitialImagePair, EstimateInitialTwoViewGeometry and the triangulation of

@@ -2013,6 +2013,84 @@ int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_images, const uint32_t* im
                            uint64_t bundle_capacity, uint64_t* overlap_offsets, uint32_t* overlap_image_ids, uint32_t* overlap_shared,
                            double* overlap_tri_angle, uint64_t overlap_capacity, dsm_local_bundle_selection_report* report);
 
+/* ------------------------------------------------------------------ completing and merging tracks
+ * IncrementalTriangulator::CompleteTracks / CompleteAllTracks and MergeTracks / MergeAllTracks
+ * (src/sfm/incremental_triangulator.cc:231-287, Merge :588-677, Complete :679-746, Reconstruction::MergePoints3D
+ * reconstruction.cc:215-241): what IncrementalMapper::AdjustLocalBundle runs after every local bundle adjustment (MERGE then
+ * COMPLETE over one id set) and IterativeGlobalRefinement before every global one (CompleteAndMergeTracks: COMPLETE then MERGE
+ * over all points).  The correspondence graph is dsm_retriangulate's; the reprojection error is dsm_filter_points3D's
+ * (CalculateSquaredReprojectionError by qvec / tvec, DBL_MAX below a depth of epsilon).  CompleteImage is not part of this
+ * call: its creating half is EstimateTriangulation.
+ *   Rulings: points run in ascending point3D id (the reference: unordered sets); a step without a selection
+ *   takes a snapshot of the ids at its start; a merged point gets the id AddPoint3D would hand out from next_point3D_id, in
+ *   the order of the merge events of the sequential run (an intermediate merged point that is merged again consumes one),
+ *   however the device schedules the components; the camera verdict of HasBogusParams is computed per camera, not cached across
+ *   calls; a selected id merged away earlier in the call is skipped (ExistsPoint3D), merged ids are never selected. */
+typedef struct dsm_track_update_options {
+  dsm_triangulation_options tri;       /* read: the three bogus-parameter limits only */
+  double  complete_max_reproj_error;   /* 4.0 px */
+  double  merge_max_reproj_error;      /* 4.0 px */
+  int32_t complete_max_transitivity;   /* 5; < 1 is DSM_ERR_INVALID_ARGUMENT */
+  int32_t reserved;
+} dsm_track_update_options;
+
+enum { DSM_TRACKS_MERGE = 0, DSM_TRACKS_COMPLETE = 1 };
+
+typedef struct dsm_track_update_report {
+  uint32_t num_points;                 /* input points */
+  uint32_t num_steps;
+  uint32_t complete_rounds;            /* claim rounds, summed over the COMPLETE steps */
+  uint32_t complete_serial_steps;      /* COMPLETE steps finished by the serial form (claim pool exhausted, or asked for) */
+  uint32_t num_components;             /* of the last MERGE step: components holding a selected point, and the largest one */
+  uint32_t largest_component;          /*   (in selected points) */
+  uint64_t num_correspondences;        /* directed entries of the correspondence graph */
+  uint64_t complete_trials;            /* reprojection tests of Complete, as the sequential run takes them */
+  uint64_t merge_trials;               /* pairs Merge enters into merge_trials_ */
+  uint64_t num_completed, num_merged;  /* the step counts, summed per kind */
+  uint64_t num_merge_events;           /* MergePoints3D calls = ids handed out */
+  /* the smallest relative margin |a - t| / max(|a|, |t|) of every decision taken (INFINITY when never taken): err^2 against
+     the squared threshold in Complete (speculative walks of the claim rounds included) and in Merge, the depth against
+     epsilon, the bogus ratios against their bounds */
+  double min_complete_error_margin, min_merge_error_margin, min_depth_margin, min_bogus_margin;
+  double setup_ms;                     /* host validation, slot order, the tracks as lists (host clock) */
+  double graph_ms;                     /* uploads and the correspondence graph (host clock around the synchronised phase, as all below) */
+  double complete_ms;                  /* the COMPLETE steps */
+  double components_ms, schedule_ms, merge_ms; /* MERGE steps: labelling, the per-component lists (host), the runs and the ids */
+  double download_ms;                  /* the tracks written out and brought back */
+  double device_ms;                    /* first upload to the last download */
+} dsm_track_update_report;
+
+void dsm_default_track_update_options(dsm_track_update_options* o);
+
+/* The steps in order over one state, which stays on the device between them (host pointers).  Cameras, images, points2D and
+ * pairs as dsm_retriangulate_pairs takes them, without points2D_point3D: feature -> point follows from the tracks.
+ *   points3D: point3D_ids (unique), point3D_xyz (3 each), track_offsets[num_points3D + 1], track_obs ((image_id, point2D_idx)
+ *     per element, in track order)
+ *   steps[num_steps]: DSM_TRACKS_MERGE / DSM_TRACKS_COMPLETE; selected_ids[num_selected]: the id set every step runs over
+ *     (NULL: all points, a snapshot per step); next_point3D_id: the first merged id; 0 = the largest existing id + 1
+ * Outputs in ascending id: *out_num_points, out_point_ids, out_xyz (3 each), out_track_offsets[n + 1], out_track_obs
+ *   ((image_id, point2D_idx); room for the input's elements plus every point2D, i.e. at most T = points2D_offsets[num_images]
+ *   entries are written), out_modified with *out_num_modified (modified_point3D_ids_ as these steps change it, starting
+ *   empty: inserted on a completion; on a merge the two inputs erased and the merged id inserted), step_counts[num_steps]
+ *   (num_merged / num_completed as the reference returns them).  The point arrays need room for num_points3D entries.
+ *   Output arrays other than the counts may be NULL.  report may be NULL.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT, outputs untouched): what dsm_retriangulate refuses of these arguments; a track element
+ *   on an unknown or unregistered image or out of range; a feature in two tracks; complete_max_transitivity < 1; a negative
+ *   or non-finite threshold; an unknown step; a selected id that is no point3D, or repeated.
+ * The result is the same bytes for any order of the points3D and of the matches inside a pair (when no match of the pair is
+ * dropped as a duplicate). */
+int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
+                      uint32_t num_images, const uint32_t* image_ids, const uint32_t* image_camera_ids,
+                      const uint8_t* image_registered, const double* image_qvec, const double* image_tvec,
+                      const uint32_t* points2D_offsets, const double* points2D_xy, uint32_t num_pairs,
+                      const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
+                      uint32_t num_points3D, const uint64_t* point3D_ids, const double* point3D_xyz,
+                      const uint64_t* track_offsets, const uint32_t* track_obs, uint32_t num_steps, const int32_t* steps,
+                      uint64_t num_selected, const uint64_t* selected_ids, uint64_t next_point3D_id,
+                      const dsm_track_update_options* options, uint64_t* out_num_points, uint64_t* out_point_ids,
+                      double* out_xyz, uint64_t* out_track_offsets, uint32_t* out_track_obs, uint64_t* out_num_modified,
+                      uint64_t* out_modified, uint64_t* step_counts, dsm_track_update_report* report);
+
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
 
