@@ -26,8 +26,10 @@
 #include <vector>
 
 #include "ctx.h"
+#include "std_mt19937.h"
 #include "verify_camera.h"
 #include "verify_linalg.h"
+#include "wave_reduce.h"
 
 namespace {
 
@@ -66,48 +68,12 @@ struct ApParams {
 };
 
 // ------------------------------------------------------------------------------------ std::mt19937 + libstdc++ uniform_int (lane 0)
-struct ApMt {
-  uint32_t mt[624];
-  int mti;
-};
-__device__ __noinline__ void ap_mt_seed(ApMt* s, uint32_t seed) {
-  s->mt[0] = seed;
-  for (int i = 1; i < 624; ++i) s->mt[i] = 1812433253u * (s->mt[i - 1] ^ (s->mt[i - 1] >> 30)) + (uint32_t)i;
-  s->mti = 624;
-}
-__device__ __noinline__ uint32_t ap_mt_next(ApMt* s) {
-  if (s->mti >= 624) {
-    uint32_t* mt = s->mt;
-    for (int kk = 0; kk < 624; ++kk) {
-      const uint32_t y = (mt[kk] & 0x80000000u) | (mt[(kk + 1) % 624] & 0x7fffffffu);
-      mt[kk] = mt[(kk + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-    }
-    s->mti = 0;
-  }
-  uint32_t y = s->mt[s->mti++];
-  y ^= (y >> 11);
-  y ^= (y << 7) & 0x9d2c5680u;
-  y ^= (y << 15) & 0xefc60000u;
-  y ^= (y >> 18);
-  return y;
-}
-// std::uniform_int_distribution<uint32_t>(a, b), Lemire's method on 32-bit draws (b - a < 2^32 - 1 here)
-__device__ uint32_t ap_uniform(ApMt* s, uint32_t a, uint32_t b) {
-  const uint32_t range = b - a + 1u;
-  uint64_t product = (uint64_t)ap_mt_next(s) * (uint64_t)range;
-  uint32_t low = (uint32_t)product;
-  if (low < range) {
-    const uint32_t threshold = (0u - range) % range;
-    while (low < threshold) {
-      product = (uint64_t)ap_mt_next(s) * (uint64_t)range;
-      low = (uint32_t)product;
-    }
-  }
-  return (uint32_t)(product >> 32) + a;
-}
+// std_mt19937.h, the seeding and the draw out of line as this file's kernel was built with
+__device__ __noinline__ void ap_mt_seed(StdMt19937* s, uint32_t seed) { std_mt19937_seed(s, seed); }
+__device__ __noinline__ uint32_t ap_mt_next(StdMt19937* s) { return std_mt19937_next(s); }
 
 struct ApShared {
-  ApMt gen;
+  StdMt19937 gen;
   double models[4][12];  // P3P's models of the current trial, row-major 3 x 4
   int nm;
   int ok;
@@ -163,8 +129,7 @@ __device__ __noinline__ int ap_count(const ApView& v, const double* P, int lane,
     cnt += in;
     if (write_mask) v.mask[i] = (uint8_t)in;
   }
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-  return cnt;
+  return wave_sum(cnt);
 }
 // ... and its residual sum, accumulated in point order like the reference's loop
 __device__ __noinline__ double ap_sum(const ApView& v, const double* P, int lane) {
@@ -575,10 +540,7 @@ __device__ inline void ap_tree_sums(const ApView& v, int lane, double* out, F te
 #pragma unroll
     for (int c = 0; c < NC; ++c) acc[c] += in ? t[c] : 0.0;
   }
-  for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c] += __shfl_xor(acc[c], o);
-  }
+  wave_sum(acc);
 #pragma unroll
   for (int c = 0; c < NC; ++c) out[c] = acc[c];
 }
@@ -609,10 +571,7 @@ __device__ __noinline__ bool ap_epnp(const ApView& v, int n, ApShared* sm, int l
       first = i;
       break;
     }
-  for (int o = 32; o > 0; o >>= 1) {
-    const int other = __shfl_xor(first, o);
-    first = other < first ? other : first;
-  }
+  first = wave_min(first);
   if (lane == 0) {
     const double A[9] = {r6[0], r6[1], r6[2], r6[1], r6[3], r6[4], r6[2], r6[4], r6[5]};
     double U[9], V[9], D[3];
@@ -817,7 +776,7 @@ __global__ void __launch_bounds__(64) k_ap_ransac(ApParams p) {
       if (lane == 0) {
         double x[3][2], Xw[3][3];
         for (uint32_t i = 0; i < 3; ++i) {  // RandomSampler::Sample: a partial Fisher-Yates shuffle of the persistent index array
-          const uint32_t j = ap_uniform(&sm.gen, i, run.N - 1);
+          const uint32_t j = std_uniform_u32([] { return ap_mt_next(&sm.gen); }, i, run.N - 1);
           const uint32_t t = sidx[i];
           sidx[i] = sidx[j];
           sidx[j] = t;
@@ -893,10 +852,8 @@ __global__ void __launch_bounds__(64) k_ap_ransac(ApParams p) {
     double d0 = INFINITY, d1 = INFINITY;
     (void)ap_count(v, sm.best, lane, 1, &d0, &d1);  // the final mask from the best model's residuals
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    mg_res = fmin(mg_res, __shfl_xor(mg_res, o));
-    mg_depth = fmin(mg_depth, __shfl_xor(mg_depth, o));
-  }
+  mg_res = wave_fmin(mg_res);
+  mg_depth = wave_fmin(mg_depth);
   if (lane == 0) {
     out->success = success;
     out->num_trials = nt;
@@ -1091,10 +1048,7 @@ extern "C" int dsm_estimate_absolute_poses(dsm_ctx* ctx, uint32_t num_problems, 
                                            dsm_absolute_pose_result* results_out, uint8_t* inlier_mask_out, double* margins_out,
                                            dsm_absolute_pose_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_estimate_absolute_poses: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_estimate_absolute_poses", msg); };
   const auto t_host0 = std::chrono::steady_clock::now();
   const uint32_t B = num_problems;
   if (!offsets || (B && (!cameras || !estimate_focal_length || !results_out))) return fail("NULL argument");
@@ -1195,24 +1149,19 @@ extern "C" int dsm_estimate_absolute_poses(dsm_ctx* ctx, uint32_t num_problems, 
   if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   ApBufs d;
-  DevEvent ev[4];
-  for (int i = 0; i < 4; ++i) HIPCHK(ctx, hipEventCreate(&ev[i].e));
+  DevEvents<4> ev;
+  HIPCHK(ctx, ev.create());
   HIPCHK(ctx, hipEventRecord(ev[0], st));
-  auto up = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
-    hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
-    return e;
-  };
   const size_t RP1 = std::max<uint64_t>(RP, 1), T1 = std::max<uint64_t>(T, 1);
-  HIPCHK(ctx, up(d.runs, runs.data(), runs.size() * sizeof(ApRun)));
-  HIPCHK(ctx, up(d.xy, points2D, T * 16));
-  HIPCHK(ctx, up(d.X, points3D, T * 24));
-  HIPCHK(ctx, up(d.tab, tab.data(), tab.size() * 4));
-  HIPCHK(ctx, up(d.run0, run0.data(), run0.size() * 4));
-  HIPCHK(ctx, up(d.factors, factors.data(), factors.size() * 8));
-  HIPCHK(ctx, up(d.cams, cameras, (size_t)B * sizeof(dsm_camera)));
-  HIPCHK(ctx, up(d.flags, estimate_focal_length, B));
-  HIPCHK(ctx, up(d.offsets, offsets, ((size_t)B + 1) * 8));
+  HIPCHK(ctx, dev_upload(d.runs, runs.data(), runs.size() * sizeof(ApRun), st));
+  HIPCHK(ctx, dev_upload(d.xy, points2D, T * 16, st));
+  HIPCHK(ctx, dev_upload(d.X, points3D, T * 24, st));
+  HIPCHK(ctx, dev_upload(d.tab, tab.data(), tab.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.run0, run0.data(), run0.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.factors, factors.data(), factors.size() * 8, st));
+  HIPCHK(ctx, dev_upload(d.cams, cameras, (size_t)B * sizeof(dsm_camera), st));
+  HIPCHK(ctx, dev_upload(d.flags, estimate_focal_length, B, st));
+  HIPCHK(ctx, dev_upload(d.offsets, offsets, ((size_t)B + 1) * 8, st));
   for (DevBuf* b : {&d.un, &d.vn}) HIPCHK(ctx, b->reserve(RP1 * 8));
   HIPCHK(ctx, d.sidx.reserve(RP1 * 4));
   HIPCHK(ctx, d.mask.reserve(RP1));
@@ -1268,15 +1217,10 @@ extern "C" int dsm_estimate_absolute_poses(dsm_ctx* ctx, uint32_t num_problems, 
       rep.min_margin[i] = std::min(rep.min_margin[i], margins[(size_t)b * AP_MARGINS + i]);
       if (margins_out) margins_out[(size_t)b * AP_MARGINS + i] = margins[(size_t)b * AP_MARGINS + i];
     }
-  float a = 0, b2 = 0, c = 0, tot = 0;
-  HIPCHK(ctx, hipEventElapsedTime(&a, ev[0], ev[1]));
-  HIPCHK(ctx, hipEventElapsedTime(&b2, ev[1], ev[2]));
-  HIPCHK(ctx, hipEventElapsedTime(&c, ev[2], ev[3]));
-  HIPCHK(ctx, hipEventElapsedTime(&tot, ev[0], ev[3]));
-  rep.prepare_ms = a;
-  rep.ransac_ms = b2;
-  rep.choice_ms = c;
-  rep.device_ms = tot;
+  HIPCHK(ctx, ev.ms(0, 1, &rep.prepare_ms));
+  HIPCHK(ctx, ev.ms(1, 2, &rep.ransac_ms));
+  HIPCHK(ctx, ev.ms(2, 3, &rep.choice_ms));
+  HIPCHK(ctx, ev.ms(0, 3, &rep.device_ms));
   if (report) *report = rep;
   return DSM_OK;
 }

@@ -1167,37 +1167,33 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
       b_cpose, b_mask, b_ptvar, b_cammodel, b_camnp, b_camk, b_camfree, b_q, b_t, b_X, b_prm, b_cq, b_ct, b_cX, b_cprm, b_J, b_y,
       b_ge, b_cne, b_se, b_De, b_Cinv, b_ve, b_zp, b_dy, b_gf, b_cnf, b_sf, b_Df, b_ddf, b_Minv, b_b, b_x, b_r, b_z, b_p, b_qv,
       b_tmp, b_icam, b_Pc, b_Pm, b_Pg, b_Pe, b_Pd, b_Pq, b_ctl, b_trace;
-  DevEvent ev[6];  // jacobian(first): 0-1; per LM iteration: 2 CG 3 candidate 4 Jacobian 5
+  DevEvents<6> ev;  // jacobian(first): 0-1; per LM iteration: 2 CG 3 candidate 4 Jacobian 5
   int rc = DSM_OK;
-  auto up = [&](DevBuf& b, const void* src, size_t bytes) {
-    HIPTRY(b.reserve(std::max<size_t>(bytes, 8)));
-    if (rc == DSM_OK && bytes) HIPTRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
-  };
   auto alloc = [&](DevBuf& b, size_t bytes) { HIPTRY(b.reserve(std::max<size_t>(bytes, 8))); };
-  up(b_oimg, pb.o_img.data(), 4 * (size_t)n_obs);
-  up(b_opt, pb.o_pt.data(), 4 * (size_t)n_obs);
-  up(b_orun, pb.o_run.data(), 8 * (size_t)n_obs);
-  up(b_imgoff, pb.img_off.data(), 4 * ((size_t)N + 1));
-  up(b_trkoff, pb.trk_off.data(), 4 * ((size_t)P + 1));
-  up(b_trk, pb.trk.data(), 4 * (size_t)n_obs);
-  up(b_camimgoff, pb.cam_img_off.data(), 4 * ((size_t)C + 1));
-  up(b_camimgs, pb.cam_imgs.data(), 4 * pb.cam_imgs.size());
-  up(b_imgcam, img_cam.data(), 4 * (size_t)N);
-  up(b_campoff, pb.cam_poff.data(), 4 * ((size_t)C + 1));
-  up(b_camfoff, pb.cam_foff.data(), 4 * (size_t)C);
-  up(b_cammoff, pb.cam_moff.data(), 4 * (size_t)C);
-  up(b_oxy, pb.o_xy.data(), 16 * (size_t)n_obs);
-  up(b_cpose, pb.cpose.data(), N);
-  up(b_mask, pb.mask.data(), N);
-  up(b_ptvar, pb.pt_var.data(), P);
-  up(b_cammodel, cam_model.data(), 4 * (size_t)C);
-  up(b_camnp, pb.cam_np.data(), 4 * (size_t)C);
-  up(b_camk, pb.cam_k.data(), 4 * (size_t)C);
-  up(b_camfree, pb.cam_free.data(), 4 * pb.cam_free.size());
-  up(b_q, q.data(), 32 * (size_t)N);
-  up(b_t, image_tvec, 24 * (size_t)N);
-  up(b_X, X.data(), 24 * (size_t)P);
-  up(b_prm, camera_params, 8 * (size_t)n_prm);
+  HIPTRY(dev_upload(b_oimg, pb.o_img.data(), 4 * (size_t)n_obs, st));
+  HIPTRY(dev_upload(b_opt, pb.o_pt.data(), 4 * (size_t)n_obs, st));
+  HIPTRY(dev_upload(b_orun, pb.o_run.data(), 8 * (size_t)n_obs, st));
+  HIPTRY(dev_upload(b_imgoff, pb.img_off.data(), 4 * ((size_t)N + 1), st));
+  HIPTRY(dev_upload(b_trkoff, pb.trk_off.data(), 4 * ((size_t)P + 1), st));
+  HIPTRY(dev_upload(b_trk, pb.trk.data(), 4 * (size_t)n_obs, st));
+  HIPTRY(dev_upload(b_camimgoff, pb.cam_img_off.data(), 4 * ((size_t)C + 1), st));
+  HIPTRY(dev_upload(b_camimgs, pb.cam_imgs.data(), 4 * pb.cam_imgs.size(), st));
+  HIPTRY(dev_upload(b_imgcam, img_cam.data(), 4 * (size_t)N, st));
+  HIPTRY(dev_upload(b_campoff, pb.cam_poff.data(), 4 * ((size_t)C + 1), st));
+  HIPTRY(dev_upload(b_camfoff, pb.cam_foff.data(), 4 * (size_t)C, st));
+  HIPTRY(dev_upload(b_cammoff, pb.cam_moff.data(), 4 * (size_t)C, st));
+  HIPTRY(dev_upload(b_oxy, pb.o_xy.data(), 16 * (size_t)n_obs, st));
+  HIPTRY(dev_upload(b_cpose, pb.cpose.data(), N, st));
+  HIPTRY(dev_upload(b_mask, pb.mask.data(), N, st));
+  HIPTRY(dev_upload(b_ptvar, pb.pt_var.data(), P, st));
+  HIPTRY(dev_upload(b_cammodel, cam_model.data(), 4 * (size_t)C, st));
+  HIPTRY(dev_upload(b_camnp, pb.cam_np.data(), 4 * (size_t)C, st));
+  HIPTRY(dev_upload(b_camk, pb.cam_k.data(), 4 * (size_t)C, st));
+  HIPTRY(dev_upload(b_camfree, pb.cam_free.data(), 4 * pb.cam_free.size(), st));
+  HIPTRY(dev_upload(b_q, q.data(), 32 * (size_t)N, st));
+  HIPTRY(dev_upload(b_t, image_tvec, 24 * (size_t)N, st));
+  HIPTRY(dev_upload(b_X, X.data(), 24 * (size_t)P, st));
+  HIPTRY(dev_upload(b_prm, camera_params, 8 * (size_t)n_prm, st));
   alloc(b_cq, 32 * (size_t)N);
   alloc(b_ct, 24 * (size_t)N);
   alloc(b_cX, 24 * (size_t)P);
@@ -1218,11 +1214,11 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
   alloc(b_ctl, sizeof(BaCtl));
   const int max_iter = o.max_num_iterations;
   if (trace) alloc(b_trace, 8 * (size_t)DSM_BA_TRACE_COLUMNS * ((size_t)max_iter + 1));
-  for (auto& e : ev) HIPTRY(hipEventCreate(&e.e));
+  HIPTRY(ev.create());
   BaCtl init{};
   tr_init(&init, kTrInitialRadius);
   init.m_cg = INFINITY;
-  up(b_ctl, &init, sizeof(BaCtl));
+  HIPTRY(dev_upload(b_ctl, &init, sizeof(BaCtl), st));
 
   BaDev d{};
   d.n_obs = n_obs; d.n_pts = P; d.n_img = N; d.n_cam = C; d.nf = nf;
@@ -1277,8 +1273,8 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
     HIPTRY(hipMemcpyAsync(&h, d.ctl, sizeof(BaCtl), hipMemcpyDeviceToHost, st));
     HIPTRY(hipStreamSynchronize(st));
     if (rc == DSM_OK) {
-      float ms = 0.f;
-      HIPTRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+      double ms = 0;
+      HIPTRY(ev.ms(0, 1, &ms));
       ms_jac += ms;
       ms_total += ms;
       if (!std::isfinite(h.cost)) {  // the initial evaluation failed
@@ -1327,10 +1323,10 @@ extern "C" int dsm_bundle_adjust(dsm_ctx* ctx, uint32_t num_cameras, const int32
     HIPTRY(hipMemcpyAsync(&h, d.ctl, sizeof(BaCtl), hipMemcpyDeviceToHost, st));
     HIPTRY(hipStreamSynchronize(st));
     if (rc != DSM_OK) break;
-    float a = 0.f, b2 = 0.f, c2 = 0.f;
-    HIPTRY(hipEventElapsedTime(&a, ev[2], ev[3]));
-    HIPTRY(hipEventElapsedTime(&b2, ev[3], ev[4]));
-    HIPTRY(hipEventElapsedTime(&c2, ev[4], ev[5]));
+    double a = 0, b2 = 0, c2 = 0;
+    HIPTRY(ev.ms(2, 3, &a));
+    HIPTRY(ev.ms(3, 4, &b2));
+    HIPTRY(ev.ms(4, 5, &c2));
     ms_cg += a;
     ms_cand += b2;
     ms_jac += c2;

@@ -34,6 +34,33 @@ namespace {
 thread_local std::string g_create_error;
 }  // namespace
 
+// ---------------------------------------------------------------------------------- the failure paths of ctx.h
+std::string dsm_hip_message(hipError_t e, const char* file, int line) {
+  return std::string(file) + ":" + std::to_string(line) + ": " + hipGetErrorString(e);
+}
+int dsm_hip_fail(dsm_ctx* ctx, hipError_t e, const char* file, int line) {
+  ctx->err = dsm_hip_message(e, file, line);
+  return DSM_ERR_HIP;
+}
+int dsm_fail(dsm_ctx* ctx, int code, const char* entry, const char* msg) {
+  ctx->err = std::string(entry) + ": " + msg;
+  return code;
+}
+int dsm_invalid(dsm_ctx* ctx, const char* entry, const char* msg) { return dsm_fail(ctx, DSM_ERR_INVALID_ARGUMENT, entry, msg); }
+int dsm_invalid(dsm_ctx* ctx, const char* entry, const std::string& msg) { return dsm_invalid(ctx, entry, msg.c_str()); }
+// DevEvents of ctx.h
+hipError_t dev_events_create(DevEvent* ev, size_t n) {
+  hipError_t e = hipSuccess;
+  for (size_t i = 0; i < n && e == hipSuccess; ++i) e = hipEventCreate(&ev[i].e);
+  return e;
+}
+hipError_t dev_events_ms(const DevEvent& a, const DevEvent& b, double* ms) {
+  float t = 0.0f;
+  const hipError_t e = hipEventElapsedTime(&t, a, b);
+  if (e == hipSuccess) *ms = t;
+  return e;
+}
+
 // ---------------------------------------------------------------------------------- hand-over of host buffers
 // The reference's FeatureDescriptors / FeatureKeypoints are Eigen matrices and std::vectors in PAGEABLE memory
 // (/root/reference/src/feature/types.h:102-104), one allocation per image.  hipMemcpy from pageable memory goes through the
@@ -950,14 +977,15 @@ struct VerifyPlan {
   bool hyp_compact = true;  // the lane-per-hypothesis solvers of E / F take later rounds' hypotheses 64 per wave across the pairs (hyp_of_lane)
 };
 
-#define LANECHK(L, call)                                              \
-  do {                                                                \
-    hipError_t e_ = (call);                                           \
-    if (e_ != hipSuccess) {                                           \
-      (L).err = std::string(#call) + ": " + hipGetErrorString(e_);    \
-      (L).rc = DSM_ERR_HIP;                                           \
-      return;                                                         \
-    }                                                                 \
+// HIPCHK for a lane's thread: the same text into the lane's err
+static void lane_hip_fail(VerifyLane& L, hipError_t e, int line) {
+  L.err = dsm_hip_message(e, __FILE_NAME__, line);
+  L.rc = DSM_ERR_HIP;
+}
+#define LANECHK(L, call)                                            \
+  do {                                                              \
+    const hipError_t e_ = (call);                                   \
+    if (e_ != hipSuccess) return lane_hip_fail((L), e_, __LINE__);  \
   } while (0)
 
 // One lane (host thread + stream) of the phase-split pipeline: its range of the pair list, chunk by chunk.

@@ -33,6 +33,7 @@
 
 #include "block_reduce.h"
 #include "ctx.h"
+#include "std_mt19937.h"
 #include "verify_linalg.h"
 
 namespace {
@@ -42,46 +43,6 @@ constexpr int AL_CHUNK = 256;   // correspondences staged in LDS per step of the
 constexpr int kAlMaxIterationsCap = 5000;
 constexpr double kAlClearMargin = 1e-9;  // a relative cost gap no rounding of a model flips  // PROSAC's index n stays <= N - 1 up to here
 constexpr uint32_t kAlFlagUnregistered = 1, kAlFlagPointRange = 2, kAlFlagDuplicateObs = 4, kAlFlagDuplicatePoint = 8;
-
-// std::mt19937 (32-bit) and libstdc++'s uniform_int_distribution<int>(0, b) on it (Lemire), lane 0 of a workgroup
-struct AlMt {
-  uint32_t mt[624];
-  int mti;
-};
-__device__ void al_mt_seed(AlMt* s, uint32_t seed) {
-  s->mt[0] = seed;
-  for (int i = 1; i < 624; ++i) s->mt[i] = 1812433253u * (s->mt[i - 1] ^ (s->mt[i - 1] >> 30)) + (uint32_t)i;
-  s->mti = 624;
-}
-__device__ uint32_t al_mt_next(AlMt* s) {
-  if (s->mti >= 624) {
-    uint32_t* mt = s->mt;
-    for (int kk = 0; kk < 624; ++kk) {
-      const uint32_t y = (mt[kk] & 0x80000000u) | (mt[(kk + 1) % 624] & 0x7fffffffu);
-      mt[kk] = mt[(kk + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-    }
-    s->mti = 0;
-  }
-  uint32_t y = s->mt[s->mti++];
-  y ^= (y >> 11);
-  y ^= (y << 7) & 0x9d2c5680u;
-  y ^= (y << 15) & 0xefc60000u;
-  y ^= (y >> 18);
-  return y;
-}
-__device__ int al_rand_int(AlMt* s, int hi) {  // uniform on [0, hi], hi >= 0
-  const uint32_t range = (uint32_t)hi + 1u;
-  uint64_t product = (uint64_t)al_mt_next(s) * range;
-  uint32_t low = (uint32_t)product;
-  if (low < range) {
-    const uint32_t threshold = (0u - range) % range;
-    while (low < threshold) {
-      product = (uint64_t)al_mt_next(s) * range;
-      low = (uint32_t)product;
-    }
-  }
-  return (int)(product >> 32);
-}
 
 // Eigen 3.3's 3 x 3 determinant (bruteforce_det3_helper order)
 __device__ __host__ inline double al_det3(const double* m) {  // row-major
@@ -275,7 +236,7 @@ struct AlProsacOut {
 };
 
 struct AlSmem {
-  AlMt gen;
+  StdMt19937 gen;  // std::mt19937 and uniform_int_distribution<int>(0, hi) on it, lane 0 of the workgroup
   int samp[AL_BLOCK][4];
   double pts[AL_CHUNK][6];
   double cost[AL_BLOCK];
@@ -299,7 +260,7 @@ __global__ void __launch_bounds__(AL_BLOCK) k_al_prosac(const AlProblem* __restr
   const AlProblem pb = probs[blockIdx.x];
   const int lane = threadIdx.x;
   const uint32_t N = pb.N;
-  if (lane == 0) al_mt_seed(&sm.gen, pb.seed);
+  if (lane == 0) std_mt19937_seed(&sm.gen, pb.seed);
   int max_it = max_iterations, k = 0, iterations = 0;
   double best = DBL_MAX, rmin = INFINITY, cmin = INFINITY, pending = INFINITY;
   int best_cnt = 0;
@@ -318,7 +279,7 @@ __global__ void __launch_bounds__(AL_BLOCK) k_al_prosac(const AlProblem* __restr
             int r;
             bool dup;
             do {
-              r = al_rand_int(&sm.gen, n - 1);
+              r = (int)std_uniform_u32(&sm.gen, 0u, (uint32_t)(n - 1));
               dup = false;
               for (int q = 0; q < i; ++q) dup |= (s[q] == r);
             } while (dup);
@@ -329,7 +290,7 @@ __global__ void __launch_bounds__(AL_BLOCK) k_al_prosac(const AlProblem* __restr
             int r;
             bool dup;
             do {
-              r = al_rand_int(&sm.gen, n - 2);
+              r = (int)std_uniform_u32(&sm.gen, 0u, (uint32_t)(n - 2));
               dup = false;
               for (int q = 0; q < i; ++q) dup |= (s[q] == r);
             } while (dup);
@@ -609,10 +570,7 @@ extern "C" int dsm_align_clusters(dsm_ctx* ctx, uint32_t K, const uint32_t* imag
                                   int32_t* anchor_out, uint8_t* in_component, int32_t* mst_parent, double* sim3_to_anchor,
                                   uint32_t* separators, uint32_t* n_separators_out, dsm_align_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](int rc, const std::string& msg) {
-    ctx->err = "dsm_align_clusters: " + msg;
-    return rc;
-  };
+  auto fail = [ctx](int code, const char* msg) { return dsm_fail(ctx, code, "dsm_align_clusters", msg); };
   if (K == 0 || K > 65536) return fail(DSM_ERR_INVALID_ARGUMENT, "num_clusters must be in [1, 65536]");
   if (!image_offsets || !point_offsets || !obs_offsets || !n_pairs_out || !anchor_out || !in_component || !mst_parent ||
       !sim3_to_anchor || !n_separators_out || (pairs_capacity && !pairs_out))
@@ -669,8 +627,8 @@ extern "C" int dsm_align_clusters(dsm_ctx* ctx, uint32_t K, const uint32_t* imag
   if (he != hipSuccess) return fail(DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   AlBufs d;
-  DevEvent ev[4];
-  for (int i = 0; i < 4; ++i) HIPCHK(ctx, hipEventCreate(&ev[i].e));
+  DevEvents<4> ev;
+  HIPCHK(ctx, ev.create());
   HIPCHK(ctx, hipEventRecord(ev[0], st));
 
   // ------------------------------------------------------------ the join (device)
@@ -895,12 +853,10 @@ extern "C" int dsm_align_clusters(dsm_ctx* ctx, uint32_t K, const uint32_t* imag
   }
   HIPCHK(ctx, hipEventRecord(ev[3], st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  float ms[3] = {0.f, 0.f, 0.f};
-  HIPCHK(ctx, hipEventElapsedTime(&ms[0], ev[0], ev[1]));
-  HIPCHK(ctx, hipEventElapsedTime(&ms[1], ev[1], ev[2]));
-  HIPCHK(ctx, hipEventElapsedTime(&ms[2], ev[2], ev[3]));
-  rep.join_ms = ms[0], rep.prosac_ms = ms[1], rep.refit_ms = ms[2];
-  rep.device_ms = (double)ms[0] + ms[1] + ms[2];
+  HIPCHK(ctx, ev.ms(0, 1, &rep.join_ms));
+  HIPCHK(ctx, ev.ms(1, 2, &rep.prosac_ms));
+  HIPCHK(ctx, ev.ms(2, 3, &rep.refit_ms));
+  rep.device_ms = rep.join_ms + rep.prosac_ms + rep.refit_ms;
 
   // ------------------------------------------------------------ pair records
   std::vector<dsm_align_pair> out(NP);

@@ -531,17 +531,6 @@ __global__ void __launch_bounds__(128) k_cov_pool(const float* __restrict__ raw,
 }
 
 // ---- host half
-__attribute__((noinline)) int cov_hip_fail(dsm_ctx* ctx, hipError_t e) {
-  ctx->err = std::string("dsm_extract_covariant_sift: ") + hipGetErrorString(e);
-  return DSM_ERR_HIP;
-}
-#define COV_CHK(call)                                     \
-  do {                                                    \
-    const hipError_t e_ = (call);                         \
-    if (e_ != hipSuccess) return cov_hip_fail(ctx, e_);   \
-  } while (0)
-
-inline uint32_t cov_grid(uint64_t n, int block = SIFT_BLOCK) { return (uint32_t)((n + block - 1) / block); }
 inline long cov_floor(double x) {  // vl_floor_d
   const long xi = (long)x;
   if (x >= 0 || (double)xi == x) return xi;
@@ -921,11 +910,11 @@ int cov_upload_consts(dsm_ctx* ctx, CovSiftState& d, hipStream_t st) {
   memcpy(blob.data() + d.at_hat41, hat41.data(), sizeof(double) * COV_OR_SIDE);
   memcpy(blob.data() + d.at_mask, mask.data(), sizeof(float) * COV_OR_N);
   memcpy(blob.data() + d.at_counts, d.cell_counts, sizeof(d.cell_counts));
-  COV_CHK(d.buf[CovSiftState::consts].reserve(blob.size()));
-  COV_CHK(d.buf[CovSiftState::table].reserve(table.size() * sizeof(CovSample)));
-  COV_CHK(hipMemcpyAsync(d.buf[CovSiftState::consts].p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-  COV_CHK(hipMemcpyAsync(d.buf[CovSiftState::table].p, table.data(), table.size() * sizeof(CovSample), hipMemcpyHostToDevice, st));
-  COV_CHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, d.buf[CovSiftState::consts].reserve(blob.size()));
+  HIPCHK(ctx, d.buf[CovSiftState::table].reserve(table.size() * sizeof(CovSample)));
+  HIPCHK(ctx, hipMemcpyAsync(d.buf[CovSiftState::consts].p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(d.buf[CovSiftState::table].p, table.data(), table.size() * sizeof(CovSample), hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   d.consts_ready = true;
   return DSM_OK;
 }
@@ -1004,7 +993,7 @@ static int cov_extract(dsm_ctx* ctx, const dsm_covariant_sift_options* options, 
     if (rc != DSM_OK) return rc;
   }
   for (DevEvent& e : d.ev)
-    if (!e.e) COV_CHK(hipEventCreate(&e.e));
+    if (!e.e) HIPCHK(ctx, hipEventCreate(&e.e));
   for (double& v : d.stage_ms) v = 0.0;
   auto mark = [&](int i) { return hipEventRecord(d.ev[i], st); };
   auto took = [&](int stage, int a) {  // events a, a + 1 have completed
@@ -1013,15 +1002,15 @@ static int cov_extract(dsm_ctx* ctx, const dsm_covariant_sift_options* options, 
     d.stage_ms[stage] += ms;
     return e;
   };
-  COV_CHK(d.buf[B::img].reserve((size_t)row_stride * height));
-  COV_CHK(d.buf[B::fimg].reserve((size_t)width * height * 4));
-  COV_CHK(d.buf[B::gss].reserve(total * 4));
-  COV_CHK(d.buf[B::tmp].reserve(nel0 * 4));
-  COV_CHK(d.buf[B::dog].reserve(nel0 * 4 * (g.R + 2)));
-  COV_CHK(d.buf[B::flags].reserve(nel0 * g.R));
-  COV_CHK(d.buf[B::counts].reserve(chunks0 * 4));
-  COV_CHK(d.buf[B::offs].reserve(chunks0 * 4));
-  COV_CHK(hipMemcpyAsync(d.buf[B::img].p, gray_u8, (size_t)row_stride * height, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, d.buf[B::img].reserve((size_t)row_stride * height));
+  HIPCHK(ctx, d.buf[B::fimg].reserve((size_t)width * height * 4));
+  HIPCHK(ctx, d.buf[B::gss].reserve(total * 4));
+  HIPCHK(ctx, d.buf[B::tmp].reserve(nel0 * 4));
+  HIPCHK(ctx, d.buf[B::dog].reserve(nel0 * 4 * (g.R + 2)));
+  HIPCHK(ctx, d.buf[B::flags].reserve(nel0 * g.R));
+  HIPCHK(ctx, d.buf[B::counts].reserve(chunks0 * 4));
+  HIPCHK(ctx, d.buf[B::offs].reserve(chunks0 * 4));
+  HIPCHK(ctx, hipMemcpyAsync(d.buf[B::img].p, gray_u8, (size_t)row_stride * height, hipMemcpyHostToDevice, st));
   float* gss = d.buf[B::gss].as<float>();
   float* tmp = d.buf[B::tmp].as<float>();
   float* fimg = d.buf[B::fimg].as<float>();
@@ -1062,17 +1051,17 @@ static int cov_extract(dsm_ctx* ctx, const dsm_covariant_sift_options* options, 
     if (pass == 1) {
       for (int w : tap_w)
         if (w > 256) return fail(DSM_ERR_OUT_OF_RANGE, "a smoothing half-width above 256 samples");
-      COV_CHK(d.buf[B::taps].reserve(all_taps.size() * 4));
-      COV_CHK(hipMemcpyAsync(d.buf[B::taps].p, all_taps.data(), all_taps.size() * 4, hipMemcpyHostToDevice, st));
-      COV_CHK(mark(0));
-      hipLaunchKernelGGL(k_sift_load, dim3(cov_grid((uint64_t)width * height)), dim3(SIFT_BLOCK), 0, st, fimg, d.buf[B::img].as<uint8_t>(), width, height,
+      HIPCHK(ctx, d.buf[B::taps].reserve(all_taps.size() * 4));
+      HIPCHK(ctx, hipMemcpyAsync(d.buf[B::taps].p, all_taps.data(), all_taps.size() * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(ctx, mark(0));
+      hipLaunchKernelGGL(k_sift_load, dim3(dsm_grid((uint64_t)width * height, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, fimg, d.buf[B::img].as<uint8_t>(), width, height,
                          row_stride);
       // _vl_scalespace_start_octave_from_image, :699-745: down to octave max(0, first), then up from octave 0
       const int top = std::max(0, g.first);
-      hipLaunchKernelGGL(k_sift_downsample, dim3(cov_grid((uint64_t)g.ow(top) * g.oh(top))), dim3(SIFT_BLOCK), 0, st, gss + g.level(top, g.smin),
+      hipLaunchKernelGGL(k_sift_downsample, dim3(dsm_grid((uint64_t)g.ow(top) * g.oh(top), SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, gss + g.level(top, g.smin),
                          (const float*)fimg, width, 1u << top, (uint32_t)g.ow(top), (uint32_t)g.oh(top));
       for (int op = -1; op >= g.first; --op)
-        hipLaunchKernelGGL(k_cov_upsample, dim3(cov_grid((uint64_t)g.ow(op + 1) * g.oh(op + 1))), dim3(SIFT_BLOCK), 0, st, gss + g.level(op, g.smin),
+        hipLaunchKernelGGL(k_cov_upsample, dim3(dsm_grid((uint64_t)g.ow(op + 1) * g.oh(op + 1), SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, gss + g.level(op, g.smin),
                            (const float*)(gss + g.level(op + 1, g.smin)), (uint32_t)g.ow(op + 1), (uint32_t)g.oh(op + 1));
     }
     {
@@ -1086,7 +1075,7 @@ static int cov_extract(dsm_ctx* ctx, const dsm_covariant_sift_options* options, 
     for (int oc = g.first + 1; oc <= g.last; ++oc) {  // _vl_scalespace_start_octave_from_previous_octave, :755-801
       const int prevLevelIndex = std::min(g.smin + g.R, g.smax);
       if (pass == 1)
-        hipLaunchKernelGGL(k_sift_downsample, dim3(cov_grid((uint64_t)g.ow(oc) * g.oh(oc))), dim3(SIFT_BLOCK), 0, st, gss + g.level(oc, g.smin),
+        hipLaunchKernelGGL(k_sift_downsample, dim3(dsm_grid((uint64_t)g.ow(oc) * g.oh(oc), SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, gss + g.level(oc, g.smin),
                            (const float*)(gss + g.level(oc - 1, prevLevelIndex)), (uint32_t)g.ow(oc - 1), 2u, (uint32_t)g.ow(oc), (uint32_t)g.oh(oc));
       const double sigma = sigma_of(oc, g.smin), prevSigma = sigma_of(oc - 1, prevLevelIndex);
       if (sigma > prevSigma) {
@@ -1096,8 +1085,8 @@ static int cov_extract(dsm_ctx* ctx, const dsm_covariant_sift_options* options, 
       fill_octave(oc);
     }
   }
-  COV_CHK(mark(1));
-  COV_CHK(hipGetLastError());
+  HIPCHK(ctx, mark(1));
+  HIPCHK(ctx, hipGetLastError());
 
   // ---- vl_covdet_detect (covdet.c:1991-2089): the octaves from the last to the first, COLMAP's early end at :2086
   std::vector<CovFeature> features;
@@ -1109,20 +1098,20 @@ static int cov_extract(dsm_ctx* ctx, const dsm_covariant_sift_options* options, 
     const double step = std::pow(2.0, (double)oc);
     const uint32_t ndog = nel * (uint32_t)depth, nflag = nel * (uint32_t)g.R, chunks = (nflag + SIFT_CHUNK - 1) / SIFT_CHUNK;
     float* dog = d.buf[B::dog].as<float>();
-    COV_CHK(mark(2));
-    hipLaunchKernelGGL(k_cov_dog, dim3(cov_grid(ndog)), dim3(SIFT_BLOCK), 0, st, dog, (const float*)(gss + g.level(oc, g.smin)), nel, ndog);
-    hipLaunchKernelGGL(k_sift_detect, dim3(cov_grid(nflag)), dim3(SIFT_BLOCK), 0, st, d.buf[B::flags].as<uint8_t>(), (const float*)dog, (int)w, (int)h, nflag,
+    HIPCHK(ctx, mark(2));
+    hipLaunchKernelGGL(k_cov_dog, dim3(dsm_grid(ndog, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, dog, (const float*)(gss + g.level(oc, g.smin)), nel, ndog);
+    hipLaunchKernelGGL(k_sift_detect, dim3(dsm_grid(nflag, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, d.buf[B::flags].as<uint8_t>(), (const float*)dog, (int)w, (int)h, nflag,
                        0.8 * o.peak_threshold);
     auto compact = [&](const uint32_t* offs, uint32_t* out) {
-      hipLaunchKernelGGL(k_sift_compact, dim3(cov_grid(chunks)), dim3(SIFT_BLOCK), 0, st, (const uint8_t*)d.buf[B::flags].as<uint8_t>(), nflag, chunks, offs, out);
+      hipLaunchKernelGGL(k_sift_compact, dim3(dsm_grid(chunks, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, (const uint8_t*)d.buf[B::flags].as<uint8_t>(), nflag, chunks, offs, out);
     };
     compact(nullptr, d.buf[B::counts].as<uint32_t>());
-    COV_CHK(mark(3));
-    COV_CHK(hipGetLastError());
+    HIPCHK(ctx, mark(3));
+    HIPCHK(ctx, hipGetLastError());
     counts.resize(chunks);
-    COV_CHK(hipMemcpyAsync(counts.data(), d.buf[B::counts].p, (size_t)chunks * 4, hipMemcpyDeviceToHost, st));
-    COV_CHK(hipStreamSynchronize(st));
-    COV_CHK(took(1, 2));
+    HIPCHK(ctx, hipMemcpyAsync(counts.data(), d.buf[B::counts].p, (size_t)chunks * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, took(1, 2));
     uint32_t ncand = 0;
     for (uint32_t c = 0; c < chunks; ++c) {  // exclusive scan in place
       const uint32_t k = counts[c];
@@ -1132,19 +1121,19 @@ static int cov_extract(dsm_ctx* ctx, const dsm_covariant_sift_options* options, 
     if (ncand) {
       if (ctx->memory_budget && scratch + (uint64_t)ncand * (4 + sizeof(CovCand)) > ctx->memory_budget)
         return fail(DSM_ERR_OUT_OF_RANGE, "the candidates' scratch exceeds the memory budget");
-      COV_CHK(mark(2));
-      COV_CHK(hipMemcpyAsync(d.buf[B::offs].p, counts.data(), (size_t)chunks * 4, hipMemcpyHostToDevice, st));
-      COV_CHK(d.buf[B::cand].reserve((size_t)ncand * 4));
-      COV_CHK(d.buf[B::refined].reserve((size_t)ncand * sizeof(CovCand)));
+      HIPCHK(ctx, mark(2));
+      HIPCHK(ctx, hipMemcpyAsync(d.buf[B::offs].p, counts.data(), (size_t)chunks * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(ctx, d.buf[B::cand].reserve((size_t)ncand * 4));
+      HIPCHK(ctx, d.buf[B::refined].reserve((size_t)ncand * sizeof(CovCand)));
       compact(d.buf[B::offs].as<uint32_t>(), d.buf[B::cand].as<uint32_t>());
-      hipLaunchKernelGGL(k_cov_refine, dim3(cov_grid(ncand)), dim3(SIFT_BLOCK), 0, st, d.buf[B::refined].as<CovCand>(), (const uint32_t*)d.buf[B::cand].as<uint32_t>(),
+      hipLaunchKernelGGL(k_cov_refine, dim3(dsm_grid(ncand, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, d.buf[B::refined].as<CovCand>(), (const uint32_t*)d.buf[B::cand].as<uint32_t>(),
                          ncand, (const float*)dog, (int)w, (int)h, depth);
-      COV_CHK(mark(3));
-      COV_CHK(hipGetLastError());
+      HIPCHK(ctx, mark(3));
+      HIPCHK(ctx, hipGetLastError());
       refined.resize(ncand);
-      COV_CHK(hipMemcpyAsync(refined.data(), d.buf[B::refined].p, (size_t)ncand * sizeof(CovCand), hipMemcpyDeviceToHost, st));
-      COV_CHK(hipStreamSynchronize(st));
-      COV_CHK(took(1, 2));
+      HIPCHK(ctx, hipMemcpyAsync(refined.data(), d.buf[B::refined].p, (size_t)ncand * sizeof(CovCand), hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      HIPCHK(ctx, took(1, 2));
       for (const CovCand& c : refined) {  // covdet.c:2024-2041
         bool ok = c.ok != 0;
         ok &= std::fabs(c.peak) > o.peak_threshold;
@@ -1271,8 +1260,8 @@ static int cov_extract(dsm_ctx* ctx, const dsm_covariant_sift_options* options, 
     }
     std::vector<CovPatch> jobs;
     std::vector<double> sums;
-    COV_CHK(d.buf[B::ojobs].reserve(active.size() * sizeof(CovPatch)));
-    COV_CHK(d.buf[B::oout].reserve(active.size() * 24));
+    HIPCHK(ctx, d.buf[B::ojobs].reserve(active.size() * sizeof(CovPatch)));
+    HIPCHK(ctx, d.buf[B::oout].reserve(active.size() * 24));
     while (!active.empty()) {
       if (aff_rounds >= DSM_AFFINE_SHAPE_MAX_ROUNDS) return fail(DSM_ERR_OUT_OF_RANGE, "the shape adaptation ran past its 14 rounds");
       const size_t na = active.size();
@@ -1283,15 +1272,15 @@ static int cov_extract(dsm_ctx* ctx, const dsm_covariant_sift_options* options, 
         const Shape& h = shapes[active[j]];
         cov_plan_patch(g, &jobs[j], nullptr, nullptr, COV_OR_EXTENT, 1.0 /* VL_COVDET_AA_RELATIVE_DERIVATIVE_SIGMA */, h.A, h.T, h.D0, h.D3);
       }
-      COV_CHK(hipMemcpyAsync(d.buf[B::ojobs].p, jobs.data(), na * sizeof(CovPatch), hipMemcpyHostToDevice, st));
-      COV_CHK(mark(4));
+      HIPCHK(ctx, hipMemcpyAsync(d.buf[B::ojobs].p, jobs.data(), na * sizeof(CovPatch), hipMemcpyHostToDevice, st));
+      HIPCHK(ctx, mark(4));
       hipLaunchKernelGGL(k_cov_affine_moments, dim3((uint32_t)na), dim3(COV_WAVE), 0, st, (const CovPatch*)d.buf[B::ojobs].as<CovPatch>(), (const float*)gss, hat41,
                          mask, d.buf[B::oout].as<double>());
-      COV_CHK(mark(5));
-      COV_CHK(hipGetLastError());
-      COV_CHK(hipMemcpyAsync(sums.data(), d.buf[B::oout].p, na * 24, hipMemcpyDeviceToHost, st));
-      COV_CHK(hipStreamSynchronize(st));
-      COV_CHK(took(2, 4));
+      HIPCHK(ctx, mark(5));
+      HIPCHK(ctx, hipGetLastError());
+      HIPCHK(ctx, hipMemcpyAsync(sums.data(), d.buf[B::oout].p, na * 24, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      HIPCHK(ctx, took(2, 4));
       next.clear();
       for (size_t j = 0; j < na; ++j) {  // covdet.c:2559-2598
         const uint32_t i = active[j];
@@ -1375,18 +1364,18 @@ static int cov_extract(dsm_ctx* ctx, const dsm_covariant_sift_options* options, 
       memset(jobs[i].ty, 0, sizeof(jobs[i].ty));
       memcpy(jobs[i].ty, taps.data(), taps.size() * 4);
     }
-    COV_CHK(d.buf[B::ojobs].reserve(nf * sizeof(CovOrientJob)));
-    COV_CHK(d.buf[B::oout].reserve(nf * sizeof(CovOrientOut)));
-    COV_CHK(hipMemcpyAsync(d.buf[B::ojobs].p, jobs.data(), nf * sizeof(CovOrientJob), hipMemcpyHostToDevice, st));
-    COV_CHK(mark(4));
+    HIPCHK(ctx, d.buf[B::ojobs].reserve(nf * sizeof(CovOrientJob)));
+    HIPCHK(ctx, d.buf[B::oout].reserve(nf * sizeof(CovOrientOut)));
+    HIPCHK(ctx, hipMemcpyAsync(d.buf[B::ojobs].p, jobs.data(), nf * sizeof(CovOrientJob), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, mark(4));
     hipLaunchKernelGGL(k_cov_orient, dim3((uint32_t)nf), dim3(COV_WAVE), 0, st, (const CovOrientJob*)d.buf[B::ojobs].as<CovOrientJob>(), (const float*)gss, hat41, mask,
                        d.buf[B::oout].as<CovOrientOut>());
-    COV_CHK(mark(5));
-    COV_CHK(hipGetLastError());
+    HIPCHK(ctx, mark(5));
+    HIPCHK(ctx, hipGetLastError());
     std::vector<CovOrientOut> outs(nf);
-    COV_CHK(hipMemcpyAsync(outs.data(), d.buf[B::oout].p, nf * sizeof(CovOrientOut), hipMemcpyDeviceToHost, st));
-    COV_CHK(hipStreamSynchronize(st));
-    COV_CHK(took(2, 4));
+    HIPCHK(ctx, hipMemcpyAsync(outs.data(), d.buf[B::oout].p, nf * sizeof(CovOrientOut), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, took(2, 4));
     const double binExtent = 2 * kVlPi / COV_OR_BINS;
     for (size_t i = 0; i < nf; ++i) {
       const CovFeature feature = features[i];
@@ -1465,27 +1454,27 @@ static int cov_extract(dsm_ctx* ctx, const dsm_covariant_sift_options* options, 
         cov_svd2(D, U, V, A);
         cov_plan_patch(g, &items[i * dsp_num_scales + s], nullptr, nullptr, COV_D_EXTENT, 1.0 /* kPatchRelativeSmoothing */, A, T, D[0], D[3]);
       }
-    COV_CHK(d.buf[B::items].reserve(nitems * sizeof(CovPatch)));
-    COV_CHK(d.buf[B::raw].reserve(nitems * 512));
-    COV_CHK(d.buf[B::desc8].reserve(kept * 128));
-    COV_CHK(hipMemcpyAsync(d.buf[B::items].p, items.data(), nitems * sizeof(CovPatch), hipMemcpyHostToDevice, st));
-    COV_CHK(mark(4));
+    HIPCHK(ctx, d.buf[B::items].reserve(nitems * sizeof(CovPatch)));
+    HIPCHK(ctx, d.buf[B::raw].reserve(nitems * 512));
+    HIPCHK(ctx, d.buf[B::desc8].reserve(kept * 128));
+    HIPCHK(ctx, hipMemcpyAsync(d.buf[B::items].p, items.data(), nitems * sizeof(CovPatch), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, mark(4));
     hipLaunchKernelGGL(k_cov_describe, dim3((uint32_t)nitems), dim3(COV_WAVE), 0, st, (const CovPatch*)d.buf[B::items].as<CovPatch>(), (const float*)gss, hat31,
                        (const CovSample*)d.buf[B::table].as<CovSample>(), cell_counts, d.buf[B::raw].as<float>());
-    COV_CHK(mark(5));
+    HIPCHK(ctx, mark(5));
     hipLaunchKernelGGL(k_cov_pool, dim3((uint32_t)kept), dim3(128), 0, st, (const float*)d.buf[B::raw].as<float>(), dsp_num_scales, (int)(o.domain_size_pooling != 0),
                        (int)(o.normalization == DSM_SIFT_L2), d.buf[B::desc8].as<uint8_t>());
-    COV_CHK(mark(6));
-    COV_CHK(hipGetLastError());
+    HIPCHK(ctx, mark(6));
+    HIPCHK(ctx, hipGetLastError());
     desc_host.resize(kept * 128);
-    COV_CHK(hipMemcpyAsync(desc_host.data(), d.buf[B::desc8].p, kept * 128, hipMemcpyDeviceToHost, st));
-    COV_CHK(hipStreamSynchronize(st));
-    COV_CHK(took(3, 4));
-    COV_CHK(took(4, 5));
+    HIPCHK(ctx, hipMemcpyAsync(desc_host.data(), d.buf[B::desc8].p, kept * 128, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, took(3, 4));
+    HIPCHK(ctx, took(4, 5));
     d.have_raw = true;
   }
-  COV_CHK(hipStreamSynchronize(st));
-  COV_CHK(took(0, 0));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, took(0, 0));
 
   d.n = (uint32_t)kept;
   d.scales = (uint32_t)dsp_num_scales;
@@ -1556,7 +1545,7 @@ extern "C" int dsm_get_covariant_sift_raw(dsm_ctx* ctx, uint32_t capacity, int32
   if (raw_descriptors && d.n) {
     hipError_t he = hipSetDevice(ctx->device);
     if (he == hipSuccess) he = hipMemcpy(raw_descriptors, d.buf[CovSiftState::raw].p, (size_t)d.n * d.scales * 512, hipMemcpyDeviceToHost);
-    if (he != hipSuccess) return cov_hip_fail(ctx, he);
+    HIPCHK(ctx, he);
   }
   return DSM_OK;
 }

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -76,6 +77,21 @@ struct DevBuf {
   T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// host memory into a DevBuf of at least 16 bytes; nothing is copied for bytes == 0 or a null source
+inline hipError_t dev_upload(DevBuf& b, const void* src, size_t bytes, hipStream_t st) {
+  hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
+  if (e == hipSuccess && bytes && src) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
+  return e;
+}
+// a DevBuf of at least 16 bytes, all of them set to `byte`
+inline hipError_t dev_fill(DevBuf& b, int byte, size_t bytes, hipStream_t st) {
+  hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
+  if (e == hipSuccess) e = hipMemsetAsync(b.p, byte, std::max<size_t>(bytes, 16), st);
+  return e;
+}
+// blocks of `block` threads that cover n items
+inline uint32_t dsm_grid(uint64_t n, int block) { return (uint32_t)((n + block - 1) / block); }
+
 // a hipEvent_t, destroyed when its owner goes out of scope (movable, not copyable); created by hipEventCreate(&ev.e)
 struct DevEvent {
   hipEvent_t e = nullptr;
@@ -87,6 +103,25 @@ struct DevEvent {
     if (e) (void)hipEventDestroy(e);
   }
   operator hipEvent_t() const { return e; }
+};
+
+// the events around a driver's stages: ev[i] is event i; ms(i, j, &out) is the time from event i to event j as a double
+hipError_t dev_events_create(DevEvent* ev, size_t n);                        // capi.hip
+hipError_t dev_events_ms(const DevEvent& a, const DevEvent& b, double* ms);  // capi.hip
+template <int N>
+struct DevEvents {
+  DevEvent ev[N];
+  hipError_t create() { return dev_events_create(ev, N); }
+  hipError_t ms(int i, int j, double* out) const { return dev_events_ms(ev[i], ev[j], out); }
+  DevEvent& operator[](int i) { return ev[i]; }
+};
+// the same with a size known at run time (one event per round)
+struct DevEventList {
+  std::vector<DevEvent> ev;
+  explicit DevEventList(size_t n) : ev(n) {}
+  hipError_t create() { return dev_events_create(ev.data(), ev.size()); }
+  hipError_t ms(size_t i, size_t j, double* out) const { return dev_events_ms(ev[i], ev[j], out); }
+  DevEvent& operator[](size_t i) { return ev[i]; }
 };
 
 // a hipStream_t, destroyed when its owner goes out of scope; created by hipStreamCreateWithFlags(&st.s, ...)
@@ -321,24 +356,28 @@ static const char* const dsm_check_debug_keys[] = {"DSM_K1_DOT4", "DSM_K1_RESOLV
                                                    "DSM_SOURCE_SELECTION_SERIAL", "DSM_INITIAL_PAIR_SERIAL", "DSM_NEXT_IMAGES_SERIAL", "DSM_TRACK_UPDATE_SERIAL"};
 #endif
 
-#define HIPCHK(ctx, call)                                                              \
-  do {                                                                                 \
-    hipError_t e_ = (call);                                                            \
-    if (e_ != hipSuccess) {                                                            \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                  \
-      return DSM_ERR_HIP;                                                              \
-    }                                                                                  \
+// ---- the failure paths, out of line (capi.hip): a site costs a compare and a call, no string is built inline
+// "<file>:<line>: <hipGetErrorString>", the message of every failed HIP runtime call
+std::string dsm_hip_message(hipError_t e, const char* file, int line);
+// ctx->err = dsm_hip_message(...); returns DSM_ERR_HIP
+int dsm_hip_fail(dsm_ctx* ctx, hipError_t e, const char* file, int line);
+// ctx->err = "<entry>: <msg>"; returns code / DSM_ERR_INVALID_ARGUMENT
+int dsm_fail(dsm_ctx* ctx, int code, const char* entry, const char* msg);
+int dsm_invalid(dsm_ctx* ctx, const char* entry, const char* msg);
+int dsm_invalid(dsm_ctx* ctx, const char* entry, const std::string& msg);
+
+#define HIPCHK(ctx, call)                                                                  \
+  do {                                                                                     \
+    const hipError_t e_ = (call);                                                          \
+    if (e_ != hipSuccess) return dsm_hip_fail((ctx), e_, __FILE_NAME__, __LINE__);         \
   } while (0)
 
 // the sticky form for a driver with a single exit: the first failing call is recorded in ctx->err and in the local int rc,
 // later calls still run (and later failures are not recorded)
-#define HIPTRY(call)                                                   \
-  do {                                                                 \
-    hipError_t e_ = (call);                                            \
-    if (e_ != hipSuccess && rc == DSM_OK) {                            \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);    \
-      rc = DSM_ERR_HIP;                                                \
-    }                                                                  \
+#define HIPTRY(call)                                                                               \
+  do {                                                                                             \
+    const hipError_t e_ = (call);                                                                  \
+    if (e_ != hipSuccess && rc == DSM_OK) rc = dsm_hip_fail(ctx, e_, __FILE_NAME__, __LINE__);     \
   } while (0)
 
 static inline int dsm_fail(dsm_ctx* ctx, int code, const char* msg) {

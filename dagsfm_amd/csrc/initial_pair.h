@@ -30,13 +30,6 @@
 #define IP_DEG_TO_RAD 0.0174532925199432954743716805978692718781530857086181640625  // DegToRad, util/math.h:198-200
 #define IP_PI 3.14159265358979323846
 
-// the host's set-up and driver are built for size under clang: the product library has a size cap (tests/test_capi_symbols.py)
-#ifdef __clang__
-#define IP_MINSIZE __attribute__((minsize))
-#else
-#define IP_MINSIZE
-#endif
-
 // slot flags
 #define IP_SLOT_PRIOR 1u    // the image's camera has a prior focal length
 #define IP_SLOT_FIRST 2u    // may be a first image: trials left and registered nowhere -- or, with one seed image, that image
@@ -299,7 +292,7 @@ struct IpSetup {
   }
 
   // the message of the first invalid argument, or NULL.  image_prior [num_images]: the prior flag of every image's camera.
-  IP_MINSIZE const char* load(uint32_t num_images, const uint32_t* image_ids, const uint8_t* image_prior, const uint32_t* points2D_offsets,
+  const char* load(uint32_t num_images, const uint32_t* image_ids, const uint8_t* image_prior, const uint32_t* points2D_offsets,
                    uint32_t num_pairs, const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
                    uint32_t num_problems, const uint32_t* problem_image_offsets, const uint32_t* problem_image_ids,
                    const uint32_t* num_registrations, const uint32_t* init_num_reg_trials, const uint64_t* tried_offsets,

@@ -29,6 +29,7 @@
 #define IP_HD static __host__ __device__ inline
 #define IP_D static __device__ inline
 #include "initial_pair.h"
+#include "wave_reduce.h"
 
 namespace {
 
@@ -181,20 +182,9 @@ __device__ __noinline__ void ip_to_world(const dsm_camera* cams, uint32_t image,
   image_to_world(cams[image], kp[2 * (size_t)f], kp[2 * (size_t)f + 1], u, v);
 }
 
-// TriangulatePoint (triangulation.cc:39-53): the reference-order 4 x 4 JacobiSVD, V's last column dehomogenised
+// triangulate_two_view (verify_linalg.h), one copy out of line for the kernels of this file
 __device__ __noinline__ void ip_triangulate(const double* P1, const double* P2, double u1, double v1, double u2, double v2, double* X) {
-  double A[16];
-  for (int c = 0; c < 4; ++c) {
-    A[c] = u1 * P1[8 + c] - P1[c];
-    A[4 + c] = v1 * P1[8 + c] - P1[4 + c];
-    A[8 + c] = u2 * P2[8 + c] - P2[c];
-    A[12 + c] = v2 * P2[8 + c] - P2[4 + c];
-  }
-  double V[16], sv[4];
-  pr_jacobi_svd_square_V<4>(A, V, sv);
-  X[0] = V[12] / V[15];
-  X[1] = V[13] / V[15];
-  X[2] = V[14] / V[15];
+  triangulate_two_view(P1, P2, u1, v1, u2, v2, X);
 }
 
 struct IpPoseParams {
@@ -269,11 +259,6 @@ __device__ inline void ip_pose_decide(const IpPoseParams& p, const dsm_two_view_
   *out = r;
 }
 
-__device__ inline uint32_t ip_wave_sum(uint32_t v) {
-  for (int d = 32; d > 0; d /= 2) v += __shfl_xor(v, d);
-  return v;
-}
-
 // EstimateRelativePose's acceptance for one verified candidate per one-wave workgroup: the points in front of both cameras in
 // inlier order (ballot and popcount), their angles, the median by bisection on the bits, the three tests
 __global__ void __launch_bounds__(64) k_ip_relative_pose(IpPoseParams p, IpPose* __restrict__ out) {
@@ -301,7 +286,7 @@ __global__ void __launch_bounds__(64) k_ip_relative_pose(IpPoseParams p, IpPose*
       auto count_below = [&](uint64_t v) {
         uint32_t cnt = 0;
         for (uint64_t i = lane; i < total; i += 64) cnt += ip_double_bits(ang[i]) < v;
-        return (uint64_t)ip_wave_sum(cnt);
+        return (uint64_t)wave_sum(cnt);
       };
       const double mid = ip_bits_double(ip_select_bits(total / 2, count_below));
       const double below = total % 2 == 0 ? ip_bits_double(ip_select_bits(total / 2 - 1, count_below)) : 0.0;
@@ -444,17 +429,6 @@ struct IpBufs {
   DevBuf b_img, b_src, b_off, b_list, b_seeds, b_pose, angles, t_pose, t_xyz, t_obs, t_count, t_margins;
 };
 
-// the driver's form of HIPCHK: the message names the line instead of the call's text (the product library has a size cap)
-__attribute__((noinline)) int ip_hip_fail(dsm_ctx* ctx, hipError_t e, int line) {
-  ctx->err = "dsm_find_initial_pairs: HIP error at initial_pair.hip:" + std::to_string(line) + ": " + hipGetErrorString(e);
-  return DSM_ERR_HIP;
-}
-#define IPCHK(call)                                                \
-  do {                                                             \
-    const hipError_t e_ = (call);                                  \
-    if (e_ != hipSuccess) return ip_hip_fail(ctx, e_, __LINE__);   \
-  } while (0)
-
 struct IpCand {
   uint32_t img1, img2, pair, swapped;  // image indices; pair IP_NONE: the images share no pair
 };
@@ -463,7 +437,7 @@ struct IpCand {
 
 extern "C" void dsm_default_initial_pair_options(dsm_initial_pair_options* o) { ip_default_options(o); }
 
-extern "C" IP_MINSIZE int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
+extern "C" int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
                                       uint32_t num_images, const uint32_t* image_ids, const uint32_t* image_camera_ids,
                                       const uint32_t* points2D_offsets, const double* points2D_xy, uint32_t num_pairs,
                                       const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
@@ -476,10 +450,7 @@ extern "C" IP_MINSIZE int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_came
                                       uint64_t* inlier_offsets, uint32_t* inlier_matches, uint64_t inlier_capacity,
                                       dsm_initial_pair_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](int code, const std::string& msg) {
-    ctx->err = "dsm_find_initial_pairs: " + msg;
-    return code;
-  };
+  auto fail = [ctx](int code, const char* msg) { return dsm_fail(ctx, code, "dsm_find_initial_pairs", msg); };
   const auto t_host0 = std::chrono::steady_clock::now();
   if ((num_cameras && (!camera_ids || !cameras)) || (num_images && (!image_ids || !image_camera_ids)) || !points2D_offsets || !match_offsets ||
       !problem_image_offsets || (num_problems && (!results || !tried_out_offsets || !point_offsets)))
@@ -538,54 +509,44 @@ extern "C" IP_MINSIZE int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_came
   if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   IpBufs d;
-  DevEvent ev[4], bev[4];
-  for (DevEvent& e : ev) IPCHK(hipEventCreate(&e.e));
-  for (DevEvent& e : bev) IPCHK(hipEventCreate(&e.e));
-  IPCHK(hipEventRecord(ev[0], st));
-  auto up = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
-    hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
-    return e;
-  };
-  auto zero = [&](DevBuf& b, size_t bytes) -> hipError_t {
-    hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) e = hipMemsetAsync(b.p, 0, std::max<size_t>(bytes, 16), st);
-    return e;
-  };
-  auto grid = [](uint64_t n) { return dim3((uint32_t)((n + IP_BLOCK - 1) / IP_BLOCK)); };
+  DevEvents<4> ev, bev;
+  HIPCHK(ctx, ev.create());
+  HIPCHK(ctx, bev.create());
+  HIPCHK(ctx, hipEventRecord(ev[0], st));
+  auto grid = [](uint64_t n) { return dim3(dsm_grid(n, IP_BLOCK)); };
 
   // ------------------------------------------------------------ the scene, the duplicate rule, the counts, the candidate order
   const size_t K1 = std::max<uint32_t>(num_pairs, 1);
-  IPCHK(up(d.nfeat, S.nfeat.data(), (size_t)num_images * 4));
-  IPCHK(up(d.row0, points2D_offsets, ((size_t)num_images + 1) * 4));
-  IPCHK(up(d.cams, image_cams.data(), (size_t)num_images * sizeof(dsm_camera)));
-  IPCHK(up(d.kp, points2D_xy, F * 16));
-  IPCHK(up(d.pair_img, S.pair_img.data(), S.pair_img.size() * 4));
-  IPCHK(up(d.moff, match_offsets, ((size_t)num_pairs + 1) * 8));
-  IPCHK(up(d.matches, matches, NM * 8));
-  IPCHK(d.acc.reserve(std::max<uint64_t>(NM, 16)));
-  IPCHK(zero(d.cnt, K1 * 4));
+  HIPCHK(ctx, dev_upload(d.nfeat, S.nfeat.data(), (size_t)num_images * 4, st));
+  HIPCHK(ctx, dev_upload(d.row0, points2D_offsets, ((size_t)num_images + 1) * 4, st));
+  HIPCHK(ctx, dev_upload(d.cams, image_cams.data(), (size_t)num_images * sizeof(dsm_camera), st));
+  HIPCHK(ctx, dev_upload(d.kp, points2D_xy, F * 16, st));
+  HIPCHK(ctx, dev_upload(d.pair_img, S.pair_img.data(), S.pair_img.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.moff, match_offsets, ((size_t)num_pairs + 1) * 8, st));
+  HIPCHK(ctx, dev_upload(d.matches, matches, NM * 8, st));
+  HIPCHK(ctx, d.acc.reserve(std::max<uint64_t>(NM, 16)));
+  HIPCHK(ctx, dev_fill(d.cnt, 0, K1 * 4, st));
   if (num_pairs) {
     hipLaunchKernelGGL(k_rt_dedup, dim3(num_pairs), dim3(IP_BLOCK), 0, st, num_pairs, d.pair_img.as<uint32_t>(), d.moff.as<uint64_t>(),
                        d.matches.as<uint32_t>(), d.nfeat.as<uint32_t>(), d.acc.as<uint8_t>());
     hipLaunchKernelGGL(k_ip_pair_count, dim3(num_pairs), dim3(IP_BLOCK), 0, st, num_pairs, d.moff.as<uint64_t>(), d.acc.as<uint8_t>(),
                        d.cnt.as<uint32_t>());
-    IPCHK(hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
   }
-  IPCHK(up(d.slot_off, S.slot_off.data(), S.slot_off.size() * 4));
-  IPCHK(up(d.slot_flags, S.slot_flags.data(), (size_t)n_slots * 4));
-  IPCHK(up(d.slot_prob, slot_prob.data(), (size_t)n_slots * 4));
-  IPCHK(up(d.ent_off, S.ent_off.data(), S.ent_off.size() * 4));
-  IPCHK(up(d.ent_pair, S.ent_pair.data(), (size_t)n_entries * 4));
-  IPCHK(up(d.ent_slot, S.ent_slot.data(), (size_t)n_entries * 8));
-  IPCHK(up(d.ent_tried, S.ent_tried.data(), n_entries));
-  IPCHK(up(d.ent_prob, ent_prob.data(), (size_t)n_entries * 4));
-  IPCHK(zero(d.sum, (size_t)n_slots * 4));
-  IPCHK(d.slot_rank.reserve(std::max<size_t>((size_t)n_slots * 4, 16)));
-  IPCHK(d.key.reserve(std::max<size_t>((size_t)n_entries * 16, 16)));
-  IPCHK(zero(d.cand, (size_t)n_entries * 8));
-  IPCHK(zero(d.cand_n, (size_t)std::max<uint32_t>(num_problems, 1) * 4));
-  IPCHK(d.seen.reserve(std::max<uint32_t>(n_entries, 16)));
+  HIPCHK(ctx, dev_upload(d.slot_off, S.slot_off.data(), S.slot_off.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.slot_flags, S.slot_flags.data(), (size_t)n_slots * 4, st));
+  HIPCHK(ctx, dev_upload(d.slot_prob, slot_prob.data(), (size_t)n_slots * 4, st));
+  HIPCHK(ctx, dev_upload(d.ent_off, S.ent_off.data(), S.ent_off.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.ent_pair, S.ent_pair.data(), (size_t)n_entries * 4, st));
+  HIPCHK(ctx, dev_upload(d.ent_slot, S.ent_slot.data(), (size_t)n_entries * 8, st));
+  HIPCHK(ctx, dev_upload(d.ent_tried, S.ent_tried.data(), n_entries, st));
+  HIPCHK(ctx, dev_upload(d.ent_prob, ent_prob.data(), (size_t)n_entries * 4, st));
+  HIPCHK(ctx, dev_fill(d.sum, 0, (size_t)n_slots * 4, st));
+  HIPCHK(ctx, d.slot_rank.reserve(std::max<size_t>((size_t)n_slots * 4, 16)));
+  HIPCHK(ctx, d.key.reserve(std::max<size_t>((size_t)n_entries * 16, 16)));
+  HIPCHK(ctx, dev_fill(d.cand, 0, (size_t)n_entries * 8, st));
+  HIPCHK(ctx, dev_fill(d.cand_n, 0, (size_t)std::max<uint32_t>(num_problems, 1) * 4, st));
+  HIPCHK(ctx, d.seen.reserve(std::max<uint32_t>(n_entries, 16)));
   IpOrder od;
   od.v = IpOrderView{num_problems,         d.slot_off.as<uint32_t>(), d.slot_flags.as<uint32_t>(), d.ent_off.as<uint32_t>(), d.ent_pair.as<uint32_t>(),
                      d.ent_slot.as<uint32_t>(), d.ent_tried.as<uint8_t>(),  d.cnt.as<uint32_t>(),        (uint32_t)std::max(o.init_min_num_inliers, 1)};
@@ -603,13 +564,13 @@ extern "C" IP_MINSIZE int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_came
     hipLaunchKernelGGL(k_ip_entry_keys, grid(2ull * n_entries), dim3(IP_BLOCK), 0, st, od);
     hipLaunchKernelGGL(k_ip_entry_rank, grid(2ull * n_entries), dim3(IP_BLOCK), 0, st, od);
   }
-  IPCHK(hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   std::vector<uint32_t> cnt(num_pairs), cand_raw(2 * (size_t)n_entries), cand_n(num_problems);
-  if (num_pairs) IPCHK(hipMemcpyAsync(cnt.data(), d.cnt.p, (size_t)num_pairs * 4, hipMemcpyDeviceToHost, st));
-  if (n_entries) IPCHK(hipMemcpyAsync(cand_raw.data(), d.cand.p, (size_t)n_entries * 8, hipMemcpyDeviceToHost, st));
-  if (num_problems) IPCHK(hipMemcpyAsync(cand_n.data(), d.cand_n.p, (size_t)num_problems * 4, hipMemcpyDeviceToHost, st));
-  IPCHK(hipEventRecord(ev[1], st));
-  IPCHK(hipStreamSynchronize(st));
+  if (num_pairs) HIPCHK(ctx, hipMemcpyAsync(cnt.data(), d.cnt.p, (size_t)num_pairs * 4, hipMemcpyDeviceToHost, st));
+  if (n_entries) HIPCHK(ctx, hipMemcpyAsync(cand_raw.data(), d.cand.p, (size_t)n_entries * 8, hipMemcpyDeviceToHost, st));
+  if (num_problems) HIPCHK(ctx, hipMemcpyAsync(cand_n.data(), d.cand_n.p, (size_t)num_problems * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipEventRecord(ev[1], st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
 
   // every problem's candidate list
   std::vector<std::vector<IpCand>> cands(num_problems);
@@ -659,7 +620,7 @@ extern "C" IP_MINSIZE int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_came
   std::vector<dsm_two_view_geometry> tvgs;
   std::vector<uint32_t> b_img, b_src, b_seeds, counts;
   std::vector<uint64_t> b_off;
-  float ms = 0.f;
+  double ms = 0;
   while (unfinished) {
     ++rep.num_rounds;
     uint32_t p_next = 0;
@@ -689,28 +650,28 @@ extern "C" IP_MINSIZE int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_came
         b_seeds[c] = dsm_pair_seed(image_ids[cd.img1], image_ids[cd.img2], o.user_seed);
       }
       const uint64_t total = b_off[n];
-      IPCHK(hipEventRecord(bev[0], st));
-      IPCHK(up(d.b_img, b_img.data(), b_img.size() * 4));
-      IPCHK(up(d.b_src, b_src.data(), b_src.size() * 4));
-      IPCHK(up(d.b_off, b_off.data(), b_off.size() * 8));
-      IPCHK(up(d.b_seeds, b_seeds.data(), b_seeds.size() * 4));
-      IPCHK(d.b_list.reserve(std::max<uint64_t>(total * 8, 16)));
+      HIPCHK(ctx, hipEventRecord(bev[0], st));
+      HIPCHK(ctx, dev_upload(d.b_img, b_img.data(), b_img.size() * 4, st));
+      HIPCHK(ctx, dev_upload(d.b_src, b_src.data(), b_src.size() * 4, st));
+      HIPCHK(ctx, dev_upload(d.b_off, b_off.data(), b_off.size() * 8, st));
+      HIPCHK(ctx, dev_upload(d.b_seeds, b_seeds.data(), b_seeds.size() * 4, st));
+      HIPCHK(ctx, d.b_list.reserve(std::max<uint64_t>(total * 8, 16)));
       IpBatch bt{n,        d.b_img.as<uint32_t>(),   d.b_src.as<uint32_t>(), d.b_off.as<uint64_t>(), d.b_list.as<uint32_t>(), d.moff.as<uint64_t>(),
                  d.matches.as<uint32_t>(), d.acc.as<uint8_t>(), d.nfeat.as<uint32_t>()};
       hipLaunchKernelGGL(k_ip_gather, dim3(n), dim3(IP_BLOCK), 0, st, bt);
-      IPCHK(hipGetLastError());
-      IPCHK(hipEventRecord(bev[1], st));
-      IPCHK(hipStreamSynchronize(st));  // the leaf context runs on its own stream
+      HIPCHK(ctx, hipGetLastError());
+      HIPCHK(ctx, hipEventRecord(bev[1], st));
+      HIPCHK(ctx, hipStreamSynchronize(st));  // the leaf context runs on its own stream
       IpPoseParams pp;
       uint64_t total_inliers = 0;
       int rc = dsm_verify_on_leaf(ctx, n, d.b_img.as<uint32_t>(), d.b_off.as<uint64_t>(), d.b_list.as<uint32_t>(), total, counts, d.kp.as<double>(),
                                   d.row0.as<uint32_t>(), d.cams.as<dsm_camera>(), &to, d.b_seeds.as<uint32_t>(), &pp.tvg, &pp.inl_off, &pp.inl,
                                   &total_inliers, nullptr);
       if (rc != DSM_OK) return rc;
-      IPCHK(hipSetDevice(ctx->device));
-      IPCHK(hipEventRecord(bev[2], st));
-      IPCHK(d.angles.reserve(std::max<uint64_t>(total_inliers * 8, 16)));
-      IPCHK(d.b_pose.reserve((size_t)n * sizeof(IpPose)));
+      HIPCHK(ctx, hipSetDevice(ctx->device));
+      HIPCHK(ctx, hipEventRecord(bev[2], st));
+      HIPCHK(ctx, d.angles.reserve(std::max<uint64_t>(total_inliers * 8, 16)));
+      HIPCHK(ctx, d.b_pose.reserve((size_t)n * sizeof(IpPose)));
       pp.n = n, pp.img = d.b_img.as<uint32_t>(), pp.kp = d.kp.as<double>(), pp.row0 = d.row0.as<uint32_t>(), pp.cams = d.cams.as<dsm_camera>();
       pp.angles = d.angles.as<double>(), pp.min_num_inliers = o.init_min_num_inliers, pp.max_forward = o.init_max_forward_motion;
       pp.min_tri_angle_rad = min_tri_rad;
@@ -721,19 +682,19 @@ extern "C" IP_MINSIZE int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_came
       } else {
         hipLaunchKernelGGL(k_ip_relative_pose, dim3(n), dim3(64), 0, st, pp, d.b_pose.as<IpPose>());
       }
-      IPCHK(hipGetLastError());
+      HIPCHK(ctx, hipGetLastError());
       poses.resize(n), tvgs.resize(n);
-      IPCHK(hipMemcpyAsync(poses.data(), d.b_pose.p, (size_t)n * sizeof(IpPose), hipMemcpyDeviceToHost, st));
-      IPCHK(hipMemcpyAsync(tvgs.data(), pp.tvg, (size_t)n * sizeof(dsm_two_view_geometry), hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(poses.data(), d.b_pose.p, (size_t)n * sizeof(IpPose), hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(tvgs.data(), pp.tvg, (size_t)n * sizeof(dsm_two_view_geometry), hipMemcpyDeviceToHost, st));
       h_inl_off.resize((size_t)n + 1);
-      IPCHK(hipMemcpyAsync(h_inl_off.data(), pp.inl_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
-      IPCHK(hipEventRecord(bev[3], st));
-      IPCHK(hipStreamSynchronize(st));
-      IPCHK(hipEventElapsedTime(&ms, bev[0], bev[1]));
+      HIPCHK(ctx, hipMemcpyAsync(h_inl_off.data(), pp.inl_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipEventRecord(bev[3], st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      HIPCHK(ctx, bev.ms(0, 1, &ms));
       rep.gather_ms += ms;
-      IPCHK(hipEventElapsedTime(&ms, bev[1], bev[2]));
+      HIPCHK(ctx, bev.ms(1, 2, &ms));
       rep.verify_ms += ms;
-      IPCHK(hipEventElapsedTime(&ms, bev[2], bev[3]));
+      HIPCHK(ctx, bev.ms(2, 3, &ms));
       rep.pose_ms += ms;
       rep.num_verified += n;
       // the replay: a problem's candidates in list order, the first accepted one wins
@@ -750,7 +711,7 @@ extern "C" IP_MINSIZE int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_came
           win_tvg[p].config = poses[x].config;
           win_tvg[p].tri_angle = poses[x].tri_angle;
           win_inl[p].resize(2 * (h_inl_off[x + 1] - h_inl_off[x]));
-          if (!win_inl[p].empty()) IPCHK(hipMemcpy(win_inl[p].data(), pp.inl + 2 * h_inl_off[x], win_inl[p].size() * 4, hipMemcpyDeviceToHost));
+          if (!win_inl[p].empty()) HIPCHK(ctx, hipMemcpy(win_inl[p].data(), pp.inl + 2 * h_inl_off[x], win_inl[p].size() * 4, hipMemcpyDeviceToHost));
           rep.num_speculated += c1 - x - 1;
           break;
         }
@@ -760,7 +721,7 @@ extern "C" IP_MINSIZE int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_came
       }
     }
   }
-  IPCHK(hipEventRecord(ev[2], st));
+  HIPCHK(ctx, hipEventRecord(ev[2], st));
 
   // ------------------------------------------------------------ the winners' points
   std::vector<uint32_t> wins;
@@ -782,15 +743,15 @@ extern "C" IP_MINSIZE int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_came
       for (int k = 0; k < 3; ++k) pose[7 * (size_t)w + 4 + k] = win_tvg[wins[w]].tvec[k];
     }
     const uint64_t total = t_off[nw], T1 = std::max<uint64_t>(total, 1);
-    IPCHK(up(d.b_img, b_img.data(), b_img.size() * 4));
-    IPCHK(up(d.b_src, b_src.data(), b_src.size() * 4));
-    IPCHK(up(d.b_off, t_off.data(), t_off.size() * 8));
-    IPCHK(up(d.t_pose, pose.data(), pose.size() * 8));
-    IPCHK(d.b_list.reserve(T1 * 8));
-    IPCHK(d.t_xyz.reserve(T1 * 24));
-    IPCHK(d.t_obs.reserve(T1 * 8));
-    IPCHK(zero(d.t_count, (size_t)nw * 4));
-    IPCHK(d.t_margins.reserve((size_t)nw * 16));
+    HIPCHK(ctx, dev_upload(d.b_img, b_img.data(), b_img.size() * 4, st));
+    HIPCHK(ctx, dev_upload(d.b_src, b_src.data(), b_src.size() * 4, st));
+    HIPCHK(ctx, dev_upload(d.b_off, t_off.data(), t_off.size() * 8, st));
+    HIPCHK(ctx, dev_upload(d.t_pose, pose.data(), pose.size() * 8, st));
+    HIPCHK(ctx, d.b_list.reserve(T1 * 8));
+    HIPCHK(ctx, d.t_xyz.reserve(T1 * 24));
+    HIPCHK(ctx, d.t_obs.reserve(T1 * 8));
+    HIPCHK(ctx, dev_fill(d.t_count, 0, (size_t)nw * 4, st));
+    HIPCHK(ctx, d.t_margins.reserve((size_t)nw * 16));
     IpBatch bt{nw,       d.b_img.as<uint32_t>(),   d.b_src.as<uint32_t>(), d.b_off.as<uint64_t>(), d.b_list.as<uint32_t>(), d.moff.as<uint64_t>(),
                d.matches.as<uint32_t>(), d.acc.as<uint8_t>(), d.nfeat.as<uint32_t>()};
     hipLaunchKernelGGL(k_ip_gather, dim3(nw), dim3(IP_BLOCK), 0, st, bt);
@@ -804,23 +765,20 @@ extern "C" IP_MINSIZE int dsm_find_initial_pairs(dsm_ctx* ctx, uint32_t num_came
     } else {
       hipLaunchKernelGGL(k_ip_triangulate, dim3(nw), dim3(IP_BLOCK), 0, st, tp);
     }
-    IPCHK(hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
     t_xyz.resize(3 * T1), t_obs.resize(2 * T1);
-    IPCHK(hipMemcpyAsync(t_count.data(), d.t_count.p, (size_t)nw * 4, hipMemcpyDeviceToHost, st));
-    IPCHK(hipMemcpyAsync(t_margins.data(), d.t_margins.p, (size_t)nw * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(t_count.data(), d.t_count.p, (size_t)nw * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(t_margins.data(), d.t_margins.p, (size_t)nw * 16, hipMemcpyDeviceToHost, st));
     if (total) {
-      IPCHK(hipMemcpyAsync(t_xyz.data(), d.t_xyz.p, total * 24, hipMemcpyDeviceToHost, st));
-      IPCHK(hipMemcpyAsync(t_obs.data(), d.t_obs.p, total * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(t_xyz.data(), d.t_xyz.p, total * 24, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(t_obs.data(), d.t_obs.p, total * 8, hipMemcpyDeviceToHost, st));
     }
   }
-  IPCHK(hipEventRecord(ev[3], st));
-  IPCHK(hipStreamSynchronize(st));
-  IPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-  rep.graph_ms = ms;
-  IPCHK(hipEventElapsedTime(&ms, ev[2], ev[3]));
-  rep.triangulate_ms = ms;
-  IPCHK(hipEventElapsedTime(&ms, ev[0], ev[3]));
-  rep.device_ms = ms;
+  HIPCHK(ctx, hipEventRecord(ev[3], st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, ev.ms(0, 1, &rep.graph_ms));
+  HIPCHK(ctx, ev.ms(2, 3, &rep.triangulate_ms));
+  HIPCHK(ctx, ev.ms(0, 3, &rep.device_ms));
 
   // ------------------------------------------------------------ the results
   uint64_t n_tried = 0, n_points = 0, n_inl = 0, at_inl = 0;

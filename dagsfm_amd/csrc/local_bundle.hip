@@ -32,6 +32,7 @@
 #include "ba_project.h"
 #include "ctx.h"
 #include "trust_region.h"
+#include "wave_reduce.h"
 
 namespace {
 
@@ -119,10 +120,7 @@ __device__ __noinline__ void lb_quat_plus(const double* x, const double* d, doub
 
 // the workgroup's fixed-order sum / max / min (every thread returns it).  op 0: sum, 1: max, 2: min
 __device__ __noinline__ double lb_reduce(double v, double* red, int tid, int op) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const double w = __shfl_xor(v, o);
-    v = op == 0 ? v + w : (op == 1 ? fmax(v, w) : fmin(v, w));
-  }
+  v = wave_reduce(v, [op](double a, double w) { return op == 0 ? a + w : (op == 1 ? fmax(a, w) : fmin(a, w)); });
   __syncthreads();
   if ((tid & 63) == 0) red[tid >> 6] = v;
   __syncthreads();
@@ -802,10 +800,7 @@ extern "C" int dsm_adjust_local_bundles(dsm_ctx* ctx, uint32_t num_problems, con
                                         dsm_local_bundle_result* results_out, double* margins_out, double* trace_out,
                                         dsm_local_bundle_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_adjust_local_bundles: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_adjust_local_bundles", msg); };
   const auto t_host0 = std::chrono::steady_clock::now();
   const uint32_t B = num_problems;
   dsm_local_bundle_options o;
@@ -990,8 +985,8 @@ extern "C" int dsm_adjust_local_bundles(dsm_ctx* ctx, uint32_t num_problems, con
       }
     }
     if (col > LB_RMAX)
-      return fail("the reduced camera system of problem " + std::to_string(b) + " has " + std::to_string(col) +
-                  " columns, above DSM_LOCAL_BUNDLE_MAX_REDUCED_DIM = 128: a problem of that size belongs to dsm_bundle_adjust");
+      return dsm_invalid(ctx, "dsm_adjust_local_bundles", "the reduced camera system of problem " + std::to_string(b) + " has " + std::to_string(col) +
+                         " columns, above DSM_LOCAL_BUNDLE_MAX_REDUCED_DIM = 128: a problem of that size belongs to dsm_bundle_adjust");
     pb.R = (uint32_t)col;
     r_max = std::max(r_max, col);
     pb.o_G = G_total;
@@ -1062,38 +1057,33 @@ extern "C" int dsm_adjust_local_bundles(dsm_ctx* ctx, uint32_t num_problems, con
   if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   LbBufs d;
-  DevEvent ev[4];
-  for (int i = 0; i < 4; ++i) HIPCHK(ctx, hipEventCreate(&ev[i].e));
+  DevEvents<4> ev;
+  HIPCHK(ctx, ev.create());
   HIPCHK(ctx, hipEventRecord(ev[0], st));
-  auto up = [&](DevBuf& buf, const void* src, size_t bytes) -> hipError_t {
-    hipError_t e = buf.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st);
-    return e;
-  };
   const size_t nI = h_img_cam.size(), nC = h_cam_model.size(), nP = h_pt_var.size(), nO = h_obs_img.size();
   const size_t trace_rows = (size_t)B * (size_t)(o.max_num_iterations + 1);
-  HIPCHK(ctx, up(d.prob, prob.data(), (size_t)B * sizeof(LbProblem)));
-  HIPCHK(ctx, up(d.img_cam, h_img_cam.data(), nI * 4));
-  HIPCHK(ctx, up(d.img_qcol, h_qcol.data(), nI * 4));
-  HIPCHK(ctx, up(d.img_tcol, h_tcol.data(), nI * 12));
-  HIPCHK(ctx, up(d.img_q, h_q.data(), nI * 32));
-  HIPCHK(ctx, up(d.img_t, h_t.data(), nI * 24));
-  HIPCHK(ctx, up(d.cam_model, h_cam_model.data(), nC * 4));
-  HIPCHK(ctx, up(d.cam_col, h_cam_col.data(), nC * 4));
-  HIPCHK(ctx, up(d.cam_k, h_cam_k.data(), nC * 4));
-  HIPCHK(ctx, up(d.cam_fr, h_cam_fr.data(), nC * 12));
-  HIPCHK(ctx, up(d.cam_prm, h_prm.data(), nC * 96));
-  HIPCHK(ctx, up(d.pt_X, h_X.data(), nP * 24));
-  HIPCHK(ctx, up(d.pt_var, h_pt_var.data(), nP));
-  HIPCHK(ctx, up(d.var_pt, h_var_pt.data(), nP * 4));
-  HIPCHK(ctx, up(d.track, h_track.data(), h_track.size() * 4));
-  HIPCHK(ctx, up(d.img_list, h_img_list.data(), h_img_list.size() * 4));
-  HIPCHK(ctx, up(d.img_obs, h_img_obs.data(), nO * 4));
-  HIPCHK(ctx, up(d.cam_list, h_cam_list.data(), h_cam_list.size() * 4));
-  HIPCHK(ctx, up(d.cam_obs, h_cam_obs.data(), nO * 4));
-  HIPCHK(ctx, up(d.obs_img, h_obs_img.data(), nO * 4));
-  HIPCHK(ctx, up(d.obs_pt, h_obs_pt.data(), nO * 4));
-  HIPCHK(ctx, up(d.obs_xy, h_xy.data(), nO * 16));
+  HIPCHK(ctx, dev_upload(d.prob, prob.data(), (size_t)B * sizeof(LbProblem), st));
+  HIPCHK(ctx, dev_upload(d.img_cam, h_img_cam.data(), nI * 4, st));
+  HIPCHK(ctx, dev_upload(d.img_qcol, h_qcol.data(), nI * 4, st));
+  HIPCHK(ctx, dev_upload(d.img_tcol, h_tcol.data(), nI * 12, st));
+  HIPCHK(ctx, dev_upload(d.img_q, h_q.data(), nI * 32, st));
+  HIPCHK(ctx, dev_upload(d.img_t, h_t.data(), nI * 24, st));
+  HIPCHK(ctx, dev_upload(d.cam_model, h_cam_model.data(), nC * 4, st));
+  HIPCHK(ctx, dev_upload(d.cam_col, h_cam_col.data(), nC * 4, st));
+  HIPCHK(ctx, dev_upload(d.cam_k, h_cam_k.data(), nC * 4, st));
+  HIPCHK(ctx, dev_upload(d.cam_fr, h_cam_fr.data(), nC * 12, st));
+  HIPCHK(ctx, dev_upload(d.cam_prm, h_prm.data(), nC * 96, st));
+  HIPCHK(ctx, dev_upload(d.pt_X, h_X.data(), nP * 24, st));
+  HIPCHK(ctx, dev_upload(d.pt_var, h_pt_var.data(), nP, st));
+  HIPCHK(ctx, dev_upload(d.var_pt, h_var_pt.data(), nP * 4, st));
+  HIPCHK(ctx, dev_upload(d.track, h_track.data(), h_track.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.img_list, h_img_list.data(), h_img_list.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.img_obs, h_img_obs.data(), nO * 4, st));
+  HIPCHK(ctx, dev_upload(d.cam_list, h_cam_list.data(), h_cam_list.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.cam_obs, h_cam_obs.data(), nO * 4, st));
+  HIPCHK(ctx, dev_upload(d.obs_img, h_obs_img.data(), nO * 4, st));
+  HIPCHK(ctx, dev_upload(d.obs_pt, h_obs_pt.data(), nO * 4, st));
+  HIPCHK(ctx, dev_upload(d.obs_xy, h_xy.data(), nO * 16, st));
   HIPCHK(ctx, d.img_cq.reserve(std::max<size_t>(nI * 32, 16)));
   HIPCHK(ctx, d.img_ct.reserve(std::max<size_t>(nI * 24, 16)));
   HIPCHK(ctx, d.cam_cprm.reserve(std::max<size_t>(nC * 96, 16)));
@@ -1193,15 +1183,10 @@ extern "C" int dsm_adjust_local_bundles(dsm_ctx* ctx, uint32_t num_problems, con
       for (int a = 0; a < 3; ++a) point_xyz[3 * p + a] = r_X[3 * (pb.o_pt + r) + a];
     }
   }
-  float a = 0, s = 0, c = 0, tot = 0;
-  HIPCHK(ctx, hipEventElapsedTime(&a, ev[0], ev[1]));
-  HIPCHK(ctx, hipEventElapsedTime(&s, ev[1], ev[2]));
-  HIPCHK(ctx, hipEventElapsedTime(&c, ev[2], ev[3]));
-  HIPCHK(ctx, hipEventElapsedTime(&tot, ev[0], ev[3]));
-  rep.upload_ms = a;
-  rep.solve_ms = s;
-  rep.download_ms = c;
-  rep.device_ms = tot;
+  HIPCHK(ctx, ev.ms(0, 1, &rep.upload_ms));
+  HIPCHK(ctx, ev.ms(1, 2, &rep.solve_ms));
+  HIPCHK(ctx, ev.ms(2, 3, &rep.download_ms));
+  HIPCHK(ctx, ev.ms(0, 3, &rep.device_ms));
   if (report) *report = rep;
   return DSM_OK;
 }

@@ -191,7 +191,7 @@ struct NiSetup {
   bool out_of_range = false;
 
   // the images, the pairs and the problems through IpSetup (the validation of dsm_find_initial_pairs)
-  IP_MINSIZE const char* load_graph(uint32_t num_images, const uint32_t* image_ids, const uint32_t* points2D_offsets, uint32_t num_pairs,
+  const char* load_graph(uint32_t num_images, const uint32_t* image_ids, const uint32_t* points2D_offsets, uint32_t num_pairs,
                                     const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches, uint32_t num_problems,
                                     const uint32_t* problem_image_offsets, const uint32_t* problem_image_ids) {
     dsm_initial_pair_options ipo;
@@ -205,7 +205,7 @@ struct NiSetup {
 
   // the slots in the caller's order (IpSetup keeps a problem's slots by ascending image id) and the state of their observations;
   // num_points (or NULL) [num_problems + 1]: the CSR of the problems' points
-  IP_MINSIZE const char* load_state(uint32_t num_problems, const uint32_t* image_ids, const uint32_t* problem_image_ids,
+  const char* load_state(uint32_t num_problems, const uint32_t* image_ids, const uint32_t* problem_image_ids,
                                     const uint8_t* slot_registered, const uint64_t* slot_obs_offsets, const int32_t* slot_obs_point3D,
                                     const uint64_t* point_offsets) {
     if (!slot_obs_offsets) return "NULL argument";
@@ -246,7 +246,7 @@ struct NiSetup {
   }
 
   // dsm_find_next_images: the message of the first invalid argument, or NULL
-  IP_MINSIZE const char* load(uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras, uint32_t num_images,
+  const char* load(uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras, uint32_t num_images,
                               const uint32_t* image_ids, const uint32_t* image_camera_ids, const uint32_t* points2D_offsets,
                               const double* points2D_xy, uint32_t num_pairs, const uint32_t* pair_image_ids, const uint64_t* match_offsets,
                               const uint32_t* matches, uint32_t num_problems, const uint32_t* problem_image_offsets,
@@ -461,7 +461,7 @@ struct LbSetup {
   std::vector<double> pose;
   bool out_of_range = false;
 
-  IP_MINSIZE const char* load(uint32_t num_images, const uint32_t* image_ids, const uint32_t* points2D_offsets, uint32_t num_problems,
+  const char* load(uint32_t num_images, const uint32_t* image_ids, const uint32_t* points2D_offsets, uint32_t num_problems,
                               const uint32_t* problem_image_offsets, const uint32_t* problem_image_ids, const uint8_t* slot_registered,
                               const uint64_t* slot_obs_offsets, const int32_t* slot_obs_point3D, const double* slot_qvec, const double* slot_tvec,
                               const uint64_t* point_offsets, const double* point_xyz, uint32_t num_queries, const uint32_t* query_problem,

@@ -31,6 +31,7 @@
 #define IP_HD static __host__ __device__ inline
 #define IP_D static __device__ inline
 #include "next_images.h"
+#include "wave_reduce.h"
 
 namespace {
 
@@ -54,11 +55,6 @@ __global__ void __launch_bounds__(NI_BLOCK) k_ni_visibility(NiView v) {
   }
 }
 
-__device__ inline uint32_t ni_wave_sum(uint32_t x) {
-  for (int d = 32; d > 0; d /= 2) x += __shfl_xor(x, d);
-  return x;
-}
-
 // the counts, the score and the key of one slot per one-wave workgroup: lane r owns row r of the occupancy
 __global__ void __launch_bounds__(64) k_ni_slot(NiView v) {
   __shared__ uint32_t occ[2 * NI_DIM];  // the finest level: 64 rows of 64 bits, 512 bytes
@@ -68,7 +64,7 @@ __global__ void __launch_bounds__(64) k_ni_slot(NiView v) {
   const uint64_t w0 = v.word_off[s], w1 = v.word_off[s + 1];
   uint32_t nv = 0, no = 0;
   for (uint64_t w = w0 + lane; w < w1; w += 64) nv += __popc(v.vis[w]), no += __popc(v.has[w]);
-  nv = ni_wave_sum(nv), no = ni_wave_sum(no);
+  nv = wave_sum(nv), no = wave_sum(no);
   const uint32_t flags = v.slot_flags[s], img = v.slot_img[s];
   uint64_t score = 0;
   if (!(flags & NI_SLOT_REGISTERED)) {  // (uniform over the workgroup)
@@ -86,7 +82,7 @@ __global__ void __launch_bounds__(64) k_ni_slot(NiView v) {
     uint64_t row = (uint64_t)occ[2 * lane] | ((uint64_t)occ[2 * lane + 1] << 32);
     uint32_t dim = NI_DIM;
     for (int level = NI_LEVELS - 1; level >= 0; --level, dim /= 2) {
-      const uint32_t occupied = ni_wave_sum(lane < dim ? (uint32_t)__popcll(row) : 0u);
+      const uint32_t occupied = wave_sum(lane < dim ? (uint32_t)__popcll(row) : 0u);
       score += occupied * ni_level_weight(level);
       rows[lane] = row;
       __syncthreads();
@@ -224,7 +220,7 @@ __global__ void __launch_bounds__(64) k_lb_tri_angle(LbView v, LbItems it) {
   auto count_below = [&](uint64_t x) {
     uint32_t cnt = 0;
     for (uint64_t f = lane; f < n; f += 64) cnt += bits[f] < x;
-    return (uint64_t)ni_wave_sum(cnt);
+    return (uint64_t)wave_sum(cnt);
   };
   const uint64_t sel = ip_select_bits(lb_percentile_index(it.count[c]), count_below);
   if (lane == 0) it.tri_angle[c] = ip_bits_double(sel);
@@ -263,21 +259,11 @@ struct NiBufs {
   DevBuf bits, num_visible, num_observations, score, key, order, order_n;
 };
 
-__attribute__((noinline)) int ni_hip_fail(dsm_ctx* ctx, hipError_t e, int line) {
-  ctx->err = "dsm_find_next_images: HIP error at next_images.hip:" + std::to_string(line) + ": " + hipGetErrorString(e);
-  return DSM_ERR_HIP;
-}
-#define NICHK(call)                                                \
-  do {                                                             \
-    const hipError_t e_ = (call);                                  \
-    if (e_ != hipSuccess) return ni_hip_fail(ctx, e_, __LINE__);   \
-  } while (0)
-
 }  // namespace
 
 extern "C" void dsm_default_next_images_options(dsm_next_images_options* o) { ni_default_options(o); }
 
-extern "C" IP_MINSIZE int dsm_find_next_images(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
+extern "C" int dsm_find_next_images(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
                                                uint32_t num_images, const uint32_t* image_ids, const uint32_t* image_camera_ids,
                                                const uint32_t* points2D_offsets, const double* points2D_xy, uint32_t num_pairs,
                                                const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
@@ -288,10 +274,7 @@ extern "C" IP_MINSIZE int dsm_find_next_images(dsm_ctx* ctx, uint32_t num_camera
                                                uint64_t next_capacity, uint32_t* slot_num_visible, uint32_t* slot_num_observations,
                                                uint64_t* slot_score, dsm_next_images_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](int code, const std::string& msg) {
-    ctx->err = "dsm_find_next_images: " + msg;
-    return code;
-  };
+  auto fail = [ctx](int code, const char* msg) { return dsm_fail(ctx, code, "dsm_find_next_images", msg); };
   const auto t_host0 = std::chrono::steady_clock::now();
   dsm_next_images_options o;
   if (options)
@@ -323,36 +306,27 @@ extern "C" IP_MINSIZE int dsm_find_next_images(dsm_ctx* ctx, uint32_t num_camera
   if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   NiBufs d;
-  DevEvent ev[3], bev[4];
-  for (DevEvent& e : ev) NICHK(hipEventCreate(&e.e));
-  for (DevEvent& e : bev) NICHK(hipEventCreate(&e.e));
-  NICHK(hipEventRecord(ev[0], st));
-  auto up = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
-    hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
-    return e;
-  };
-  auto zero = [&](DevBuf& b, size_t bytes) -> hipError_t {
-    hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) e = hipMemsetAsync(b.p, 0, std::max<size_t>(bytes, 16), st);
-    return e;
-  };
+  DevEvents<3> ev;
+  DevEvents<4> bev;
+  HIPCHK(ctx, ev.create());
+  HIPCHK(ctx, bev.create());
+  HIPCHK(ctx, hipEventRecord(ev[0], st));
 
   // ------------------------------------------------------------ the scene and the duplicate rule
-  NICHK(up(d.nfeat, N.S.nfeat.data(), (size_t)num_images * 4));
-  NICHK(up(d.row0, points2D_offsets, ((size_t)num_images + 1) * 4));
-  NICHK(up(d.img_wh, N.img_wh.data(), N.img_wh.size() * 8));
-  NICHK(up(d.kp, points2D_xy, F * 16));
-  NICHK(up(d.pair_img, N.S.pair_img.data(), N.S.pair_img.size() * 4));
-  NICHK(up(d.moff, match_offsets, ((size_t)num_pairs + 1) * 8));
-  NICHK(up(d.matches, matches, NM * 8));
-  NICHK(d.acc.reserve(std::max<uint64_t>(NM, 16)));
+  HIPCHK(ctx, dev_upload(d.nfeat, N.S.nfeat.data(), (size_t)num_images * 4, st));
+  HIPCHK(ctx, dev_upload(d.row0, points2D_offsets, ((size_t)num_images + 1) * 4, st));
+  HIPCHK(ctx, dev_upload(d.img_wh, N.img_wh.data(), N.img_wh.size() * 8, st));
+  HIPCHK(ctx, dev_upload(d.kp, points2D_xy, F * 16, st));
+  HIPCHK(ctx, dev_upload(d.pair_img, N.S.pair_img.data(), N.S.pair_img.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.moff, match_offsets, ((size_t)num_pairs + 1) * 8, st));
+  HIPCHK(ctx, dev_upload(d.matches, matches, NM * 8, st));
+  HIPCHK(ctx, d.acc.reserve(std::max<uint64_t>(NM, 16)));
   if (num_pairs) {
     hipLaunchKernelGGL(k_rt_dedup, dim3(num_pairs), dim3(NI_BLOCK), 0, st, num_pairs, d.pair_img.as<uint32_t>(), d.moff.as<uint64_t>(),
                        d.matches.as<uint32_t>(), d.nfeat.as<uint32_t>(), d.acc.as<uint8_t>());
-    NICHK(hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
   }
-  NICHK(hipEventRecord(ev[1], st));
+  HIPCHK(ctx, hipEventRecord(ev[1], st));
 
   // ------------------------------------------------------------ the batches: whole problems, cut where the memory budget asks
   std::vector<uint32_t> h_nv(n_slots), h_no(n_slots), h_order(n_slots), h_order_n(num_problems);
@@ -365,7 +339,7 @@ extern "C" IP_MINSIZE int dsm_find_next_images(dsm_ctx* ctx, uint32_t num_camera
   };
   std::vector<uint32_t> b_slot_off, b_ent_off, b_ent_slot, b_slot_prob;
   std::vector<uint64_t> b_obs_off, b_word_off;
-  float ms = 0.f;
+  double ms = 0;
   for (uint32_t p0 = 0; p0 < num_problems;) {
     uint32_t p1 = p0;
     uint64_t bytes = 0;
@@ -384,25 +358,25 @@ extern "C" IP_MINSIZE int dsm_find_next_images(dsm_ctx* ctx, uint32_t num_camera
       for (uint32_t s = b_slot_off[p]; s < b_slot_off[p + 1]; ++s) b_slot_prob[s] = p;
     for (uint32_t s = 0; s <= nS; ++s) b_obs_off[s] = N.obs_off[sb + s] - ob, b_word_off[s] = N.word_off[sb + s] - wb;
     for (size_t i = 0; i < b_ent_slot.size(); ++i) b_ent_slot[i] = N.ent_slot[2 * (size_t)eb + i] - sb;
-    NICHK(hipEventRecord(bev[0], st));
-    NICHK(up(d.slot_off, b_slot_off.data(), b_slot_off.size() * 4));
-    NICHK(up(d.ent_off, b_ent_off.data(), b_ent_off.size() * 4));
-    NICHK(up(d.slot_prob, b_slot_prob.data(), (size_t)nS * 4));
-    NICHK(up(d.slot_img, N.slot_img.data() + sb, (size_t)nS * 4));
-    NICHK(up(d.slot_id, N.slot_id.data() + sb, (size_t)nS * 4));
-    NICHK(up(d.slot_flags, N.slot_flags.data() + sb, (size_t)nS * 4));
-    NICHK(up(d.obs_off, b_obs_off.data(), b_obs_off.size() * 8));
-    NICHK(up(d.word_off, b_word_off.data(), b_word_off.size() * 8));
-    NICHK(up(d.obs_point, nO ? slot_obs_point3D + ob : nullptr, nO * 4));
-    NICHK(up(d.ent_pair, N.ent_pair.data() + eb, (size_t)nE * 4));
-    NICHK(up(d.ent_slot, b_ent_slot.data(), b_ent_slot.size() * 4));
-    NICHK(zero(d.bits, 2 * nW * 4));
-    NICHK(d.num_visible.reserve(std::max<size_t>((size_t)nS * 4, 16)));
-    NICHK(d.num_observations.reserve(std::max<size_t>((size_t)nS * 4, 16)));
-    NICHK(d.score.reserve(std::max<size_t>((size_t)nS * 8, 16)));
-    NICHK(d.key.reserve(std::max<size_t>((size_t)nS * 8, 16)));
-    NICHK(zero(d.order, (size_t)nS * 4));
-    NICHK(zero(d.order_n, (size_t)nP * 4));
+    HIPCHK(ctx, hipEventRecord(bev[0], st));
+    HIPCHK(ctx, dev_upload(d.slot_off, b_slot_off.data(), b_slot_off.size() * 4, st));
+    HIPCHK(ctx, dev_upload(d.ent_off, b_ent_off.data(), b_ent_off.size() * 4, st));
+    HIPCHK(ctx, dev_upload(d.slot_prob, b_slot_prob.data(), (size_t)nS * 4, st));
+    HIPCHK(ctx, dev_upload(d.slot_img, N.slot_img.data() + sb, (size_t)nS * 4, st));
+    HIPCHK(ctx, dev_upload(d.slot_id, N.slot_id.data() + sb, (size_t)nS * 4, st));
+    HIPCHK(ctx, dev_upload(d.slot_flags, N.slot_flags.data() + sb, (size_t)nS * 4, st));
+    HIPCHK(ctx, dev_upload(d.obs_off, b_obs_off.data(), b_obs_off.size() * 8, st));
+    HIPCHK(ctx, dev_upload(d.word_off, b_word_off.data(), b_word_off.size() * 8, st));
+    HIPCHK(ctx, dev_upload(d.obs_point, nO ? slot_obs_point3D + ob : nullptr, nO * 4, st));
+    HIPCHK(ctx, dev_upload(d.ent_pair, N.ent_pair.data() + eb, (size_t)nE * 4, st));
+    HIPCHK(ctx, dev_upload(d.ent_slot, b_ent_slot.data(), b_ent_slot.size() * 4, st));
+    HIPCHK(ctx, dev_fill(d.bits, 0, 2 * nW * 4, st));
+    HIPCHK(ctx, d.num_visible.reserve(std::max<size_t>((size_t)nS * 4, 16)));
+    HIPCHK(ctx, d.num_observations.reserve(std::max<size_t>((size_t)nS * 4, 16)));
+    HIPCHK(ctx, d.score.reserve(std::max<size_t>((size_t)nS * 8, 16)));
+    HIPCHK(ctx, d.key.reserve(std::max<size_t>((size_t)nS * 8, 16)));
+    HIPCHK(ctx, dev_fill(d.order, 0, (size_t)nS * 4, st));
+    HIPCHK(ctx, dev_fill(d.order_n, 0, (size_t)nP * 4, st));
     NiView v;
     v.n_problems = nP, v.n_slots = nS, v.n_entries = nE;
     v.slot_off = d.slot_off.as<uint32_t>(), v.slot_img = d.slot_img.as<uint32_t>(), v.slot_id = d.slot_id.as<uint32_t>();
@@ -418,39 +392,37 @@ extern "C" IP_MINSIZE int dsm_find_next_images(dsm_ctx* ctx, uint32_t num_camera
 #ifdef DSM_CHECK_BUILD
       hipLaunchKernelGGL(k_ni_serial, dim3(1), dim3(1), 0, st, v);
 #endif
-      NICHK(hipEventRecord(bev[1], st));
-      NICHK(hipEventRecord(bev[2], st));
+      HIPCHK(ctx, hipEventRecord(bev[1], st));
+      HIPCHK(ctx, hipEventRecord(bev[2], st));
     } else {
       if (nE) hipLaunchKernelGGL(k_ni_visibility, dim3(nE), dim3(NI_BLOCK), 0, st, v);
-      NICHK(hipEventRecord(bev[1], st));
+      HIPCHK(ctx, hipEventRecord(bev[1], st));
       if (nS) hipLaunchKernelGGL(k_ni_slot, dim3(nS), dim3(64), 0, st, v);
-      NICHK(hipEventRecord(bev[2], st));
+      HIPCHK(ctx, hipEventRecord(bev[2], st));
       if (nS) hipLaunchKernelGGL(k_ni_rank, dim3((nS + NI_BLOCK - 1) / NI_BLOCK), dim3(NI_BLOCK), 0, st, v, d.slot_prob.as<uint32_t>());
     }
-    NICHK(hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
     if (nS) {
-      NICHK(hipMemcpyAsync(h_nv.data() + sb, d.num_visible.p, (size_t)nS * 4, hipMemcpyDeviceToHost, st));
-      NICHK(hipMemcpyAsync(h_no.data() + sb, d.num_observations.p, (size_t)nS * 4, hipMemcpyDeviceToHost, st));
-      NICHK(hipMemcpyAsync(h_score.data() + sb, d.score.p, (size_t)nS * 8, hipMemcpyDeviceToHost, st));
-      NICHK(hipMemcpyAsync(h_order.data() + sb, d.order.p, (size_t)nS * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(h_nv.data() + sb, d.num_visible.p, (size_t)nS * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(h_no.data() + sb, d.num_observations.p, (size_t)nS * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(h_score.data() + sb, d.score.p, (size_t)nS * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(h_order.data() + sb, d.order.p, (size_t)nS * 4, hipMemcpyDeviceToHost, st));
     }
-    NICHK(hipMemcpyAsync(h_order_n.data() + p0, d.order_n.p, (size_t)nP * 4, hipMemcpyDeviceToHost, st));
-    NICHK(hipEventRecord(bev[3], st));
-    NICHK(hipStreamSynchronize(st));
-    NICHK(hipEventElapsedTime(&ms, bev[0], bev[1]));
+    HIPCHK(ctx, hipMemcpyAsync(h_order_n.data() + p0, d.order_n.p, (size_t)nP * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipEventRecord(bev[3], st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, bev.ms(0, 1, &ms));
     rep.visibility_ms += ms;
-    NICHK(hipEventElapsedTime(&ms, bev[1], bev[2]));
+    HIPCHK(ctx, bev.ms(1, 2, &ms));
     rep.score_ms += ms;
-    NICHK(hipEventElapsedTime(&ms, bev[2], bev[3]));
+    HIPCHK(ctx, bev.ms(2, 3, &ms));
     rep.rank_ms += ms;
     p0 = p1;
   }
-  NICHK(hipEventRecord(ev[2], st));
-  NICHK(hipStreamSynchronize(st));
-  NICHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-  rep.graph_ms = ms;
-  NICHK(hipEventElapsedTime(&ms, ev[0], ev[2]));
-  rep.device_ms = ms;
+  HIPCHK(ctx, hipEventRecord(ev[2], st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, ev.ms(0, 1, &rep.graph_ms));
+  HIPCHK(ctx, ev.ms(0, 2, &rep.device_ms));
 
   // ------------------------------------------------------------ the results
   uint64_t total = 0;
@@ -480,7 +452,7 @@ extern "C" IP_MINSIZE int dsm_find_next_images(dsm_ctx* ctx, uint32_t num_camera
 
 extern "C" void dsm_default_local_bundle_selection_options(dsm_local_bundle_selection_options* o) { lb_default_options(o); }
 
-extern "C" IP_MINSIZE int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_images, const uint32_t* image_ids, const uint32_t* points2D_offsets,
+extern "C" int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_images, const uint32_t* image_ids, const uint32_t* points2D_offsets,
                                                  uint32_t num_problems, const uint32_t* problem_image_offsets, const uint32_t* problem_image_ids,
                                                  const uint8_t* slot_registered, const uint64_t* slot_obs_offsets, const int32_t* slot_obs_point3D,
                                                  const double* slot_qvec, const double* slot_tvec, const uint64_t* point_offsets,
@@ -490,10 +462,7 @@ extern "C" IP_MINSIZE int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_imag
                                                  uint64_t* overlap_offsets, uint32_t* overlap_image_ids, uint32_t* overlap_shared,
                                                  double* overlap_tri_angle, uint64_t overlap_capacity, dsm_local_bundle_selection_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](int code, const std::string& msg) {
-    ctx->err = "dsm_find_local_bundles: " + msg;
-    return code;
-  };
+  auto fail = [ctx](int code, const char* msg) { return dsm_fail(ctx, code, "dsm_find_local_bundles", msg); };
   const auto t_host0 = std::chrono::steady_clock::now();
   dsm_local_bundle_selection_options o;
   if (options)
@@ -524,42 +493,32 @@ extern "C" IP_MINSIZE int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_imag
   if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   LbBufs d;
-  DevEvent ev[3], bev[3];
-  for (DevEvent& e : ev) NICHK(hipEventCreate(&e.e));
-  for (DevEvent& e : bev) NICHK(hipEventCreate(&e.e));
-  NICHK(hipEventRecord(ev[0], st));
-  auto up = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
-    hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
-    return e;
-  };
-  auto zero = [&](DevBuf& b, size_t bytes) -> hipError_t {
-    hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) e = hipMemsetAsync(b.p, 0, std::max<size_t>(bytes, 16), st);
-    return e;
-  };
-  auto grid = [](uint64_t n) { return dim3((uint32_t)((n + NI_BLOCK - 1) / NI_BLOCK)); };
+  DevEvents<3> ev, bev;
+  HIPCHK(ctx, ev.create());
+  HIPCHK(ctx, bev.create());
+  HIPCHK(ctx, hipEventRecord(ev[0], st));
+  auto grid = [](uint64_t n) { return dim3(dsm_grid(n, NI_BLOCK)); };
 
   // ------------------------------------------------------------ the state, the centres, the tracks
   std::vector<uint32_t> obs_slot(n_obs);
   for (uint32_t s = 0; s < n_slots; ++s)
     for (uint64_t i = N.obs_off[s]; i < N.obs_off[s + 1]; ++i) obs_slot[i] = s;
-  NICHK(up(d.slot_off, N.slot_off.data(), N.slot_off.size() * 4));
-  NICHK(up(d.slot_id, N.slot_id.data(), (size_t)n_slots * 4));
-  NICHK(up(d.slot_flags, N.slot_flags.data(), (size_t)n_slots * 4));
-  NICHK(up(d.slot_prob, L.slot_prob.data(), (size_t)n_slots * 4));
-  NICHK(up(d.obs_off, N.obs_off.data(), N.obs_off.size() * 8));
-  NICHK(up(d.obs_point, slot_obs_point3D, n_obs * 4));
-  NICHK(up(d.obs_slot, obs_slot.data(), n_obs * 4));
-  NICHK(up(d.point_off, point_offsets, ((size_t)num_problems + 1) * 8));
-  NICHK(up(d.point_xyz, point_xyz, n_points * 24));
-  NICHK(up(d.pose, L.pose.data(), L.pose.size() * 8));
-  NICHK(d.center.reserve(std::max<size_t>((size_t)n_slots * 24, 16)));
-  NICHK(zero(d.trk_start, (n_points + 1) * 4));
-  NICHK(zero(d.trk_fill, n_points * 4));
-  NICHK(d.trk_slot.reserve(std::max<uint64_t>(n_obs * 4, 16)));
-  NICHK(up(d.q_slot, L.q_slot.data(), (size_t)num_queries * 4));
-  NICHK(up(d.row_off, L.row_off.data(), L.row_off.size() * 8));
+  HIPCHK(ctx, dev_upload(d.slot_off, N.slot_off.data(), N.slot_off.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.slot_id, N.slot_id.data(), (size_t)n_slots * 4, st));
+  HIPCHK(ctx, dev_upload(d.slot_flags, N.slot_flags.data(), (size_t)n_slots * 4, st));
+  HIPCHK(ctx, dev_upload(d.slot_prob, L.slot_prob.data(), (size_t)n_slots * 4, st));
+  HIPCHK(ctx, dev_upload(d.obs_off, N.obs_off.data(), N.obs_off.size() * 8, st));
+  HIPCHK(ctx, dev_upload(d.obs_point, slot_obs_point3D, n_obs * 4, st));
+  HIPCHK(ctx, dev_upload(d.obs_slot, obs_slot.data(), n_obs * 4, st));
+  HIPCHK(ctx, dev_upload(d.point_off, point_offsets, ((size_t)num_problems + 1) * 8, st));
+  HIPCHK(ctx, dev_upload(d.point_xyz, point_xyz, n_points * 24, st));
+  HIPCHK(ctx, dev_upload(d.pose, L.pose.data(), L.pose.size() * 8, st));
+  HIPCHK(ctx, d.center.reserve(std::max<size_t>((size_t)n_slots * 24, 16)));
+  HIPCHK(ctx, dev_fill(d.trk_start, 0, (n_points + 1) * 4, st));
+  HIPCHK(ctx, dev_fill(d.trk_fill, 0, n_points * 4, st));
+  HIPCHK(ctx, d.trk_slot.reserve(std::max<uint64_t>(n_obs * 4, 16)));
+  HIPCHK(ctx, dev_upload(d.q_slot, L.q_slot.data(), (size_t)num_queries * 4, st));
+  HIPCHK(ctx, dev_upload(d.row_off, L.row_off.data(), L.row_off.size() * 8, st));
   LbView v;
   v.n_problems = num_problems, v.n_slots = n_slots, v.n_queries = num_queries, v.n_obs = n_obs, v.n_points = n_points;
   v.slot_off = d.slot_off.as<uint32_t>(), v.slot_id = d.slot_id.as<uint32_t>(), v.slot_flags = d.slot_flags.as<uint32_t>();
@@ -578,8 +537,8 @@ extern "C" IP_MINSIZE int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_imag
     hipLaunchKernelGGL(k_lb_scan, dim3(1), dim3(NI_BLOCK), 0, st, d.trk_start.as<uint32_t>(), n_points);
     if (n_obs) hipLaunchKernelGGL(k_lb_track_hist, grid(n_obs), dim3(NI_BLOCK), 0, st, v, d.obs_slot.as<uint32_t>(), 1);
   }
-  NICHK(hipGetLastError());
-  NICHK(hipEventRecord(ev[1], st));
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipEventRecord(ev[1], st));
 
   // ------------------------------------------------------------ the batches: whole queries, cut where the memory budget asks
   struct Answer {
@@ -596,7 +555,7 @@ extern "C" IP_MINSIZE int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_imag
   std::vector<uint64_t> it_off;
   std::vector<double> it_angle;
   std::vector<uint8_t> used;
-  float ms = 0.f;
+  double ms = 0;
   for (uint32_t q0 = 0; q0 < num_queries;) {
     uint32_t q1 = q0;
     uint64_t bytes = 0;
@@ -611,12 +570,12 @@ extern "C" IP_MINSIZE int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_imag
     row_query.resize(n_rows);
     for (uint32_t q = q0; q < q1; ++q)
       for (uint64_t r = L.row_off[q]; r < L.row_off[q + 1]; ++r) row_query[r - r_base] = q;
-    NICHK(hipEventRecord(bev[0], st));
-    NICHK(up(d.row_query, row_query.data(), n_rows * 4));
-    NICHK(zero(d.shared, n_rows * 4));
-    NICHK(zero(d.ov_slot, n_rows * 4));
-    NICHK(zero(d.q_points, (size_t)nq * 4));
-    NICHK(zero(d.ov_n, (size_t)nq * 4));
+    HIPCHK(ctx, hipEventRecord(bev[0], st));
+    HIPCHK(ctx, dev_upload(d.row_query, row_query.data(), n_rows * 4, st));
+    HIPCHK(ctx, dev_fill(d.shared, 0, n_rows * 4, st));
+    HIPCHK(ctx, dev_fill(d.ov_slot, 0, n_rows * 4, st));
+    HIPCHK(ctx, dev_fill(d.q_points, 0, (size_t)nq * 4, st));
+    HIPCHK(ctx, dev_fill(d.ov_n, 0, (size_t)nq * 4, st));
     v.shared = d.shared.as<uint32_t>(), v.q_points = d.q_points.as<uint32_t>(), v.ov_slot = d.ov_slot.as<uint32_t>(), v.ov_n = d.ov_n.as<uint32_t>();
     if (serial) {
 #ifdef DSM_CHECK_BUILD
@@ -626,16 +585,16 @@ extern "C" IP_MINSIZE int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_imag
       hipLaunchKernelGGL(k_lb_shared, dim3(nq), dim3(NI_BLOCK), 0, st, v, q0, nq);
       if (n_rows) hipLaunchKernelGGL(k_lb_overlap_rank, grid(n_rows), dim3(NI_BLOCK), 0, st, v, q0, n_rows, d.row_query.as<uint32_t>());
     }
-    NICHK(hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
     h_shared.resize(n_rows), h_ov_slot.resize(n_rows), h_ov_n.resize(nq), h_points.resize(nq);
     if (n_rows) {
-      NICHK(hipMemcpyAsync(h_shared.data(), d.shared.p, n_rows * 4, hipMemcpyDeviceToHost, st));
-      NICHK(hipMemcpyAsync(h_ov_slot.data(), d.ov_slot.p, n_rows * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(h_shared.data(), d.shared.p, n_rows * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(h_ov_slot.data(), d.ov_slot.p, n_rows * 4, hipMemcpyDeviceToHost, st));
     }
-    NICHK(hipMemcpyAsync(h_ov_n.data(), d.ov_n.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-    NICHK(hipMemcpyAsync(h_points.data(), d.q_points.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-    NICHK(hipEventRecord(bev[1], st));
-    NICHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpyAsync(h_ov_n.data(), d.ov_n.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(h_points.data(), d.q_points.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipEventRecord(bev[1], st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     // the overlap lists; the items: every image a threshold of a chained query can reach
     it_slots.clear(), it_count.clear(), it_query.clear(), it_off.assign(1, 0);
     for (uint32_t q = q0; q < q1; ++q) {
@@ -658,11 +617,11 @@ extern "C" IP_MINSIZE int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_imag
     const uint32_t n_items = (uint32_t)it_count.size();
     it_angle.resize(n_items);
     if (n_items) {
-      NICHK(up(d.it_slots, it_slots.data(), it_slots.size() * 4));
-      NICHK(up(d.it_off, it_off.data(), it_off.size() * 8));
-      NICHK(up(d.it_count, it_count.data(), it_count.size() * 4));
-      NICHK(d.it_bits.reserve(std::max<uint64_t>(it_off.back() * 8, 16)));
-      NICHK(d.it_angle.reserve((size_t)n_items * 8));
+      HIPCHK(ctx, dev_upload(d.it_slots, it_slots.data(), it_slots.size() * 4, st));
+      HIPCHK(ctx, dev_upload(d.it_off, it_off.data(), it_off.size() * 8, st));
+      HIPCHK(ctx, dev_upload(d.it_count, it_count.data(), it_count.size() * 4, st));
+      HIPCHK(ctx, d.it_bits.reserve(std::max<uint64_t>(it_off.back() * 8, 16)));
+      HIPCHK(ctx, d.it_angle.reserve((size_t)n_items * 8));
       LbItems it{n_items, d.it_slots.as<uint32_t>(), d.it_off.as<uint64_t>(), d.it_count.as<uint32_t>(), d.it_bits.as<uint64_t>(), d.it_angle.as<double>()};
       if (serial) {
 #ifdef DSM_CHECK_BUILD
@@ -671,14 +630,14 @@ extern "C" IP_MINSIZE int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_imag
       } else {
         hipLaunchKernelGGL(k_lb_tri_angle, dim3(n_items), dim3(64), 0, st, v, it);
       }
-      NICHK(hipGetLastError());
-      NICHK(hipMemcpyAsync(it_angle.data(), d.it_angle.p, (size_t)n_items * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipGetLastError());
+      HIPCHK(ctx, hipMemcpyAsync(it_angle.data(), d.it_angle.p, (size_t)n_items * 8, hipMemcpyDeviceToHost, st));
     }
-    NICHK(hipEventRecord(bev[2], st));
-    NICHK(hipStreamSynchronize(st));
-    NICHK(hipEventElapsedTime(&ms, bev[0], bev[1]));
+    HIPCHK(ctx, hipEventRecord(bev[2], st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, bev.ms(0, 1, &ms));
     rep.overlap_ms += ms;
-    NICHK(hipEventElapsedTime(&ms, bev[1], bev[2]));
+    HIPCHK(ctx, bev.ms(1, 2, &ms));
     rep.angles_ms += ms;
     rep.num_angles += n_items;
     for (uint32_t c = 0; c < n_items; ++c) answers[it_query[2 * c]].tri_angle[it_query[2 * c + 1]] = it_angle[c];
@@ -700,12 +659,10 @@ extern "C" IP_MINSIZE int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_imag
     }
     q0 = q1;
   }
-  NICHK(hipEventRecord(ev[2], st));
-  NICHK(hipStreamSynchronize(st));
-  NICHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-  rep.tracks_ms = ms;
-  NICHK(hipEventElapsedTime(&ms, ev[0], ev[2]));
-  rep.device_ms = ms;
+  HIPCHK(ctx, hipEventRecord(ev[2], st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, ev.ms(0, 1, &rep.tracks_ms));
+  HIPCHK(ctx, ev.ms(0, 2, &rep.device_ms));
 
   // ------------------------------------------------------------ the results
   uint64_t n_bundle = 0, n_overlap = 0;

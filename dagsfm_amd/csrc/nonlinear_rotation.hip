@@ -722,9 +722,7 @@ extern "C" int dsm_view_graph_rotation_averaging_nonlinear(dsm_ctx* ctx, uint32_
     if (trace && h.iter >= 0)
       HIPTRY(hipMemcpyAsync(trace, d_trace.p, ((size_t)h.iter + 1) * DSM_NLR_TRACE_COLUMNS * 8, hipMemcpyDeviceToHost, st));
     HIPTRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIPTRY(hipEventElapsedTime(&ms, ev0, ev1));
-    rep.device_ms = ms;
+    HIPTRY(dev_events_ms(ev0, ev1, &rep.device_ms));
   }
   if (rc != DSM_OK) (void)hipStreamSynchronize(st);
   rep.termination = h.term == NL_LINEAR_SOLVER_FAILED || !h.done ? DSM_BA_FAILURE : h.term;

@@ -1111,10 +1111,7 @@ extern "C" int dsm_patch_match(dsm_ctx* ctx, const dsm_patch_match_options* opti
                                const float* depth_min, const float* depth_max, float* const* out_depth, float* const* out_normal,
                                float* const* out_sel_prob, uint8_t* const* out_mask) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_patch_match: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_patch_match", msg); };
   dsm_patch_match_options o;
   if (options)
     o = *options;
@@ -1284,8 +1281,8 @@ extern "C" int dsm_patch_match(dsm_ctx* ctx, const dsm_patch_match_options* opti
   P.tex = d_tables + taps_floats + 256;
 
   const int total_sweeps = 4 * o.num_iterations;
-  std::vector<DevEvent> ev(5 + 2 * (size_t)total_sweeps);
-  for (DevEvent& e : ev) HIPCHK(ctx, hipEventCreate(&e.e));
+  DevEventList ev(5 + 2 * (size_t)total_sweeps);
+  HIPCHK(ctx, ev.create());
 
   bool resident_uploaded = false;
   const size_t smem = 2048 + (size_t)(2 * radius + 1) * 3 * PM_LANES;
@@ -1484,8 +1481,8 @@ extern "C" int dsm_patch_match(dsm_ctx* ctx, const dsm_patch_match_options* opti
     HIPCHK(ctx, hipEventRecord(ev[e++], st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     for (size_t k = 0; k + 1 < e; ++k) {
-      float t = 0.0f;
-      HIPCHK(ctx, hipEventElapsedTime(&t, ev[k], ev[k + 1]));
+      double t = 0;
+      HIPCHK(ctx, ev.ms(k, k + 1, &t));
       int stage;
       if (k < 3)
         stage = (int)k;

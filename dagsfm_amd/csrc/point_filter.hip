@@ -32,6 +32,8 @@
 #include "block_reduce.h"
 #include "camera_bogus.h"
 #include "ctx.h"
+#include "tri_angle.h"
+#include "wave_reduce.h"
 
 namespace {
 
@@ -79,19 +81,6 @@ __device__ inline double pf_margin(double a, double thr) {
   if (!isfinite(a)) return INFINITY;
   const double den = fmax(fabs(a), fabs(thr));
   return den > 0.0 ? fabs(a - thr) / den : 0.0;
-}
-
-template <int W>
-__device__ inline uint32_t pf_sum(uint32_t v) {
-  if (W == 64)
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-template <int W>
-__device__ inline double pf_min(double v) {
-  if (W == 64)
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-  return v;
 }
 
 // the one instantiation of the projection this file carries (ba_project.h's double path)
@@ -155,7 +144,7 @@ __device__ inline void pf_track(const PfParams& p, uint32_t pid, int lane) {
   if (p.isel && !sel) {
     uint32_t any = 0;
     for (uint32_t i = lane; i < L; i += W) any += p.isel[p.oimg[b + i]] != 0;
-    sel = pf_sum<W>(any) != 0;
+    sel = (W == 64 ? wave_sum(any) : any) != 0;
   }
   uint32_t n_neg = 0;
   double mgd = INFINITY;
@@ -164,8 +153,8 @@ __device__ inline void pf_track(const PfParams& p, uint32_t pid, int lane) {
     mgd = fmin(mgd, pf_margin(d, DBL_EPSILON));
     n_neg += d < DBL_EPSILON;
   }
-  n_neg = pf_sum<W>(n_neg);
-  mgd = pf_min<W>(mgd);
+  if (W == 64) n_neg = wave_sum(n_neg);
+  if (W == 64) mgd = wave_fmin(mgd);
   if (!((p.passes & 1u) || (sel && (p.passes & 10u)))) mgd = INFINITY;
   bool keep = true, drop_neg = false, drop_err = false;
   uint32_t len = L, nf1 = 0, od1 = 0, nf2 = 0, od2 = 0, delpass = 0;
@@ -197,8 +186,8 @@ __device__ inline void pf_track(const PfParams& p, uint32_t pid, int lane) {
         if (e != DBL_MAX) mge = fmin(mge, pf_margin(e, p.thr2));
         marked += e > p.thr2;
       }
-      marked = pf_sum<W>(marked);
-      mge = pf_min<W>(mge);
+      if (W == 64) marked = wave_sum(marked);
+      if (W == 64) mge = wave_fmin(mge);
       if (marked >= len - 1) {
         keep = false;
         delpass = 2;
@@ -244,21 +233,6 @@ __device__ inline void pf_track(const PfParams& p, uint32_t pid, int lane) {
   }
 }
 
-// CalculateTriangulationAngle (triangulation.cc:122-145); NaN when the ratio rounds outside [-1, 1], as the reference's
-__device__ inline double pf_tri_angle(const double* c1, const double* c2, const double* X) {
-  const double b0 = c1[0] - c2[0], b1 = c1[1] - c2[1], b2 = c1[2] - c2[2];
-  const double r0 = X[0] - c1[0], r1 = X[1] - c1[1], r2 = X[2] - c1[2];
-  const double s0 = X[0] - c2[0], s1 = X[1] - c2[1], s2 = X[2] - c2[2];
-  const double base2 = (b0 * b0 + b1 * b1) + b2 * b2;
-  const double ray1 = (r0 * r0 + r1 * r1) + r2 * r2, ray2 = (s0 * s0 + s1 * s1) + s2 * s2;
-  const double den = 2.0 * sqrt(ray1 * ray2);
-  if (den == 0.0) return 0.0;
-  const double nom = (ray1 + ray2) - base2;
-  const double a = fabs(acos(nom / den));
-  const double c = M_PI - a;
-  return c < a ? c : a;  // std::min(a, c): NaN stays NaN
-}
-
 // pass 3 of one point
 template <int W>
 __device__ inline void pf_angles(const PfParams& p, uint32_t pid, int lane) {
@@ -277,7 +251,7 @@ __device__ inline void pf_angles(const PfParams& p, uint32_t pid, int lane) {
       const double* c1 = p.pose + (size_t)PF_POSE * p.oimg[b + i1] + 12;
       for (uint32_t i2 = 0; i2 < i1; ++i2) {
         if (!p.alive[b + i2]) continue;
-        const double a = pf_tri_angle(c1, p.pose + (size_t)PF_POSE * p.oimg[b + i2] + 12, X);
+        const double a = tri_angle_libm(c1, p.pose + (size_t)PF_POSE * p.oimg[b + i2] + 12, X);
         ++pairs;
         const double m = pf_margin(a, p.min_angle);
         if (a >= p.min_angle) {
@@ -313,7 +287,7 @@ __device__ inline void pf_angles(const PfParams& p, uint32_t pid, int lane) {
         while (i1 * (i1 - 1) / 2 > k) --i1;
         while ((i1 + 1) * i1 / 2 <= k) ++i1;
         const uint64_t i2 = k - i1 * (i1 - 1) / 2;
-        const double a = pf_tri_angle(p.pose + (size_t)PF_POSE * p.alist[b + i1] + 12, p.pose + (size_t)PF_POSE * p.alist[b + i2] + 12, X);
+        const double a = tri_angle_libm(p.pose + (size_t)PF_POSE * p.alist[b + i1] + 12, p.pose + (size_t)PF_POSE * p.alist[b + i2] + 12, X);
         m = pf_margin(a, p.min_angle);
         pass = a >= p.min_angle;
       }
@@ -324,7 +298,7 @@ __device__ inline void pf_angles(const PfParams& p, uint32_t pid, int lane) {
         pairs += (uint64_t)first + 1;
         found = true;
       } else {
-        mg = fmin(mg, pf_min<64>(m));
+        mg = fmin(mg, wave_fmin(m));
         pairs += min((uint64_t)64, total - base);
       }
     }
@@ -351,7 +325,7 @@ __device__ inline void pf_mean(const PfParams& p, uint32_t pid, int lane) {
   const uint32_t b = p.toff[pid], L = p.toff[pid + 1] - b;
   uint32_t len = 0;
   for (uint32_t i = lane; i < L; i += W) len += p.alive[b + i] != 0;
-  len = pf_sum<W>(len);
+  if (W == 64) len = wave_sum(len);
   if (lane != 0) return;
   double s = 0.0;
   for (uint32_t i = 0; i < L; ++i) {
@@ -444,11 +418,6 @@ __global__ void __launch_bounds__(PF_BLOCK) k_pf_verdict(uint32_t N, const uint3
   filtered[i] = (!reg || reg[i]) && (!img_has[i] || cam_bogus[img_cam[i]]);
 }
 
-__device__ inline uint64_t pf_wave_sum64(uint64_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o);
-  return v;
-}
-
 // Block k takes the points [k * chunk, (k + 1) * chunk): the per-point results out (keep, error), the counts to ctr (integer
 // atomics), the margins' minima to mg (atomicMin on the bit patterns: non-negative doubles order like their bits), and the
 // block's partials of the two sums to part[0 .. nb), part[nb .. 2 nb)
@@ -483,11 +452,11 @@ __global__ void __launch_bounds__(PF_BLOCK) k_pf_reduce(uint32_t P, uint32_t chu
     m[2] = fmin(m[2], q.mg_angle);
   }
   for (int k = 0; k < PF_COUNTERS; ++k) {
-    const uint64_t s = pf_wave_sum64(c[k]);
+    const uint64_t s = wave_sum(c[k]);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(&ctr[k], (unsigned long long)s);
   }
   for (int k = 0; k < 3; ++k) {
-    const double s = pf_min<64>(m[k]);
+    const double s = wave_fmin(m[k]);
     if ((threadIdx.x & 63) == 0) atomicMin(&mg[k], (unsigned long long)__double_as_longlong(s));
   }
   write_partials<PF_BLOCK, 2>(v, sh, part);
@@ -532,7 +501,6 @@ hipError_t pf_scan(PfBufs& d, uint32_t n, hipStream_t st) {
   return hipGetLastError();
 }
 
-inline uint32_t pf_grid(uint64_t n) { return (uint32_t)((n + PF_BLOCK - 1) / PF_BLOCK); }
 
 }  // namespace
 
@@ -555,10 +523,7 @@ extern "C" int dsm_filter_points3D(dsm_ctx* ctx, uint32_t num_cameras, const dsm
                                    double* point_error, uint32_t* kept_track_offsets, uint32_t* kept_obs, uint8_t* image_filtered,
                                    dsm_point_filter_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_filter_points3D: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_filter_points3D", msg); };
   const auto t_host0 = std::chrono::steady_clock::now();
   const uint32_t C = num_cameras, N = num_images, P = num_points;
   if (!track_offsets || (C && !cameras) || (N && (!image_camera || !image_qvec || !image_tvec)) || (P && !point_xyz))
@@ -618,33 +583,23 @@ extern "C" int dsm_filter_points3D(dsm_ctx* ctx, uint32_t num_cameras, const dsm
   if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   PfBufs d;
-  DevEvent ev[8];
-  for (int i = 0; i < 8; ++i) HIPCHK(ctx, hipEventCreate(&ev[i].e));
+  DevEvents<8> ev;
+  HIPCHK(ctx, ev.create());
   HIPCHK(ctx, hipEventRecord(ev[0], st));
-  auto up = [&](DevBuf& buf, const void* src, size_t bytes) -> hipError_t {
-    hipError_t e = buf.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess && bytes && src) e = hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st);
-    return e;
-  };
-  auto zero = [&](DevBuf& buf, size_t bytes) -> hipError_t {
-    hipError_t e = buf.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) e = hipMemsetAsync(buf.p, 0, std::max<size_t>(bytes, 16), st);
-    return e;
-  };
-  HIPCHK(ctx, up(d.cams, cameras, (size_t)C * sizeof(dsm_camera)));
-  HIPCHK(ctx, up(d.cam_bogus, cam_bogus.data(), cam_bogus.size()));
-  HIPCHK(ctx, up(d.img_cam, image_camera, (size_t)N * 4));
-  HIPCHK(ctx, up(d.img_q, image_qvec, (size_t)N * 32));
-  HIPCHK(ctx, up(d.img_t, image_tvec, (size_t)N * 24));
-  if (image_registered) HIPCHK(ctx, up(d.reg, image_registered, N));
-  HIPCHK(ctx, up(d.xyz, point_xyz, (size_t)P * 24));
-  HIPCHK(ctx, up(d.toff, track_offsets, ((size_t)P + 1) * 4));
-  HIPCHK(ctx, up(d.oimg, obs_image, (size_t)n * 4));
-  HIPCHK(ctx, up(d.oxy, obs_xy, (size_t)n * 16));
-  if (point_selected) HIPCHK(ctx, up(d.psel, point_selected, P));
-  if (image_selected) HIPCHK(ctx, up(d.isel, image_selected, N));
-  HIPCHK(ctx, up(d.lane_list, lane_list.data(), lane_list.size() * 4));
-  HIPCHK(ctx, up(d.wave_list, wave_list.data(), wave_list.size() * 4));
+  HIPCHK(ctx, dev_upload(d.cams, cameras, (size_t)C * sizeof(dsm_camera), st));
+  HIPCHK(ctx, dev_upload(d.cam_bogus, cam_bogus.data(), cam_bogus.size(), st));
+  HIPCHK(ctx, dev_upload(d.img_cam, image_camera, (size_t)N * 4, st));
+  HIPCHK(ctx, dev_upload(d.img_q, image_qvec, (size_t)N * 32, st));
+  HIPCHK(ctx, dev_upload(d.img_t, image_tvec, (size_t)N * 24, st));
+  if (image_registered) HIPCHK(ctx, dev_upload(d.reg, image_registered, N, st));
+  HIPCHK(ctx, dev_upload(d.xyz, point_xyz, (size_t)P * 24, st));
+  HIPCHK(ctx, dev_upload(d.toff, track_offsets, ((size_t)P + 1) * 4, st));
+  HIPCHK(ctx, dev_upload(d.oimg, obs_image, (size_t)n * 4, st));
+  HIPCHK(ctx, dev_upload(d.oxy, obs_xy, (size_t)n * 16, st));
+  if (point_selected) HIPCHK(ctx, dev_upload(d.psel, point_selected, P, st));
+  if (image_selected) HIPCHK(ctx, dev_upload(d.isel, image_selected, N, st));
+  HIPCHK(ctx, dev_upload(d.lane_list, lane_list.data(), lane_list.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.wave_list, wave_list.data(), wave_list.size() * 4, st));
   HIPCHK(ctx, d.pose.reserve(std::max<size_t>(N, 1) * PF_POSE * 8));
   HIPCHK(ctx, d.depth.reserve((size_t)n * 8 + 16));
   HIPCHK(ctx, d.e2.reserve((size_t)n * 8 + 16));
@@ -656,19 +611,19 @@ extern "C" int dsm_filter_points3D(dsm_ctx* ctx, uint32_t num_cameras, const dsm
   HIPCHK(ctx, d.kobs.reserve((size_t)n * 4 + 16));
   HIPCHK(ctx, d.koff.reserve(((size_t)P + 1) * 4 + 16));
   HIPCHK(ctx, d.okeep.reserve((size_t)n + 16));
-  HIPCHK(ctx, zero(d.img_has, N));
+  HIPCHK(ctx, dev_fill(d.img_has, 0, N, st));
   HIPCHK(ctx, d.filtered.reserve((size_t)N + 16));
   HIPCHK(ctx, d.pkeep.reserve((size_t)P + 16));
   HIPCHK(ctx, d.perr.reserve((size_t)P * 8 + 16));
   // counters, then the three margins' bit patterns (INFINITY), then the two sums
-  const uint32_t nb = std::max<uint32_t>(1, std::min<uint32_t>(PF_REDUCE_BLOCKS, pf_grid(P)));
+  const uint32_t nb = std::max<uint32_t>(1, std::min<uint32_t>(PF_REDUCE_BLOCKS, dsm_grid(P, PF_BLOCK)));
   const uint32_t chunk = (P + nb - 1) / nb;
   std::vector<unsigned long long> ctr0(PF_COUNTERS + 3 + 2, 0);
   {
     const double inf = INFINITY;
     for (int k = 0; k < 3; ++k) memcpy(&ctr0[PF_COUNTERS + k], &inf, 8);
   }
-  HIPCHK(ctx, up(d.ctr, ctr0.data(), ctr0.size() * 8));
+  HIPCHK(ctx, dev_upload(d.ctr, ctr0.data(), ctr0.size() * 8, st));
   HIPCHK(ctx, d.part.reserve((size_t)2 * nb * 8));
 
   PfParams prm;
@@ -699,28 +654,28 @@ extern "C" int dsm_filter_points3D(dsm_ctx* ctx, uint32_t num_cameras, const dsm
   const uint32_t* ll = d.lane_list.as<uint32_t>();
   const uint32_t* wl = d.wave_list.as<uint32_t>();
   HIPCHK(ctx, hipEventRecord(ev[1], st));
-  if (N) hipLaunchKernelGGL(k_pf_images, dim3(pf_grid(N)), dim3(PF_BLOCK), 0, st, prm);
-  if (n) hipLaunchKernelGGL(k_pf_residuals, dim3(pf_grid(n)), dim3(PF_BLOCK), 0, st, prm);
+  if (N) hipLaunchKernelGGL(k_pf_images, dim3(dsm_grid(N, PF_BLOCK)), dim3(PF_BLOCK), 0, st, prm);
+  if (n) hipLaunchKernelGGL(k_pf_residuals, dim3(dsm_grid(n, PF_BLOCK)), dim3(PF_BLOCK), 0, st, prm);
   HIPCHK(ctx, hipEventRecord(ev[2], st));
-  if (nl) hipLaunchKernelGGL(k_pf_lane<0>, dim3(pf_grid(nl)), dim3(PF_BLOCK), 0, st, prm, ll, nl);
+  if (nl) hipLaunchKernelGGL(k_pf_lane<0>, dim3(dsm_grid(nl, PF_BLOCK)), dim3(PF_BLOCK), 0, st, prm, ll, nl);
   if (nw) hipLaunchKernelGGL(k_pf_wave<0>, dim3(nw), dim3(64), 0, st, prm, wl, nw);
   HIPCHK(ctx, hipEventRecord(ev[3], st));
   if (o.passes & DSM_FILTER_TRIANGULATION_ANGLE) {
-    if (nl) hipLaunchKernelGGL(k_pf_lane<1>, dim3(pf_grid(nl)), dim3(PF_BLOCK), 0, st, prm, ll, nl);
+    if (nl) hipLaunchKernelGGL(k_pf_lane<1>, dim3(dsm_grid(nl, PF_BLOCK)), dim3(PF_BLOCK), 0, st, prm, ll, nl);
     if (nw) hipLaunchKernelGGL(k_pf_wave<1>, dim3(nw), dim3(64), 0, st, prm, wl, nw);
   }
   HIPCHK(ctx, hipEventRecord(ev[4], st));
   if (o.passes & DSM_FILTER_MEAN_ERROR) {
-    if (nl) hipLaunchKernelGGL(k_pf_lane<2>, dim3(pf_grid(nl)), dim3(PF_BLOCK), 0, st, prm, ll, nl);
+    if (nl) hipLaunchKernelGGL(k_pf_lane<2>, dim3(dsm_grid(nl, PF_BLOCK)), dim3(PF_BLOCK), 0, st, prm, ll, nl);
     if (nw) hipLaunchKernelGGL(k_pf_wave<2>, dim3(nw), dim3(64), 0, st, prm, wl, nw);
   }
   HIPCHK(ctx, hipEventRecord(ev[5], st));
-  hipLaunchKernelGGL(k_pf_flags, dim3(pf_grid((uint64_t)n + 1)), dim3(PF_BLOCK), 0, st, prm, d.flag.as<uint32_t>(), d.okeep.as<uint8_t>());
+  hipLaunchKernelGGL(k_pf_flags, dim3(dsm_grid((uint64_t)n + 1, PF_BLOCK)), dim3(PF_BLOCK), 0, st, prm, d.flag.as<uint32_t>(), d.okeep.as<uint8_t>());
   HIPCHK(ctx, pf_scan(d, n + 1, st));
-  hipLaunchKernelGGL(k_pf_emit, dim3(pf_grid(std::max<uint64_t>(n, (uint64_t)P + 1))), dim3(PF_BLOCK), 0, st, prm, d.flag.as<uint32_t>(),
+  hipLaunchKernelGGL(k_pf_emit, dim3(dsm_grid(std::max<uint64_t>(n, (uint64_t)P + 1), PF_BLOCK)), dim3(PF_BLOCK), 0, st, prm, d.flag.as<uint32_t>(),
                      d.pos.as<uint32_t>(), d.kobs.as<uint32_t>(), d.koff.as<uint32_t>(), d.img_has.as<uint8_t>());
   if (N)
-    hipLaunchKernelGGL(k_pf_verdict, dim3(pf_grid(N)), dim3(PF_BLOCK), 0, st, N, prm.img_cam, image_registered ? d.reg.as<uint8_t>() : nullptr,
+    hipLaunchKernelGGL(k_pf_verdict, dim3(dsm_grid(N, PF_BLOCK)), dim3(PF_BLOCK), 0, st, N, prm.img_cam, image_registered ? d.reg.as<uint8_t>() : nullptr,
                        d.img_has.as<uint8_t>(), d.cam_bogus.as<uint8_t>(), d.filtered.as<uint8_t>());
   unsigned long long* ctr = d.ctr.as<unsigned long long>();
   hipLaunchKernelGGL(k_pf_reduce, dim3(nb), dim3(PF_BLOCK), 0, st, P, chunk, prm.pts, d.pkeep.as<uint8_t>(), d.perr.as<double>(), ctr,
@@ -764,16 +719,15 @@ extern "C" int dsm_filter_points3D(dsm_ctx* ctx, uint32_t num_cameras, const dsm
     rep.num_images_filtered += filt[i];
     if (image_filtered) image_filtered[i] = filt[i];
   }
-  float t[7] = {0, 0, 0, 0, 0, 0, 0}, tot = 0;
-  for (int i = 0; i < 7; ++i) HIPCHK(ctx, hipEventElapsedTime(&t[i], ev[i], ev[i + 1]));
-  HIPCHK(ctx, hipEventElapsedTime(&tot, ev[0], ev[7]));
+  double t[7] = {0, 0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < 7; ++i) HIPCHK(ctx, ev.ms(i, i + 1, &t[i]));
+  HIPCHK(ctx, ev.ms(0, 7, &rep.device_ms));
   rep.upload_ms = t[0];
   rep.residuals_ms = t[1];
   rep.tracks_ms = t[2] + t[4];
   rep.angles_ms = t[3];
   rep.compaction_ms = t[5];
   rep.download_ms = t[6];
-  rep.device_ms = tot;
   if (report) *report = rep;
   return DSM_OK;
 }

@@ -23,6 +23,7 @@
 #include "ba_project.h"
 #include "ctx.h"
 #include "trust_region.h"
+#include "wave_reduce.h"
 
 namespace {
 
@@ -79,11 +80,6 @@ __device__ __noinline__ void pr_project(int model, int np, const double* prm, do
 }
 __device__ __noinline__ void pr_quat_plus(const double* x, const double* d, double* out) { ba_quat_plus(x, d, out); }
 
-__device__ inline double pr_wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // The cost 1/2 sum rho(|r|^2) of state st over the inlier points (every lane returns it); with jac the corrected rows go to the
 // workspace.  Corrector (ceres/internal/corrector.cc): CauchyLoss has rho'' < 0, so the first branch holds for every residual:
 // residual and Jacobian rows are both scaled by sqrt(rho').
@@ -128,7 +124,7 @@ __device__ __noinline__ double pr_eval(const PrView& v, const PrShared* sm, cons
     row[(size_t)(2 * PR_P) * N] = sq * r0;
     row[(size_t)(2 * PR_P + 1) * N] = sq * r1;
   }
-  return pr_wave_sum(acc);
+  return wave_sum(acc);
 }
 
 // J'J (row a: entries a .. P - 1) and J'r from the workspace rows, one row of the triangle per pass
@@ -149,7 +145,7 @@ __device__ __noinline__ void pr_normal(const PrView& v, PrShared* sm, int lane) 
       acc[PR_P] += j0 * row[(size_t)(2 * PR_P) * N] + j1 * row[(size_t)(2 * PR_P + 1) * N];
     }
 #pragma unroll
-    for (int b = 0; b <= PR_P; ++b) acc[b] = pr_wave_sum(acc[b]);
+    for (int b = 0; b <= PR_P; ++b) acc[b] = wave_sum(acc[b]);
     if (lane == 0) {
 #pragma unroll
       for (int b = 0; b < PR_P; ++b)
@@ -272,7 +268,7 @@ __global__ void __launch_bounds__(64) k_pr_refine(PrParams p) {
   v.c = p.c;
   int n_in = 0;
   for (int i = lane; i < v.N; i += 64) n_in += v.mask[i] != 0;
-  for (int o = 32; o > 0; o >>= 1) n_in += __shfl_xor(n_in, o);
+  n_in = wave_sum(n_in);
   dsm_pose_refinement_result* out = &p.res[b];
   if (lane == 0) {
     tr_init(&sm, kTrInitialRadius);
@@ -382,10 +378,7 @@ extern "C" int dsm_refine_absolute_poses(dsm_ctx* ctx, uint32_t num_problems, co
                                          const dsm_pose_refinement_options* options, dsm_pose_refinement_result* results_out,
                                          double* margins_out, uint8_t* steps_out, dsm_pose_refinement_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_refine_absolute_poses: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_refine_absolute_poses", msg); };
   const auto t_host0 = std::chrono::steady_clock::now();
   const uint32_t B = num_problems;
   if (!offsets || (B && (!cameras || !qvecs_in || !tvecs_in || !refine_flags || !results_out))) return fail("NULL argument");
@@ -434,23 +427,18 @@ extern "C" int dsm_refine_absolute_poses(dsm_ctx* ctx, uint32_t num_problems, co
   if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   PrBufs d;
-  DevEvent ev[4];
-  for (int i = 0; i < 4; ++i) HIPCHK(ctx, hipEventCreate(&ev[i].e));
+  DevEvents<4> ev;
+  HIPCHK(ctx, ev.create());
   HIPCHK(ctx, hipEventRecord(ev[0], st));
-  auto up = [&](DevBuf& buf, const void* src, size_t bytes) -> hipError_t {
-    hipError_t e = buf.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st);
-    return e;
-  };
   const size_t steps_bytes = (size_t)B * (size_t)o.max_num_iterations;
-  HIPCHK(ctx, up(d.cams, cameras, (size_t)B * sizeof(dsm_camera)));
-  HIPCHK(ctx, up(d.offsets, offsets, ((size_t)B + 1) * 8));
-  HIPCHK(ctx, up(d.xy, points2D, T * 16));
-  HIPCHK(ctx, up(d.X, points3D, T * 24));
-  HIPCHK(ctx, up(d.mask, inlier_mask, T));
-  HIPCHK(ctx, up(d.q, qvecs_in, (size_t)B * 32));
-  HIPCHK(ctx, up(d.t, tvecs_in, (size_t)B * 24));
-  HIPCHK(ctx, up(d.flags, refine_flags, B));
+  HIPCHK(ctx, dev_upload(d.cams, cameras, (size_t)B * sizeof(dsm_camera), st));
+  HIPCHK(ctx, dev_upload(d.offsets, offsets, ((size_t)B + 1) * 8, st));
+  HIPCHK(ctx, dev_upload(d.xy, points2D, T * 16, st));
+  HIPCHK(ctx, dev_upload(d.X, points3D, T * 24, st));
+  HIPCHK(ctx, dev_upload(d.mask, inlier_mask, T, st));
+  HIPCHK(ctx, dev_upload(d.q, qvecs_in, (size_t)B * 32, st));
+  HIPCHK(ctx, dev_upload(d.t, tvecs_in, (size_t)B * 24, st));
+  HIPCHK(ctx, dev_upload(d.flags, refine_flags, B, st));
   HIPCHK(ctx, d.ws.reserve(std::max<size_t>(T, 1) * PR_ROW * 8));
   HIPCHK(ctx, d.res.reserve((size_t)B * sizeof(dsm_pose_refinement_result)));
   HIPCHK(ctx, d.margins.reserve((size_t)B * PR_MARGINS * 8));
@@ -492,15 +480,10 @@ extern "C" int dsm_refine_absolute_poses(dsm_ctx* ctx, uint32_t num_problems, co
       if (margins_out) margins_out[(size_t)b * PR_MARGINS + i] = margins[(size_t)b * PR_MARGINS + i];
     }
   }
-  float a = 0, s = 0, c = 0, tot = 0;
-  HIPCHK(ctx, hipEventElapsedTime(&a, ev[0], ev[1]));
-  HIPCHK(ctx, hipEventElapsedTime(&s, ev[1], ev[2]));
-  HIPCHK(ctx, hipEventElapsedTime(&c, ev[2], ev[3]));
-  HIPCHK(ctx, hipEventElapsedTime(&tot, ev[0], ev[3]));
-  rep.upload_ms = a;
-  rep.solve_ms = s;
-  rep.download_ms = c;
-  rep.device_ms = tot;
+  HIPCHK(ctx, ev.ms(0, 1, &rep.upload_ms));
+  HIPCHK(ctx, ev.ms(1, 2, &rep.solve_ms));
+  HIPCHK(ctx, ev.ms(2, 3, &rep.download_ms));
+  HIPCHK(ctx, ev.ms(0, 3, &rep.device_ms));
   if (report) *report = rep;
   return DSM_OK;
 }

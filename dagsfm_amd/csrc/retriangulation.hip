@@ -36,6 +36,7 @@
 
 #include "camera_bogus.h"
 #include "ctx.h"
+#include "tri_angle.h"
 #include "rt_graph.h"
 #include "verify_camera.h"
 #include "verify_linalg.h"
@@ -133,39 +134,10 @@ __device__ inline bool rt_depth(const RtView& w, const double* X, double* margin
   return z >= DBL_EPSILON;
 }
 
-// CalculateTriangulationAngle (triangulation.cc:122-142)
-__device__ inline double rt_tri_angle(const double* c1, const double* c2, const double* X) {
-  const double b0 = c1[0] - c2[0], b1 = c1[1] - c2[1], b2 = c1[2] - c2[2];
-  const double baseline2 = (b0 * b0 + b1 * b1) + b2 * b2;
-  const double p0 = X[0] - c1[0], p1 = X[1] - c1[1], p2 = X[2] - c1[2];
-  const double q0 = X[0] - c2[0], q1 = X[1] - c2[1], q2 = X[2] - c2[2];
-  const double ray1 = (p0 * p0 + p1 * p1) + p2 * p2, ray2 = (q0 * q0 + q1 * q1) + q2 * q2;
-  const double den = 2.0 * sqrt(ray1 * ray2);
-  if (den == 0.0) return 0.0;
-  const double angle = fabs(acos((ray1 + ray2 - baseline2) / den));
-  return fmin(angle, M_PI - angle);
-}
-
 __device__ inline bool rt_angle_ok(double angle, double min_angle, double* margin) {
   const double m = fabs(angle - min_angle) / min_angle;
   if (m < *margin) *margin = m;
   return angle >= min_angle;
-}
-
-// TriangulatePoint (triangulation.cc:39-53): the reference-order 4 x 4 JacobiSVD, V's last column dehomogenised
-__device__ void rt_triangulate2(const RtView& a, const RtView& b, double* X) {
-  double A[16];
-  for (int c = 0; c < 4; ++c) {
-    A[c] = a.u * a.P[8 + c] - a.P[c];
-    A[4 + c] = a.v * a.P[8 + c] - a.P[4 + c];
-    A[8 + c] = b.u * b.P[8 + c] - b.P[c];
-    A[12 + c] = b.v * b.P[8 + c] - b.P[4 + c];
-  }
-  double V[16], sv[4];
-  pr_jacobi_svd_square_V<4>(A, V, sv);
-  X[0] = V[12] / V[15];
-  X[1] = V[13] / V[15];
-  X[2] = V[14] / V[15];
 }
 
 // the eigenvector of the smallest eigenvalue of a symmetric 4 x 4 matrix (cyclic Jacobi; SelfAdjointEigenSolver's col(0))
@@ -291,7 +263,7 @@ __device__ bool rt_estimate_multi(RtLane& L, const double* X0, double* X) {
       RtView wj;
       rt_view(L, j, &wj);
       if (!(rt_residual(wj, X0) <= L.prm.max_residual)) continue;
-      if (rt_angle_ok(rt_tri_angle(wi.C, wj.C, X), L.prm.min_tri_angle, &L.mg[2])) return true;
+      if (rt_angle_ok(tri_angle_libm(wi.C, wj.C, X), L.prm.min_tri_angle, &L.mg[2])) return true;
     }
   }
   return false;
@@ -323,9 +295,9 @@ __device__ bool rt_loransac(RtLane& L, const uint32_t* tab, const uint32_t* tab_
     rt_view(L, a, &wa);
     rt_view(L, b, &wb);
     double X[3];
-    rt_triangulate2(wa, wb, X);
+    triangulate_two_view(wa.P, wb.P, wa.u, wa.v, wb.u, wb.v, X);
     const bool d0 = rt_depth(wa, X, &L.mg[3]);
-    const bool ok = d0 && rt_depth(wb, X, &L.mg[3]) && rt_angle_ok(rt_tri_angle(wa.C, wb.C, X), L.prm.min_tri_angle, &L.mg[2]);
+    const bool ok = d0 && rt_depth(wb, X, &L.mg[3]) && rt_angle_ok(tri_angle_libm(wa.C, wb.C, X), L.prm.min_tri_angle, &L.mg[2]);
     if (!ok) continue;
     uint32_t c;
     double s;
@@ -690,10 +662,7 @@ extern "C" int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint3
                                  uint64_t* touched_point_ids, uint64_t* n_touched, uint32_t* num_tris_per_separator,
                                  uint64_t* num_tris_out, dsm_triangulation_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_retriangulate: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_retriangulate", msg); };
   const auto t_host0 = std::chrono::steady_clock::now();
   if ((num_cameras && (!camera_ids || !cameras)) || (num_images && (!image_ids || !image_camera_ids || !image_registered || !image_qvec ||
                                                                      !image_tvec)) ||
@@ -718,7 +687,7 @@ extern "C" int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint3
                                           image_qvec, image_tvec, points2D_offsets, points2D_xy, points2D_point3D, num_points3D, point3D_ids,
                                           point3D_xyz, num_pairs, pair_image_ids, match_offsets, matches, next_point3D_id, o,
                                           &rep.min_bogus_margin);
-    if (!msg.empty()) return fail(msg);
+    if (!msg.empty()) return fail(msg.c_str());
   }
   const std::vector<uint32_t>&order = scn.order, &nfeat = scn.nfeat, &foff = scn.foff, &img_cam = scn.img_cam, &feat_img = scn.feat_img,
                              &pair_img = scn.pair_img;
@@ -756,27 +725,22 @@ extern "C" int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint3
   if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   RtBufs d;
-  DevEvent ev[5];
-  for (int i = 0; i < 5; ++i) HIPCHK(ctx, hipEventCreate(&ev[i].e));
+  DevEvents<5> ev;
+  HIPCHK(ctx, ev.create());
   HIPCHK(ctx, hipEventRecord(ev[0], st));
   const size_t F1 = std::max<uint64_t>(F, 1);
-  auto up = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
-    hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
-    return e;
-  };
 
   // ------------------------------------------------------------ the correspondence graph (device)
-  HIPCHK(ctx, up(d.nfeat, nfeat.data(), nfeat.size() * 4));
-  HIPCHK(ctx, up(d.foff, foff.data(), foff.size() * 4));
+  HIPCHK(ctx, dev_upload(d.nfeat, nfeat.data(), nfeat.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.foff, foff.data(), foff.size() * 4, st));
   HIPCHK(ctx, d.goff.reserve((F1 + 1) * 4));
   uint32_t E = 0;
   HIPCHK(ctx, d.cnt.reserve((F1 + 1) * 4));
   HIPCHK(ctx, hipMemsetAsync(d.cnt.p, 0, (F1 + 1) * 4, st));
   if (NM) {
-    HIPCHK(ctx, up(d.pair_img, pair_img.data(), pair_img.size() * 4));
-    HIPCHK(ctx, up(d.moff, match_offsets, ((size_t)num_pairs + 1) * 8));
-    HIPCHK(ctx, up(d.matches, matches, NM * 8));
+    HIPCHK(ctx, dev_upload(d.pair_img, pair_img.data(), pair_img.size() * 4, st));
+    HIPCHK(ctx, dev_upload(d.moff, match_offsets, ((size_t)num_pairs + 1) * 8, st));
+    HIPCHK(ctx, dev_upload(d.matches, matches, NM * 8, st));
     HIPCHK(ctx, d.acc.reserve(NM));
     hipLaunchKernelGGL(k_rt_dedup, dim3(num_pairs), dim3(RT_BLOCK), 0, st, num_pairs, d.pair_img.as<uint32_t>(), d.moff.as<uint64_t>(),
                        d.matches.as<uint32_t>(), d.nfeat.as<uint32_t>(), d.acc.as<uint8_t>());
@@ -802,23 +766,23 @@ extern "C" int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint3
 
   // ------------------------------------------------------------ the problems: Find on the device, non-empty ones kept
   std::vector<dsm_camera> cams(cameras, cameras + num_cameras);
-  HIPCHK(ctx, up(d.feat_img, feat_img.data(), F * 4));
-  HIPCHK(ctx, up(d.img_ok, img_ok.data(), num_images));
-  HIPCHK(ctx, up(d.img_cam, img_cam.data(), num_images * 4));
-  HIPCHK(ctx, up(d.cams, cams.data(), cams.size() * sizeof(dsm_camera)));
-  HIPCHK(ctx, up(d.xy, xy.data(), F * 16));
+  HIPCHK(ctx, dev_upload(d.feat_img, feat_img.data(), F * 4, st));
+  HIPCHK(ctx, dev_upload(d.img_ok, img_ok.data(), num_images, st));
+  HIPCHK(ctx, dev_upload(d.img_cam, img_cam.data(), num_images * 4, st));
+  HIPCHK(ctx, dev_upload(d.cams, cams.data(), cams.size() * sizeof(dsm_camera), st));
+  HIPCHK(ctx, dev_upload(d.xy, xy.data(), F * 16, st));
   HIPCHK(ctx, d.uv.reserve(F1 * 16));
-  HIPCHK(ctx, up(d.img_P, img_P.data(), img_P.size() * 8));
-  HIPCHK(ctx, up(d.img_C, img_C.data(), img_C.size() * 8));
-  HIPCHK(ctx, up(d.pid, pid0.data(), F * 4));
-  HIPCHK(ctx, up(d.pxyz, point3D_xyz, (size_t)num_points3D * 24));
+  HIPCHK(ctx, dev_upload(d.img_P, img_P.data(), img_P.size() * 8, st));
+  HIPCHK(ctx, dev_upload(d.img_C, img_C.data(), img_C.size() * 8, st));
+  HIPCHK(ctx, dev_upload(d.pid, pid0.data(), F * 4, st));
+  HIPCHK(ctx, dev_upload(d.pxyz, point3D_xyz, (size_t)num_points3D * 24, st));
   if (F)
     hipLaunchKernelGGL(k_rt_normalize, dim3((uint32_t)((F + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, st, (uint32_t)F, d.feat_img.as<uint32_t>(),
                        d.img_ok.as<uint8_t>(), d.img_cam.as<uint32_t>(), d.cams.as<dsm_camera>(), d.xy.as<double>(), d.uv.as<double>());
   const uint32_t Q0 = (uint32_t)cand.size();
   std::vector<uint32_t> cnt(Q0);
   if (Q0) {
-    HIPCHK(ctx, up(d.ref, cand.data(), (size_t)Q0 * 4));
+    HIPCHK(ctx, dev_upload(d.ref, cand.data(), (size_t)Q0 * 4, st));
     HIPCHK(ctx, d.pcnt.reserve((size_t)Q0 * 4));
     hipLaunchKernelGGL(k_rt_find, dim3((Q0 + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, Q0, d.ref.as<uint32_t>(), d.goff.as<uint32_t>(),
                        d.val2.as<uint32_t>(), d.feat_img.as<uint32_t>(), d.img_ok.as<uint8_t>(), (const uint32_t*)nullptr, d.pcnt.as<uint32_t>(),
@@ -843,8 +807,8 @@ extern "C" int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint3
   uint32_t maxn = 2;
   for (uint32_t q = 0; q < Q; ++q) maxn = std::max(maxn, pmoff[q + 1] - pmoff[q] + 1);
   if (Q) {
-    HIPCHK(ctx, up(d.ref, pref.data(), (size_t)Q * 4));
-    HIPCHK(ctx, up(d.pmoff, pmoff.data(), ((size_t)Q + 1) * 4));
+    HIPCHK(ctx, dev_upload(d.ref, pref.data(), (size_t)Q * 4, st));
+    HIPCHK(ctx, dev_upload(d.pmoff, pmoff.data(), ((size_t)Q + 1) * 4, st));
     HIPCHK(ctx, d.mem.reserve(std::max<size_t>(M * 4, 16)));
     hipLaunchKernelGGL(k_rt_find, dim3((Q + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, Q, d.ref.as<uint32_t>(), d.goff.as<uint32_t>(),
                        d.val2.as<uint32_t>(), d.feat_img.as<uint32_t>(), d.img_ok.as<uint8_t>(), d.pmoff.as<uint32_t>(), (uint32_t*)nullptr,
@@ -858,8 +822,8 @@ extern "C" int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint3
     tab_off[n] = (uint32_t)tab.size();
     for (uint32_t k = 0; k <= n; ++k) tab.push_back(rt_num_trials(k, n, o.ransac_confidence));
   }
-  HIPCHK(ctx, up(d.tab, tab.data(), tab.size() * 4));
-  HIPCHK(ctx, up(d.tab_off, tab_off.data(), tab_off.size() * 4));
+  HIPCHK(ctx, dev_upload(d.tab, tab.data(), tab.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.tab_off, tab_off.data(), tab_off.size() * 4, st));
   const size_t Q1 = std::max<uint32_t>(Q, 1), S1 = std::max<uint64_t>(S, 1);
   for (DevBuf* b : {&d.cont, &d.ncreated, &d.ncl, &d.trials, &d.run}) HIPCHK(ctx, b->reserve(Q1 * 4));
   HIPCHK(ctx, d.margins.reserve(Q1 * kRtMargins * 8));
@@ -902,8 +866,8 @@ extern "C" int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint3
   prm.num_points = num_points3D;
   HIPCHK(ctx, hipEventRecord(ev[2], st));
   if (Q) HIPCHK(ctx, hipMemcpyAsync(d.run.p, run.data(), (size_t)Q * 4, hipMemcpyHostToDevice, st));
-  std::vector<DevEvent> rev(4 * (size_t)nrounds);  // per round: before Continue, Create, apply, after apply
-  for (auto& e : rev) HIPCHK(ctx, hipEventCreate(&e.e));
+  DevEventList rev(4 * (size_t)nrounds);  // per round: before Continue, Create, apply, after apply
+  HIPCHK(ctx, rev.create());
   const double* nx = d.nxyz.as<double>();
   for (uint32_t r = 1; r <= nrounds; ++r) {  // every round enqueued back to back: the schedule needs no result
     const uint32_t R = roff[r + 1] - roff[r];
@@ -1022,17 +986,17 @@ extern "C" int dsm_retriangulate(dsm_ctx* ctx, uint32_t num_cameras, const uint3
   rep.num_new_points = pnew;
   rep.num_new_observations = nobs;
   rep.num_continued = ncont;
-  float g_ms = 0, solve_ms = 0, dl_ms = 0, tot_ms = 0;
-  HIPCHK(ctx, hipEventElapsedTime(&g_ms, ev[0], ev[1]));
-  HIPCHK(ctx, hipEventElapsedTime(&solve_ms, ev[2], ev[3]));
-  HIPCHK(ctx, hipEventElapsedTime(&dl_ms, ev[3], ev[4]));
-  HIPCHK(ctx, hipEventElapsedTime(&tot_ms, ev[0], ev[4]));
+  double g_ms = 0, solve_ms = 0, dl_ms = 0, tot_ms = 0;
+  HIPCHK(ctx, ev.ms(0, 1, &g_ms));
+  HIPCHK(ctx, ev.ms(2, 3, &solve_ms));
+  HIPCHK(ctx, ev.ms(3, 4, &dl_ms));
+  HIPCHK(ctx, ev.ms(0, 4, &tot_ms));
   double cont_ms = 0, create_ms = 0, apply_ms = 0;
   for (uint32_t r = 0; r < nrounds; ++r) {
-    float a = 0, b = 0, c = 0;
-    HIPCHK(ctx, hipEventElapsedTime(&a, rev[4 * r], rev[4 * r + 1]));
-    HIPCHK(ctx, hipEventElapsedTime(&b, rev[4 * r + 1], rev[4 * r + 2]));
-    HIPCHK(ctx, hipEventElapsedTime(&c, rev[4 * r + 2], rev[4 * r + 3]));
+    double a = 0, b = 0, c = 0;
+    HIPCHK(ctx, rev.ms(4 * r, 4 * r + 1, &a));
+    HIPCHK(ctx, rev.ms(4 * r + 1, 4 * r + 2, &b));
+    HIPCHK(ctx, rev.ms(4 * r + 2, 4 * r + 3, &c));
     cont_ms += a;
     create_ms += b;
     apply_ms += c;
@@ -1217,10 +1181,10 @@ __global__ void k_rp_solve(uint32_t W, uint32_t w0, uint32_t j0, uint32_t j1, co
     rt_load(f1, feat_img, img_P, img_C, uv, &va);
     rt_load(f2, feat_img, img_P, img_C, uv, &vb);
     double X[3];
-    rt_triangulate2(va, vb, X);
+    triangulate_two_view(va.P, vb.P, va.u, va.v, vb.u, vb.v, X);
     oc = RC_CREATE_FAILED;
     const bool d0 = rt_depth(va, X, &mg[2]);
-    if (d0 && rt_depth(vb, X, &mg[2]) && rt_angle_ok(rt_tri_angle(va.C, vb.C, X), prm.min_tri_angle, &mg[1])) {
+    if (d0 && rt_depth(vb, X, &mg[2]) && rt_angle_ok(tri_angle_libm(va.C, vb.C, X), prm.min_tri_angle, &mg[1])) {
       uint32_t c = 0;
       for (int s = 0; s < 2; ++s) {
         double cd;
@@ -1269,10 +1233,7 @@ extern "C" int dsm_retriangulate_pairs(dsm_ctx* ctx, uint32_t num_cameras, const
                                        uint32_t* pair_num_total_corrs, uint32_t* pair_num_tri_corrs, uint8_t* pair_status,
                                        uint64_t* num_tris_out, dsm_pair_retriangulation_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_retriangulate_pairs: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_retriangulate_pairs", msg); };
   const auto t_host0 = std::chrono::steady_clock::now();
   if ((num_cameras && (!camera_ids || !cameras)) || (num_images && (!image_ids || !image_camera_ids || !image_registered || !image_qvec ||
                                                                      !image_tvec)) ||
@@ -1298,7 +1259,7 @@ extern "C" int dsm_retriangulate_pairs(dsm_ctx* ctx, uint32_t num_cameras, const
                                           image_qvec, image_tvec, points2D_offsets, points2D_xy, points2D_point3D, num_points3D, point3D_ids,
                                           point3D_xyz, num_pairs, pair_image_ids, match_offsets, matches, next_point3D_id, o,
                                           &rep.min_bogus_margin);
-    if (!msg.empty()) return fail(msg);
+    if (!msg.empty()) return fail(msg.c_str());
   }
   const uint64_t F = S.F, NM = S.NM;
   const size_t F1 = std::max<uint64_t>(F, 1), K1 = std::max<uint32_t>(num_pairs, 1);
@@ -1316,26 +1277,21 @@ extern "C" int dsm_retriangulate_pairs(dsm_ctx* ctx, uint32_t num_cameras, const
   if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
   hipStream_t st = ctx->stream;
   RpBufs d;
-  DevEvent ev[5];
-  for (int i = 0; i < 5; ++i) HIPCHK(ctx, hipEventCreate(&ev[i].e));
+  DevEvents<5> ev;
+  HIPCHK(ctx, ev.create());
   HIPCHK(ctx, hipEventRecord(ev[0], st));
-  auto up = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
-    hipError_t e = b.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
-    return e;
-  };
 
   // ------------------------------------------------------------ the duplicate rule, the counts per feature, the ranks (device)
   std::vector<uint32_t> ctotal(num_pairs, 0), cbeg(num_pairs, 0), tri0(num_pairs, 0);
-  HIPCHK(ctx, up(d.nfeat, S.nfeat.data(), S.nfeat.size() * 4));
-  HIPCHK(ctx, up(d.foff, S.foff.data(), S.foff.size() * 4));
+  HIPCHK(ctx, dev_upload(d.nfeat, S.nfeat.data(), S.nfeat.size() * 4, st));
+  HIPCHK(ctx, dev_upload(d.foff, S.foff.data(), S.foff.size() * 4, st));
   HIPCHK(ctx, d.deg.reserve(F1 * 4));
   HIPCHK(ctx, hipMemsetAsync(d.deg.p, 0, F1 * 4, st));
-  HIPCHK(ctx, up(d.pid, S.pid0.data(), F * 4));
+  HIPCHK(ctx, dev_upload(d.pid, S.pid0.data(), F * 4, st));
   if (NM) {
-    HIPCHK(ctx, up(d.pair_img, S.pair_img.data(), S.pair_img.size() * 4));
-    HIPCHK(ctx, up(d.moff, match_offsets, ((size_t)num_pairs + 1) * 8));
-    HIPCHK(ctx, up(d.matches, matches, NM * 8));
+    HIPCHK(ctx, dev_upload(d.pair_img, S.pair_img.data(), S.pair_img.size() * 4, st));
+    HIPCHK(ctx, dev_upload(d.moff, match_offsets, ((size_t)num_pairs + 1) * 8, st));
+    HIPCHK(ctx, dev_upload(d.matches, matches, NM * 8, st));
     HIPCHK(ctx, d.acc.reserve(NM));
     HIPCHK(ctx, d.rank.reserve(NM * 4));
     HIPCHK(ctx, d.total.reserve(K1 * 4));
@@ -1359,8 +1315,8 @@ extern "C" int dsm_retriangulate_pairs(dsm_ctx* ctx, uint32_t num_cameras, const
   std::vector<uint32_t> corr(2 * C);
   HIPCHK(ctx, d.corr.reserve(C1 * 8));
   HIPCHK(ctx, d.tri.reserve(K1 * 4));
-  HIPCHK(ctx, up(d.total, ctotal.data(), (size_t)num_pairs * 4));
-  HIPCHK(ctx, up(d.cbeg, cbeg.data(), (size_t)num_pairs * 4));
+  HIPCHK(ctx, dev_upload(d.total, ctotal.data(), (size_t)num_pairs * 4, st));
+  HIPCHK(ctx, dev_upload(d.cbeg, cbeg.data(), (size_t)num_pairs * 4, st));
   if (C) {
     hipLaunchKernelGGL(k_rp_place, dim3(num_pairs), dim3(RT_BLOCK), 0, st, num_pairs, d.pair_img.as<uint32_t>(), d.moff.as<uint64_t>(),
                        d.matches.as<uint32_t>(), d.rank.as<uint32_t>(), d.foff.as<uint32_t>(), d.cbeg.as<uint32_t>(), d.corr.as<uint32_t>());
@@ -1372,15 +1328,15 @@ extern "C" int dsm_retriangulate_pairs(dsm_ctx* ctx, uint32_t num_cameras, const
     HIPCHK(ctx, hipMemcpyAsync(tri0.data(), d.tri.p, (size_t)num_pairs * 4, hipMemcpyDeviceToHost, st));
   }
   // ImageToWorld of every feature of a usable image, and the poses
-  HIPCHK(ctx, up(d.feat_img, S.feat_img.data(), F * 4));
-  HIPCHK(ctx, up(d.img_ok, S.img_ok.data(), num_images));
-  HIPCHK(ctx, up(d.img_cam, S.img_cam.data(), (size_t)num_images * 4));
-  HIPCHK(ctx, up(d.cams, cameras, (size_t)num_cameras * sizeof(dsm_camera)));
-  HIPCHK(ctx, up(d.xy, S.xy.data(), F * 16));
+  HIPCHK(ctx, dev_upload(d.feat_img, S.feat_img.data(), F * 4, st));
+  HIPCHK(ctx, dev_upload(d.img_ok, S.img_ok.data(), num_images, st));
+  HIPCHK(ctx, dev_upload(d.img_cam, S.img_cam.data(), (size_t)num_images * 4, st));
+  HIPCHK(ctx, dev_upload(d.cams, cameras, (size_t)num_cameras * sizeof(dsm_camera), st));
+  HIPCHK(ctx, dev_upload(d.xy, S.xy.data(), F * 16, st));
   HIPCHK(ctx, d.uv.reserve(F1 * 16));
-  HIPCHK(ctx, up(d.img_P, S.img_P.data(), S.img_P.size() * 8));
-  HIPCHK(ctx, up(d.img_C, S.img_C.data(), S.img_C.size() * 8));
-  HIPCHK(ctx, up(d.pxyz, point3D_xyz, (size_t)num_points3D * 24));
+  HIPCHK(ctx, dev_upload(d.img_P, S.img_P.data(), S.img_P.size() * 8, st));
+  HIPCHK(ctx, dev_upload(d.img_C, S.img_C.data(), S.img_C.size() * 8, st));
+  HIPCHK(ctx, dev_upload(d.pxyz, point3D_xyz, (size_t)num_points3D * 24, st));
   if (F) {
     hipLaunchKernelGGL(k_rt_normalize, dim3((uint32_t)((F + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, st, (uint32_t)F, d.feat_img.as<uint32_t>(),
                        d.img_ok.as<uint8_t>(), d.img_cam.as<uint32_t>(), d.cams.as<dsm_camera>(), d.xy.as<double>(), d.uv.as<double>());
@@ -1456,13 +1412,13 @@ extern "C" int dsm_retriangulate_pairs(dsm_ctx* ctx, uint32_t num_cameras, const
   prm.num_points = num_points3D;
   if ((uint64_t)num_points3D + C >= 0x7fffffffu) return fail("too many points3D and correspondences");
   HIPCHK(ctx, hipEventRecord(ev[2], st));
-  HIPCHK(ctx, up(d.status, status.data(), num_pairs));
-  HIPCHK(ctx, up(d.open_status, open_status.data(), num_pairs));
-  HIPCHK(ctx, up(d.wl_pair, wl_pair.data(), (size_t)NC * 4));
-  HIPCHK(ctx, up(d.wl_off, wl_off.data(), ((size_t)NC + 1) * 4));
+  HIPCHK(ctx, dev_upload(d.status, status.data(), num_pairs, st));
+  HIPCHK(ctx, dev_upload(d.open_status, open_status.data(), num_pairs, st));
+  HIPCHK(ctx, dev_upload(d.wl_pair, wl_pair.data(), (size_t)NC * 4, st));
+  HIPCHK(ctx, dev_upload(d.wl_off, wl_off.data(), ((size_t)NC + 1) * 4, st));
   const bool timed = nrounds <= kRpTimedRounds;
-  std::vector<DevEvent> rev(timed ? 3 * (size_t)nrounds : 0);  // per round: before the gate, before the solve, after it
-  for (auto& e : rev) HIPCHK(ctx, hipEventCreate(&e.e));
+  DevEventList rev(timed ? 3 * (size_t)nrounds : 0);  // per round: before the gate, before the solve, after it
+  HIPCHK(ctx, rev.create());
   for (uint32_t r = 1; r <= nrounds; ++r) {  // every round enqueued back to back: the schedule needs no result
     const uint32_t j0 = roff[r], j1 = roff[r + 1], W = wl_off[j1] - wl_off[j0];
     if (j1 == j0) continue;
@@ -1568,15 +1524,15 @@ extern "C" int dsm_retriangulate_pairs(dsm_ctx* ctx, uint32_t num_cameras, const
   *n_continued = ncont;
   *n_touched = nt;
   *num_tris_out = rep.num_tris;
-  float g_ms = 0, rounds_ms = 0, dl_ms = 0, tot_ms = 0;
-  HIPCHK(ctx, hipEventElapsedTime(&g_ms, ev[0], ev[1]));
-  HIPCHK(ctx, hipEventElapsedTime(&rounds_ms, ev[2], ev[3]));
-  HIPCHK(ctx, hipEventElapsedTime(&dl_ms, ev[3], ev[4]));
-  HIPCHK(ctx, hipEventElapsedTime(&tot_ms, ev[0], ev[4]));
+  double g_ms = 0, rounds_ms = 0, dl_ms = 0, tot_ms = 0;
+  HIPCHK(ctx, ev.ms(0, 1, &g_ms));
+  HIPCHK(ctx, ev.ms(2, 3, &rounds_ms));
+  HIPCHK(ctx, ev.ms(3, 4, &dl_ms));
+  HIPCHK(ctx, ev.ms(0, 4, &tot_ms));
   for (uint32_t r = 0; timed && r < nrounds; ++r) {
-    float a = 0, b = 0;
-    HIPCHK(ctx, hipEventElapsedTime(&a, rev[3 * r], rev[3 * r + 1]));
-    HIPCHK(ctx, hipEventElapsedTime(&b, rev[3 * r + 1], rev[3 * r + 2]));
+    double a = 0, b = 0;
+    HIPCHK(ctx, rev.ms(3 * r, 3 * r + 1, &a));
+    HIPCHK(ctx, rev.ms(3 * r + 1, 3 * r + 2, &b));
     rep.gate_ms += a;
     rep.solve_ms += b;
   }

@@ -940,9 +940,7 @@ int dsm_retrieval_index(dsm_ctx* ctx) {
   }
   HIPCHK(ctx, hipEventRecord(r->ev1, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  float ms = 0.f;
-  HIPCHK(ctx, hipEventElapsedTime(&ms, r->ev0, r->ev1));
-  r->index_ms = ms;
+  HIPCHK(ctx, dev_events_ms(r->ev0, r->ev1, &r->index_ms));
   r->indexed = true;
   return DSM_OK;
 }
@@ -1016,9 +1014,7 @@ int dsm_retrieval_query(dsm_ctx* ctx, uint32_t num_neighbors, uint32_t max_num_i
   }
   HIPCHK(ctx, hipEventRecord(r->ev1, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  float ms = 0.f;
-  HIPCHK(ctx, hipEventElapsedTime(&ms, r->ev0, r->ev1));
-  r->query_ms = ms;
+  HIPCHK(ctx, dev_events_ms(r->ev0, r->ev1, &r->query_ms));
   HIPCHK(ctx, hipMemcpy(counts, r->d_out_cnt.p, (size_t)NI * 4, hipMemcpyDefault));
   HIPCHK(ctx, hipMemcpy(image_idx, r->d_out_idx.p, (size_t)NI * max_num_images * 4, hipMemcpyDefault));
   HIPCHK(ctx, hipMemcpy(scores, r->d_out_score.p, (size_t)NI * max_num_images * 4, hipMemcpyDefault));

@@ -622,9 +622,7 @@ extern "C" int dsm_view_graph_rotation_averaging(dsm_ctx* ctx, uint32_t n_pairs,
     HIPTRY(hipMemcpyAsync(relh.data(), d_rel.p, m3 * 8, hipMemcpyDeviceToHost, st));
     HIPTRY(hipMemcpyAsync(&h, d_ctl.p, sizeof(RaCtl), hipMemcpyDeviceToHost, st));
     HIPTRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIPTRY(hipEventElapsedTime(&ms, ev0, ev1));
-    rep.device_ms = ms;
+    HIPTRY(dev_events_ms(ev0, ev1, &rep.device_ms));
   }
   if (rc != DSM_OK) (void)hipStreamSynchronize(st);
   rep.total_cg_iterations = h.cg_total;

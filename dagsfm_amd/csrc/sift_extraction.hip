@@ -322,18 +322,6 @@ __global__ void __launch_bounds__(64) k_sift_describe(const SiftJob* __restrict_
   }
 }
 
-// one out-of-line failure path for the whole call (HIPCHK builds a string at every site)
-__attribute__((noinline)) int sift_hip_fail(dsm_ctx* ctx, hipError_t e) {
-  ctx->err = std::string("dsm_extract_sift: ") + hipGetErrorString(e);
-  return DSM_ERR_HIP;
-}
-#define SIFT_CHK(call)                                      \
-  do {                                                      \
-    const hipError_t e_ = (call);                           \
-    if (e_ != hipSuccess) return sift_hip_fail(ctx, e_);    \
-  } while (0)
-
-inline uint32_t sift_grid(uint64_t n, int block = SIFT_BLOCK) { return (uint32_t)((n + block - 1) / block); }
 inline int sift_shift(int x, int n) { return n >= 0 ? x << n : x >> -n; }  // VL_SHIFT_LEFT
 
 // the Gaussian of _vl_sift_smooth (sift.c:782-798), by the host libm as the reference's
@@ -427,13 +415,13 @@ extern "C" int dsm_extract_sift(dsm_ctx* ctx, const dsm_sift_options* options, c
     double tab[SIFT_EXPN_SZ + 2];
     for (int k = 0; k < SIFT_EXPN_SZ + 1; ++k) tab[k] = std::exp(-(double)k * (25.0 / SIFT_EXPN_SZ));
     tab[SIFT_EXPN_SZ + 1] = 0.0;
-    SIFT_CHK(d.buf[SiftState::expn].reserve(sizeof(tab)));
-    SIFT_CHK(hipMemcpyAsync(d.buf[SiftState::expn].p, tab, sizeof(tab), hipMemcpyHostToDevice, st));
-    SIFT_CHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, d.buf[SiftState::expn].reserve(sizeof(tab)));
+    HIPCHK(ctx, hipMemcpyAsync(d.buf[SiftState::expn].p, tab, sizeof(tab), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     d.expn_ready = true;
   }
   for (DevEvent& e : d.ev)
-    if (!e.e) SIFT_CHK(hipEventCreate(&e.e));
+    if (!e.e) HIPCHK(ctx, hipEventCreate(&e.e));
   for (double& v : d.stage_ms) v = 0.0;
   auto mark = [&](int i) { return hipEventRecord(d.ev[i], st); };
   auto took = [&](int stage, int a) {  // events a, a + 1 have completed
@@ -442,15 +430,15 @@ extern "C" int dsm_extract_sift(dsm_ctx* ctx, const dsm_sift_options* options, c
     d.stage_ms[stage] += ms;
     return e;
   };
-  SIFT_CHK(d.buf[SiftState::img].reserve((size_t)row_stride * height));
-  SIFT_CHK(d.buf[SiftState::oct].reserve(nel0 * 4 * (S + 3)));
-  SIFT_CHK(d.buf[SiftState::tmp].reserve(nel0 * 4));
-  SIFT_CHK(d.buf[SiftState::dog].reserve(nel0 * 4 * (S + 2)));
-  SIFT_CHK(d.buf[SiftState::grad].reserve(nel0 * 8 * S));
-  SIFT_CHK(d.buf[SiftState::flags].reserve(nel0 * S));
-  SIFT_CHK(d.buf[SiftState::counts].reserve(chunks0 * 4));
-  SIFT_CHK(d.buf[SiftState::offs].reserve(chunks0 * 4));
-  SIFT_CHK(hipMemcpyAsync(d.buf[SiftState::img].p, gray_u8, (size_t)row_stride * height, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, d.buf[SiftState::img].reserve((size_t)row_stride * height));
+  HIPCHK(ctx, d.buf[SiftState::oct].reserve(nel0 * 4 * (S + 3)));
+  HIPCHK(ctx, d.buf[SiftState::tmp].reserve(nel0 * 4));
+  HIPCHK(ctx, d.buf[SiftState::dog].reserve(nel0 * 4 * (S + 2)));
+  HIPCHK(ctx, d.buf[SiftState::grad].reserve(nel0 * 8 * S));
+  HIPCHK(ctx, d.buf[SiftState::flags].reserve(nel0 * S));
+  HIPCHK(ctx, d.buf[SiftState::counts].reserve(chunks0 * 4));
+  HIPCHK(ctx, d.buf[SiftState::offs].reserve(chunks0 * 4));
+  HIPCHK(ctx, hipMemcpyAsync(d.buf[SiftState::img].p, gray_u8, (size_t)row_stride * height, hipMemcpyHostToDevice, st));
   float* oct = d.buf[SiftState::oct].as<float>();
   float* tmp = d.buf[SiftState::tmp].as<float>();
 
@@ -474,8 +462,8 @@ extern "C" int dsm_extract_sift(dsm_ctx* ctx, const dsm_sift_options* options, c
   }
   for (int k = 0; k < S + 4; ++k)
     if (tap_w[k] > 256) return fail(DSM_ERR_OUT_OF_RANGE, "a smoothing half-width above 256 samples");
-  SIFT_CHK(d.buf[SiftState::taps].reserve(all_taps.size() * 4));
-  SIFT_CHK(hipMemcpyAsync(d.buf[SiftState::taps].p, all_taps.data(), all_taps.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, d.buf[SiftState::taps].reserve(all_taps.size() * 4));
+  HIPCHK(ctx, hipMemcpyAsync(d.buf[SiftState::taps].p, all_taps.data(), all_taps.size() * 4, hipMemcpyHostToDevice, st));
   auto smooth = [&](float* out, const float* in, uint32_t w, uint32_t h, int slot) {  // _vl_sift_smooth: columns into tmp, rows into out
     const float* taps = d.buf[SiftState::taps].as<float>() + tap_at[slot];
     const int W = tap_w[slot];
@@ -498,13 +486,13 @@ extern "C" int dsm_extract_sift(dsm_ctx* ctx, const dsm_sift_options* options, c
     // below 2 x 2 update_gradient is undefined, below 3 x 3 nothing is detected, and every later octave is smaller still
     if (wi < 2 || hi < 2) break;
     const uint32_t w = (uint32_t)wi, h = (uint32_t)hi, nel = w * h;
-    SIFT_CHK(mark(0));
+    HIPCHK(ctx, mark(0));
     if (oc == o_min) {  // vl_sift_process_first_octave, sift.c:1015-1052
       float* fimg = o_min == 0 ? oct : d.buf[SiftState::dog].as<float>();  // the float image: a buffer that is free until the DoG
-      hipLaunchKernelGGL(k_sift_load, dim3(sift_grid((uint64_t)width * height)), dim3(SIFT_BLOCK), 0, st, fimg, d.buf[SiftState::img].as<uint8_t>(), width, height, row_stride);
+      hipLaunchKernelGGL(k_sift_load, dim3(dsm_grid((uint64_t)width * height, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, fimg, d.buf[SiftState::img].as<uint8_t>(), width, height, row_stride);
       if (o_min < 0) {
         auto up = [&](float* dst, const float* src, uint32_t ww, uint32_t hh) {
-          hipLaunchKernelGGL(k_sift_upsample_rows, dim3(sift_grid((uint64_t)ww * hh)), dim3(SIFT_BLOCK), 0, st, dst, src, ww, hh);
+          hipLaunchKernelGGL(k_sift_upsample_rows, dim3(dsm_grid((uint64_t)ww * hh, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, dst, src, ww, hh);
         };
         up(tmp, fimg, width, height);
         up(oct, tmp, height, 2 * width);
@@ -513,59 +501,59 @@ extern "C" int dsm_extract_sift(dsm_ctx* ctx, const dsm_sift_options* options, c
           up(oct, tmp, width << -q, 2 * (height << -q));
         }
       } else if (o_min > 0) {
-        hipLaunchKernelGGL(k_sift_downsample, dim3(sift_grid(nel)), dim3(SIFT_BLOCK), 0, st, oct, (const float*)fimg, width, 1u << o_min, w, h);
+        hipLaunchKernelGGL(k_sift_downsample, dim3(dsm_grid(nel, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, oct, (const float*)fimg, width, 1u << o_min, w, h);
       }
       if (tap_w[0]) smooth(oct, oct, w, h, 0);
     } else {  // vl_sift_process_next_octave, sift.c:1105-1126: level min(s_min + S, s_max) of the previous octave, every second sample
       const int s_best = std::min(s_min + S, s_max);
       // (the source level starts at (s_best - s_min) pw ph >= 4 nel: the new base does not reach it)
-      hipLaunchKernelGGL(k_sift_downsample, dim3(sift_grid(nel)), dim3(SIFT_BLOCK), 0, st, oct, (const float*)(oct + (size_t)(s_best - s_min) * pw * ph), pw,
+      hipLaunchKernelGGL(k_sift_downsample, dim3(dsm_grid(nel, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, oct, (const float*)(oct + (size_t)(s_best - s_min) * pw * ph), pw,
                          2u, w, h);
       if (tap_w[1]) smooth(oct, oct, w, h, 1);
     }
     pw = w;
     ph = h;
-    SIFT_CHK(mark(1));
+    HIPCHK(ctx, mark(1));
     for (int s = s_min + 1; s <= s_max; ++s)
       smooth(oct + (size_t)(s - s_min) * nel, oct + (size_t)(s - s_min - 1) * nel, w, h, 2 + (s - s_min - 1));
-    SIFT_CHK(mark(2));
-    SIFT_CHK(hipGetLastError());
+    HIPCHK(ctx, mark(2));
+    HIPCHK(ctx, hipGetLastError());
     if (w < 3 || h < 3) continue;  // no interior sample: nothing to detect (its smoothing is not in the stage times)
 
     // vl_sift_detect
     const uint32_t ndog = nel * (uint32_t)(S + 2), nflag = nel * (uint32_t)S, chunks = (nflag + SIFT_CHUNK - 1) / SIFT_CHUNK;
-    hipLaunchKernelGGL(k_sift_dog, dim3(sift_grid(ndog)), dim3(SIFT_BLOCK), 0, st, d.buf[SiftState::dog].as<float>(), (const float*)oct, nel, ndog);
-    hipLaunchKernelGGL(k_sift_detect, dim3(sift_grid(nflag)), dim3(SIFT_BLOCK), 0, st, d.buf[SiftState::flags].as<uint8_t>(), (const float*)d.buf[SiftState::dog].as<float>(), (int)w, (int)h,
+    hipLaunchKernelGGL(k_sift_dog, dim3(dsm_grid(ndog, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, d.buf[SiftState::dog].as<float>(), (const float*)oct, nel, ndog);
+    hipLaunchKernelGGL(k_sift_detect, dim3(dsm_grid(nflag, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, d.buf[SiftState::flags].as<uint8_t>(), (const float*)d.buf[SiftState::dog].as<float>(), (int)w, (int)h,
                        nflag, 0.8 * tp);
     auto compact = [&](const uint32_t* offs, uint32_t* out) {
-      hipLaunchKernelGGL(k_sift_compact, dim3(sift_grid(chunks)), dim3(SIFT_BLOCK), 0, st, (const uint8_t*)d.buf[SiftState::flags].as<uint8_t>(), nflag, chunks, offs, out);
+      hipLaunchKernelGGL(k_sift_compact, dim3(dsm_grid(chunks, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, (const uint8_t*)d.buf[SiftState::flags].as<uint8_t>(), nflag, chunks, offs, out);
     };
     compact(nullptr, d.buf[SiftState::counts].as<uint32_t>());
-    SIFT_CHK(mark(3));
-    SIFT_CHK(hipGetLastError());
+    HIPCHK(ctx, mark(3));
+    HIPCHK(ctx, hipGetLastError());
     counts.resize(chunks);
-    SIFT_CHK(hipMemcpyAsync(counts.data(), d.buf[SiftState::counts].p, (size_t)chunks * 4, hipMemcpyDeviceToHost, st));
-    SIFT_CHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpyAsync(counts.data(), d.buf[SiftState::counts].p, (size_t)chunks * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     uint32_t ncand = 0;
     for (uint32_t c = 0; c < chunks; ++c) {  // exclusive scan in place
       const uint32_t k = counts[c];
       counts[c] = ncand;
       ncand += k;
     }
-    for (int k = 0; k < 3; ++k) SIFT_CHK(took(k, k));
+    for (int k = 0; k < 3; ++k) HIPCHK(ctx, took(k, k));
     if (ncand == 0) continue;
     // what depends on the image: the candidates' records, and at most 4 orientations of each with a float and a byte descriptor
     if (ctx->memory_budget && scratch + (uint64_t)ncand * (4 + sizeof(SiftCand) + sizeof(SiftKey) + 36 + 4 * (sizeof(SiftJob) + 640)) > ctx->memory_budget)
       return fail(DSM_ERR_OUT_OF_RANGE, "the candidates' scratch exceeds the memory budget");
-    SIFT_CHK(mark(4));
-    SIFT_CHK(hipMemcpyAsync(d.buf[SiftState::offs].p, counts.data(), (size_t)chunks * 4, hipMemcpyHostToDevice, st));
-    SIFT_CHK(d.buf[SiftState::cand].reserve((size_t)ncand * 4));
-    SIFT_CHK(d.buf[SiftState::refined].reserve((size_t)ncand * sizeof(SiftCand)));
+    HIPCHK(ctx, mark(4));
+    HIPCHK(ctx, hipMemcpyAsync(d.buf[SiftState::offs].p, counts.data(), (size_t)chunks * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, d.buf[SiftState::cand].reserve((size_t)ncand * 4));
+    HIPCHK(ctx, d.buf[SiftState::refined].reserve((size_t)ncand * sizeof(SiftCand)));
     compact(d.buf[SiftState::offs].as<uint32_t>(), d.buf[SiftState::cand].as<uint32_t>());
-    hipLaunchKernelGGL(k_sift_refine, dim3(sift_grid(ncand)), dim3(SIFT_BLOCK), 0, st, d.buf[SiftState::refined].as<SiftCand>(), (const uint32_t*)d.buf[SiftState::cand].as<uint32_t>(), ncand,
+    hipLaunchKernelGGL(k_sift_refine, dim3(dsm_grid(ncand, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, d.buf[SiftState::refined].as<SiftCand>(), (const uint32_t*)d.buf[SiftState::cand].as<uint32_t>(), ncand,
                        (const float*)d.buf[SiftState::dog].as<float>(), (int)w, (int)h, S, tp, te);
-    SIFT_CHK(mark(5));
-    SIFT_CHK(hipGetLastError());
+    HIPCHK(ctx, mark(5));
+    HIPCHK(ctx, hipGetLastError());
     // host layout: ncand SiftCand | ncand SiftKey | ncand x 4 angles | ncand counts | 4 ncand SiftJob
     const size_t at_keys = (size_t)ncand * sizeof(SiftCand), at_ang = at_keys + (size_t)ncand * sizeof(SiftKey), at_nang = at_ang + (size_t)ncand * 32,
                  at_jobs = (at_nang + (size_t)ncand * 4 + 7) / 8 * 8;
@@ -575,8 +563,8 @@ extern "C" int dsm_extract_sift(dsm_ctx* ctx, const dsm_sift_options* options, c
     double* angles = reinterpret_cast<double*>(host.data() + at_ang);
     int32_t* nangles = reinterpret_cast<int32_t*>(host.data() + at_nang);
     SiftJob* jobs = reinterpret_cast<SiftJob*>(host.data() + at_jobs);
-    SIFT_CHK(hipMemcpyAsync(host.data(), d.buf[SiftState::refined].p, (size_t)ncand * sizeof(SiftCand), hipMemcpyDeviceToHost, st));
-    SIFT_CHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpyAsync(host.data(), d.buf[SiftState::refined].p, (size_t)ncand * sizeof(SiftCand), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     // the good ones in order, with the host's pow (sift.c:1414-1424)
     const double xper = std::pow(2.0, oc);
     uint32_t nk = 0;
@@ -589,34 +577,34 @@ extern "C" int dsm_extract_sift(dsm_ctx* ctx, const dsm_sift_options* options, c
       k.y = (float)(c.yn * xper);
       k.sigma = (float)(sigma0 * std::pow(2.0, c.sn / S) * xper);
     }
-    SIFT_CHK(took(3, 4));
+    HIPCHK(ctx, took(3, 4));
     if (nk == 0) continue;  // sift.cc:306-308
 
     // orientations
     const uint32_t ngrad = nel * (uint32_t)S;
-    SIFT_CHK(mark(6));
-    hipLaunchKernelGGL(k_sift_grad, dim3(sift_grid(ngrad)), dim3(SIFT_BLOCK), 0, st, d.buf[SiftState::grad].as<float>(), (const float*)oct, (int)w, (int)h, ngrad);
-    SIFT_CHK(mark(7));
+    HIPCHK(ctx, mark(6));
+    hipLaunchKernelGGL(k_sift_grad, dim3(dsm_grid(ngrad, SIFT_BLOCK)), dim3(SIFT_BLOCK), 0, st, d.buf[SiftState::grad].as<float>(), (const float*)oct, (int)w, (int)h, ngrad);
+    HIPCHK(ctx, mark(7));
     for (uint32_t i = 0; i < nk; ++i) {  // upright: one orientation of 0 (sift.cc:340-342)
       angles[4 * (size_t)i] = 0.0;
       nangles[i] = 1;
     }
     if (!o.upright) {
-      SIFT_CHK(d.buf[SiftState::keys].reserve((size_t)nk * sizeof(SiftKey)));
-      SIFT_CHK(d.buf[SiftState::angles].reserve((size_t)nk * 32));
-      SIFT_CHK(d.buf[SiftState::nangles].reserve((size_t)nk * 4));
-      SIFT_CHK(hipMemcpyAsync(d.buf[SiftState::keys].p, keys, (size_t)nk * sizeof(SiftKey), hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_sift_orient, dim3(sift_grid(nk, 64)), dim3(64), 0, st, (const SiftKey*)d.buf[SiftState::keys].as<SiftKey>(), nk, (const float*)d.buf[SiftState::grad].as<float>(),
+      HIPCHK(ctx, d.buf[SiftState::keys].reserve((size_t)nk * sizeof(SiftKey)));
+      HIPCHK(ctx, d.buf[SiftState::angles].reserve((size_t)nk * 32));
+      HIPCHK(ctx, d.buf[SiftState::nangles].reserve((size_t)nk * 4));
+      HIPCHK(ctx, hipMemcpyAsync(d.buf[SiftState::keys].p, keys, (size_t)nk * sizeof(SiftKey), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_sift_orient, dim3(dsm_grid(nk, 64)), dim3(64), 0, st, (const SiftKey*)d.buf[SiftState::keys].as<SiftKey>(), nk, (const float*)d.buf[SiftState::grad].as<float>(),
                          (const double*)d.buf[SiftState::expn].as<double>(), (int)w, (int)h, xper, d.buf[SiftState::angles].as<double>(), d.buf[SiftState::nangles].as<int32_t>());
-      SIFT_CHK(mark(8));
-      SIFT_CHK(hipGetLastError());
-      SIFT_CHK(hipMemcpyAsync(angles, d.buf[SiftState::angles].p, (size_t)nk * 32, hipMemcpyDeviceToHost, st));
-      SIFT_CHK(hipMemcpyAsync(nangles, d.buf[SiftState::nangles].p, (size_t)nk * 4, hipMemcpyDeviceToHost, st));
-      SIFT_CHK(hipStreamSynchronize(st));
-      SIFT_CHK(took(5, 7));
+      HIPCHK(ctx, mark(8));
+      HIPCHK(ctx, hipGetLastError());
+      HIPCHK(ctx, hipMemcpyAsync(angles, d.buf[SiftState::angles].p, (size_t)nk * 32, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(nangles, d.buf[SiftState::nangles].p, (size_t)nk * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      HIPCHK(ctx, took(5, 7));
     }
-    SIFT_CHK(hipEventSynchronize(d.ev[7]));
-    SIFT_CHK(took(4, 6));
+    HIPCHK(ctx, hipEventSynchronize(d.ev[7]));
+    HIPCHK(ctx, took(4, 6));
     // the first max_num_orientations of every keypoint (sift.cc:351-352), sin / cos by the host libm (sift.c:1961-1962)
     uint32_t nj = 0;
     for (uint32_t i = 0; i < nk; ++i) {
@@ -636,19 +624,19 @@ extern "C" int dsm_extract_sift(dsm_ctx* ctx, const dsm_sift_options* options, c
     kp_all.resize((f0 + nj) * 4);
     if (descriptors_out) desc_all.resize((f0 + nj) * 128);
     if (descriptors_out && nj) {
-      SIFT_CHK(d.buf[SiftState::jobs].reserve((size_t)nj * sizeof(SiftJob)));
-      SIFT_CHK(d.buf[SiftState::descf].reserve((size_t)nj * 512));
-      SIFT_CHK(d.buf[SiftState::desc8].reserve((size_t)nj * 128));
-      SIFT_CHK(hipMemcpyAsync(d.buf[SiftState::jobs].p, jobs, (size_t)nj * sizeof(SiftJob), hipMemcpyHostToDevice, st));
-      SIFT_CHK(mark(8));
-      hipLaunchKernelGGL(k_sift_describe, dim3(sift_grid(nj, 64)), dim3(64), 0, st, (const SiftJob*)d.buf[SiftState::jobs].as<SiftJob>(), nj, (const float*)d.buf[SiftState::grad].as<float>(),
+      HIPCHK(ctx, d.buf[SiftState::jobs].reserve((size_t)nj * sizeof(SiftJob)));
+      HIPCHK(ctx, d.buf[SiftState::descf].reserve((size_t)nj * 512));
+      HIPCHK(ctx, d.buf[SiftState::desc8].reserve((size_t)nj * 128));
+      HIPCHK(ctx, hipMemcpyAsync(d.buf[SiftState::jobs].p, jobs, (size_t)nj * sizeof(SiftJob), hipMemcpyHostToDevice, st));
+      HIPCHK(ctx, mark(8));
+      hipLaunchKernelGGL(k_sift_describe, dim3(dsm_grid(nj, 64)), dim3(64), 0, st, (const SiftJob*)d.buf[SiftState::jobs].as<SiftJob>(), nj, (const float*)d.buf[SiftState::grad].as<float>(),
                          (const double*)d.buf[SiftState::expn].as<double>(), (int)w, (int)h, xper, (int)(o.normalization == DSM_SIFT_L2), d.buf[SiftState::descf].as<float>(),
                          d.buf[SiftState::desc8].as<uint8_t>());
-      SIFT_CHK(hipGetLastError());
-      SIFT_CHK(mark(9));
-      SIFT_CHK(hipMemcpyAsync(desc_all.data() + f0 * 128, d.buf[SiftState::desc8].p, (size_t)nj * 128, hipMemcpyDeviceToHost, st));
-      SIFT_CHK(hipStreamSynchronize(st));
-      SIFT_CHK(took(6, 8));
+      HIPCHK(ctx, hipGetLastError());
+      HIPCHK(ctx, mark(9));
+      HIPCHK(ctx, hipMemcpyAsync(desc_all.data() + f0 * 128, d.buf[SiftState::desc8].p, (size_t)nj * 128, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      HIPCHK(ctx, took(6, 8));
     }
     // the groups per DoG level (sift.cc:310-384)
     int prev_level = -1;
@@ -671,7 +659,7 @@ extern "C" int dsm_extract_sift(dsm_ctx* ctx, const dsm_sift_options* options, c
       level_first.back() = (uint32_t)(f0 + j);
     }
   }
-  SIFT_CHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
 
   // max_num_features (sift.cc:387-398): the coarsest levels until the count of keypoints exceeds it, the crossing level kept whole
   size_t first_level_to_keep = 0;

@@ -191,6 +191,7 @@ extern "C" void dsm_default_source_selection_options(dsm_source_selection_option
 }
 
 static inline size_t ss_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// not dsm_grid (ctx.h): the grid of a grid-stride kernel, clamped to [1, SS_MAX_GRID] in 64 bits
 static inline uint32_t ss_grid(uint64_t n) {
   const uint64_t g = (n + SS_BLOCK - 1) / SS_BLOCK;
   return (uint32_t)(g < 1 ? 1 : (g > SS_MAX_GRID ? SS_MAX_GRID : g));
@@ -270,8 +271,8 @@ extern "C" int dsm_select_source_images(dsm_ctx* ctx, const dsm_source_selection
   if (ctx->memory_budget && need > ctx->memory_budget) return ss_refuse(ctx, "the items and tables", need, ctx->memory_budget, true);
   if (need > (uint64_t)(free_b * 0.9)) return ss_refuse(ctx, "the items and tables", need, (uint64_t)(free_b * 0.9), false);
 
-  DevEvent ev[7];
-  for (DevEvent& e : ev) HIPCHK(ctx, hipEventCreate(&e.e));
+  DevEvents<7> ev;
+  HIPCHK(ctx, ev.create());
   HIPCHK(ctx, hipEventRecord(ev[0], st));
   HIPCHK(ctx, ctx->d_ss_model.reserve(model_bytes));
   SsDev d;
@@ -317,7 +318,6 @@ extern "C" int dsm_select_source_images(dsm_ctx* ctx, const dsm_source_selection
   }
   d.n_elems = n_elems;
   d.n_items = n_items;
-  float t = 0;
   uint64_t h_counters[8] = {0};
   uint64_t items_valid = 0, n_pairs = 0, n_list = 0;
 
@@ -368,12 +368,9 @@ extern "C" int dsm_select_source_images(dsm_ctx* ctx, const dsm_source_selection
     if (n_list) HIPCHK(ctx, hipMemcpyAsync(list_img.data(), w.list_img, n_list * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipEventRecord(ev[3], st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    HIPCHK(ctx, hipEventElapsedTime(&t, ev[0], ev[1]));
-    ms[0] = t;
-    HIPCHK(ctx, hipEventElapsedTime(&t, ev[1], ev[2]));
-    ms[2] = t;
-    HIPCHK(ctx, hipEventElapsedTime(&t, ev[2], ev[3]));
-    ms[5] = t;
+    HIPCHK(ctx, ev.ms(0, 1, &ms[0]));
+    HIPCHK(ctx, ev.ms(1, 2, &ms[2]));
+    HIPCHK(ctx, ev.ms(2, 3, &ms[5]));
     ms[6] = (double)items_valid;
     ms[7] = (double)n_pairs;
     ms[8] = (double)h_counters[2];
@@ -472,8 +469,7 @@ extern "C" int dsm_select_source_images(dsm_ctx* ctx, const dsm_source_selection
   HIPCHK(ctx, hipEventRecord(ev[6], st));
   HIPCHK(ctx, hipStreamSynchronize(st));
   for (int k = 0; k < 6; ++k) {
-    HIPCHK(ctx, hipEventElapsedTime(&t, ev[k], ev[k + 1]));
-    ms[k] = t;
+    HIPCHK(ctx, ev.ms(k, k + 1, &ms[k]));
   }
   ms[6] = (double)items_valid;
   ms[7] = (double)n_pairs;

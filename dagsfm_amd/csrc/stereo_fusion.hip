@@ -306,8 +306,8 @@ extern "C" int dsm_fuse_stereo(dsm_ctx* ctx, const dsm_stereo_fusion_options* op
 
   // ---- upload ----
   hipStream_t st = ctx->stream;
-  DevEvent ev[5];
-  for (DevEvent& e : ev) HIPCHK(ctx, hipEventCreate(&e.e));
+  DevEvents<5> ev;
+  HIPCHK(ctx, ev.create());
   HIPCHK(ctx, hipEventRecord(ev[0], st));
   HIPCHK(ctx, ctx->d_sf_maps.reserve(resident));
   size_t lanes_bytes = seed_bytes + sf_align(big_slots * slot_bytes) + 3 * 256 + 64;
@@ -395,9 +395,8 @@ extern "C" int dsm_fuse_stereo(dsm_ctx* ctx, const dsm_stereo_fusion_options* op
   d.vis_words = vis_words;
   HIPCHK(ctx, hipEventRecord(ev[1], st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  float t = 0;
-  HIPCHK(ctx, hipEventElapsedTime(&t, ev[0], ev[1]));
-  ms[0] = t;
+  double t = 0;
+  HIPCHK(ctx, ev.ms(0, 1, &ms[0]));
 
   // ---- the images in the reference's order ----
   std::vector<dsm_fused_point> h_points;
@@ -424,7 +423,7 @@ extern "C" int dsm_fuse_stereo(dsm_ctx* ctx, const dsm_stereo_fusion_options* op
       uint64_t h_counters[2] = {0, 0};
       HIPCHK(ctx, hipMemcpyAsync(h_counters, counters, sizeof(h_counters), hipMemcpyDeviceToHost, st));
       HIPCHK(ctx, hipStreamSynchronize(st));
-      HIPCHK(ctx, hipEventElapsedTime(&t, ev[0], ev[1]));
+      HIPCHK(ctx, ev.ms(0, 1, &t));
       ms[1] += t;
       n_out = h_counters[0];
       traversals += h_counters[1];
@@ -451,11 +450,11 @@ extern "C" int dsm_fuse_stereo(dsm_ctx* ctx, const dsm_stereo_fusion_options* op
         uint32_t h_ctrl[4] = {0, 0, 0, 0};
         HIPCHK(ctx, hipMemcpyAsync(h_ctrl, d.ctrl, sizeof(h_ctrl), hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
-        HIPCHK(ctx, hipEventElapsedTime(&t, ev[0], ev[1]));
+        HIPCHK(ctx, ev.ms(0, 1, &t));
         ms[1] += t;
-        HIPCHK(ctx, hipEventElapsedTime(&t, ev[1], ev[2]));
+        HIPCHK(ctx, ev.ms(1, 2, &t));
         ms[2] += t;
-        HIPCHK(ctx, hipEventElapsedTime(&t, ev[2], ev[3]));
+        HIPCHK(ctx, ev.ms(2, 3, &t));
         ms[3] += t;
         ++rounds;
         if (!h_ctrl[SF_PENDING]) break;
@@ -485,7 +484,7 @@ extern "C" int dsm_fuse_stereo(dsm_ctx* ctx, const dsm_stereo_fusion_options* op
     }
     HIPCHK(ctx, hipEventRecord(ev[4], st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    HIPCHK(ctx, hipEventElapsedTime(&t, ev[0], ev[4]));
+    HIPCHK(ctx, ev.ms(0, 4, &t));
     ms[4] += t;
     const auto h0 = std::chrono::steady_clock::now();
     points.insert(points.end(), h_points.begin(), h_points.end());

@@ -42,6 +42,7 @@
 #define TU_HD_MEMBER __device__ inline
 #define TU_FETCH_INC(ptr) atomicAdd((ptr), 1u)
 #include "track_update_load.h"
+#include "wave_reduce.h"
 
 namespace {
 
@@ -165,11 +166,6 @@ __global__ void __launch_bounds__(TU_BLOCK) k_tu_wave_list(TuDev d, const uint32
   if (d.v.alive[slot] && d.v.len[slot] > TU_LANE_CUT) wlist[atomicAdd(wcount, 1u)] = i;
 }
 
-__device__ inline double tu_wave_min(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-  return v;
-}
-
 // The same walk for a long track, one wave per point.  The 64 lanes take 64 correspondences of a queue element at a time: a lane
 // per (queue element, correspondence) candidate runs the reference's tests in their order, the tested and the accepted
 // candidates are compacted by ballot and prefix count, so the point's pool list and its accepted list (in LDS: the queue of the
@@ -247,8 +243,8 @@ __global__ void __launch_bounds__(64) k_tu_speculate_wave(TuDev d, const uint32_
     qlo = level_lo;
     qhi = t < v.max_transitivity - 1 ? count : level_lo;
   }
-  mg.complete_error = tu_wave_min(mg.complete_error);
-  mg.depth = tu_wave_min(mg.depth);
+  mg.complete_error = wave_fmin(mg.complete_error);
+  mg.depth = wave_fmin(mg.depth);
   if (lane != 0) return;
   if (head != TU_NIL) d.pool_next[last] = TU_NIL;
   if (overflow) atomicExch(&d.ctr[TU_C_OVERFLOW], 1u);
@@ -377,8 +373,8 @@ struct TuWaveTest {
       const unsigned long long fail = __ballot(!in);
       const uint32_t stop = fail ? (uint32_t)__ffsll((long long)fail) - 1 : 63u;
       if (lane > stop) le = ld = INFINITY;
-      mg->merge_error = fmin(mg->merge_error, tu_wave_min(le));
-      mg->depth = fmin(mg->depth, tu_wave_min(ld));
+      mg->merge_error = fmin(mg->merge_error, wave_fmin(le));
+      mg->depth = fmin(mg->depth, wave_fmin(ld));
       if (fail) return false;
       if (n < 64) return true;
     }
@@ -480,7 +476,6 @@ hipError_t tu_scan(TuBufs& d, uint32_t n, hipStream_t st) {
   return hipGetLastError();
 }
 
-inline uint32_t tu_grid(uint64_t n) { return (uint32_t)((n + TU_BLOCK - 1) / TU_BLOCK); }
 inline double tu_ms(std::chrono::steady_clock::time_point a) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
 }
@@ -501,10 +496,7 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
                                  double* out_xyz, uint64_t* out_track_offsets, uint32_t* out_track_obs, uint64_t* out_num_modified,
                                  uint64_t* out_modified, uint64_t* step_counts, dsm_track_update_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_update_tracks: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_update_tracks", msg); };
   const auto t_host0 = std::chrono::steady_clock::now();
   if (!out_num_points || !out_num_modified || (num_steps && !step_counts)) return fail("NULL argument");
   TuHost H;
@@ -513,7 +505,7 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
                                     image_qvec, image_tvec, points2D_offsets, points2D_xy, num_pairs, pair_image_ids, match_offsets,
                                     matches, num_points3D, point3D_ids, point3D_xyz, track_offsets, track_obs, num_steps, steps,
                                     num_selected, selected_ids, next_point3D_id, options);
-    if (!msg.empty()) return fail(msg);
+    if (!msg.empty()) return fail(msg.c_str());
   }
   bool serial = false;
   uint64_t pool_limit = 0;
@@ -535,29 +527,19 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
   hipStream_t st = ctx->stream;
   TuBufs b;
   const auto t_dev0 = std::chrono::steady_clock::now();
-  auto up = [&](DevBuf& buf, const void* src, size_t bytes) -> hipError_t {
-    hipError_t e = buf.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st);
-    return e;
-  };
-  auto fill = [&](DevBuf& buf, int byte, size_t bytes) -> hipError_t {
-    hipError_t e = buf.reserve(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) e = hipMemsetAsync(buf.p, byte, std::max<size_t>(bytes, 16), st);
-    return e;
-  };
   const uint64_t F = H.F, NM = H.NM;
   const uint32_t P = H.P, S = H.S, N = H.N;
   const size_t F1 = std::max<uint64_t>(F, 1);
 
   // ------------------------------------------------------------ the correspondence graph (rt_graph.h, as dsm_retriangulate)
-  HIPCHK(ctx, up(b.nfeat, H.nfeat.data(), H.nfeat.size() * 4));
-  HIPCHK(ctx, up(b.foff, H.foff.data(), H.foff.size() * 4));
-  HIPCHK(ctx, fill(b.cnt, 0, (F1 + 1) * 4));
+  HIPCHK(ctx, dev_upload(b.nfeat, H.nfeat.data(), H.nfeat.size() * 4, st));
+  HIPCHK(ctx, dev_upload(b.foff, H.foff.data(), H.foff.size() * 4, st));
+  HIPCHK(ctx, dev_fill(b.cnt, 0, (F1 + 1) * 4, st));
   uint32_t E = 0;
   if (NM) {
-    HIPCHK(ctx, up(b.pair_img, H.pair_img.data(), H.pair_img.size() * 4));
-    HIPCHK(ctx, up(b.moff, match_offsets, ((size_t)num_pairs + 1) * 8));
-    HIPCHK(ctx, up(b.matches, matches, NM * 8));
+    HIPCHK(ctx, dev_upload(b.pair_img, H.pair_img.data(), H.pair_img.size() * 4, st));
+    HIPCHK(ctx, dev_upload(b.moff, match_offsets, ((size_t)num_pairs + 1) * 8, st));
+    HIPCHK(ctx, dev_upload(b.matches, matches, NM * 8, st));
     HIPCHK(ctx, b.acc_m.reserve(NM));
     hipLaunchKernelGGL(k_rt_dedup, dim3(num_pairs), dim3(RT_GRAPH_BLOCK), 0, st, num_pairs, b.pair_img.as<uint32_t>(), b.moff.as<uint64_t>(),
                        b.matches.as<uint32_t>(), b.nfeat.as<uint32_t>(), b.acc_m.as<uint8_t>());
@@ -574,41 +556,41 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
     hipLaunchKernelGGL(k_rt_emit, dim3(num_pairs), dim3(RT_GRAPH_BLOCK), 0, st, num_pairs, b.pair_img.as<uint32_t>(), b.moff.as<uint64_t>(),
                        b.matches.as<uint32_t>(), b.acc_m.as<uint8_t>(), b.foff.as<uint32_t>(), b.goff.as<uint32_t>(), b.cnt.as<uint32_t>(),
                        b.epair.as<uint32_t>(), b.gval.as<uint32_t>());
-    hipLaunchKernelGGL(k_rt_segsort, dim3(tu_grid(F)), dim3(RT_GRAPH_BLOCK), 0, st, (uint32_t)F, b.goff.as<uint32_t>(), b.epair.as<uint32_t>(),
+    hipLaunchKernelGGL(k_rt_segsort, dim3(dsm_grid(F, TU_BLOCK)), dim3(RT_GRAPH_BLOCK), 0, st, (uint32_t)F, b.goff.as<uint32_t>(), b.epair.as<uint32_t>(),
                        b.gval.as<uint32_t>());
     HIPCHK(ctx, hipGetLastError());
   }
   rep.num_correspondences = E;
 
   // ------------------------------------------------------------ the scene and the state
-  HIPCHK(ctx, up(b.cams, cameras, (size_t)num_cameras * sizeof(dsm_camera)));
-  HIPCHK(ctx, up(b.img_cam, H.img_cam.data(), (size_t)N * 4));
-  HIPCHK(ctx, up(b.img_reg, H.img_reg.data(), N));
-  HIPCHK(ctx, up(b.img_bogus, H.img_bogus.data(), N));
-  HIPCHK(ctx, up(b.pose, H.pose.data(), H.pose.size() * 8));
-  HIPCHK(ctx, up(b.feat_img, H.feat_img.data(), F * 4));
-  HIPCHK(ctx, up(b.xy, points2D_xy, F * 16));
-  HIPCHK(ctx, up(b.img_ids, image_ids, (size_t)N * 4));
-  HIPCHK(ctx, up(b.f2p, H.f2p.data(), F * 4));
-  HIPCHK(ctx, up(b.fnext, H.fnext.data(), F * 4));
-  HIPCHK(ctx, up(b.xyz, H.xyz.data(), (size_t)S * 24));
-  HIPCHK(ctx, up(b.head, H.head.data(), (size_t)S * 4));
-  HIPCHK(ctx, up(b.tail, H.tail.data(), (size_t)S * 4));
-  HIPCHK(ctx, up(b.len, H.len.data(), (size_t)S * 4));
-  HIPCHK(ctx, up(b.alive, H.alive.data(), S));
-  HIPCHK(ctx, fill(b.modified, 0, S));
-  for (DevBuf* x : {&b.stamp, &b.born, &b.done, &b.ev_pos, &b.ev_depth, &b.parent, &b.label}) HIPCHK(ctx, fill(*x, 0, (size_t)S * 4));
-  HIPCHK(ctx, up(b.num_slots, &P, 4));
-  HIPCHK(ctx, fill(b.claim, 0xff, F1 * 8));
-  HIPCHK(ctx, fill(b.tested, 0xff, F1 * 8));
-  HIPCHK(ctx, fill(b.ctr, 0, TU_C_WORDS * 4));
+  HIPCHK(ctx, dev_upload(b.cams, cameras, (size_t)num_cameras * sizeof(dsm_camera), st));
+  HIPCHK(ctx, dev_upload(b.img_cam, H.img_cam.data(), (size_t)N * 4, st));
+  HIPCHK(ctx, dev_upload(b.img_reg, H.img_reg.data(), N, st));
+  HIPCHK(ctx, dev_upload(b.img_bogus, H.img_bogus.data(), N, st));
+  HIPCHK(ctx, dev_upload(b.pose, H.pose.data(), H.pose.size() * 8, st));
+  HIPCHK(ctx, dev_upload(b.feat_img, H.feat_img.data(), F * 4, st));
+  HIPCHK(ctx, dev_upload(b.xy, points2D_xy, F * 16, st));
+  HIPCHK(ctx, dev_upload(b.img_ids, image_ids, (size_t)N * 4, st));
+  HIPCHK(ctx, dev_upload(b.f2p, H.f2p.data(), F * 4, st));
+  HIPCHK(ctx, dev_upload(b.fnext, H.fnext.data(), F * 4, st));
+  HIPCHK(ctx, dev_upload(b.xyz, H.xyz.data(), (size_t)S * 24, st));
+  HIPCHK(ctx, dev_upload(b.head, H.head.data(), (size_t)S * 4, st));
+  HIPCHK(ctx, dev_upload(b.tail, H.tail.data(), (size_t)S * 4, st));
+  HIPCHK(ctx, dev_upload(b.len, H.len.data(), (size_t)S * 4, st));
+  HIPCHK(ctx, dev_upload(b.alive, H.alive.data(), S, st));
+  HIPCHK(ctx, dev_fill(b.modified, 0, S, st));
+  for (DevBuf* x : {&b.stamp, &b.born, &b.done, &b.ev_pos, &b.ev_depth, &b.parent, &b.label}) HIPCHK(ctx, dev_fill(*x, 0, (size_t)S * 4, st));
+  HIPCHK(ctx, dev_upload(b.num_slots, &P, 4, st));
+  HIPCHK(ctx, dev_fill(b.claim, 0xff, F1 * 8, st));
+  HIPCHK(ctx, dev_fill(b.tested, 0xff, F1 * 8, st));
+  HIPCHK(ctx, dev_fill(b.ctr, 0, TU_C_WORDS * 4, st));
   const size_t n_acc = TU_A_STEPS + (size_t)num_steps;
   std::vector<unsigned long long> acc0(n_acc, 0);
   {
     const double inf = INFINITY;
     for (int k = 0; k < 3; ++k) memcpy(&acc0[TU_A_MG + k], &inf, 8);
   }
-  HIPCHK(ctx, up(b.acc, acc0.data(), n_acc * 8));
+  HIPCHK(ctx, dev_upload(b.acc, acc0.data(), n_acc * 8, st));
   // the claim pool: every feature can be accepted by several pending walks of a round; four entries per feature cover what a
   // round of a real scene speculates, and a round that needs more ends in the serial form
   const uint64_t pool_cap64 = pool_limit ? pool_limit - 1 : std::min<uint64_t>(4 * F + 1024, 0x7fffffffu);
@@ -646,7 +628,7 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
     const std::vector<uint32_t> list = tu_step_list(H);
     const uint32_t n = (uint32_t)list.size();
     if (n == 0) continue;
-    HIPCHK(ctx, up(b.list, list.data(), (size_t)n * 4));
+    HIPCHK(ctx, dev_upload(b.list, list.data(), (size_t)n * 4, st));
     const uint32_t* dl = b.list.as<uint32_t>();
     if (steps[s] == DSM_TRACKS_COMPLETE) {
       const auto t0 = std::chrono::steady_clock::now();
@@ -654,8 +636,8 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
       bool to_serial = serial;
       uint32_t nw = 0;
       if (!serial) {
-        HIPCHK(ctx, fill(b.wcount, 0, 16));
-        hipLaunchKernelGGL(k_tu_wave_list, dim3(tu_grid(n)), dim3(TU_BLOCK), 0, st, d, dl, n, b.wlist.as<uint32_t>(), b.wcount.as<uint32_t>());
+        HIPCHK(ctx, dev_fill(b.wcount, 0, 16, st));
+        hipLaunchKernelGGL(k_tu_wave_list, dim3(dsm_grid(n, TU_BLOCK)), dim3(TU_BLOCK), 0, st, d, dl, n, b.wlist.as<uint32_t>(), b.wcount.as<uint32_t>());
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipMemcpyAsync(&nw, b.wcount.p, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
@@ -664,9 +646,9 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
       while (!to_serial) {
         if (tag == 0) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "dsm_update_tracks: more than 2^32 claim rounds");
         HIPCHK(ctx, hipMemsetAsync(b.ctr.p, 0, TU_C_WORDS * 4, st));
-        hipLaunchKernelGGL(k_tu_speculate, dim3(tu_grid(n)), dim3(TU_BLOCK), 0, st, d, dl, n, tag);
+        hipLaunchKernelGGL(k_tu_speculate, dim3(dsm_grid(n, TU_BLOCK)), dim3(TU_BLOCK), 0, st, d, dl, n, tag);
         if (nw) hipLaunchKernelGGL(k_tu_speculate_wave, dim3(nw), dim3(64), 0, st, d, dl, b.wlist.as<uint32_t>(), nw, tag);
-        hipLaunchKernelGGL(k_tu_commit, dim3(tu_grid(n)), dim3(TU_BLOCK), 0, st, d, dl, n, tag, s);
+        hipLaunchKernelGGL(k_tu_commit, dim3(dsm_grid(n, TU_BLOCK)), dim3(TU_BLOCK), 0, st, d, dl, n, tag, s);
         HIPCHK(ctx, hipGetLastError());
         uint32_t c[TU_C_WORDS];
         HIPCHK(ctx, hipMemcpyAsync(c, b.ctr.p, sizeof(c), hipMemcpyDeviceToHost, st));
@@ -697,9 +679,9 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
         for (uint32_t i = 0; i < n; ++i) comp_pos[i] = i;
         rep.num_components = 1, rep.largest_component = n;
       } else {
-        hipLaunchKernelGGL(k_tu_parent_init, dim3(tu_grid(S)), dim3(TU_BLOCK), 0, st, S, d.parent);
-        if (F) hipLaunchKernelGGL(k_tu_hook, dim3(tu_grid(F)), dim3(TU_BLOCK), 0, st, d);
-        hipLaunchKernelGGL(k_tu_label, dim3(tu_grid(S)), dim3(TU_BLOCK), 0, st, S, d.parent, b.label.as<uint32_t>());
+        hipLaunchKernelGGL(k_tu_parent_init, dim3(dsm_grid(S, TU_BLOCK)), dim3(TU_BLOCK), 0, st, S, d.parent);
+        if (F) hipLaunchKernelGGL(k_tu_hook, dim3(dsm_grid(F, TU_BLOCK)), dim3(TU_BLOCK), 0, st, d);
+        hipLaunchKernelGGL(k_tu_label, dim3(dsm_grid(S, TU_BLOCK)), dim3(TU_BLOCK), 0, st, S, d.parent, b.label.as<uint32_t>());
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipMemcpyAsync(label.data(), b.label.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipMemcpyAsync(cur_len.data(), b.len.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
@@ -733,10 +715,10 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
         t0 = std::chrono::steady_clock::now();
       }
       const uint32_t ncomp = (uint32_t)comp_off.size() - 1;
-      HIPCHK(ctx, up(b.comp_off, comp_off.data(), comp_off.size() * 4));
-      HIPCHK(ctx, up(b.comp_pos, comp_pos.data(), (size_t)n * 4));
+      HIPCHK(ctx, dev_upload(b.comp_off, comp_off.data(), comp_off.size() * 4, st));
+      HIPCHK(ctx, dev_upload(b.comp_pos, comp_pos.data(), (size_t)n * 4, st));
       if (n_lane)
-        hipLaunchKernelGGL(k_tu_merge_lane, dim3(tu_grid(n_lane)), dim3(TU_BLOCK), 0, st, d, dl, b.comp_off.as<uint32_t>(), b.comp_pos.as<uint32_t>(), n_lane, s);
+        hipLaunchKernelGGL(k_tu_merge_lane, dim3(dsm_grid(n_lane, TU_BLOCK)), dim3(TU_BLOCK), 0, st, d, dl, b.comp_off.as<uint32_t>(), b.comp_pos.as<uint32_t>(), n_lane, s);
       if (ncomp > n_lane)
         hipLaunchKernelGGL(k_tu_merge, dim3(ncomp - n_lane), dim3(64), 0, st, d, dl, b.comp_off.as<uint32_t>(), b.comp_pos.as<uint32_t>(), n_lane, ncomp, s);
       HIPCHK(ctx, hipGetLastError());
@@ -774,10 +756,10 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
   if (total > F) return dsm_fail(ctx, DSM_ERR_HIP, "dsm_update_tracks: the tracks hold more elements than there are points2D");
   std::vector<uint32_t> obs(2 * (size_t)total);
   if (n_out && total && out_track_obs) {
-    HIPCHK(ctx, up(b.out_slot, out.data(), (size_t)n_out * 4));
-    HIPCHK(ctx, up(b.out_off, off.data(), ((size_t)n_out + 1) * 8));
+    HIPCHK(ctx, dev_upload(b.out_slot, out.data(), (size_t)n_out * 4, st));
+    HIPCHK(ctx, dev_upload(b.out_off, off.data(), ((size_t)n_out + 1) * 8, st));
     HIPCHK(ctx, b.out_obs.reserve((size_t)total * 8));
-    hipLaunchKernelGGL(k_tu_emit, dim3(tu_grid(n_out)), dim3(TU_BLOCK), 0, st, d, b.out_slot.as<uint32_t>(), b.out_off.as<uint64_t>(), n_out,
+    hipLaunchKernelGGL(k_tu_emit, dim3(dsm_grid(n_out, TU_BLOCK)), dim3(TU_BLOCK), 0, st, d, b.out_slot.as<uint32_t>(), b.out_off.as<uint64_t>(), n_out,
                        b.img_ids.as<uint32_t>(), b.foff.as<uint32_t>(), b.out_obs.as<uint32_t>());
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out_track_obs, b.out_obs.p, (size_t)total * 8, hipMemcpyDeviceToHost, st));

@@ -370,10 +370,7 @@ extern "C" void dsm_default_undistort_options(dsm_undistort_options* o) {  // Un
 extern "C" int dsm_undistort_cameras(dsm_ctx* ctx, const dsm_undistort_options* options, uint32_t n, const dsm_camera* cameras,
                                      dsm_camera* out_cameras) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_undistort_cameras: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_undistort_cameras", msg); };
   if (n && (!cameras || !out_cameras)) return fail("NULL argument");
   dsm_undistort_options o;
   if (options)
@@ -450,13 +447,13 @@ extern "C" int dsm_undistort_cameras(dsm_ctx* ctx, const dsm_undistort_options* 
   }
 
   std::vector<double> mm((size_t)8 * n, 0.0);
-  float scan_ms = 0.0f;
+  double scan_ms = 0;
   if (n_items) {
     hipError_t he = hipSetDevice(ctx->device);
     if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
     hipStream_t st = ctx->stream;
-    DevEvent ev[2];
-    for (int i = 0; i < 2; ++i) HIPCHK(ctx, hipEventCreate(&ev[i].e));
+    DevEvents<2> ev;
+    HIPCHK(ctx, ev.create());
     // the cameras, the per-pixel values and the minima / maxima share one scratch buffer
     const size_t cams_bytes = ((size_t)n * sizeof(UdBorderCam) + 255) & ~(size_t)255;
     const size_t vals_bytes = ((size_t)n_items * 8 + 255) & ~(size_t)255;
@@ -474,7 +471,7 @@ extern "C" int dsm_undistort_cameras(dsm_ctx* ctx, const dsm_undistort_options* 
     HIPCHK(ctx, hipEventRecord(ev[1], st));
     HIPCHK(ctx, hipMemcpyAsync(mm.data(), d_mm, (size_t)n * 64, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    HIPCHK(ctx, hipEventElapsedTime(&scan_ms, ev[0], ev[1]));
+    HIPCHK(ctx, ev.ms(0, 1, &scan_ms));
   }
 
   // :779-839, the scalar tail in the reference's order
@@ -517,23 +514,20 @@ extern "C" int dsm_undistort_cameras(dsm_ctx* ctx, const dsm_undistort_options* 
 extern "C" int dsm_undistort_points2D(dsm_ctx* ctx, uint32_t n_cameras, const dsm_camera* cameras, const dsm_camera* undistorted_cameras,
                                       uint64_t n_points, const uint32_t* camera_index, double* xy) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_undistort_points2D: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_undistort_points2D", msg); };
   if ((n_cameras && (!cameras || !undistorted_cameras)) || (n_points && (!camera_index || !xy))) return fail("NULL argument");
   if (n_points >= ((uint64_t)1 << 31) * UD_BLOCK) return fail("too many points");
   for (uint32_t i = 0; i < n_cameras; ++i)
     if (!cam_model_exists(cameras[i].model_id) || !cam_model_exists(undistorted_cameras[i].model_id)) return fail("an unknown camera model");
   for (uint64_t i = 0; i < n_points; ++i)
     if (camera_index[i] >= n_cameras) return fail("a point on a camera index out of range");
-  float ms = 0.0f;
+  double ms = 0;
   if (n_points) {
     hipError_t he = hipSetDevice(ctx->device);
     if (he != hipSuccess) return dsm_fail(ctx, DSM_ERR_HIP, hipGetErrorString(he));
     hipStream_t st = ctx->stream;
-    DevEvent ev[2];
-    for (int i = 0; i < 2; ++i) HIPCHK(ctx, hipEventCreate(&ev[i].e));
+    DevEvents<2> ev;
+    HIPCHK(ctx, ev.create());
     const size_t cams_bytes = ((size_t)n_cameras * sizeof(dsm_camera) + 255) & ~(size_t)255;
     const size_t idx_bytes = ((size_t)n_points * 4 + 255) & ~(size_t)255;
     HIPCHK(ctx, ctx->d_ud_points.reserve(2 * cams_bytes + idx_bytes + (size_t)n_points * 16));
@@ -553,7 +547,7 @@ extern "C" int dsm_undistort_points2D(dsm_ctx* ctx, uint32_t n_cameras, const ds
     HIPCHK(ctx, hipEventRecord(ev[1], st));
     HIPCHK(ctx, hipMemcpyAsync(xy, d_xy, (size_t)n_points * 16, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    HIPCHK(ctx, ev.ms(0, 1, &ms));
   }
   mark_ready(ctx);
   ctx->undistortion_ms[1] = ms;
@@ -565,10 +559,7 @@ extern "C" int dsm_warp_images(dsm_ctx* ctx, const dsm_camera* source_camera, co
                                uint8_t* dst, uint64_t dst_row_stride, uint64_t dst_image_stride, dsm_camera* out_scaled_target_camera,
                                int32_t* out_needs_rescale, double* out_source_xy) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_warp_images: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_warp_images", msg); };
   if (!source_camera) return fail("source_camera is NULL (a size-only camera, model_id DSM_CAMERA_SIZE_ONLY, gives the size of a warp without cameras)");
   if (channels != 1 && channels != 3) return fail("channels must be 1 or 3");
   const bool size_only = source_camera->model_id == DSM_CAMERA_SIZE_ONLY;
@@ -651,8 +642,8 @@ extern "C" int dsm_warp_images(dsm_ctx* ctx, const dsm_camera* source_camera, co
     p.src = ctx->d_ud_src.as<uint8_t>() + UD_SRC_HEAD;
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_ud_src.p, kernel_cams, sizeof(kernel_cams), hipMemcpyHostToDevice, st));
     p.dst = ctx->d_ud_dst.as<uint8_t>();
-    DevEvent ev[4];
-    for (int i = 0; i < 4; ++i) HIPCHK(ctx, hipEventCreate(&ev[i].e));
+    DevEvents<4> ev;
+    HIPCHK(ctx, ev.create());
     for (uint64_t first = 0; first < std::max<uint32_t>(n_images, 1); first += chunk) {
       const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, n_images - std::min<uint64_t>(first, n_images));
       p.n_images = cnt;
@@ -672,8 +663,8 @@ extern "C" int dsm_warp_images(dsm_ctx* ctx, const dsm_camera* source_camera, co
       HIPCHK(ctx, hipEventRecord(ev[3], st));
       HIPCHK(ctx, hipStreamSynchronize(st));
       for (int k = 0; k < 3; ++k) {
-        float t = 0.0f;
-        HIPCHK(ctx, hipEventElapsedTime(&t, ev[k], ev[k + 1]));
+        double t = 0;
+        HIPCHK(ctx, ev.ms(k, k + 1, &t));
         ms[k] += t;
       }
     }

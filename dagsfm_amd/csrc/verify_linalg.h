@@ -739,6 +739,24 @@ DSM_DEV void pr_jacobi_svd_square_V(const double (&A_rowmajor)[N * N], double (&
   }
 }
 
+// TriangulatePoint (triangulation.cc:39-53) of one point seen at (u1, v1) and (u2, v2) by the row-major 3 x 4 matrices P1 and P2:
+// the reference-order 4 x 4 JacobiSVD, V's last column dehomogenised.  The one statement for the stages outside the
+// verification (re-triangulation, the initial pair); verify_kernels.hip's triangulate_point is the hot path's own.
+static __device__ void triangulate_two_view(const double* P1, const double* P2, double u1, double v1, double u2, double v2, double* X) {
+  double A[16];
+  for (int c = 0; c < 4; ++c) {
+    A[c] = u1 * P1[8 + c] - P1[c];
+    A[4 + c] = v1 * P1[8 + c] - P1[4 + c];
+    A[8 + c] = u2 * P2[8 + c] - P2[c];
+    A[12 + c] = v2 * P2[8 + c] - P2[4 + c];
+  }
+  double V[16], sv[4];
+  pr_jacobi_svd_square_V<4>(A, V, sv);
+  X[0] = V[12] / V[15];
+  X[1] = V[13] / V[15];
+  X[2] = V[14] / V[15];
+}
+
 // Eigenvalues of an upper-Hessenberg n x n matrix T (column-major, ld = LD, destroyed):
 // EigenSolver(C, false) for companion matrices (the Hessenberg reduction is the identity on
 // them: every sub-sub-diagonal entry is already zero).  Returns false on non-convergence.

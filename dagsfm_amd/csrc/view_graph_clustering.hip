@@ -633,9 +633,7 @@ extern "C" int dsm_view_graph_cluster(dsm_ctx* ctx, uint32_t n_pairs, const uint
         for (uint32_t j = 0; j < k; ++j) ctx->cluster_vectors[(size_t)n * k + j] = Xh[(size_t)n * m + j];
       ctx->cluster_rows = N;
       ctx->cluster_cols = k;
-      float ms = 0.f;
-      HIPTRY(hipEventElapsedTime(&ms, ev0, ev1));
-      rep.device_ms = ms;
+      HIPTRY(dev_events_ms(ev0, ev1, &rep.device_ms));
     }
     if (rc != DSM_OK) (void)hipStreamSynchronize(st);
     if (rc != DSM_OK) {

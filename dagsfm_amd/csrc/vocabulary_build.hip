@@ -563,10 +563,7 @@ extern "C" void dsm_default_vocabulary_build_options(dsm_vocabulary_build_option
 extern "C" int dsm_retrieval_quantize(dsm_ctx* ctx, const dsm_vocabulary_build_options* options, const uint8_t* descriptors, uint64_t n,
                                       int (*rand_fn)(void*), void* user, uint32_t* num_words_out, uint8_t* words, float* centers) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_retrieval_quantize: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_retrieval_quantize", msg); };
   dsm_vocabulary_build_options o;
   dsm_default_vocabulary_build_options(&o);
   if (options) o = *options;
@@ -648,12 +645,12 @@ extern "C" int dsm_retrieval_quantize(dsm_ctx* ctx, const dsm_vocabulary_build_o
   int32_t* d_draws = const_cast<int32_t*>(A.draws);
   int32_t* d_idx = const_cast<int32_t*>(A.idx);
 
-  DevEvent ev[8];
-  for (auto& e : ev) HIPCHK(ctx, hipEventCreate(&e.e));
+  DevEvents<8> ev;
+  HIPCHK(ctx, ev.create());
   double ms[DSM_VOCABULARY_BUILD_STAGES] = {0};
   auto add_ms = [&](int stage, int e0, int e1) {
-    float t = 0.0f;
-    if (hipEventElapsedTime(&t, ev[e0], ev[e1]) == hipSuccess) ms[stage] += t;
+    double t = 0;
+    if (ev.ms(e0, e1, &t) == hipSuccess) ms[stage] += t;
   };
 
   // the tree of this call replaces the last one's
@@ -1002,10 +999,7 @@ extern "C" int dsm_get_vocabulary_tree(dsm_ctx* ctx, uint32_t* num_nodes, dsm_vo
 extern "C" int dsm_retrieval_train_embedding(dsm_ctx* ctx, const uint8_t* descriptors, uint64_t n, const uint8_t* words, uint32_t num_words,
                                              const float* projection, const int32_t* word_ids, float* thresholds, uint8_t* has_embedding) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [&](const std::string& msg) {
-    ctx->err = "dsm_retrieval_train_embedding: " + msg;
-    return DSM_ERR_INVALID_ARGUMENT;
-  };
+  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_retrieval_train_embedding", msg); };
   if ((n && !descriptors) || !words || !projection || !thresholds || !has_embedding) return fail("NULL argument");
   if (num_words == 0 || num_words > 0x7ffffffeu) return fail("num_words out of range");
   if (n > 0x7fffffffull) return fail("more than 2^31 - 1 descriptors");
@@ -1045,8 +1039,8 @@ extern "C" int dsm_retrieval_train_embedding(dsm_ctx* ctx, const uint8_t* descri
   float* d_thr = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(d_seg) + seg_b);
   uint8_t* d_has = reinterpret_cast<uint8_t*>(d_thr) + thr_b;
 
-  DevEvent ev[2];
-  for (auto& e : ev) HIPCHK(ctx, hipEventCreate(&e.e));
+  DevEvents<2> ev;
+  HIPCHK(ctx, ev.create());
   std::vector<float> projT(128 * 64);
   for (int i = 0; i < 64; ++i)
     for (int j = 0; j < 128; ++j) projT[j * 64 + i] = projection[i * 128 + j];
@@ -1082,9 +1076,7 @@ extern "C" int dsm_retrieval_train_embedding(dsm_ctx* ctx, const uint8_t* descri
   HIPCHK(ctx, hipMemcpyAsync(thresholds, d_thr, (size_t)num_words * 64 * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipMemcpyAsync(has_embedding, d_has, num_words, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
-  float t = 0.0f;
-  HIPCHK(ctx, hipEventElapsedTime(&t, ev[0], ev[1]));
-  ctx->vocabulary_build_ms[5] = t;
+  HIPCHK(ctx, ev.ms(0, 1, &ctx->vocabulary_build_ms[5]));
   ctx->vocabulary_build_ready = true;
   return DSM_OK;
 }
