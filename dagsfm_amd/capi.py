@@ -204,7 +204,8 @@ class TriangulationOptions(ctypes.Structure):
 
 
 class TrackUpdateOptions(ctypes.Structure):
-    """dsm_track_update_options: of `tri` only the three bogus-parameter limits are read."""
+    """dsm_track_update_options: of `tri` dsm_update_tracks reads the three bogus-parameter limits only; dsm_complete_images also
+    min_angle, ignore_two_view_tracks, ransac_confidence, ransac_max_num_trials and max_transitivity (which must be 1)."""
     _fields_ = [("tri", TriangulationOptions), ("complete_max_reproj_error", ctypes.c_double),
                 ("merge_max_reproj_error", ctypes.c_double), ("complete_max_transitivity", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
@@ -227,6 +228,22 @@ _TRACK_UPDATE_ARGTYPES = ([ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ct
                           + [ctypes.c_uint32] + [ctypes.c_void_p] * 3 + [ctypes.c_uint32] + [ctypes.c_void_p] * 4
                           + [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                              ctypes.POINTER(TrackUpdateOptions)] + [ctypes.c_void_p] * 9)
+
+
+class CompleteImagesReport(ctypes.Structure):
+    """dsm_complete_images_report; `steps` is the report of the steps that ran first."""
+    _fields_ = [("num_images", ctypes.c_uint32), ("num_rounds", ctypes.c_uint32), ("num_items", ctypes.c_uint64),
+                ("num_estimated_ahead", ctypes.c_uint64), ("num_serial_items", ctypes.c_uint64), ("complete_trials", ctypes.c_uint64),
+                ("ransac_trials", ctypes.c_uint64), ("num_new_points", ctypes.c_uint64), ("num_new_observations", ctypes.c_uint64),
+                ("num_completed_observations", ctypes.c_uint64), ("min_residual_margin", ctypes.c_double),
+                ("min_support_margin", ctypes.c_double), ("min_angle_margin", ctypes.c_double), ("min_depth_margin", ctypes.c_double),
+                ("min_complete_error_margin", ctypes.c_double), ("min_bogus_margin", ctypes.c_double), ("estimate_ms", ctypes.c_double),
+                ("commit_ms", ctypes.c_double), ("device_ms", ctypes.c_double), ("steps", TrackUpdateReport)]
+
+
+# dsm_complete_images: dsm_update_tracks's arguments with the image list before the options and image_num_tris before the report
+_COMPLETE_IMAGES_ARGTYPES = (_TRACK_UPDATE_ARGTYPES[:25] + [ctypes.c_uint32, ctypes.c_void_p] + _TRACK_UPDATE_ARGTYPES[25:-1]
+                             + [ctypes.c_void_p, ctypes.c_void_p])
 
 
 class TriangulationReport(ctypes.Structure):
@@ -717,6 +734,7 @@ def lib(check=False):
         L.dsm_default_track_update_options.argtypes = [ctypes.POINTER(TrackUpdateOptions)]
         L.dsm_default_track_update_options.restype = None
         L.dsm_update_tracks.argtypes = [vp] + _TRACK_UPDATE_ARGTYPES
+        L.dsm_complete_images.argtypes = [vp] + _COMPLETE_IMAGES_ARGTYPES
         L.dsm_default_match_options.argtypes = [ctypes.POINTER(MatchOptions)]
         L.dsm_default_match_options.restype = None
         L.dsm_default_two_view_options.argtypes = [ctypes.POINTER(TwoViewOptions)]
@@ -1464,8 +1482,9 @@ def track_update_host_lib():
     return _libs["track_update_host"]
 
 
-def _update_tracks(call, scene, steps, selected, next_point3D_id, options):
-    """The marshalling dsm_update_tracks and its host build share.  call(args) -> the return code."""
+def _update_tracks(call, scene, steps, selected, next_point3D_id, options, complete_images=None):
+    """The marshalling dsm_update_tracks, its host build and dsm_complete_images share.  call(args) -> the return code.
+    complete_images: the image ids of dsm_complete_images (None: the other two)."""
     a = lambda key, dt, shape=-1: np.ascontiguousarray(scene[key], dt).reshape(shape)
     cam_ids = a("camera_ids", np.uint32)
     cams = (Camera * max(len(cam_ids), 1))(*scene["cameras"])
@@ -1479,21 +1498,32 @@ def _update_tracks(call, scene, steps, selected, next_point3D_id, options):
     st = np.ascontiguousarray(steps, np.int32).reshape(-1)
     sel = None if selected is None else np.ascontiguousarray(selected, np.uint64).reshape(-1)
     P, T = len(pids), int(poff[-1]) if len(poff) else 0
-    oid, oxyz, ooff = np.zeros(max(P, 1), np.uint64), np.zeros((max(P, 1), 3)), np.zeros(P + 1, np.uint64)
-    oobs, omod, counts = np.zeros((max(T, 1), 2), np.uint32), np.zeros(max(P, 1), np.uint64), np.zeros(max(len(st), 1), np.uint64)
+    ci = None if complete_images is None else np.ascontiguousarray(complete_images, np.uint32).reshape(-1)
+    R = P + (T if ci is not None else 0)  # room of the point arrays: every point2D of a listed image can add a point
+    oid, oxyz, ooff = np.zeros(max(R, 1), np.uint64), np.zeros((max(R, 1), 3)), np.zeros(R + 1, np.uint64)
+    oobs, omod, counts = np.zeros((max(T, 1), 2), np.uint32), np.zeros(max(R, 1), np.uint64), np.zeros(max(len(st), 1), np.uint64)
     n, nm = ctypes.c_uint64(0), ctypes.c_uint64(0)
-    rep = TrackUpdateReport()
+    rep = TrackUpdateReport() if ci is None else CompleteImagesReport()
     o = options if options is not None else default_track_update_options()
     ptr = lambda x: x.ctypes.data
-    rc = call([len(cam_ids), ptr(cam_ids), ctypes.addressof(cams), N, ptr(img_ids), ptr(img_cam), ptr(reg), ptr(qvec), ptr(tvec),
-               ptr(poff), ptr(xy), len(pairs), ptr(pairs), ptr(moff), ptr(m), P, ptr(pids), ptr(pxyz), ptr(toff), ptr(tobs),
-               len(st), ptr(st), 0 if sel is None else len(sel), None if sel is None else ptr(sel), int(next_point3D_id),
-               ctypes.byref(o), ctypes.addressof(n), ptr(oid), ptr(oxyz), ptr(ooff), ptr(oobs), ctypes.addressof(nm), ptr(omod),
-               ptr(counts), ctypes.addressof(rep)])
+    args = [len(cam_ids), ptr(cam_ids), ctypes.addressof(cams), N, ptr(img_ids), ptr(img_cam), ptr(reg), ptr(qvec), ptr(tvec),
+            ptr(poff), ptr(xy), len(pairs), ptr(pairs), ptr(moff), ptr(m), P, ptr(pids), ptr(pxyz), ptr(toff), ptr(tobs),
+            len(st), ptr(st), 0 if sel is None else len(sel), None if sel is None else ptr(sel), int(next_point3D_id)]
+    tris = None
+    if ci is not None:
+        tris = np.zeros(max(len(ci), 1), np.uint64)
+        args += [len(ci), ptr(ci)]
+    args += [ctypes.byref(o), ctypes.addressof(n), ptr(oid), ptr(oxyz), ptr(ooff), ptr(oobs), ctypes.addressof(nm), ptr(omod), ptr(counts)]
+    if ci is not None:
+        args.append(ptr(tris))
+    rc = call(args + [ctypes.addressof(rep)])
     k = n.value
-    return rc, {"point_ids": oid[:k].copy(), "xyz": oxyz[:k].copy(), "track_offsets": ooff[:k + 1].copy(),
-                "track_obs": oobs[:int(ooff[k])].copy(), "modified": omod[:nm.value].copy(), "step_counts": counts[:len(st)].copy(),
-                "report": rep}
+    out = {"point_ids": oid[:k].copy(), "xyz": oxyz[:k].copy(), "track_offsets": ooff[:k + 1].copy(),
+           "track_obs": oobs[:int(ooff[k])].copy(), "modified": omod[:nm.value].copy(), "step_counts": counts[:len(st)].copy(),
+           "report": rep}
+    if ci is not None:
+        out["image_num_tris"] = tris[:len(ci)].copy()
+    return rc, out
 
 
 def update_tracks_host(scene, steps, selected=None, next_point3D_id=0, options=None, **kw):
@@ -1819,7 +1849,7 @@ CHECK_OPTION_KEYS = ("DSM_K1_DOT4", "DSM_K1_RESOLVE_KERNEL", "DSM_VERIFY_DEBUG",
                      "DSM_FINAL_WAVES", "DSM_VERIFY_LEGACY", "DSM_VERIFY_FIXED_BATCH", "DSM_VERIFY_LANE_SPLIT", "DSM_DEBUG_SAMPLER_MODE",
                      "DSM_VOCAB_ASSIGN_VALU", "DSM_VERIFY_HOST_LOOP", "DSM_SCORE_PREFILTER", "DSM_VERIFY_REPLAY_GRID", "DSM_REPLAY_LEGACY", "DSM_FLANN_GROUP", "DSM_FLANN_STATS", "DSM_ELU_LDS", "DSM_HYP_GRID", "DSM_SPEC_MARGIN",
                      "DSM_POSE_FULL", "DSM_PATCH_MATCH_LANES", "DSM_NORMS_EXACT", "DSM_FUSION_SERIAL", "DSM_SOURCE_SELECTION_SERIAL",
-                     "DSM_INITIAL_PAIR_SERIAL", "DSM_NEXT_IMAGES_SERIAL", "DSM_TRACK_UPDATE_SERIAL")
+                     "DSM_INITIAL_PAIR_SERIAL", "DSM_NEXT_IMAGES_SERIAL", "DSM_TRACK_UPDATE_SERIAL", "DSM_COMPLETE_IMAGE_SERIAL")
 DEBUG_OPTION_KEYS = PRODUCT_OPTION_KEYS  # what a deployer's library knows
 
 
@@ -2940,6 +2970,27 @@ class Context:
     def merge_and_complete_tracks(self, scene, ids, **kw):
         """The order of AdjustLocalBundle: MERGE, then COMPLETE, over one id set."""
         return self.update_tracks(scene, [TRACKS_MERGE, TRACKS_COMPLETE], ids, **kw)
+
+    def complete_images(self, scene, image_ids, steps=(), selected=None, next_point3D_id=0, options=None, **kw):
+        """dsm_complete_images (IncrementalTriangulator::CompleteImage, DESIGN.md 33): the steps of update_tracks first (there may
+        be none), then CompleteImage of every listed image in the given order, over one state on the device.  Returns the dict
+        of update_tracks (new points included, in ascending id) plus image_num_tris (what CompleteImage returns per image) and
+        the CompleteImagesReport as report.  capi.apply_track_update takes the result as it is."""
+        assert options is None or not kw, "pass a TrackUpdateOptions or keywords, not both"
+        o = options if options is not None else default_track_update_options(**kw)
+        rc, out = _update_tracks(lambda args: self._L.dsm_complete_images(self._h, *args), scene, list(steps), selected, next_point3D_id, o,
+                                 complete_images=image_ids)
+        self._chk(rc)
+        return out
+
+    def adjust_local_bundle_tracks(self, scene, image_id, variable_ids, **kw):
+        """The tail of IncrementalMapper::AdjustLocalBundle in one call: MergeTracks and CompleteTracks over the variable point
+        ids, then CompleteImage of the image.  Adds num_merged_observations and num_completed_observations as the reference's
+        report sums them (CompleteTracks + CompleteImage)."""
+        out = self.complete_images(scene, [image_id], [TRACKS_MERGE, TRACKS_COMPLETE], variable_ids, **kw)
+        out["num_merged_observations"] = int(out["step_counts"][0])
+        out["num_completed_observations"] = int(out["step_counts"][1]) + int(out["image_num_tris"][0])
+        return out
 
     def find_initial_pairs(self, scene, problems, options=None, **kw):
         """dsm_find_initial_pairs (FindInitialImagePair, EstimateInitialTwoViewGeometry and the triangulation of

@@ -22,6 +22,14 @@
 //                     of its outer point, depth), and the host numbers the events in one ordered pass.
 //   output      k_tu_emit writes the tracks out in ascending id.
 // The check build's DSM_TRACK_UPDATE_SERIAL=1 runs both steps on one lane; =pool:<n> limits the claim pool to n entries.
+//
+// dsm_complete_images is the same driver with IncrementalTriangulator::CompleteImage of a list of images behind
+// the steps, over the same state:
+//   k_ci_find      per (listed image, point2D) item: is it a candidate for a new point, and how long is its estimation list
+//   k_ci_estimate  EstimateTriangulation (rt_loransac.h with the reprojection residual) of every candidate, a lane each
+//   k_ci_commit    the reference's loop in its order on one lane: Complete's walk, the skips, the estimates' results, AddPoint3D
+// The check build's DSM_COMPLETE_IMAGE_SERIAL=1 leaves every estimate to the commit lane; =pool:<n> limits the estimates that
+// run ahead to n list entries.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -37,6 +45,7 @@
 #include "ba_project.h"
 #include "ctx.h"
 #include "rt_graph.h"
+#include "rt_loransac.h"
 
 #define TU_HD __device__ inline
 #define TU_HD_MEMBER __device__ inline
@@ -443,7 +452,238 @@ __global__ void __launch_bounds__(TU_BLOCK) k_tu_emit(TuDev d, const uint32_t* _
   }
 }
 
+// ------------------------------------------------------------------ CompleteImage
+// An item is one (listed image, point2D) in (list position, point2D_idx) order.  What an item does depends on the state its
+// predecessors leave (has its point2D a point, has a correspondence one), but what a creating item ESTIMATES does not: its
+// list is Find's at transitivity 1 over the graph and the images' verdicts, the views are the scene's, and the only carried
+// value (RANSACOptions::min_num_trials of a list above 15 entries) is checked at the commit.  So the estimates of all
+// candidates run ahead, a lane each (k_ci_estimate), and one ordered pass (k_ci_commit) takes the reference's decisions in the
+// reference's order on one lane: Complete's walk for a point2D with a point, the three skips, the estimate's result, AddPoint3D.
+constexpr uint32_t CI_MAX_LIST = 8192;  // entries of one estimation list (the trial table grows with its square)
+enum : uint8_t { CI_NOT_RUN = 0, CI_FAILED = 1, CI_OK = 2 };
+enum { CI_A_RTRIALS = 0, CI_A_POINTS, CI_A_OBS, CI_A_SERIAL, CI_A_COMPLETED, CI_A_CTRIALS, CI_A_AHEAD, CI_A_ERROR, CI_A_MG, CI_A_WORDS = CI_A_MG + 4 };
+
+// the camera's WorldToImage, one copy out of line for the residual inside LORANSAC
+__device__ __noinline__ void ci_world_to_image(const dsm_camera* cam, double u, double v, double* x, double* y) {
+  ba_world_to_image<double>(cam->model_id, cam->params, u, v, x, y);
+}
+
+// ResidualType::REPROJECTION_ERROR: CalculateSquaredReprojectionError, the projection-matrix overload (projection.cc:138-157)
+struct RtReproj {
+  const dsm_camera* cams;
+  const uint32_t* img_cam;
+  const uint32_t* feat_img;
+  const double* xy;
+  __device__ inline double operator()(const RtView& w, uint32_t f, const double* X, double max_residual, double* mg) const {
+    const double z = rt_row(w.P, 2, X);
+    if (mg) {
+      const double m = tu_margin(z, DBL_EPSILON);
+      if (m < mg[3]) mg[3] = m;
+    }
+    if (z < DBL_EPSILON) return DBL_MAX;
+    const double x = rt_row(w.P, 0, X), y = rt_row(w.P, 1, X);
+    const double inv = 1.0 / z;
+    double px, py;
+    ci_world_to_image(cams + img_cam[feat_img[f]], inv * x, inv * y, &px, &py);
+    const double dx = px - xy[2 * (size_t)f], dy = py - xy[2 * (size_t)f + 1];
+    const double r = dx * dx + dy * dy;
+    if (mg) {
+      const double m = tu_margin(r, max_residual);
+      if (m < mg[0]) mg[0] = m;
+    }
+    return r;
+  }
+};
+
+struct CiDev {
+  uint32_t Q;                   // items
+  uint32_t pool_cap;            // list entries the estimates that run ahead may hold
+  const uint32_t* item_feat;    // [Q] the item's point2D as a feature
+  const uint32_t* item_first;   // [Q] the first item of its image
+  uint32_t* n_list;             // [Q] entries of the estimation list (correspondences kept by Find, then the point2D), 0: no candidate
+  const uint32_t* loff;         // [Q + 1] the lists in the pool
+  const uint8_t* img_ok;        // [N] registered, camera without bogus parameters
+  const double* img_P;          // [N][12]
+  const double* img_C;          // [N][3]
+  const double* uv;             // [F][2] ImageToWorld
+  const uint32_t* tab;          // ComputeNumTrials by (n, inliers), the host's libm
+  const uint32_t* tab_off;
+  RtParams prm;
+  int32_t* clist;               // [pool] the lists, the level's positions (0 .. n - 1) and the inlier masks of the estimates
+  int32_t* lvl;
+  uint8_t* mask;
+  uint8_t* est_state;           // [Q]
+  double* est_xyz;              // [Q][3]
+  uint32_t* est_trials;         // [Q]
+  unsigned long long* est_min;  // [Q] the carried min_num_trials the estimate ran with (lists above 15 entries)
+  int32_t* ser_clist;           // [longest list] the same for an estimate on the commit lane
+  int32_t* ser_lvl;
+  uint8_t* ser_mask;
+  unsigned long long* acc;      // [CI_A_WORDS]
+  unsigned long long* tris;     // [listed images]
+};
+
+__device__ inline bool ci_two_view(const TuView& v, uint32_t f) {  // CorrespondenceGraph::IsTwoViewObservation
+  if (v.goff[f + 1] - v.goff[f] != 1) return false;
+  const uint32_t g = v.gval[v.goff[f]];
+  return v.goff[g + 1] - v.goff[g] == 1;
+}
+
+// A candidate is an item that can still create: its point2D has no point, it is no ignored two-view observation, Find keeps a
+// correspondence and none of the kept ones has a point.  Features only ever gain points, so an item that is no candidate
+// against the state the steps leave is none at its turn either.
+__global__ void __launch_bounds__(TU_BLOCK) k_ci_find(TuDev d, CiDev c) {
+  const uint32_t q = blockIdx.x * TU_BLOCK + threadIdx.x;
+  if (q >= c.Q) return;
+  const TuView& v = d.v;
+  const uint32_t f = c.item_feat[q];
+  uint32_t n = 0;
+  bool cand = v.f2p[f] < 0 && !(c.prm.ignore_two_view && ci_two_view(v, f));
+  for (uint32_t e = v.goff[f]; e < v.goff[f + 1] && cand; ++e) {
+    const uint32_t g = v.gval[e];
+    if (!c.img_ok[v.feat_img[g]]) continue;
+    if (v.f2p[g] >= 0) cand = false;
+    ++n;
+  }
+  c.n_list[q] = cand && n ? n + 1 : 0;
+}
+
+// EstimateTriangulation of item q into the given list storage (n entries): success, X, the inlier mask; trials and margins
+// added to the caller's
+__device__ __noinline__ bool ci_estimate_item(const TuView& v, const CiDev& c, uint32_t q, uint32_t n, int32_t* clist, int32_t* lvl,
+                                              uint8_t* mask, uint64_t carried_min_trials, double* X, uint32_t* trials, double* mg) {
+  const uint32_t f = c.item_feat[q];
+  uint32_t m = 0;
+  for (uint32_t e = v.goff[f]; e < v.goff[f + 1] && m + 1 < n; ++e) {
+    const uint32_t g = v.gval[e];
+    if (c.img_ok[v.feat_img[g]]) clist[m++] = (int32_t)g;
+  }
+  clist[m++] = (int32_t)f;
+  for (uint32_t i = 0; i < m; ++i) lvl[i] = (int32_t)i;
+  RtLaneT<RtReproj> L;
+  L.feat_img = v.feat_img, L.img_P = c.img_P, L.img_C = c.img_C, L.uv = c.uv, L.clist = clist, L.idx = lvl, L.n = (int)m, L.prm = c.prm;
+  L.res.cams = v.cams, L.res.img_cam = v.img_cam, L.res.feat_img = v.feat_img, L.res.xy = v.xy;
+  for (int k = 0; k < kRtMargins; ++k) L.mg[k] = mg[k];
+  const bool ok = m >= 2 && rt_loransac(L, c.tab, c.tab_off, X, trials, carried_min_trials);
+  if (ok)
+    for (uint32_t i = 0; i < m; ++i) {
+      RtView w;
+      rt_view(L, (int)i, &w);
+      mask[i] = L.res(w, rt_feature(L, (int)i), X, c.prm.max_residual, nullptr) <= c.prm.max_residual;
+    }
+  for (int k = 0; k < kRtMargins; ++k) mg[k] = L.mg[k];
+  return ok;
+}
+
+__device__ inline void ci_fold_margins(unsigned long long* acc, const double* mg) {
+  for (int k = 0; k < 4; ++k) atomicMin(&acc[CI_A_MG + k], (unsigned long long)__double_as_longlong(mg[k]));  // non-negative doubles
+}
+
+// The estimates that run ahead: a lane per candidate whose list has room in the pool.  A list above 15 entries runs with the
+// min_num_trials the nearest candidate before it in its image would leave (the commit checks it against the carried one).
+__global__ void __launch_bounds__(TU_BLOCK) k_ci_estimate(TuDev d, CiDev c) {
+  const uint32_t q = blockIdx.x * TU_BLOCK + threadIdx.x;
+  if (q >= c.Q) return;
+  const uint32_t n = c.n_list[q];
+  if (n == 0 || c.loff[q + 1] > c.pool_cap) return;
+  unsigned long long carried = 0;
+  if (n > 15)
+    for (uint32_t p = q; p-- > c.item_first[q];) {
+      const uint32_t np = c.n_list[p];
+      if (np >= 2 && np <= 15) {
+        carried = (unsigned long long)np * (np - 1) / 2;
+        break;
+      }
+    }
+  const uint32_t at = c.loff[q];
+  double X[3] = {0.0, 0.0, 0.0}, mg[kRtMargins];
+  for (int k = 0; k < kRtMargins; ++k) mg[k] = INFINITY;
+  uint32_t trials = 0;
+  const bool ok = ci_estimate_item(d.v, c, q, n, c.clist + at, c.lvl + at, c.mask + at, carried, X, &trials, mg);
+  for (int k = 0; k < 3; ++k) c.est_xyz[3 * (size_t)q + k] = X[k];
+  c.est_trials[q] = trials;
+  c.est_min[q] = carried;
+  c.est_state[q] = ok ? CI_OK : CI_FAILED;
+  ci_fold_margins(c.acc, mg);
+  atomicAdd(&c.acc[CI_A_AHEAD], 1ull);
+}
+
+// The ordered pass, on one lane: the reference's loop over the listed images and their point2Ds.
+__global__ void k_ci_commit(TuDev d, CiDev c, uint32_t num_listed, const uint32_t* __restrict__ item_off) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const TuView& v = d.v;
+  TuMargins mg{INFINITY, INFINITY, INFINITY};
+  double emg[kRtMargins];
+  for (int k = 0; k < kRtMargins; ++k) emg[k] = INFINITY;
+  uint64_t ctrials = 0, rtrials = 0, npoints = 0, nobs = 0, nserial = 0, ncompleted = 0;
+  for (uint32_t a = 0; a < num_listed; ++a) {
+    uint64_t tris = 0, carried = 0;  // tri_options is set up per image: min_num_trials starts at 0
+    for (uint32_t q = item_off[a]; q < item_off[a + 1]; ++q) {
+      const uint32_t f = c.item_feat[q];
+      if (v.f2p[f] >= 0) {  // Complete existing track
+        const uint32_t k = tu_complete(v, (uint32_t)v.f2p[f], &mg, &ctrials);
+        tris += k;
+        ncompleted += k;
+        continue;
+      }
+      const uint32_t n = c.n_list[q];
+      if (n == 0) continue;
+      bool taken = false;  // Find's num_triangulated, against the state as it is now
+      for (uint32_t e = v.goff[f]; e < v.goff[f + 1] && !taken; ++e) {
+        const uint32_t g = v.gval[e];
+        taken = c.img_ok[v.feat_img[g]] && v.f2p[g] >= 0;
+      }
+      if (taken) continue;
+      if (n <= 15) carried = (uint64_t)n * (n - 1) / 2;
+      const int32_t* cl = c.clist + c.loff[q];
+      const uint8_t* mk = c.mask + c.loff[q];
+      double X[3];
+      uint32_t trials = 0;
+      bool ok;
+      if (c.est_state[q] != CI_NOT_RUN && (n <= 15 || c.est_min[q] == carried)) {
+        ok = c.est_state[q] == CI_OK;
+        trials = c.est_trials[q];
+        for (int k = 0; k < 3; ++k) X[k] = c.est_xyz[3 * (size_t)q + k];
+      } else {
+        ok = ci_estimate_item(v, c, q, n, c.ser_clist, c.ser_lvl, c.ser_mask, carried, X, &trials, emg);
+        cl = c.ser_clist, mk = c.ser_mask;
+        ++nserial;
+      }
+      rtrials += trials;
+      if (!ok) continue;
+      const uint32_t m = TU_FETCH_INC(v.num_slots);  // AddPoint3D
+      if (m >= v.S) {
+        atomicExch(&c.acc[CI_A_ERROR], 1ull);
+        return;
+      }
+      for (int k = 0; k < 3; ++k) v.xyz[3 * (size_t)m + k] = X[k];
+      v.head[m] = v.tail[m] = TU_NIL;
+      v.len[m] = 0;
+      for (uint32_t i = 0; i < n; ++i)
+        if (mk[i]) tu_append(v, m, (uint32_t)cl[i]);
+      v.alive[m] = 1;
+      v.modified[m] = 1;
+      v.ev_pos[m] = q;
+      v.ev_depth[m] = 0;
+      tris += v.len[m];
+      nobs += v.len[m];
+      ++npoints;
+    }
+    c.tris[a] = tris;
+  }
+  atomicAdd(&c.acc[CI_A_RTRIALS], (unsigned long long)rtrials);
+  atomicAdd(&c.acc[CI_A_POINTS], (unsigned long long)npoints);
+  atomicAdd(&c.acc[CI_A_OBS], (unsigned long long)nobs);
+  atomicAdd(&c.acc[CI_A_SERIAL], (unsigned long long)nserial);
+  atomicAdd(&c.acc[CI_A_COMPLETED], (unsigned long long)ncompleted);
+  atomicAdd(&c.acc[CI_A_CTRIALS], (unsigned long long)ctrials);
+  ci_fold_margins(c.acc, emg);
+  tu_fold_margins(d.acc, mg);
+}
+
 struct TuBufs {
+  DevBuf img_ok, img_P, img_C, uv, tab, tab_off, item_feat, item_first, item_off, n_list, loff, clist, lvl, mask, est_state, est_xyz, est_trials,
+      est_min, ser_clist, ser_lvl, ser_mask, ci_acc, tris;
   DevBuf pair_img, moff, matches, nfeat, foff, acc_m, cnt, goff, scan_s[4], scan_x[4], epair, gval;
   DevBuf cams, img_cam, img_reg, img_bogus, pose, feat_img, xy, img_ids;
   DevBuf f2p, fnext, xyz, head, tail, len, alive, modified, stamp, born, done, num_slots, ev_pos, ev_depth;
@@ -480,23 +720,163 @@ inline double tu_ms(std::chrono::steady_clock::time_point a) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
 }
 
-}  // namespace
+// the listed images of dsm_complete_images, validated: their indices in list order
+struct CiCall {
+  bool on = false;  // dsm_complete_images (dsm_update_tracks otherwise)
+  std::vector<uint32_t> img;
+  uint64_t* image_num_tris = nullptr;
+  dsm_complete_images_report* report = nullptr;
+};
 
-extern "C" void dsm_default_track_update_options(dsm_track_update_options* o) { tu_default_options(o); }
+// CompleteImage of the listed images over the device-resident state of the driver (after its steps).  *first_slot .. the
+// counter's new value are the points it adds, in the order of the sequential run.
+int tu_complete_images(dsm_ctx* ctx, TuHost& H, TuBufs& b, TuDev& d, const CiCall& ci, dsm_complete_images_report& rep) {
+  hipStream_t st = ctx->stream;
+  const uint32_t N = H.N, A = (uint32_t)ci.img.size();
+  const uint64_t F = H.F;
+  bool serial = false;
+  uint64_t pool_limit = 0;
+#ifdef DSM_CHECK_BUILD
+  if (const char* s = ctx->dbg("DSM_COMPLETE_IMAGE_SERIAL")) {
+    if (strncmp(s, "pool:", 5) == 0)
+      pool_limit = strtoull(s + 5, nullptr, 10) + 1;  // + 1: 0 means no limit
+    else
+      serial = atoi(s) != 0;
+  }
+#endif
+  auto t0 = std::chrono::steady_clock::now();
+  std::vector<uint32_t> item_off(A + 1, 0), item_feat, item_first;
+  for (uint32_t a = 0; a < A; ++a) {
+    const uint32_t i = ci.img[a];
+    if (H.img_reg[i] && !H.img_bogus[i])  // the reference returns 0 for the others
+      for (uint32_t k = H.foff[i]; k < H.foff[i + 1]; ++k) {
+        item_feat.push_back(k);
+        item_first.push_back(item_off[a]);
+      }
+    item_off[a + 1] = (uint32_t)item_feat.size();
+  }
+  const uint32_t Q = (uint32_t)item_feat.size();
+  rep.num_items = Q;
+  HIPCHK(ctx, dev_fill(b.tris, 0, (size_t)std::max(A, 1u) * 8, st));
+  std::vector<unsigned long long> acc0(CI_A_WORDS, 0);
+  {
+    const double inf = INFINITY;
+    for (int k = 0; k < 4; ++k) memcpy(&acc0[CI_A_MG + k], &inf, 8);
+  }
+  HIPCHK(ctx, dev_upload(b.ci_acc, acc0.data(), CI_A_WORDS * 8, st));
+  std::vector<unsigned long long> acc1(acc0);
+  if (Q) {
+    // the views: [R | t], the centre -R^T t (retriangulation.hip's rt_load_scene), ImageToWorld of the usable images' features
+    std::vector<uint8_t> img_ok(N);
+    std::vector<double> img_P(12 * (size_t)N), img_C(3 * (size_t)N);
+    for (uint32_t i = 0; i < N; ++i) {
+      img_ok[i] = H.img_reg[i] && !H.img_bogus[i];
+      const double* T = &H.pose[(size_t)TU_POSE * i];
+      for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k) img_P[12 * (size_t)i + 4 * r + k] = T[3 * r + k];
+        img_P[12 * (size_t)i + 4 * r + 3] = T[9 + r];
+      }
+      for (int k = 0; k < 3; ++k) img_C[3 * (size_t)i + k] = -((T[k] * T[9] + T[3 + k] * T[10]) + T[6 + k] * T[11]);
+    }
+    HIPCHK(ctx, dev_upload(b.img_ok, img_ok.data(), N, st));
+    HIPCHK(ctx, dev_upload(b.img_P, img_P.data(), img_P.size() * 8, st));
+    HIPCHK(ctx, dev_upload(b.img_C, img_C.data(), img_C.size() * 8, st));
+    HIPCHK(ctx, b.uv.reserve(std::max<size_t>((size_t)F * 16, 16)));
+    hipLaunchKernelGGL(k_rt_normalize, dim3(dsm_grid(F, TU_BLOCK)), dim3(TU_BLOCK), 0, st, (uint32_t)F, d.v.feat_img, b.img_ok.as<uint8_t>(), d.v.img_cam,
+                       d.v.cams, d.v.xy, b.uv.as<double>());
+    HIPCHK(ctx, dev_upload(b.item_feat, item_feat.data(), (size_t)Q * 4, st));
+    HIPCHK(ctx, dev_upload(b.item_first, item_first.data(), (size_t)Q * 4, st));
+    HIPCHK(ctx, dev_upload(b.item_off, item_off.data(), item_off.size() * 4, st));
+    HIPCHK(ctx, b.n_list.reserve((size_t)Q * 4));
+    CiDev c{};
+    c.Q = Q;
+    c.item_feat = b.item_feat.as<uint32_t>(), c.item_first = b.item_first.as<uint32_t>(), c.n_list = b.n_list.as<uint32_t>();
+    c.img_ok = b.img_ok.as<uint8_t>(), c.img_P = b.img_P.as<double>(), c.img_C = b.img_C.as<double>(), c.uv = b.uv.as<double>();
+    c.prm.max_residual = H.o.complete_max_reproj_error * H.o.complete_max_reproj_error;
+    c.prm.min_tri_angle = H.o.tri.min_angle * kRtDegToRad;
+    c.prm.ignore_two_view = H.o.tri.ignore_two_view_tracks;
+    c.prm.max_trials = H.o.tri.ransac_max_num_trials;
+    c.acc = b.ci_acc.as<unsigned long long>(), c.tris = b.tris.as<unsigned long long>();
+    hipLaunchKernelGGL(k_ci_find, dim3(dsm_grid(Q, TU_BLOCK)), dim3(TU_BLOCK), 0, st, d, c);
+    HIPCHK(ctx, hipGetLastError());
+    std::vector<uint32_t> n_list(Q), loff(Q + 1, 0);
+    HIPCHK(ctx, hipMemcpyAsync(n_list.data(), b.n_list.p, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    uint32_t maxn = 2;
+    uint64_t M = 0;
+    for (uint32_t q = 0; q < Q; ++q) {
+      loff[q] = (uint32_t)std::min<uint64_t>(M, 0xffffffffu);
+      M += n_list[q];
+      maxn = std::max(maxn, n_list[q]);
+    }
+    loff[Q] = (uint32_t)std::min<uint64_t>(M, 0xffffffffu);
+    if (maxn > CI_MAX_LIST) return dsm_fail(ctx, DSM_ERR_OUT_OF_RANGE, "dsm_complete_images: a correspondence list of more than 8192 entries");
+    // the estimate pool: the lists of all candidates; a limit (the check build's pool:<n>, or 2^32 entries) leaves the lists
+    // behind it to the commit lane
+    const uint64_t pool_cap = serial ? 0 : std::min<uint64_t>(pool_limit ? pool_limit - 1 : M, 0xfffffff0u);
+    const uint64_t pool_alloc = std::min<uint64_t>(pool_cap, M);
+    c.pool_cap = (uint32_t)pool_cap;
+    HIPCHK(ctx, dev_upload(b.loff, loff.data(), loff.size() * 4, st));
+    // ComputeNumTrials for n <= maxn (the host's libm), as dsm_retriangulate
+    std::vector<uint32_t> tab_off(maxn + 1, 0), tab;
+    for (uint32_t n = 2; n <= maxn; ++n) {
+      tab_off[n] = (uint32_t)tab.size();
+      for (uint32_t k = 0; k <= n; ++k) tab.push_back(rt_num_trials(k, n, H.o.tri.ransac_confidence));
+    }
+    HIPCHK(ctx, dev_upload(b.tab, tab.data(), tab.size() * 4, st));
+    HIPCHK(ctx, dev_upload(b.tab_off, tab_off.data(), tab_off.size() * 4, st));
+    c.prm.tab_n = maxn;
+    for (DevBuf* x : {&b.clist, &b.lvl}) HIPCHK(ctx, x->reserve(std::max<size_t>((size_t)pool_alloc * 4, 16)));
+    HIPCHK(ctx, b.mask.reserve(std::max<size_t>((size_t)pool_alloc, 16)));
+    for (DevBuf* x : {&b.ser_clist, &b.ser_lvl}) HIPCHK(ctx, x->reserve((size_t)maxn * 4));
+    HIPCHK(ctx, b.ser_mask.reserve(maxn));
+    HIPCHK(ctx, dev_fill(b.est_state, CI_NOT_RUN, Q, st));
+    HIPCHK(ctx, b.est_xyz.reserve((size_t)Q * 24));
+    HIPCHK(ctx, b.est_trials.reserve((size_t)Q * 4));
+    HIPCHK(ctx, b.est_min.reserve((size_t)Q * 8));
+    c.loff = b.loff.as<uint32_t>(), c.tab = b.tab.as<uint32_t>(), c.tab_off = b.tab_off.as<uint32_t>();
+    c.clist = b.clist.as<int32_t>(), c.lvl = b.lvl.as<int32_t>(), c.mask = b.mask.as<uint8_t>(), c.est_state = b.est_state.as<uint8_t>();
+    c.est_xyz = b.est_xyz.as<double>(), c.est_trials = b.est_trials.as<uint32_t>(), c.est_min = b.est_min.as<unsigned long long>();
+    c.ser_clist = b.ser_clist.as<int32_t>(), c.ser_lvl = b.ser_lvl.as<int32_t>(), c.ser_mask = b.ser_mask.as<uint8_t>();
+    if (pool_cap) {
+      hipLaunchKernelGGL(k_ci_estimate, dim3(dsm_grid(Q, TU_BLOCK)), dim3(TU_BLOCK), 0, st, d, c);
+      HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    rep.estimate_ms = tu_ms(t0);
+    t0 = std::chrono::steady_clock::now();
+    hipLaunchKernelGGL(k_ci_commit, dim3(1), dim3(64), 0, st, d, c, A, b.item_off.as<uint32_t>());
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(acc1.data(), b.ci_acc.p, CI_A_WORDS * 8, hipMemcpyDeviceToHost, st));
+    if (ci.image_num_tris) HIPCHK(ctx, hipMemcpyAsync(ci.image_num_tris, b.tris.p, (size_t)A * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    rep.commit_ms = tu_ms(t0);
+    rep.num_rounds = 1;
+    if (acc1[CI_A_ERROR]) return dsm_fail(ctx, DSM_ERR_HIP, "dsm_complete_images: more new points than slots");
+  } else if (ci.image_num_tris) {
+    for (uint32_t a = 0; a < A; ++a) ci.image_num_tris[a] = 0;
+  }
+  rep.ransac_trials = acc1[CI_A_RTRIALS], rep.num_new_points = acc1[CI_A_POINTS], rep.num_new_observations = acc1[CI_A_OBS];
+  rep.num_serial_items = acc1[CI_A_SERIAL], rep.num_completed_observations = acc1[CI_A_COMPLETED], rep.complete_trials = acc1[CI_A_CTRIALS];
+  rep.num_estimated_ahead = acc1[CI_A_AHEAD];
+  double mg[4];
+  memcpy(mg, &acc1[CI_A_MG], 32);
+  rep.min_residual_margin = mg[0], rep.min_support_margin = mg[1], rep.min_angle_margin = mg[2], rep.min_depth_margin = mg[3];
+  return DSM_OK;
+}
 
-extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
-                                 uint32_t num_images, const uint32_t* image_ids, const uint32_t* image_camera_ids,
-                                 const uint8_t* image_registered, const double* image_qvec, const double* image_tvec,
-                                 const uint32_t* points2D_offsets, const double* points2D_xy, uint32_t num_pairs,
-                                 const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
-                                 uint32_t num_points3D, const uint64_t* point3D_ids, const double* point3D_xyz,
-                                 const uint64_t* track_offsets, const uint32_t* track_obs, uint32_t num_steps, const int32_t* steps,
-                                 uint64_t num_selected, const uint64_t* selected_ids, uint64_t next_point3D_id,
-                                 const dsm_track_update_options* options, uint64_t* out_num_points, uint64_t* out_point_ids,
-                                 double* out_xyz, uint64_t* out_track_offsets, uint32_t* out_track_obs, uint64_t* out_num_modified,
-                                 uint64_t* out_modified, uint64_t* step_counts, dsm_track_update_report* report) {
+// dsm_update_tracks, and dsm_complete_images with its listed images behind the steps
+int tu_run(dsm_ctx* ctx, const char* entry, CiCall& ci, const uint32_t* complete_image_ids, uint32_t num_complete_images, uint32_t num_cameras,
+           const uint32_t* camera_ids, const dsm_camera* cameras, uint32_t num_images, const uint32_t* image_ids,
+           const uint32_t* image_camera_ids, const uint8_t* image_registered, const double* image_qvec, const double* image_tvec,
+           const uint32_t* points2D_offsets, const double* points2D_xy, uint32_t num_pairs, const uint32_t* pair_image_ids,
+           const uint64_t* match_offsets, const uint32_t* matches, uint32_t num_points3D, const uint64_t* point3D_ids,
+           const double* point3D_xyz, const uint64_t* track_offsets, const uint32_t* track_obs, uint32_t num_steps, const int32_t* steps,
+           uint64_t num_selected, const uint64_t* selected_ids, uint64_t next_point3D_id, const dsm_track_update_options* options,
+           uint64_t* out_num_points, uint64_t* out_point_ids, double* out_xyz, uint64_t* out_track_offsets, uint32_t* out_track_obs,
+           uint64_t* out_num_modified, uint64_t* out_modified, uint64_t* step_counts, dsm_track_update_report* report) {
   if (!ctx) return DSM_ERR_INVALID_ARGUMENT;
-  auto fail = [ctx](const char* msg) { return dsm_invalid(ctx, "dsm_update_tracks", msg); };
+  auto fail = [ctx, entry](const char* msg) { return dsm_invalid(ctx, entry, msg); };
   const auto t_host0 = std::chrono::steady_clock::now();
   if (!out_num_points || !out_num_modified || (num_steps && !step_counts)) return fail("NULL argument");
   TuHost H;
@@ -506,6 +886,32 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
                                     matches, num_points3D, point3D_ids, point3D_xyz, track_offsets, track_obs, num_steps, steps,
                                     num_selected, selected_ids, next_point3D_id, options);
     if (!msg.empty()) return fail(msg.c_str());
+  }
+  if (ci.on) {
+    const dsm_triangulation_options& t = H.o.tri;
+    if (t.max_transitivity != 1) return fail("max_transitivity other than 1 is not supported");
+    if (t.ransac_max_num_trials < 1 || !(t.ransac_confidence > 0 && t.ransac_confidence < 1) || !(t.min_angle >= 0) || !std::isfinite(t.min_angle))
+      return fail("option out of range");
+    if (num_complete_images && !complete_image_ids) return fail("NULL argument");
+    std::vector<std::pair<uint32_t, uint32_t>> by_id(num_images);
+    for (uint32_t i = 0; i < num_images; ++i) by_id[i] = {image_ids[i], i};
+    std::sort(by_id.begin(), by_id.end());
+    std::vector<uint8_t> listed(num_images, 0);
+    uint64_t extra = 0;
+    for (uint32_t a = 0; a < num_complete_images; ++a) {
+      auto it = std::lower_bound(by_id.begin(), by_id.end(), std::make_pair(complete_image_ids[a], 0u));
+      if (it == by_id.end() || it->first != complete_image_ids[a]) return fail("an unknown image id in complete_image_ids");
+      if (listed[it->second]) return fail("a repeated image id in complete_image_ids");
+      listed[it->second] = 1;
+      ci.img.push_back(it->second);
+      extra += H.nfeat[it->second];
+    }
+    // every item can add one point: that many slots behind the merge events'
+    extra = std::min<uint64_t>(extra, H.F);
+    if ((uint64_t)H.S + extra >= 0x80000000ull) return fail("too many points3D");
+    H.S += (uint32_t)extra;
+    H.xyz.resize(3 * (size_t)H.S, 0.0), H.head.resize(H.S, TU_NIL), H.tail.resize(H.S, TU_NIL), H.len.resize(H.S, 0), H.alive.resize(H.S, 0);
+    H.slot_id.resize(H.S, 0);
   }
   bool serial = false;
   uint64_t pool_limit = 0;
@@ -737,6 +1143,28 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
     }
   }
 
+  // ------------------------------------------------------------ CompleteImage of the listed images
+  dsm_complete_images_report crep{};
+  std::vector<unsigned long long> acc_steps(n_acc);
+  if (ci.on) {
+    HIPCHK(ctx, hipMemcpyAsync(acc_steps.data(), b.acc.p, n_acc * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    crep.num_images = (uint32_t)ci.img.size();
+    const int rc = tu_complete_images(ctx, H, b, d, ci, crep);
+    if (rc != DSM_OK) return rc;
+    uint32_t now_used = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&now_used, b.num_slots.p, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    now_used = std::min(now_used, S);
+    if (now_used > slots_used) {  // the new points, numbered in item order behind the merge events
+      HIPCHK(ctx, hipMemcpyAsync(ev_pos.data() + slots_used, b.ev_pos.as<uint32_t>() + slots_used, (size_t)(now_used - slots_used) * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
+      std::fill(ev_depth.begin() + slots_used, ev_depth.begin() + now_used, 0u);
+      tu_assign_ids(H, slots_used, now_used, ev_pos.data(), ev_depth.data());
+      slots_used = now_used;
+    }
+  }
+
   // ------------------------------------------------------------ the results
   const auto t_out = std::chrono::steady_clock::now();
   std::vector<uint8_t> alive(S), modified(S);
@@ -793,5 +1221,64 @@ extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint3
   rep.download_ms = tu_ms(t_out);
   rep.device_ms = tu_ms(t_dev0);
   if (report) *report = rep;
+  if (ci.on && ci.report) {
+    // the Complete walks of the images fold their margins and trials into the steps' accumulators: the steps' own share is
+    // what they held before the images ran
+    crep.complete_trials += acc_steps[TU_A_CTRIALS];
+    crep.min_complete_error_margin = mg[0];
+    crep.min_depth_margin = std::min(crep.min_depth_margin, mg[2]);
+    crep.min_bogus_margin = H.bogus_margin;
+    crep.device_ms = rep.device_ms;
+    crep.steps = rep;
+    crep.steps.complete_trials = acc_steps[TU_A_CTRIALS];
+    *ci.report = crep;
+  }
   return DSM_OK;
+}
+
+}  // namespace
+
+extern "C" void dsm_default_track_update_options(dsm_track_update_options* o) { tu_default_options(o); }
+
+extern "C" int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
+                                 uint32_t num_images, const uint32_t* image_ids, const uint32_t* image_camera_ids,
+                                 const uint8_t* image_registered, const double* image_qvec, const double* image_tvec,
+                                 const uint32_t* points2D_offsets, const double* points2D_xy, uint32_t num_pairs,
+                                 const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
+                                 uint32_t num_points3D, const uint64_t* point3D_ids, const double* point3D_xyz,
+                                 const uint64_t* track_offsets, const uint32_t* track_obs, uint32_t num_steps, const int32_t* steps,
+                                 uint64_t num_selected, const uint64_t* selected_ids, uint64_t next_point3D_id,
+                                 const dsm_track_update_options* options, uint64_t* out_num_points, uint64_t* out_point_ids,
+                                 double* out_xyz, uint64_t* out_track_offsets, uint32_t* out_track_obs, uint64_t* out_num_modified,
+                                 uint64_t* out_modified, uint64_t* step_counts, dsm_track_update_report* report) {
+  CiCall ci;
+  return tu_run(ctx, "dsm_update_tracks", ci, nullptr, 0, num_cameras, camera_ids, cameras, num_images, image_ids, image_camera_ids,
+                image_registered, image_qvec, image_tvec, points2D_offsets, points2D_xy, num_pairs, pair_image_ids, match_offsets, matches,
+                num_points3D, point3D_ids, point3D_xyz, track_offsets, track_obs, num_steps, steps, num_selected, selected_ids,
+                next_point3D_id, options, out_num_points, out_point_ids, out_xyz, out_track_offsets, out_track_obs, out_num_modified,
+                out_modified, step_counts, report);
+}
+
+extern "C" int dsm_complete_images(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
+                                   uint32_t num_images, const uint32_t* image_ids, const uint32_t* image_camera_ids,
+                                   const uint8_t* image_registered, const double* image_qvec, const double* image_tvec,
+                                   const uint32_t* points2D_offsets, const double* points2D_xy, uint32_t num_pairs,
+                                   const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
+                                   uint32_t num_points3D, const uint64_t* point3D_ids, const double* point3D_xyz,
+                                   const uint64_t* track_offsets, const uint32_t* track_obs, uint32_t num_steps, const int32_t* steps,
+                                   uint64_t num_selected, const uint64_t* selected_ids, uint64_t next_point3D_id,
+                                   uint32_t num_complete_images, const uint32_t* complete_image_ids,
+                                   const dsm_track_update_options* options, uint64_t* out_num_points, uint64_t* out_point_ids,
+                                   double* out_xyz, uint64_t* out_track_offsets, uint32_t* out_track_obs, uint64_t* out_num_modified,
+                                   uint64_t* out_modified, uint64_t* step_counts, uint64_t* image_num_tris,
+                                   dsm_complete_images_report* report) {
+  CiCall ci;
+  ci.on = true;
+  ci.image_num_tris = image_num_tris;
+  ci.report = report;
+  return tu_run(ctx, "dsm_complete_images", ci, complete_image_ids, num_complete_images, num_cameras, camera_ids, cameras, num_images, image_ids,
+                image_camera_ids, image_registered, image_qvec, image_tvec, points2D_offsets, points2D_xy, num_pairs, pair_image_ids,
+                match_offsets, matches, num_points3D, point3D_ids, point3D_xyz, track_offsets, track_obs, num_steps, steps, num_selected,
+                selected_ids, next_point3D_id, options, out_num_points, out_point_ids, out_xyz, out_track_offsets, out_track_obs,
+                out_num_modified, out_modified, step_counts, nullptr);
 }

@@ -2019,15 +2019,16 @@ int dsm_find_local_bundles(dsm_ctx* ctx, uint32_t num_images, const uint32_t* im
  * reconstruction.cc:215-241): what IncrementalMapper::AdjustLocalBundle runs after every local bundle adjustment (MERGE then
  * COMPLETE over one id set) and IterativeGlobalRefinement before every global one (CompleteAndMergeTracks: COMPLETE then MERGE
  * over all points).  The correspondence graph is dsm_retriangulate's; the reprojection error is dsm_filter_points3D's
- * (CalculateSquaredReprojectionError by qvec / tvec, DBL_MAX below a depth of epsilon).  CompleteImage is not part of this
- * call: its creating half is EstimateTriangulation.
+ * (CalculateSquaredReprojectionError by qvec / tvec, DBL_MAX below a depth of epsilon).  CompleteImage is dsm_complete_images
+ * (below), which takes the same scene and runs these steps first.
  *   Rulings: points run in ascending point3D id (the reference: unordered sets); a step without a selection
  *   takes a snapshot of the ids at its start; a merged point gets the id AddPoint3D would hand out from next_point3D_id, in
  *   the order of the merge events of the sequential run (an intermediate merged point that is merged again consumes one),
  *   however the device schedules the components; the camera verdict of HasBogusParams is computed per camera, not cached across
  *   calls; a selected id merged away earlier in the call is skipped (ExistsPoint3D), merged ids are never selected. */
 typedef struct dsm_track_update_options {
-  dsm_triangulation_options tri;       /* read: the three bogus-parameter limits only */
+  dsm_triangulation_options tri;       /* dsm_update_tracks reads the three bogus-parameter limits only; dsm_complete_images also
+                                          min_angle, ignore_two_view_tracks, ransac_confidence, ransac_max_num_trials, max_transitivity */
   double  complete_max_reproj_error;   /* 4.0 px */
   double  merge_max_reproj_error;      /* 4.0 px */
   int32_t complete_max_transitivity;   /* 5; < 1 is DSM_ERR_INVALID_ARGUMENT */
@@ -2090,6 +2091,62 @@ int dsm_update_tracks(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera
                       const dsm_track_update_options* options, uint64_t* out_num_points, uint64_t* out_point_ids,
                       double* out_xyz, uint64_t* out_track_offsets, uint32_t* out_track_obs, uint64_t* out_num_modified,
                       uint64_t* out_modified, uint64_t* step_counts, dsm_track_update_report* report);
+
+/* ------------------------------------------------------------------ completing an image's observations
+ * IncrementalTriangulator::CompleteImage (src/sfm/incremental_triangulator.cc:119-229), the last call of
+ * IncrementalMapper::AdjustLocalBundle's tail (MergeTracks, CompleteTracks, CompleteImage): in point2D order over one state, a
+ * point2D with a point runs Complete(point) (dsm_update_tracks's walk), one without runs Find at transitivity 1,
+ * EstimateTriangulation with REPROJECTION_ERROR residuals (LORANSAC, CombinationSampler, InlierSupportMeasurer; the
+ * projection-matrix overload of CalculateSquaredReprojectionError) and AddPoint3D of the inliers.
+ *   Rulings: the listed images run in the given order; RANSACOptions::min_num_trials is carried from one point2D
+ *   to the next inside an image as the reference carries it (assigned C(n, 2) only where the list holds n <= 15 entries, 0 at
+ *   the start of every image); new ids continue the counter the steps' merge events draw from, in the order of the sequential
+ *   run; ransac_confidence and ransac_max_num_trials are read from the options (the reference: 0.9999 and 10000). */
+typedef struct dsm_complete_images_report {
+  uint32_t num_images;                 /* listed images */
+  uint32_t num_rounds;                 /* ordered commit passes over the items (one per call that has items) */
+  uint64_t num_items;                  /* (listed image, point2D) items of the registered images on passing cameras */
+  uint64_t num_estimated_ahead;        /* creating candidates whose estimate ran ahead of the commit pass, a lane each */
+  uint64_t num_serial_items;           /* creating items whose estimate ran on the commit lane: no room in the estimate pool, a carried
+                                          min_num_trials other than the predicted one, or the serial form asked for */
+  uint64_t complete_trials;            /* reprojection tests of Complete, the steps' included */
+  uint64_t ransac_trials;              /* LORANSAC trials of the estimates the sequential run takes */
+  uint64_t num_new_points, num_new_observations;   /* AddPoint3D calls and their track elements */
+  uint64_t num_completed_observations; /* what the Complete walks of the images added */
+  /* the smallest relative margin of every decision taken (INFINITY when never taken; estimates that ran ahead and were not
+     used are included): the squared reprojection residual against max_error^2, equal-count support sums against each other,
+     the triangulation angle against min_angle, depths against epsilon, Complete's squared error against its threshold, the
+     bogus ratios against their bounds */
+  double min_residual_margin, min_support_margin, min_angle_margin, min_depth_margin, min_complete_error_margin, min_bogus_margin;
+  double estimate_ms;                  /* the candidates, their lists and the estimates that run ahead (host clock, synchronised) */
+  double commit_ms;                    /* the ordered pass: the Complete walks, the creations, the remaining estimates */
+  double device_ms;                    /* first upload to the last download, the steps included */
+  dsm_track_update_report steps;       /* the report of the steps (its download_ms and device_ms cover the whole call) */
+} dsm_complete_images_report;
+
+/* dsm_update_tracks's arguments (scene, state, steps -- there may be none --, selection, next_point3D_id, options), then
+ * complete_image_ids[num_complete_images] (unique): the steps run first, then CompleteImage for every listed image in the
+ * given order, all over one device-resident state.  An unregistered image or one on a camera with bogus parameters
+ * contributes 0.  complete_max_reproj_error is Complete's threshold and the RANSAC max_error; complete_max_transitivity is
+ * read by the Complete walks only.
+ * Outputs as dsm_update_tracks, with new points: the point arrays need room for num_points3D plus the points2D of the listed
+ *   images; image_num_tris[num_complete_images] is what CompleteImage returns per image.  report may be NULL.
+ * Invalid (DSM_ERR_INVALID_ARGUMENT, outputs untouched): what dsm_update_tracks refuses; an unknown or repeated image id in
+ *   complete_image_ids; tri.max_transitivity != 1; ransac_max_num_trials < 1; a confidence outside (0, 1); a negative or
+ *   non-finite min_angle.  A correspondence list of more than 8192 entries is DSM_ERR_OUT_OF_RANGE. */
+int dsm_complete_images(dsm_ctx* ctx, uint32_t num_cameras, const uint32_t* camera_ids, const dsm_camera* cameras,
+                        uint32_t num_images, const uint32_t* image_ids, const uint32_t* image_camera_ids,
+                        const uint8_t* image_registered, const double* image_qvec, const double* image_tvec,
+                        const uint32_t* points2D_offsets, const double* points2D_xy, uint32_t num_pairs,
+                        const uint32_t* pair_image_ids, const uint64_t* match_offsets, const uint32_t* matches,
+                        uint32_t num_points3D, const uint64_t* point3D_ids, const double* point3D_xyz,
+                        const uint64_t* track_offsets, const uint32_t* track_obs, uint32_t num_steps, const int32_t* steps,
+                        uint64_t num_selected, const uint64_t* selected_ids, uint64_t next_point3D_id,
+                        uint32_t num_complete_images, const uint32_t* complete_image_ids,
+                        const dsm_track_update_options* options, uint64_t* out_num_points, uint64_t* out_point_ids,
+                        double* out_xyz, uint64_t* out_track_offsets, uint32_t* out_track_obs, uint64_t* out_num_modified,
+                        uint64_t* out_modified, uint64_t* step_counts, uint64_t* image_num_tris,
+                        dsm_complete_images_report* report);
 
 void dsm_default_match_options(dsm_match_options* o);
 void dsm_default_two_view_options(dsm_two_view_options* o);
